@@ -2,8 +2,18 @@
 """
 bench.py — throughput of the SVI training hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config C1..C5] [--strong] [--repeats R]
+  python bench.py --gpus N --steps K --warmup W [--config C1..C5] [--strong] [--dump-outputs DIR] [--full [--repeats R]]
   (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL)
+
+A plain run measures the headline figure and nothing else: set-up, the untimed state-free pass, --warmup SVI steps,
+PREROLL_PASSES gradient-only passes (no optimizer update: they keep the clocks up without moving the training state), then
+ONE timed region of exactly --steps steps; `ms_per_step` is that region's time / --steps.  --dump-outputs DIR then writes
+what the timed path computed in its last step as DIR/<name>.npy: every entry of the model's state_dict after the step
+(`param.<key>`, float32), the step's four loss scalars (`loss_terms`: loss, and the three ELBO terms, float64) and the loss
+of every timed step (`loss_per_step`, float64).  Data, noise and weights are seeded, and the number of optimizer steps is
+--warmup + --steps, so the same arguments give the same inputs on every run.
+--full adds everything below: the other precision leg, repeated and converged regions, kernel events and rooflines, the
+CPU baseline, the trainer / inference legs and the side configs (N = 1), both scalings and the conv config (N > 1).
 
 Headline workload (BASELINE.json configs[1], "C2"): iVAE, data_dim (28, 28), latent_dim 2, invariances ['r','t'],
 Bernoulli likelihood, batch 256 PER GPU (weak scaling; --strong: 256 GLOBAL, sharded), bf16 as that config names it:
@@ -94,6 +104,8 @@ if os.path.exists(_traffic_file):
 EV_EVERY = 8                     # (N > 1: the all-reduce's torch events, every EV_EVERY-th step)
 EV_PER_REGION = 1                # decoder / conv launches carrying HIP events per timed region, taken mid-region (a launch with events
                                  # costs the stream ~11 us: profiles/r05ay_bench_region_timing.txt); the measured regions' samples are pooled
+PREROLL_PASSES = 100            # (plain run) gradient-only passes in front of the one timed region, a fixed count: see --full's
+                                 # preroll below for why a short region wants them
 PREROLL_MS, PREROLL_MAX = 10.0, 100   # untimed steps enqueued right in front of every timed region's opening synchronisation: ~10 ms of
                                  # them (at most 100; counted from the first region's step time, the same on every rank).  A 20-step
                                  # region is 2 ms — after the idle gap between regions it ran at a colder GPU's clocks (decoder
@@ -295,17 +307,18 @@ def _run(args, cfg, fused, pv, pvdist, td, dev, rank, world, B, attrs=None):
     # ring's global minibatches of world*B; strong scaling: the global minibatch is B_global = world*B too (B = global/world)
     data = make_data(cfg, ring_n * world * B, gen)
     data = [t.view(ring_n, world, B, *t.shape[1:])[:, rank].contiguous().to(dev) for t in data]
-    R = max(1, args.repeats)
-    n_eps = args.warmup + 2 * args.steps               # noise ring (the first warmup + steps draws are the seeded stream)
+    full = args.full
+    R = max(1, args.repeats) if full else 1
+    n_eps = args.warmup + (2 if full else 1) * args.steps    # noise ring (the first warmup + steps draws are the seeded stream)
     torch.manual_seed(1)
     eps_all = torch.empty(n_eps, world, B, model.z_dim).normal_()[:, rank].contiguous().to(dev)
-    n_ev = max(1, min(EV_PER_REGION, args.steps))
+    n_ev = max(1, min(EV_PER_REGION, args.steps)) if full else 0     # (plain run: no events in the timed region)
     ev_at = {min(args.steps - 1, int((2 * j_ + 1) * args.steps / (2 * n_ev))): j_ for j_ in range(n_ev)}   # step index -> sample slot
     events = HipEvents(n_ev * R)                        # one set per measured region (warm-up regions re-record set 0)
     conv = cfg["kind"] in ("ved", "ivae_conv")
     cevents = HipEvents(n_ev * R) if conv else None
     preroll_env = os.environ.get("PV_BENCH_PREROLL")            # (experiments: a fixed count)
-    preroll_n = [int(preroll_env) if preroll_env is not None else 0]   # set after the first region (its step time is the estimate)
+    preroll_n = [int(preroll_env) if (preroll_env is not None and full) else 0]   # set after the first region (its step time is the estimate)
     cflops = C.c_double(0.0)
     arev = TorchEvents()
     hist = torch.zeros(n_eps, 4, device=dev)
@@ -357,12 +370,15 @@ def _run(args, cfg, fused, pv, pvdist, td, dev, rank, world, B, attrs=None):
             eng.loss_and_grads(x, eps_all[k], scalars_out=hist[k])
             eng.adam_step()
 
+    def free_pass():
+        if ved:
+            eng.loss_and_grads(data[0][0], eps_all[0], 1.0, data[1][0])
+        else:
+            eng.loss_and_grads(data[0][0], eps_all[0])
+
     # one untimed, state-free pass first (gradients only, no optimizer update, no collective on real data): module
     # loading and first-launch costs never land in a timed region, whatever --warmup is
-    if ved:
-        eng.loss_and_grads(data[0][0], eps_all[0], 1.0, data[1][0])
-    else:
-        eng.loss_and_grads(data[0][0], eps_all[0])
+    free_pass()
     if multi:
         reduce_(torch.zeros_like(eng.grad))
     for i in range(args.warmup):
@@ -388,7 +404,7 @@ def _run(args, cfg, fused, pv, pvdist, td, dev, rank, world, B, attrs=None):
             sample = i in ev_at
             j = slot * n_ev + ev_at.get(i, 0)
             step(base + i, events.pairs[j] if sample else None, cevents.pairs[j] if (sample and conv) else None,
-                 True if (i % EV_EVERY == 0 and multi) else None)
+                 True if (i % EV_EVERY == 0 and multi and full) else None)
             note_first(base + i)
         if multi:
             td.barrier()
@@ -398,6 +414,17 @@ def _run(args, cfg, fused, pv, pvdist, td, dev, rank, world, B, attrs=None):
             td.all_reduce(t, op=td.ReduceOp.MAX)
         return t.item()
 
+    if not full:
+        # the plain run: the fixed preroll, then exactly --steps timed steps
+        for _ in range(PREROLL_PASSES):
+            free_pass()
+        t = region(args.warmup)
+        losses_first = hist[:, 0].cpu().clone()
+        base = args.warmup + args.steps
+        return dict(regions=[t], discarded=0, all_regions=[t], kms=[], cms=[], conv_flops=0.0, ar_ms=[],
+                    losses_head=losses_head, losses_first=losses_first, first_after_warmup=first_after["t"].item(),
+                    preroll=PREROLL_PASSES, ev_samples_per_region=0, last_loss=hist[(base - 1) % n_eps, 0].item(),
+                    outputs=_outputs(args, model, hist, base, n_eps), eng=eng, model=model)
     all_regions, base = [], args.warmup
     first = region(base)
     if preroll_env is None:                             # (max over ranks already: the same count everywhere)
@@ -423,7 +450,41 @@ def _run(args, cfg, fused, pv, pvdist, td, dev, rank, world, B, attrs=None):
                 kms=events.elapsed_ms() if not ved else [], cms=cevents.elapsed_ms() if conv else [],
                 conv_flops=cflops.value, ar_ms=arev.elapsed_ms(), losses_head=losses_head, losses_first=losses_first,
                 first_after_warmup=first_after["t"].item(), preroll=preroll_n[0], ev_samples_per_region=n_ev,
-                last_loss=hist[(base - 1) % n_eps, 0].item(), eng=eng, model=model)
+                last_loss=hist[(base - 1) % n_eps, 0].item(), outputs=_outputs(args, model, hist, base, n_eps),
+                eng=eng, model=model)
+
+
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 20            # an array of more elements is written as a fixed, seeded sample of this many
+
+
+def _outputs(args, model, hist, base, n_eps):
+    """(--dump-outputs) what the caller of the timed path holds after its last step (step index base - 1): name -> numpy array."""
+    if not args.dump_outputs:
+        return None
+    import numpy as np
+    torch.cuda.synchronize()
+    slots = [(base - args.steps + i) % n_eps for i in range(args.steps)]
+    out = {"loss_per_step": hist[slots, 0].double().cpu().numpy(),
+           "loss_terms": hist[(base - 1) % n_eps].double().cpu().numpy()}
+    for k, v in model.state_dict().items():
+        a = v.detach().cpu()
+        a = (a.float() if a.is_floating_point() else a.double()).numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        out["param." + k] = a
+    return out
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, over the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _kernel_name(fused, units, grads=1, lik=0, fold=False):
@@ -493,7 +554,7 @@ def measure(args, name, cfg, fused, ctx, attrs=None):
            "loss_per_image_step0": (r["losses_head"][0].item() if args.warmup > 0 else r["first_after_warmup"]) / (B * world),
            "preroll_steps": r["preroll"], "kernel_event_samples_per_region": r["ev_samples_per_region"],
            "loss_per_image_first_timed_step": r["losses_first"][args.warmup].item() / (B * world),
-           "loss_per_image_last_step": r["last_loss"] / (B * world)}
+           "loss_per_image_last_step": r["last_loss"] / (B * world), "outputs": r["outputs"]}
     if (world > 1 or FORCE_DIST) and r["ar_ms"]:
         out["collective"] = COLLECTIVE["used"]
         out["allreduce_ms"] = sum(r["ar_ms"]) / len(r["ar_ms"])
@@ -569,7 +630,7 @@ def measure(args, name, cfg, fused, ctx, attrs=None):
 def sub_config(name, args):
     """Times another config in its own process (N = 1) and returns its compact record."""
     cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(args.sub_steps), "--warmup", "10",
-           "--repeats", "3", "--no-cpu-baseline", "--no-configs"]
+           "--full", "--repeats", "3", "--no-cpu-baseline", "--no-configs"]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -646,12 +707,34 @@ def inference_leg(pv, dev):
     return out
 
 
+def headline(args, name, cfg, leg, world, B):
+    """The result line's contract fields (a plain run prints these alone)."""
+    return {
+        "metric": "images/sec (SVI step)", "value": leg["value"], "unit": "images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": leg["ms_per_step"],
+        "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
+        "dtype": leg["dtype"], "data": "synthetic",
+        "config": {"workload": "%s %s, batch %d per GPU (global %d), %s, SVI step = ELBO+grads+%sAdam"
+                               % (name, cfg["desc"], B, B * world, leg["arith"], "allreduce+" if world > 1 else ""),
+                   "parallelism": "dp%d" % world, "path": leg["path"], "baseline_config": name},
+        "elbo": {k: leg[k] for k in ("loss_per_image_first_timed_step", "loss_per_image_last_step", "loss_per_image_step0")},
+        "timing": {"preroll_passes": PREROLL_PASSES,
+                   "note": "one timed region of exactly --steps steps after --warmup steps and preroll_passes gradient-only "
+                           "passes; --full for the repeated regions, the other precision, rooflines and the side measurements"},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the other precision leg, repeated regions, rooflines, the CPU "
+                         "baseline, the trainer / inference legs, the side configs (N = 1), both scalings (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=5, help="(--full) timed regions of --steps steps; the median is reported")
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--no-legs", action="store_true", help="skip the trainer / inference legs of the default N=1 run")
     ap.add_argument("--strong", action="store_true", help="strong scaling: the config's batch is the GLOBAL batch, sharded")
@@ -706,6 +789,17 @@ def main():
     if args.fused is None:
         args.fused = int(os.environ.get("PV_BENCH_FUSED", "3" if name == "C2" else "2"))
     main_leg = measure(args, name, cfg, args.fused, ctx)
+    outputs = main_leg.pop("outputs")
+    if outputs is not None and rank == 0:
+        write_outputs(args.dump_outputs, outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, name, cfg, main_leg, world, B)))
+            sys.stdout.flush()
+        if world > 1 or FORCE_DIST:
+            pvdist.close_native()
+            td.destroy_process_group()
+        return
     alt = None
     if args.fused in (2, 3) and not args.no_alt:
         alt = measure(args, name, cfg, 5 - args.fused, ctx)      # the same workload on the other precision
@@ -731,14 +825,9 @@ def main():
         except Exception as e:                   # (must not take the headline line down)
             c5w = {"error": repr(e)[:300]}
     if rank == 0:
-        out = {
-            "metric": "images/sec (SVI step)", "value": main_leg["value"], "unit": "images/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_leg["ms_per_step"],
-            "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
-            "dtype": main_leg["dtype"], "data": "synthetic",
-            "config": {"workload": "%s %s, batch %d per GPU (global %d), %s, SVI step = ELBO+grads+%sAdam"
-                                   % (name, cfg["desc"], B, B * world, main_leg["arith"], "allreduce+" if world > 1 else ""),
-                       "parallelism": "dp%d" % world, "path": main_leg["path"], "baseline_config": name},
+        out = headline(args, name, cfg, main_leg, world, B)
+        del out["elbo"], out["timing"]
+        out.update({
             "repeats": len(main_leg["regions_s"]), "ms_per_step_all": main_leg["ms_per_step_all"],
             "regions_discarded": main_leg["regions_discarded"], "ms_per_step_warming": main_leg["ms_per_step_warming"],
             "timing": {"preroll_steps": main_leg["preroll_steps"],
@@ -753,7 +842,7 @@ def main():
             "step_algorithmic_tflops": main_leg.get("step_algorithmic_tflops"),
             "elbo": {k: main_leg[k] for k in ("loss_per_image_first_timed_step", "loss_per_image_last_step",
                                               "loss_per_image_step0")},
-        }
+        })
         for k in ("roofline_conv", "roofline_step", "allreduce_ms", "allreduce_ms_samples", "allreduce_exposed_ms", "collective"):
             if k in main_leg:
                 out[k] = main_leg[k]

@@ -5,6 +5,6 @@ args=${@:---steps 200 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseli
 export PV_LIB_PATH=$PWD/pyroved_amd/libpyroved_amd_exp.so
 for i in 1 2 3; do
   for v in $vals; do
-    env $name=$v python bench.py $args 2>&1 | tail -1 | cut -c1-140 | sed "s/^/$name=$v /"
+    env $name=$v python bench.py --full $args 2>&1 | tail -1 | cut -c1-140 | sed "s/^/$name=$v /"
   done
 done

@@ -11,13 +11,13 @@ PV_LIB_PATH=$V python -m pytest tests/test_gpu_parity.py -q -k "bf16_mode_steps 
 echo "== step time (bench.py C2 bf16, --steps 200), alternating"
 for i in 1 2 3; do
   for l in $R/pyroved_amd/libpyroved_amd.so $V; do
-    PV_LIB_PATH=$l python bench.py --steps 200 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | sed "s|^|$(basename $l) |" | cut -c1-190
+    PV_LIB_PATH=$l python bench.py --full --steps 200 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | sed "s|^|$(basename $l) |" | cut -c1-190
   done
 done
 echo "== LDS counters of the hosting launch"
 for l in $R/pyroved_amd/libpyroved_amd.so $V; do
   n=$(basename $l .so)
-  (cd /tmp && rm -rf /tmp/pmc_$n && PV_LIB_PATH=$l timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d /tmp/pmc_$n -o pmc -- python $R/bench.py --steps 6 --warmup 2 --repeats 1 --no-alt --no-cpu-baseline --no-configs --no-legs > /dev/null 2>&1)
+  (cd /tmp && rm -rf /tmp/pmc_$n && PV_LIB_PATH=$l timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d /tmp/pmc_$n -o pmc -- python $R/bench.py --full --steps 6 --warmup 2 --repeats 1 --no-alt --no-cpu-baseline --no-configs --no-legs > /dev/null 2>&1)
   f=$(find /tmp/pmc_$n -name "*counter_collection.csv" | head -1)
   python - "$f" "$n" <<'PY'
 import csv, sys, collections

@@ -6,7 +6,7 @@ args=${@:---steps 100 --warmup 5 --repeats 2 --no-alt --no-configs --no-legs --n
 export PV_LIB_PATH=$PWD/pyroved_amd/libpyroved_amd_exp.so TMPDIR=/tmp
 R=$PWD
 for v in $vals; do
-  (cd /tmp && rm -rf /tmp/ks_$v && env $name=$v timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o t -- python $R/bench.py $args > /tmp/ks_$v.log 2>&1)
+  (cd /tmp && rm -rf /tmp/ks_$v && env $name=$v timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o t -- python $R/bench.py --full $args > /tmp/ks_$v.log 2>&1)
   echo "== $name=$v   $(grep BENCH-SUMMARY /tmp/ks_$v.log | cut -c1-110)"
   python - /tmp/ks_$v/t_kernel_stats.csv <<'PY'
 import csv, sys

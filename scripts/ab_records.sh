@@ -4,9 +4,9 @@
 export PV_LIB_PATH=$PWD/pyroved_amd/libpyroved_amd_exp.so
 for i in 1 2 3; do
 for a in 0 1024; do
-PV_FD_ABLATE=$a python bench.py --steps 200 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/bf16 rowmajor_fp32=$a /"
-PV_FD_ABLATE=$a python bench.py --steps 100 --warmup 5 --fused 2 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/fp32class rowmajor_fp32=$a /"
+PV_FD_ABLATE=$a python bench.py --full --steps 200 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/bf16 rowmajor_fp32=$a /"
+PV_FD_ABLATE=$a python bench.py --full --steps 100 --warmup 5 --fused 2 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/fp32class rowmajor_fp32=$a /"
 done; done
 for a in 0 1024; do
-PV_FD_ABLATE=$a python bench.py --config C3 --steps 20 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/C3 fp32class rowmajor_fp32=$a /"
+PV_FD_ABLATE=$a python bench.py --full --config C3 --steps 20 --warmup 5 --no-alt --no-configs --no-legs --no-cpu-baseline 2>&1 | tail -1 | cut -c1-150 | sed "s/^/C3 fp32class rowmajor_fp32=$a /"
 done

@@ -5,7 +5,7 @@ for v in $1; do
   if [ $v = base ]; then L=""; else L="PV_LIB_PATH=pyroved_amd/variants/lib_$v.so"; fi
   for c in C5 C4; do
   echo -n "$v $c: "
-  env $L timeout 300 python bench.py --config $c --fused 2 --steps 40 --warmup 10 --repeats 3 --no-cpu-baseline --no-legs --no-alt --no-configs 2>/dev/null | python scripts/benchline.py
+  env $L timeout 300 python bench.py --full --config $c --fused 2 --steps 40 --warmup 10 --repeats 3 --no-cpu-baseline --no-legs --no-alt --no-configs 2>/dev/null | python scripts/benchline.py
   done
 done
 done

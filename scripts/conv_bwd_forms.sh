@@ -16,7 +16,7 @@ for form in "5 1" "4 1" "5 4" "4 4"; do
   python -m pytest tests/test_gpu_parity.py -q -k "(full_size_c4 and 2-) or (full_size_c5 and fp32-)" 2>&1 | tail -1 >> $out
   grep -E "^C[45]|layers.0.weight|layers.3.weight|layers.10.weight|worst" gpurun_out/grad_margin_masked.txt >> $out
   for c in C4 C5; do
-    python bench.py --config $c --steps 20 --warmup 5 --no-alt --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --config $c --steps 20 --warmup 5 --no-alt --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('$c ms_per_step', round(d['ms_per_step'], 4))" >> $out
   done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Kernel timeline of one SVI step (start offset, duration, gap to the previous kernel) from a rocprofv3 kernel trace.
 TAG=${1:-tl}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$TAG -o tl -- python $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline ${BENCH_ARGS} > $R/$OUT/run.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$TAG -o tl -- python $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline ${BENCH_ARGS} > $R/$OUT/run.log 2>&1)
 f=$(find /tmp/tl_$TAG -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY' | tee $OUT/timeline.txt
 import csv, sys

@@ -4,7 +4,7 @@
 #   bash scripts/gpu_timeline_cfg.sh <tag> <C4|C5> [extra bench args]
 TAG=${1:-tlc}; CFG=${2:-C5}; shift; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tlc_$TAG -o tl -- python $R/bench.py --config $CFG --steps 8 --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $R/$OUT/run.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tlc_$TAG -o tl -- python $R/bench.py --full --config $CFG --steps 8 --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $R/$OUT/run.log 2>&1)
 f=$(find /tmp/tlc_$TAG -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY' | tee $OUT/timeline.txt
 import csv, sys

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Step period by position in a timed region (bench.py --steps K): is a short region slower per step, and where?
 K=${1:-20}; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
-cd /tmp && rm -rf /tmp/rp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/rp -o rp -- python $R/bench.py --steps $K --warmup 5 --repeats 3 --no-cpu-baseline --no-configs --no-legs --no-alt > /dev/null 2>&1
+cd /tmp && rm -rf /tmp/rp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/rp -o rp -- python $R/bench.py --full --steps $K --warmup 5 --repeats 3 --no-cpu-baseline --no-configs --no-legs --no-alt > /dev/null 2>&1
 f=$(find /tmp/rp -name "*kernel_trace.csv" | head -1)
 python - "$f" $K <<'PY'
 import csv, sys, statistics as st

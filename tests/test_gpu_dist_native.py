@@ -162,7 +162,7 @@ def test_bench_multirank_path_over_nccl_world1(gpu_device):
     max-over-ranks timing) at world size 1 — the only form a one-GPU box can run it in: the line must parse, say which
     collective ran (the library's), carry its event-timed duration and the single-GPU ELBO."""
     env = dict(os.environ, PV_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29563")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--repeats", "2", "--no-configs",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--repeats", "2", "--no-configs",
            "--no-legs", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-3000:]

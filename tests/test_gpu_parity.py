@@ -1699,7 +1699,7 @@ def test_bench_multirank_path_on_one_gpu(gpu_device, mode):
     env = dict(os.environ, PV_BENCH_BACKEND="gloo", PV_BENCH_ONE_DEVICE="1")
     cmd = [_sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29531" if mode == "weak" else "29533", os.path.join(root, "bench.py"), "--gpus", "2",
-           "--steps", "6", "--warmup", "2", "--repeats", "2"] + (["--strong"] if mode == "strong" else [])
+           "--steps", "6", "--warmup", "2", "--full", "--repeats", "2"] + (["--strong"] if mode == "strong" else [])
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1722,6 +1722,38 @@ def test_bench_multirank_path_on_one_gpu(gpu_device, mode):
         # ELBO (544.5358 per image from the fp32 oracle; bench.py's own rel_err_step0 line at N = 1)
         assert "global 256" in d["config"]["workload"]
         assert abs(d["fp32_class"]["loss_per_image_step0"] - 544.5358) < 0.02
+
+
+def test_bench_plain_run_line_and_outputs(gpu_device, tmp_path):
+    """A plain bench.py run: one JSON line with the contract fields, exactly --steps timed steps, and --dump-outputs writes
+    the last step's state and losses; the same arguments give the same losses on a second run."""
+    import json
+    import subprocess
+    import sys as _sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        cmd = [_sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+               "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["dtype"] == "bf16"
+        assert "roofline" not in line and "cpu_baseline" not in line and "configs" not in line
+        arrays = {p.name[:-4]: np.load(p) for p in d.glob("*.npy")}
+        assert arrays["loss_per_step"].shape == (5,) and arrays["loss_terms"].shape == (4,)
+        assert arrays["loss_per_step"][-1] == arrays["loss_terms"][0]
+        np.testing.assert_allclose(arrays["loss_per_step"][0] / 256, line["elbo"]["loss_per_image_first_timed_step"], rtol=1e-6)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert any(n.startswith("param.decoder.") for n in arrays) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        runs.append(arrays)
+    assert sorted(runs[0]) == sorted(runs[1])
+    np.testing.assert_allclose(runs[1]["loss_per_step"], runs[0]["loss_per_step"], rtol=1e-5)
 
 
 @pytest.mark.parametrize("kind", ["ivae", "ssivae"])
