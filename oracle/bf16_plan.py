@@ -1,0 +1,241 @@
+"""
+oracle/bf16_plan.py — a rounding plan for the oracle's spatial decoder: the bf16 throughput step restated operand for operand.
+
+TEST INFRASTRUCTURE, NOT PRODUCT (like the rest of oracle/).  `Config.bf16_plan = Bf16Plan(...)` makes `sdecoder_forward`
+compute the decoder's hidden layers with the operand values the HIP kernel feeds its matrix cores, bit for bit; only the
+accumulation stays exact (the dtype of the caller, float64 in the tests).  With the field unset (the default) the oracle's
+code path is unchanged.  The rounding points, from the kernel sources (pyroved_amd/csrc/):
+
+8-wave kernel, `pv_sdec_w8_kernel` (kernel="w8"; pv_sdec_fused_w8.hip):
+  * weight images hold bf16(C W), C = 2 log2(e), the product C W formed in fp32 (pv_fb_layout.h:94 `s1 = p.scale`,
+    pv_sdec_fused_bf16.hip:1826 `p.scale`); the biases enter as fp32 C b (WO_VEC, pv_sdec_fused_w8.hip:48, filled at :802-803).
+    The MFMAs deliver C * pre-activation: emulated as h_b @ bf16(C W)^T + fp32(C b), never as bf16(W).
+  * the coordinate layer is one MFMA per block on (hi, lo) bf16 pairs (fb_split, pv_fb_layout.h:14): C Wc, C bc and x' split,
+    three products wh xh + wh xl + wl xh per coordinate (lo x lo dropped) plus bh + bl, on top of the fp32 C hz
+    (A table :805-819, B operand :998-1005, the MFMA :1023).  Emulated as written.
+  * tanh of the scaled pre-activation is 1 - 2 rcp(exp2(C x) + 1) in fp32 (w8_tanhc :81, w8_tanh8 :246); restated here
+    in fp32 (exact division and exp2 in place of the 1-ulp hardware approximations).  Its cancellation near 0 is kept.
+  * h0, h1 -> bf16 (w8_cvt8 :295 at :1026 and :1034; the tail's w8_cvt4 :461); h2 stays fp32 for the logit (:1039-1044)
+    and goes to bf16 for the d(wo) column sum (pA at :1047, consumed at :1102; the tail's h2b at :1315).
+  * dpre2 = (wo - wo h2^2) dlda in fp32 (:1048-1049, :1105), -> bf16 (w8_cvt8 at :1106; tail :1301).
+  * the tanh derivatives use the bf16 h: d (h_b^2 - 1) (w8_mul_dtanh :279, w8_mul_dtanh4 :468); after layer 2 the kernel
+    carries -C dpre1, rounded to bf16 (:1123 / tail :1330), after layer 1 C^2 dpre0, rounded to bf16 (:1128 / tail :1336).
+    dW1 / db1 are un-scaled by -1/C where the record is written (:1489-1490, :1500), dpre0 by 1/C^2 where it leaves the
+    kernel (dL/d(hz) :896, the row-local coordinate backward :1143, dWc / dbc).
+  * records: each workgroup's partial dW1 / dW2 is rounded to bf16 once, round to nearest even (`pack2` :1464-1467, of the
+    fp32 value accW1 * -1/C and accW2), and pv_latent_bwd_reduce sums the partials in fp32 in a fixed order.  Partition:
+    units of 16 rows, workgroup g of G = pv_sdec_fused_grid(units) = min(units, CUs) (pv_sdec_fused.hip:504) owns units
+    [g units / G, (g + 1) units / G) (:905), the last of which is a column-parallel tail when the range is 1 mod 8 (:920).
+  * NOT emulated (fp32-class): the row-local coordinate backward (table of Wc hi / lo, :1141), the column sums of dlda h2 /
+    dpre0 / dpre0 x' against hi / lo B operands (:1102, :1168); the logit, the likelihood and dL/dlogit (fp32
+    transcendentals); the per-workgroup fp32 vectors (db1, db2, d(wo), dbo, dWc, dbc); the guide (encoder, fc_latent) folded
+    into the prologue or run as its own launch — fp32 in another summation order.
+  * model.decode() does NOT run this kernel: pv_ivae_decode launches the split-precision (fp32-class) build whatever the
+    training precision (pv_plan.hip:1217-1218, x3 = true) — the plain oracle is its reference.
+
+4-wave kernel, plain-bf16 build `pv_sdec_fused_bf16_kernel<., ., FB_P_BF16>` (kernel="w4"; fused == 3 on small problems,
+pv_sdec_fused_bf16.hip):
+  * unscaled images bf16(W) (scale 0 -> 1, pv_fb_layout.h:94), fp32 biases; h0 in fp32 from an fp32 coordinate layer
+    (:1032-1043); tanh = fb_tanh8 (:362) of the fp32 pre-activation times C.
+  * h0, h1 -> bf16 for the forward and wgrad operands (fb_presplit :1044, :1057), but the tanh derivatives use the FP32 h
+    (fb_mul_dtanh :384 with tB / h0 at :1168, :1179); d(wo) from the fp32 h2 (KEEP_WO, :1120).
+  * dpre2 and dpre1 -> bf16 (fb_presplit :1149, :1169); dpre0 stays fp32 (:1179 onwards, coordinate backward in fp32).
+  * records in fp32 (PV_REC_LANE_F32): no record rounding; the reduce's order is fp32 summation order only.
+
+Rounding to bf16 is always from the fp32 value (`x.float().bfloat16()`), the kernel's single rounding of an fp32 register.
+"""
+import math
+from dataclasses import dataclass, field
+from typing import List, Optional, Tuple
+
+import torch
+
+C_F32 = float(torch.tensor(2.0 * math.log2(math.e), dtype=torch.float32))      # W8_C as the fp32 the kernel holds
+UNIT = 16                                                                      # rows per unit (FD_UNIT)
+W8_WAVES = 8
+
+
+def bf16(x: torch.Tensor) -> torch.Tensor:
+    """Round to bf16 (nearest even) from the fp32 value, returned in x's dtype."""
+    return x.float().bfloat16().to(x.dtype)
+
+
+def f32(x: torch.Tensor) -> torch.Tensor:
+    """Round to fp32, returned in x's dtype."""
+    return x.float().to(x.dtype)
+
+
+def split(x: torch.Tensor):
+    """fb_split (pv_fb_layout.h:14): x -> (bf16(x), bf16(x - bf16(x))) of the fp32 value."""
+    hi = bf16(x)
+    return hi, bf16(f32(f32(x) - hi))
+
+
+def tanh_c(cx: torch.Tensor) -> torch.Tensor:
+    """The kernels' tanh of the scaled pre-activation cx = C x: 1 - 2 / (exp2(cx) + 1), every step in fp32."""
+    e = torch.exp2(cx.float())
+    return (1.0 - 2.0 * (1.0 / (e + 1.0))).to(cx.dtype)
+
+
+def partition(units: int, grid: int) -> List[Tuple[int, int, bool]]:
+    """The 8-wave kernel's work split: (u_lo, u_hi, has_tail) per workgroup (pv_sdec_fused_w8.hip:905, :920)."""
+    out = []
+    for g in range(grid):
+        lo, hi = g * units // grid, (g + 1) * units // grid
+        out.append((lo, hi, (hi - lo) % W8_WAVES == 1))
+    return out
+
+
+def grid_of(units: int, cus: int) -> int:
+    """pv_sdec_fused_grid (pv_sdec_fused.hip:504)."""
+    return max(1, min(units, cus))
+
+
+@dataclass
+class Bf16Plan:
+    """Where the bf16 throughput step rounds (module docstring).
+    kernel: "w8" (pv_sdec_w8_kernel, images of C W, packed bf16 records) or "w4" (the 4-wave FB_P_BF16 build).
+    cus: the device's compute units (the grid of the record partition).
+    round_records: emulate the bf16 rounding of each workgroup's partial dW1 / dW2 (w8 only).
+    exact: every rounding off and C exact (the restated backward must then equal autograd of the plain decoder).
+    After a backward, `partials` holds the per-workgroup partials {key: (G, 128, 128) tensor}, un-scaled, unrounded."""
+    kernel: str = "w8"
+    cus: int = 256
+    round_records: bool = True
+    exact: bool = False
+    partials: dict = field(default_factory=dict, repr=False)
+
+    def __post_init__(self):
+        assert self.kernel in ("w8", "w4"), self.kernel
+
+    @property
+    def scale(self) -> float:
+        return (2.0 * math.log2(math.e) if self.exact else C_F32) if self.kernel == "w8" else 1.0
+
+    @property
+    def c(self) -> float:
+        return 2.0 * math.log2(math.e) if self.exact else C_F32
+
+    def ops(self):
+        """(round to bf16, round to fp32, tanh of C x) — identities / exact tanh when `exact`."""
+        if self.exact:
+            return (lambda t: t), (lambda t: t), (lambda cx: torch.tanh(cx / self.c))
+        return bf16, f32, tanh_c
+
+    def sdecoder_forward(self, p, cfg, x_coord, z):
+        import torch.nn.functional as F
+        assert cfg.activation == "tanh" and cfg.n_hidden_d == 2, "the fused decoder kernels: two tanh layers"
+        b, n = x_coord.shape[:2]
+        hz = F.linear(z, p["decoder.coord_latent.fc_latent.weight"])         # the guide's side: fp32, not emulated
+        a = _Decoder.apply(self, x_coord, hz,
+                           p["decoder.coord_latent.fc_coord.weight"], p["decoder.coord_latent.fc_coord.bias"],
+                           p["decoder.fc_layers.0.weight"], p["decoder.fc_layers.0.bias"],
+                           p["decoder.fc_layers.2.weight"], p["decoder.fc_layers.2.bias"],
+                           p["decoder.out.weight"], p["decoder.out.bias"])
+        out = a.reshape(b * n, 1)
+        if cfg.sigmoid_d:
+            out = torch.sigmoid(out)
+        return out.view(-1, *cfg.data_dim)
+
+    # ---- the pieces the tests look at ----
+    def record_sum(self, part: torch.Tensor, key: str) -> torch.Tensor:
+        """Sum of per-workgroup partials (G, ...) as the reduce forms it: rounded records (w8, round_records) or exact."""
+        if self.kernel == "w8" and self.round_records and not self.exact:
+            if key == "W1":
+                # the kernel holds -C dW1 in fp32 and writes bf16(acc * -1/C): restate the fp32 accumulator, then that product
+                acc = f32(part * -self.scale)
+                part = bf16(f32(acc * f32(torch.tensor(-1.0 / self.scale, dtype=torch.float64)).to(acc.dtype)))
+            else:
+                part = bf16(part)
+        return part.sum(0)
+
+
+class _Decoder(torch.autograd.Function):
+    """The fused decoder's logit a (B N,) from x' (B, N, cd), hz = fc_latent(z) (B, 128) and the decoder parameters, with the
+    kernel's operand roundings in forward and backward (module docstring).  Exact (float64) accumulation."""
+
+    @staticmethod
+    def forward(ctx, plan, xc, hz, Wc, bc, W1, b1, W2, b2, wo, bo):
+        dt = torch.float64
+        b, n, cd = xc.shape
+        assert (b * n) % UNIT == 0, "the fused decoder kernels run whole 16-row units only"
+        s, C = plan.scale, plan.c
+        bf16, f32, tanh_c = plan.ops()
+        xr = xc.reshape(b * n, cd).to(dt)
+        pre0 = xr @ Wc.to(dt).t() + bc.to(dt) + hz.to(dt).repeat_interleave(n, 0)
+        if plan.kernel == "w8" and not plan.exact:
+            # the coordinate layer on the matrix cores: C Wc, C bc and x' as (hi, lo) bf16 pairs, three products per term
+            # (wh xh + wh xl + wl xh: lo x lo dropped), the fp32 C hz as the accumulator's initial value
+            wh, wl = split(f32(Wc.to(dt) * s))
+            xh, xl = split(f32(xr))
+            bh, bl = split(f32(bc.to(dt) * s))
+            cpre0 = xh @ wh.t() + xl @ wh.t() + xh @ wl.t() + bh + bl + f32(hz.to(dt) * s).repeat_interleave(n, 0)
+            h0 = tanh_c(f32(cpre0))
+        elif plan.kernel == "w8":
+            h0 = tanh_c(f32(pre0 * s))
+        else:
+            h0 = tanh_c(f32(f32(pre0) * C))                  # fb_tanh8: fp32 pre0, times C in fp32
+        h0b = bf16(h0)
+        I1 = bf16(f32(W1.to(dt) * s))                            # weight images: bf16(fp32(s W))
+        I2 = bf16(f32(W2.to(dt) * s))
+        cb1, cb2 = f32(b1.to(dt) * s), f32(b2.to(dt) * s)
+        t1 = f32(h0b @ I1.t() + cb1)                             # s pre1 (fp32 accumulator)
+        h1 = tanh_c(t1 if plan.kernel == "w8" else f32(t1 * C))
+        h1b = bf16(h1)
+        t2 = f32(h1b @ I2.t() + cb2)
+        h2 = tanh_c(t2 if plan.kernel == "w8" else f32(t2 * C))
+        a = h2 @ wo.to(dt).reshape(-1) + bo.to(dt).reshape(())
+        ctx.plan, ctx.shape = plan, (b, n, cd)
+        ctx.save_for_backward(xr, Wc, W1, W2, wo, h0, h0b, h1, h1b, h2, I1, I2)
+        ctx.dtypes = [t.dtype for t in (xc, hz, Wc, bc, W1, b1, W2, b2, wo, bo)]
+        return a.to(xc.dtype)
+
+    @staticmethod
+    def backward(ctx, ga):
+        plan = ctx.plan
+        b, n, cd = ctx.shape
+        xr, Wc, W1, W2, wo, h0, h0b, h1, h1b, h2, I1, I2 = ctx.saved_tensors
+        dt = torch.float64
+        s = plan.scale
+        bf16, f32, _ = plan.ops()
+        w8 = plan.kernel == "w8"
+        dlda = f32(ga.to(dt).reshape(-1))                         # fp32 dL/dlogit (row weight folded in)
+        wov = wo.to(dt).reshape(-1)
+        dbo = dlda.sum().reshape(1)
+        dwo = (dlda @ (bf16(h2) if w8 else h2)).reshape(1, -1)
+        g2 = f32(wov - wov * f32(h2 * h2))                       # wo (1 - h2^2) in fp32
+        P2 = bf16(f32(g2 * dlda[:, None]))                       # dpre2 -> bf16
+        m1 = f32(P2 @ I2)                                        # s dL/dh1
+        if w8:
+            P1 = bf16(f32(m1 * f32(h1b * h1b - 1.0)))             # -C dpre1 (w8_mul_dtanh: the bf16 h)
+            m0 = f32(P1 @ I1)                                    # -C^2 dL/dh0
+            P0 = bf16(f32(m0 * f32(h0b * h0b - 1.0)))             # C^2 dpre0
+            dpre0 = P0 / (s * s)
+            u1 = -1.0 / s                                        # what turns sum P1 h0 into dW1
+        else:
+            P1 = bf16(f32(m1 * f32(1.0 - h1 * h1)))              # dpre1 (fb_mul_dtanh: the fp32 h)
+            m0 = f32(P1 @ I1)
+            dpre0 = f32(m0 * f32(1.0 - h0 * h0))                  # fp32, not rounded
+            u1 = 1.0
+        # weight gradients of the hidden layers: per-workgroup partials, then the reduce
+        units = (b * n) // UNIT
+        G = grid_of(units, plan.cus)
+        parts = partition(units, G) if w8 else [(g * units // G, (g + 1) * units // G, False) for g in range(G)]
+        pw1 = torch.empty(G, *W1.shape, dtype=dt)
+        pw2 = torch.empty(G, *W2.shape, dtype=dt)
+        for g, (lo, hi, _) in enumerate(parts):
+            r0, r1 = lo * UNIT, hi * UNIT
+            pw1[g] = (P1[r0:r1].t() @ h0b[r0:r1]) * u1
+            pw2[g] = P2[r0:r1].t() @ h1b[r0:r1]
+        plan.partials = {"W1": pw1, "W2": pw2}
+        dW1 = plan.record_sum(pw1, "W1")
+        dW2 = plan.record_sum(pw2, "W2")
+        db1 = P1.sum(0) * u1
+        db2 = P2.sum(0)
+        # coordinate layer (fp32-class in both kernels)
+        dhz = dpre0.reshape(b, n, -1).sum(1)
+        dWc = dpre0.t() @ xr
+        dbc = dpre0.sum(0)
+        dxc = (dpre0 @ Wc.to(dt)).reshape(b, n, cd)
+        outs = (dxc, dhz, dWc, dbc, dW1, db1, dW2, db2, dwo, dbo)
+        return (None,) + tuple(o.to(t) for o, t in zip(outs, ctx.dtypes))

@@ -68,6 +68,7 @@ class Config:
     bufs: Optional[dict] = None    # batch-norm buffers of the conv encoder (set by SVIOracle), always training mode: the
                                    # reference's iVAE never calls eval() (models/base.py:121-143)
     conv_decisions: Optional[object] = None     # test infrastructure (ConvDecisions): record / apply the conv encoder's sign and winner decisions
+    bf16_plan: Optional[object] = None          # test infrastructure (oracle/bf16_plan.Bf16Plan): the decoder with the bf16 kernels' roundings
     custom_encoder: Optional[object] = None     # iVAE.set_encoder(user module): a callable x -> (z_loc, z_scale) in torch
     custom_decoder: Optional[object] = None     # iVAE.set_decoder(user module): (x_coord_prime, z) -> loc, or z -> loc (vanilla)
     custom_label_net: Optional[object] = None   # ssiVAE.set_classifier / ss_reg_iVAE.set_regressor(user module): x -> probabilities / means
@@ -201,6 +202,8 @@ def jencoder_forward(p: Params, cfg: Config, x):
 
 def sdecoder_forward(p: Params, cfg: Config, x_coord, z):
     """sDecoderNet.forward + coord_latent.forward (nets/fc.py:189-199, 220-237)."""
+    if cfg.bf16_plan is not None:
+        return cfg.bf16_plan.sdecoder_forward(p, cfg, x_coord, z)
     act = _ACT[cfg.activation]
     b, n = x_coord.shape[:2]
     h_x = F.linear(x_coord.reshape(b * n, -1), p["decoder.coord_latent.fc_coord.weight"],

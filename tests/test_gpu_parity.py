@@ -1512,7 +1512,9 @@ BF16_CASES = ["ivae_28x28_rt_b256", "ivae_28x28_r_b128", "ivae_28x28_r_b32_blobs
 @pytest.mark.parametrize("name", BF16_CASES)
 def test_bf16_mode_steps_vs_golden_and_oracle(gpu_device, name):
     """The mixed-precision mode (fused=3 / SVItrainer(precision="bf16")): the two hidden-layer contractions of the
-    spatial decoder take bf16 operands (fp32 accumulate), everything else is fp32.  Bars: the ELBO to BASELINE.json's
+    spatial decoder take bf16 operands (fp32 accumulate); the 8-wave kernel also rounds h2 for d(wo), carries the tanh
+    derivative from the bf16 activations and writes its per-workgroup dW1 / dW2 records as bf16 (oracle/bf16_plan.py lists
+    every rounding point; tests/test_gpu_bf16_emulated.py holds the mode to a reference that rounds there too).  Bars: the ELBO to BASELINE.json's
     1e-4 at the benchmark sizes (batch >= 128 at 28x28; rounding errors do not average out on a handful of 8x8
     samples: 5e-4 there), the encoder's outputs as in fp32, every gradient tensor to 3e-2 relative L2 of the fp32
     oracle's (measured: 2e-4 .. 1.5e-2) from identical parameters at every step."""
