@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PV_ABI_VERSION 16
+#define PV_ABI_VERSION 17
 
 /* error codes (negative; positive values are hipError_t) */
 #define PV_EINVAL   (-1)   /* bad argument / unsupported configuration */
@@ -43,6 +43,15 @@ enum pv_act {
 
 /* decoder likelihoods: utils/prob.py:25-29 (get_sampler) */
 enum pv_lik { PV_LIK_BERNOULLI = 0, PV_LIK_GAUSSIAN = 1, PV_LIK_CBERNOULLI = 2 /* ContinuousBernoulli(probs) */ };
+
+/* (v17) the form of the KL term between the guide q(z|x) = N(mu, sigma) and the N(0, 1) prior (pv_ivae_plan.kl_mode,
+ * pv_ved_plan.kl_mode).  z = mu + sigma * eps is drawn once per sample for the likelihood either way.
+ *   PV_KL_SAMPLED   log q(z|x) - log p(z) at the drawn z: Pyro's Trace_ELBO with one particle (trainers/svi.py:64-92, the
+ *                   reference trainer's default `loss`);
+ *   PV_KL_ANALYTIC  the closed form sum_i 0.5 (sigma_i^2 + mu_i^2 - 1) - log sigma_i: Pyro's TraceMeanField_ELBO
+ *                   (kl_divergence(guide, model) at the `latent` site, scaled by poutine.scale(beta)) — the same
+ *                   expectation, lower gradient variance.  Not with discrete_dim > 0. */
+enum pv_kl_mode { PV_KL_SAMPLED = 0, PV_KL_ANALYTIC = 1 };
 
 #define PV_MAX_LAYERS 8
 
@@ -144,7 +153,10 @@ typedef struct pv_ivae_plan {
   const float* grid;      /* (N, coord_dim) generate_grid(data_dim) (coord.py:21-44)      */
   void*        ws;        /* workspace, >= pv_ivae_workspace_bytes(plan) bytes            */
   int64_t      ws_bytes;
-  float*       scalars;   /* out, 4 floats: loss, sum log p(x|z), beta*sum log p(z), beta*sum log q(z|x) */
+  float*       scalars;   /* out, 4 floats: loss, sum log p(x|z), beta*sum log p(z), beta*sum log q(z|x); loss = -([1] + [2] - [3]).
+                             kl_mode == PV_KL_ANALYTIC: [2], [3] hold those terms' expectations under q,
+                             beta*sum(-(mu^2 + sigma^2)/2 - log sqrt(2 pi)) and beta*sum(-1/2 - log sigma - log sqrt(2 pi)),
+                             so that [3] - [2] = beta * KL and the relation above holds unchanged */
   float*       z_loc;     /* out (B, z_dim), may be NULL                                  */
   float*       z_scale;   /* out (B, z_dim), may be NULL                                  */
   float*       loc;       /* out (B, N) decoder output, may be NULL ((K*B, N) for jiVAE)  */
@@ -215,7 +227,11 @@ typedef struct pv_ivae_plan {
    *   (pv_sdec_fused_bf16.hip); forward-only launches ignore 21 / 28.  Further values name dropped variants that only
    *   the experiments build of the library contains (csrc/Makefile `experiments`); elsewhere they are PV_EINVAL. ---- */
   int32_t dec_kernel;
-  int32_t reserved0;
+  /* ---- (v17) enum pv_kl_mode (the former reserved0: a zeroed field is the sampled form, as before).  Values outside the enum and
+   *   PV_KL_ANALYTIC with discrete_dim > 0 (the enumerated / sampled-class jiVAE objectives have no mean-field form) are PV_EINVAL
+   *   from the workspace queries and from every step / loss call.  The analytic form keeps the guide out of the throughput decoder
+   *   launch (pv_ivae_guide_folds == 0: that kernel has no register to spare for a second form). ---- */
+  int32_t kl_mode;
 } pv_ivae_plan;
 
 /* Library / ABI version (PV_ABI_VERSION). */
@@ -295,7 +311,8 @@ int pv_ivae_uses_fused(const pv_ivae_plan* plan);
 int pv_ivae_guide_folds(const pv_ivae_plan* plan);
 
 /* Trace_ELBO.loss_and_grads for iVAE.guide + iVAE.model (models/ivae.py:165-221,
- * pyro's Trace_ELBO with one particle): writes plan->scalars and, when
+ * pyro's Trace_ELBO with one particle; plan->kl_mode == PV_KL_ANALYTIC: TraceMeanField_ELBO,
+ *   loss = -sum_b log p(x_b|z_b) + beta sum_b sum_i KL_bi): writes plan->scalars and, when
  * want_grads != 0, d(loss)/d(params) into plan->grads (every entry overwritten).
  * Replaces: trainers/svi.py:107 `self.svi.step(x)` up to (not including) the
  * optimizer.  */
@@ -430,6 +447,7 @@ typedef struct pv_ved_plan {
                                       gradients to ~1e-2, the ELBO to 1e-4 (SVItrainer(precision="bf16")).
                                       (pv_ivae_plan's convolutional encoder: fused == 3 selects 3, conv_wide 2)             */
   int32_t flags;                   /* (v14) PV_PLAN_NO_SIDE_STREAM                                                          */
+  int32_t kl_mode;                 /* (v17) enum pv_kl_mode, as in pv_ivae_plan (other values: PV_EINVAL)                   */
   float*       params;
   float*       grads;
   float*       adam_m;
@@ -452,7 +470,8 @@ typedef struct pv_ved_plan {
 /* Workspace bytes for pv_ved_* calls with this plan; < 0: unsupported plan. */
 int64_t pv_ved_workspace_bytes(const pv_ved_plan* plan);
 
-/* Trace_ELBO.loss_and_grads for VED.guide + VED.model (models/ved.py:122-163): plan->scalars and, when
+/* Trace_ELBO.loss_and_grads (plan->kl_mode == PV_KL_ANALYTIC: TraceMeanField_ELBO's) for VED.guide + VED.model
+ * (models/ved.py:122-163): plan->scalars and, when
  * want_grads != 0, plan->grads (every entry overwritten).  Replaces trainers/svi.py:109 `self.svi.step(x, y)`
  * up to the optimizer (pv_adam_step). */
 int pv_ved_loss_and_grads(const pv_ved_plan* plan, int want_grads, void* stream);

@@ -13,7 +13,7 @@ import threading
 
 import torch  # noqa: F401  (must be imported first: it loads the HIP runtime libamdhip64.so.7 the library binds to)
 
-PV_ABI_VERSION = 16
+PV_ABI_VERSION = 17
 # pv_ivae_plan.flags / pv_ved_plan.flags / pv_convnet_plan.flags
 PV_PLAN_ENC_TWO_LAUNCH, PV_PLAN_NO_SIDE_STREAM, PV_PLAN_ENC_NO_WAIT, PV_PLAN_NO_DEC1D, PV_PLAN_NO_ENC_FOLD = 1, 2, 4, 8, 16
 PV_PLAN_CONV_X3 = 64
@@ -23,6 +23,8 @@ PV_MAX_LAYERS = 8
 # enum pv_act / pv_lik (include/pyroved_amd.h)
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2, "lrelu": 3, "softplus": 4, "gelu": 5, "sigmoid": 6}
 LIK = {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2}
+# enum pv_kl_mode: the sampled log q - log p of Trace_ELBO / the closed-form KL of TraceMeanField_ELBO
+KL = {"sampled": 0, "analytic": 1}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PV_LIB_PATH: the experiments build (csrc/Makefile `experiments`: libpyroved_amd_exp.so) or a profiling build; the shipped
@@ -77,7 +79,7 @@ class pv_ivae_plan(C.Structure):
         ("ev_start", C.c_void_p), ("ev_stop", C.c_void_p),
         ("class_onehot", C.c_void_p),
         ("conv_ev_start", C.c_void_p), ("conv_ev_stop", C.c_void_p), ("conv_ev_flops", C.c_void_p),
-        ("dec_kernel", C.c_int32), ("reserved0", C.c_int32),
+        ("dec_kernel", C.c_int32), ("kl_mode", C.c_int32),
     ]
 
 
@@ -91,7 +93,7 @@ class pv_ved_plan(C.Structure):
         ("enc", pv_op * PV_MAX_OPS), ("dec", pv_op * PV_MAX_OPS),
         ("head", pv_layer), ("l2f", pv_layer),
         ("dec_c0", C.c_int32), ("dec_dim0", C.c_int32 * 2), ("bn_eval", C.c_int32),
-        ("conv_bf16", C.c_int32), ("flags", C.c_int32),
+        ("conv_bf16", C.c_int32), ("flags", C.c_int32), ("kl_mode", C.c_int32),
         ("params", C.c_void_p), ("grads", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p),
         ("n_params", C.c_int64),
         ("x", C.c_void_p), ("y", C.c_void_p), ("eps", C.c_void_p),

@@ -117,6 +117,17 @@ __device__ __forceinline__ float pv_act_grad2(float y, float pre, int act) {
   return act == PV_ACT_TANH ? 1.0f - y * y : act == PV_ACT_SIGMOID ? y * (1.0f - y) : lin;
 }
 
+// ---- the KL term of the guide's Normal against the N(0, 1) prior (pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode) ----
+// The summands of scalars[2] (lp) and scalars[3] (lq) for one latent coordinate, before beta.
+//   PV_KL_SAMPLED   log p(z), log q(z|x) at the drawn z = mu + sig eps (torch Normal.log_prob; Pyro's Trace_ELBO) — the forward
+//                   kernels keep their own literal expressions for this form and call this for the other one only;
+//   PV_KL_ANALYTIC  their expectations under q: E log p = -(mu^2 + sig^2)/2 - log sqrt(2 pi), E log q = -1/2 - log sig - log sqrt(2 pi),
+//                   so that lq - lp = KL(N(mu, sig) || N(0, 1)) (torch.distributions.kl_divergence; Pyro's TraceMeanField_ELBO).
+__device__ __forceinline__ void pv_kl_analytic_terms(float mu, float sig, float& lq, float& lp) {
+  lq = -0.5f - logf(sig) - 0.91893853320467274178f;
+  lp = -(mu * mu + sig * sig) / 2.0f - 0.91893853320467274178f;
+}
+
 // torch.distributions.ContinuousBernoulli(probs = sigmoid(a)).log_prob(x) (utils/prob.py:27) and d(-log_prob)/da.
 //   probs -> clamp_probs; logits = log(p) - log1p(-p); log_prob = -BCEWithLogits(logits, x) + log C(p), with
 //   log C(p) = log|log1p(-p) - log p| - log|1 - 2p| outside (0.499, 0.501] and its Taylor expansion

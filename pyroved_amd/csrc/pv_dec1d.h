@@ -24,7 +24,8 @@ struct PvD1L2f { const float* z; const float* wt; const float* bias; float* dz; 
 // and written to head_out (B, ldh)
 struct PvD1Head { const float* head; const float* eps; float* z; float* z_scale; float* z_loc_out; float* z_scale_out; float* kl_part;
                   float* dhead; int ldh; float beta;
-                  const float* part = nullptr; const float* bias = nullptr; float* head_out = nullptr; int nseg = 0; };
+                  const float* part = nullptr; const float* bias = nullptr; float* head_out = nullptr; int nseg = 0;
+                  int kl_mode = PV_KL_SAMPLED; };
 inline bool pv_dec1d_l2f_ok(int zd) { return zd >= 1 && zd <= 8; }
 // the observation likelihood of the stack's output (fc.py:143-152 through pv_lik_one; one output channel) in the forward launch:
 // y (B, per) the target, loc / dlda (B, per) optional, llb[b] = the sample's log-likelihood

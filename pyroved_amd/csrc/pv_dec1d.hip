@@ -54,7 +54,7 @@ struct D1Args {
   int zd;
   // the head in the same launches (h_head != null): forward z from [mu | softplus input] and eps, backward dhead
   const float* h_head; const float* h_eps; float* h_z; float* h_zs; float* h_zlo; float* h_zso; float* h_kl; float* h_dhead;
-  int h_ldh; float h_beta;
+  int h_ldh; float h_beta; int h_kl_mode;
   const float* h_part; const float* h_bias; float* h_hout; int h_nseg;     // forward: head from its partial sums (pv_convhead_fwd_partials)
   // forward: the observation likelihood of the last step's result (y != null)
   const float* y; float* loc; float* dlda; float* llb;
@@ -357,8 +357,12 @@ __global__ __launch_bounds__(D1_THREADS) void pv_dec1d_kernel(D1Args A) {
             const float sig = pv_softplus(sp), ep = A.h_eps[(int64_t)b * A.zd + k];
             const float zz = mu + sig * ep, d = zz - mu;
             hz[k] = zz;
-            hz[8 + k] = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - 0.91893853320467274178f;      // torch Normal.log_prob
-            hz[16 + k] = -(zz * zz) / 2.0f - 0.91893853320467274178f;
+            if (A.h_kl_mode == PV_KL_SAMPLED) {
+              hz[8 + k] = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - 0.91893853320467274178f;      // torch Normal.log_prob
+              hz[16 + k] = -(zz * zz) / 2.0f - 0.91893853320467274178f;
+            } else {
+              pv_kl_analytic_terms(mu, sig, hz[8 + k], hz[16 + k]);
+            }
             A.h_z[(int64_t)b * A.zd + k] = zz; A.h_zs[(int64_t)b * A.zd + k] = sig;
             if (A.h_zlo) A.h_zlo[(int64_t)b * A.zd + k] = mu;
             if (A.h_zso) A.h_zso[(int64_t)b * A.zd + k] = sig;
@@ -502,8 +506,14 @@ __global__ __launch_bounds__(D1_THREADS) void pv_dec1d_kernel(D1Args A) {
           const int64_t e = (int64_t)b * A.zd + tid;
           const float zz = A.h_z[e], sig = A.h_zs[e], ep = A.h_eps[e];
           const float sp = A.h_head[(int64_t)b * A.h_ldh + A.zd + tid];
-          const float g = v + A.h_beta * zz;           // d(-ll - beta log p(z)) / dz
-          const float dsig = g * ep - A.h_beta / sig;  // + beta d(log q) / d(sigma) (total derivative)
+          float g, dsig;
+          if (A.h_kl_mode == PV_KL_SAMPLED) {
+            g = v + A.h_beta * zz;                     // d(-ll - beta log p(z)) / dz
+            dsig = g * ep - A.h_beta / sig;            // + beta d(log q) / d(sigma) (total derivative)
+          } else {                                     // analytic KL: beta mu, beta (sigma - 1 / sigma)
+            g = v + A.h_beta * A.h_head[(int64_t)b * A.h_ldh + tid];
+            dsig = v * ep + A.h_beta * (sig - 1.0f / sig);
+          }
           const float sgm = sp > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-sp));
           A.h_dhead[(int64_t)b * A.h_ldh + tid] = g;
           A.h_dhead[(int64_t)b * A.h_ldh + A.zd + tid] = dsig * sgm;
@@ -683,7 +693,7 @@ int pv_dec1d_fwd(const float* params, const pv_op* ops, int n, const float* wt, 
   if (hd) {
     if (!l2f || !hd->head || !hd->eps || !hd->z || !hd->z_scale || !hd->kl_part) return PV_EINVAL;
     A.h_head = hd->head; A.h_eps = hd->eps; A.h_z = hd->z; A.h_zs = hd->z_scale; A.h_zlo = hd->z_loc_out; A.h_zso = hd->z_scale_out;
-    A.h_kl = hd->kl_part; A.h_ldh = hd->ldh; A.h_beta = hd->beta;
+    A.h_kl = hd->kl_part; A.h_ldh = hd->ldh; A.h_beta = hd->beta; A.h_kl_mode = hd->kl_mode;
     if (hd->part) {
       if (!hd->head_out || hd->nseg < 1 || hd->ldh != 2 * l2f->zd) return PV_EINVAL;
       if ((int64_t)hd->nseg * hd->ldh > D1_THREADS) return PV_EINVAL;    // (one partial sum per thread of the staging pass)
@@ -709,7 +719,7 @@ int pv_dec1d_bwd(const pv_op* ops, int n, const float* wt, int B, int L0, int C0
   if (hd) {
     if (!l2f || !hd->head || !hd->eps || !hd->z || !hd->z_scale || !hd->dhead) return PV_EINVAL;
     A.h_head = hd->head; A.h_eps = hd->eps; A.h_z = hd->z; A.h_zs = hd->z_scale; A.h_dhead = hd->dhead; A.h_ldh = hd->ldh;
-    A.h_beta = hd->beta;
+    A.h_beta = hd->beta; A.h_kl_mode = hd->kl_mode;
   }
   if (l2f) {
     if (!pv_dec1d_l2f_ok(l2f->zd) || !l2f->wt || !l2f->dz || (A.op[A.n - 1].N & 3) != 0) return PV_EINVAL;

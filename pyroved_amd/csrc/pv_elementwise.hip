@@ -44,9 +44,16 @@ __global__ __launch_bounds__(256) void pv_head_fwd_kernel(PvHead h) {
     if (h.z_scale_out) h.z_scale_out[e] = sig;
     const float d = z - mu;
     const float wb = h.w ? h.w[b] : 1.0f;
-    // torch.distributions.Normal.log_prob
-    lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);
-    lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+    if (h.kl_mode == PV_KL_SAMPLED) {
+      // torch.distributions.Normal.log_prob
+      lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);
+      lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+    } else {
+      float aq, ap;
+      pv_kl_analytic_terms(mu, sig, aq, ap);
+      lq += wb * aq;
+      lp += wb * ap;
+    }
   }
   lp = block_sum_256(lp, sm);
   lq = block_sum_256(lq, sm);
@@ -138,8 +145,15 @@ __global__ __launch_bounds__(256) void pv_head_fwd_blocks_kernel(PvHead h) {
     if (h.z_scale_out) h.z_scale_out[e] = sig;
     const float d = z - mu;
     const float wb = h.w ? h.w[b] : 1.0f;
-    lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);
-    lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+    if (h.kl_mode == PV_KL_SAMPLED) {
+      lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);
+      lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+    } else {
+      float aq, ap;
+      pv_kl_analytic_terms(mu, sig, aq, ap);
+      lq += wb * aq;
+      lp += wb * ap;
+    }
   }
   lp = pv_block_sum(lp, sm);
   lq = pv_block_sum(lq, sm);
@@ -744,23 +758,30 @@ int pv_scale_rows(float* v, const float* w, int64_t rows, int64_t N, hipStream_t
 }
 
 __global__ void pv_row_elbo_kernel(const float* __restrict__ row_ll, const float* __restrict__ z, const float* __restrict__ head,
-                                   const float* __restrict__ z_scale, int B, int zd, int ldh, float beta, float* __restrict__ out) {
+                                   const float* __restrict__ z_scale, int B, int zd, int ldh, float beta, float* __restrict__ out,
+                                   int kl_mode) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   float kl = 0.0f;
   for (int i = 0; i < zd; ++i) {
     const float zz = z[(int64_t)b * zd + i], mu = head[(int64_t)b * ldh + i], sig = z_scale[(int64_t)b * zd + i];
     const float d = zz - mu;
-    const float lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI;
-    const float lp = -(zz * zz) / 2.0f - LOG_SQRT_2PI;
-    kl += lp - lq;
+    if (kl_mode == PV_KL_SAMPLED) {
+      const float lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI;
+      const float lp = -(zz * zz) / 2.0f - LOG_SQRT_2PI;
+      kl += lp - lq;
+    } else {
+      float aq, ap;
+      pv_kl_analytic_terms(mu, sig, aq, ap);
+      kl += ap - aq;
+    }
   }
   out[b] = row_ll[b] + beta * kl;
 }
 int pv_row_elbo(const float* row_ll, const float* z, const float* head, const float* z_scale, int B, int z_dim, int ldh,
-                float beta, float* out, hipStream_t s) {
+                float beta, float* out, hipStream_t s, int kl_mode) {
   hipLaunchKernelGGL(pv_row_elbo_kernel, dim3((B + 63) / 64), dim3(64), 0, s, row_ll, z, head, z_scale, B, z_dim, ldh, beta,
-                     out);
+                     out, kl_mode);
   PV_LAUNCH_CHECK();
   return 0;
 }

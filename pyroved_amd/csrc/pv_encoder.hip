@@ -343,8 +343,15 @@ __device__ __forceinline__ void enc_fwd_body(const PvEncFwd& e, int rbk, float (
       if (e.z_scale_out) e.z_scale_out[(int64_t)row * zd + i] = sig;
       const float d = z - mu;
       const float wb = e.w ? e.w[row] : 1.0f;
-      lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);      // torch Normal.log_prob
-      lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+      if (e.kl_mode == PV_KL_SAMPLED) {
+        lq += wb * (-(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI);      // torch Normal.log_prob
+        lp += wb * (-(z * z) / 2.0f - LOG_SQRT_2PI);
+      } else {
+        float aq, ap;
+        pv_kl_analytic_terms(mu, sig, aq, ap);
+        lq += wb * aq;
+        lp += wb * ap;
+      }
       act[cur ^ 1][rr][i] = z;                     // keep z for the split below
     }
   }

@@ -22,7 +22,8 @@
 #define GI_P_WAVE (64 * 17)                           // floats of a wave's partial-sum transpose buffer (pv_gemv16.h)
 #define GI_LOG_SQRT_2PI 0.91893853320467274178f
 
-__global__ __launch_bounds__(GI_THREADS) void pv_guide_img_kernel(PvEncFold e, PvFbPrep prep, float hz_mul, int n_img, int has_prep) {
+__global__ __launch_bounds__(GI_THREADS) void pv_guide_img_kernel(PvEncFold e, PvFbPrep prep, float hz_mul, int n_img, int has_prep,
+                                                                  int kl_mode) {
   __shared__ __attribute__((aligned(16))) float h1s[128];
   __shared__ __attribute__((aligned(16))) float h2s[128];
   __shared__ __attribute__((aligned(16))) float hds[64];
@@ -116,8 +117,12 @@ __global__ __launch_bounds__(GI_THREADS) void pv_guide_img_kernel(PvEncFold e, P
       if (e.z_loc_out) e.z_loc_out[b * zd + lane] = mu;
       if (e.z_scale_out) e.z_scale_out[b * zd + lane] = sig;
       const float d = z - mu;
-      lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - GI_LOG_SQRT_2PI;
-      lp = -(z * z) / 2.0f - GI_LOG_SQRT_2PI;
+      if (kl_mode == PV_KL_SAMPLED) {
+        lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - GI_LOG_SQRT_2PI;
+        lp = -(z * z) / 2.0f - GI_LOG_SQRT_2PI;
+      } else {
+        pv_kl_analytic_terms(mu, sig, lq, lp);     // the analytic-KL objective: the terms' expectations under q
+      }
       zs[lane] = z;
     }
     lp = pv_wave_sum(lp);
@@ -159,7 +164,7 @@ bool pv_guide_img_ok(const PvEncFold& e, int B) {
          e.enc1.in_dim % 4 == 0 && e.head.in_dim % 4 == 0 && e.head.out_dim <= 64 && e.z_dim <= 16 && e.lat_in <= 16;
 }
 
-int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, int B, hipStream_t s) {
+int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, int B, hipStream_t s, int kl_mode) {
   if (!pv_guide_img_ok(e, B)) return PV_EINVAL;
   // guests: 8 workgroups split the two 128 x 128 matrices' image rows, a few more the zero fill when it is long
   int guests = 0;
@@ -169,7 +174,7 @@ int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, 
   }
   const PvFbPrep pz = prep ? *prep : PvFbPrep{};
   hipLaunchKernelGGL(pv_guide_img_kernel, dim3(B + guests), dim3(GI_THREADS), 0, s, e, pz, hz_mul == 0.0f ? 1.0f : hz_mul, B,
-                     prep ? 1 : 0);
+                     prep ? 1 : 0, kl_mode);
   PV_LAUNCH_CHECK();
   return 0;
 }

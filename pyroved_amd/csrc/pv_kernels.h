@@ -19,6 +19,7 @@ struct PvHead {
   int ldh;               // row stride of head (0: 2*z_dim)
   int scale_direct;      // 1: the second half of head IS z_scale (external encoder), not its softplus input
   const float* w;        // (B) per-sample weights of the KL sums (plan->row_w) or null
+  int kl_mode;           // PV_KL_SAMPLED / PV_KL_ANALYTIC: what the two KL sums hold (pv_kl_terms)
   // pv_head_fwd_blocks only (a conv encoder's tail as ONE launch of ceil(B / 16) workgroups, 16 samples each):
   //   ch_part != null: head[b][j] = ch_bias[j] + sum_seg ch_part[b][seg][j] first (pv_convhead_fwd_partials; ldh == ch_out), into head_w
   //   hz != null: hz[b][j] = sum_k zin[b * ldz + k] Wz[j * lat_in + k] last (fc_latent of the spatial decoder, lat_in <= 16)
@@ -101,6 +102,7 @@ struct PvHeadBwd {
   int scale_direct;      // 1: head's second half is z_scale itself: dhead's second half = dloss/dz_scale
   const float* w;        // (B) per-sample weights (plan->row_w): scale the KL terms' derivatives (the decoder's arrive
                          // weighted already) or null
+  int kl_mode;           // PV_KL_SAMPLED / PV_KL_ANALYTIC (pv_head_bwd_math_kl)
 };
 int pv_head_bwd(const PvHeadBwd& h, hipStream_t s);
 
@@ -136,6 +138,16 @@ __device__ __forceinline__ void pv_head_bwd_math(float dz, float z, float sig, f
   const float sgm = scale_direct ? 1.0f : (sp > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-sp)));   // softplus'
   ds = dsig * sgm;
 }
+// The same for either form of the KL term (mu: the coordinate's z_loc).  Analytic: d(beta KL)/dmu = beta mu,
+// d(beta KL)/dsigma = beta (sigma - 1/sigma); dz reaches sigma through z = mu + sigma eps as before.
+__device__ __forceinline__ void pv_head_bwd_math_kl(int kl_mode, float dz, float z, float mu, float sig, float ep, float sp, float bw,
+                                                    int scale_direct, float& g, float& ds) {
+  if (kl_mode == PV_KL_SAMPLED) { pv_head_bwd_math(dz, z, sig, ep, sp, bw, scale_direct, g, ds); return; }
+  g = dz + bw * mu;
+  const float dsig = dz * ep + bw * (sig - 1.0f / sig);
+  const float sgm = scale_direct ? 1.0f : (sp > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-sp)));   // softplus'
+  ds = dsig * sgm;
+}
 template <class FC, class FK>
 __device__ __forceinline__ void pv_head_bwd_elem(const PvHeadBwd& h, int b, int i, FC dz_coord, FK dz_content,
                                                  float* dh_copy = nullptr) {
@@ -143,8 +155,8 @@ __device__ __forceinline__ void pv_head_bwd_elem(const PvHeadBwd& h, int b, int 
   const int e = b * h.z_dim + i;
   const int ldh = h.ldh > 0 ? h.ldh : 2 * h.z_dim;
   float g, ds;
-  pv_head_bwd_math(dz, h.z[e], h.z_scale[e], h.eps[e], h.head[(int64_t)b * ldh + h.z_dim + i], h.w ? h.beta * h.w[b] : h.beta,
-                   h.scale_direct, g, ds);
+  pv_head_bwd_math_kl(h.kl_mode, dz, h.z[e], h.head[(int64_t)b * ldh + i], h.z_scale[e], h.eps[e],
+                      h.head[(int64_t)b * ldh + h.z_dim + i], h.w ? h.beta * h.w[b] : h.beta, h.scale_direct, g, ds);
   h.dhead[(int64_t)b * ldh + i] = g;
   h.dhead[(int64_t)b * ldh + h.z_dim + i] = ds;
   if (dh_copy) { dh_copy[i] = g; dh_copy[h.z_dim + i] = ds; }
@@ -201,8 +213,9 @@ int pv_jiv_expand(const float* head, int ldh, const float* z, int z_dim, int n_c
                   float* sw, float* scalars, float beta_disc, int B, int K, hipStream_t s);
 int pv_scale_rows(float* v, const float* w, int64_t rows, int64_t N, hipStream_t s);
 // out[b] = row_ll[b] + beta * sum_i (log p(z_bi) - log q(z_bi | x_b))   (mu = head[b*ldh + i])
+// (kl_mode == PV_KL_ANALYTIC: ... - beta * sum_i KL_bi)
 int pv_row_elbo(const float* row_ll, const float* z, const float* head, const float* z_scale, int B, int z_dim, int ldh,
-                float beta, float* out, hipStream_t s);
+                float beta, float* out, hipStream_t s, int kl_mode = PV_KL_SAMPLED);
 // dst[b][i] += src[b*lds + i], i < n
 int pv_add_cols(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t B, int n, hipStream_t s);
 struct PvFusedOffsets;
@@ -267,6 +280,7 @@ struct PvEncFwd {
   int B, z_dim, c_dim, coord_dim, has_r, has_t, has_s;
   float tp0, tp1, sc_prior;
   float beta, beta_disc;            // the KL partials in kl_part are stored scaled by these
+  int kl_mode;                      // PV_KL_SAMPLED / PV_KL_ANALYTIC (pv_kernels.h: pv_kl_analytic_terms)
   // jiVAE (K > 0): head = [mu | softplus input | class logits]; alpha = softmax(logits); tp, zy, hz are written for
   // the K*B decoder samples ordered [k][b] (zy = [z content | onehot(k)]); sw[k*B + b] = alpha[b][k]
   int K; float* alpha; float* sw;

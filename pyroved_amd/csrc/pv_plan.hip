@@ -105,6 +105,8 @@ bool valid_plan(const pv_ivae_plan* p) {
   if (p->coord_dim > 0 && p->out.out_dim != 1) return false;
   if (p->coord_dim == 0 && p->out.out_dim != p->n_pix) return false;
   if (p->dec_kernel != 0 && !pv_sdec_fused_sel_valid(p->fused, p->dec_kernel)) return false;
+  if (p->kl_mode != PV_KL_SAMPLED && p->kl_mode != PV_KL_ANALYTIC) return false;
+  if (p->kl_mode == PV_KL_ANALYTIC && p->discrete_dim > 0) return false;            // (TraceEnum_ELBO has no mean-field form)
   return true;
 }
 
@@ -669,7 +671,8 @@ int weigh_llb(const pv_ivae_plan* p, const Layout& L, hipStream_t s) {
 int extra_outputs(const pv_ivae_plan* p, const Layout& L, const float* dzc, int64_t lat_in, hipStream_t s) {
   const int64_t B = p->batch;
   if (p->row_elbo)
-    PV_TRY(pv_row_elbo(L.row_ll, L.z, L.head, L.z_scale, (int)B, p->z_dim, (int)plan_head_w(p), p->beta, p->row_elbo, s));
+    PV_TRY(pv_row_elbo(L.row_ll, L.z, L.head, L.z_scale, (int)B, p->z_dim, (int)plan_head_w(p), p->beta, p->row_elbo, s,
+                       p->kl_mode));
   if (p->dy && dzc) {
     const pv_layer& l0 = p->enc[0];
     const int64_t N = p->n_pix, c = p->c_dim;
@@ -696,7 +699,7 @@ int latent_encoder_bwd(const pv_ivae_plan* p, const Layout& L, int64_t lat_in, i
   hb.has_r = p->has_r; hb.has_t = p->has_t; hb.has_s = p->has_s;
   hb.tp0 = p->t_prior[0]; hb.tp1 = p->t_prior[1]; hb.sc_prior = p->sc_prior; hb.beta = p->beta;
   hb.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
-  hb.w = p->row_w;
+  hb.w = p->row_w; hb.kl_mode = p->kl_mode;
   PV_TRY(pv_head_bwd(hb, s));
   PV_TRY(encoder_bwd(p, L, nullptr, 0, s));
   return extra_outputs(p, L, L.dzc, lat_in, s);
@@ -723,7 +726,7 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
     e.z_loc_out = p->z_loc; e.z_scale_out = p->z_scale;
     e.tp = p->coord_dim > 0 ? L.tp : nullptr; e.zy = L.zy; e.kl_part = L.kl_part;
     e.beta = p->beta; e.beta_disc = p->beta_disc; e.K = (int)plan_K(p); e.alpha = L.alpha; e.sw = L.sw;
-    e.w = p->row_w;
+    e.w = p->row_w; e.kl_mode = p->kl_mode;
     if (p->coord_dim > 0) { e.hz = L.hz; e.Wz = p->params + p->fc_latent.w_off; e.H0 = p->fc_coord.out_dim; }
     e.hz_scale = hz_scale;
     e.flags = (p->flags & PV_PLAN_ENC_TWO_LAUNCH) ? nullptr : L.enc_flags;
@@ -755,7 +758,7 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
   h.B = p->batch; h.z_dim = p->z_dim; h.c_dim = p->c_dim; h.coord_dim = p->coord_dim;
   h.has_r = p->has_r; h.has_t = p->has_t; h.has_s = p->has_s;
   h.tp0 = p->t_prior[0]; h.tp1 = p->t_prior[1]; h.sc_prior = p->sc_prior; h.beta = p->beta;
-  h.w = p->row_w;
+  h.w = p->row_w; h.kl_mode = p->kl_mode;
   h.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
   const int64_t K = plan_K(p);
   if (K > 0) h.zy = nullptr;                      // (written per decoder sample below)
@@ -777,7 +780,8 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
 //  per-image guide launch, pv_guide_img.hip)
 static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L);
 static bool plan_guide_may_fold(const pv_ivae_plan* p, const Layout& L) {
-  return p->fused == 3 && !(p->flags & PV_PLAN_NO_ENC_FOLD) && plan_guide_one_image(p, L);
+  // (the hosting launch computes the sampled KL form only: it sits at the register ceiling — the analytic form runs the guide as its own launch)
+  return p->fused == 3 && !(p->flags & PV_PLAN_NO_ENC_FOLD) && p->kl_mode == PV_KL_SAMPLED && plan_guide_one_image(p, L);
 }
 static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L) {
   const int64_t z = p->z_dim;
@@ -877,7 +881,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
     const bool per_image = plan_guide_one_image(p, L) && pv_guide_img_ok(ef, (int)B) &&
                            !(p->flags & (PV_PLAN_ENC_TILED | PV_PLAN_ENC_TWO_LAUNCH | PV_PLAN_ENC_NO_WAIT));
     if (per_image) {
-      PV_TRY(pv_guide_img_launch(ef, &prep, f.hz_scale, (int)B, s));
+      PV_TRY(pv_guide_img_launch(ef, &prep, f.hz_scale, (int)B, s, p->kl_mode));
       kl_n = (int)B;
     } else {
       PV_TRY(guide_fwd(p, L, s, &prep, f.hz_scale));
@@ -924,7 +928,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
   hb.B = (int)B; hb.z_dim = (int)z; hb.coord_dim = p->coord_dim;
   hb.has_r = p->has_r; hb.has_t = p->has_t; hb.has_s = p->has_s;
   hb.tp0 = p->t_prior[0]; hb.tp1 = p->t_prior[1]; hb.sc_prior = p->sc_prior; hb.beta = p->beta;
-  hb.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
+  hb.ldh = L.enc_ext ? 0 : (int)plan_head_w(p); hb.kl_mode = p->kl_mode;
   lb.K = (int)K; lb.alpha = L.alpha; lb.beta_disc = p->beta_disc;
   hb.w = p->row_w; lb.row_ll = p->row_elbo ? L.row_ll : nullptr; lb.dzc_out = p->dy ? L.dzc : nullptr;
   // compact encoder: every sample's dgrad chain runs in its latent_bwd workgroup (one dependent launch less)
@@ -946,7 +950,9 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
   PvGemm tail_probs[4];
   int tail_np = -1;
   // (f.dhz_out / dzc_out / part_rs together: the hosting 8-wave launch, or a 4-wave launch whose workgroups own one sample each)
+  // (the decoder launches' epilogue differentiates the sampled KL form only: the analytic form takes the latent-backward launch)
   if (ab_tail && want_grads && chain && f.part_rs && f.dhz_out && f.dzc_out && K == 0 && H == FD_H && !p->row_w &&
+      p->kl_mode == PV_KL_SAMPLED &&
       !p->row_elbo && !p->dy && p->head.out_dim <= 16 && p->n_enc == 2 && p->enc[0].out_dim == FD_H && p->enc[1].in_dim == FD_H &&
       p->enc[1].out_dim == FD_H && p->head.in_dim == FD_H) {      // (the epilogue's chain is written for two hidden layers of width 128)
     tail_np = compact_wgrad_problems(p, L, &wz, 1, tail_probs);

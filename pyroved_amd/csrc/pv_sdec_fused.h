@@ -111,7 +111,8 @@ __device__ inline PvEncFoldArg pv_kernarg_fold() { return nullptr; }      // (ho
 #define PV_GUIDE_IMG_MAX_BATCH 384     // (measured, scripts/ab_guide_img.py: -7..-10 % of the step at batch 64, -6..-9 % at 128, -2..-4 % at 256, +-0 at 512)
 struct PvFbPrep;
 bool pv_guide_img_ok(const PvEncFold& e, int B);
-int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, int B, hipStream_t s);
+// kl_mode: PV_KL_SAMPLED / PV_KL_ANALYTIC — what kl_part holds (a launch argument: PvEncFold is also the hosting decoder launch's, which runs the sampled form only)
+int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, int B, hipStream_t s, int kl_mode = PV_KL_SAMPLED);
 // whether the launch of (f, grads) can host the guide of `p`'s encoder (the caller checks the encoder's architecture)
 bool pv_sdec_fused_w8_fold_ok(const PvFused& f, int grid);
 // ... and whether the launcher will pick that kernel for (f, x3) at all

@@ -55,6 +55,7 @@ bool valid_ved(const pv_ved_plan* p) {
   if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI) return false;
   if (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out) return false;
   if (p->head.out_dim != 2 * p->z_dim || p->l2f.in_dim != p->z_dim) return false;
+  if (p->kl_mode != PV_KL_SAMPLED && p->kl_mode != PV_KL_ANALYTIC) return false;
   return true;
 }
 
@@ -208,7 +209,7 @@ int ved_encoder_fwd(const pv_ved_plan* p, VLayout& L, float* z_loc_out, float* z
   h.head = L.head; h.eps = with_kl ? p->eps : L.z_scale; h.z = L.z; h.z_scale = L.z_scale;
   h.z_loc_out = z_loc_out; h.z_scale_out = z_scale_out;
   h.scalars = with_kl ? p->scalars : L.dhead;       // (inference: the KL slots land in scratch)
-  h.B = (int)B; h.z_dim = p->z_dim; h.beta = with_kl ? p->beta : 0.0f;
+  h.B = (int)B; h.z_dim = p->z_dim; h.beta = with_kl ? p->beta : 0.0f; h.kl_mode = p->kl_mode;
   return pv_head_fwd(h, s);
 }
 
@@ -222,6 +223,7 @@ int ved_decoder_fwd(const pv_ved_plan* p, VLayout& L, const float* z, hipStream_
   if (L.l2f_wt && dec1d_active(p, L) && pv_dec1d_l2f_ok(p->z_dim)) {       // the Linear rides in the decoder's launch
     const PvD1L2f lf{z, L.l2f_wt, p->l2f.b_off >= 0 ? p->params + p->l2f.b_off : nullptr, nullptr, p->z_dim};
     PvD1Head hd{L.head, p->eps, L.z, L.z_scale, p->z_loc, p->z_scale, L.kl_part, nullptr, 2 * p->z_dim, p->beta};
+    hd.kl_mode = p->kl_mode;
     if (L.head_part) { hd.part = L.head_part; hd.bias = p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr; hd.head_out = L.head; hd.nseg = L.head_nseg; }
     if (lik_done) *lik_done = lk != nullptr;
     if (arm_fork) pv_fork_arm();
@@ -338,7 +340,8 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
     dz_done = L.l2f_wt && pv_dec1d_l2f_ok(p->z_dim);   // the latent gradient rides in the same launch
     const PvD1L2f lf{nullptr, L.l2f_wt, nullptr, L.dzc, p->z_dim};
     head_done = dz_done && head_folded(p, L);          // ... and the head's backward
-    const PvD1Head hd{L.head, p->eps, L.z, L.z_scale, nullptr, nullptr, nullptr, L.dhead, 2 * p->z_dim, p->beta};
+    PvD1Head hd{L.head, p->eps, L.z, L.z_scale, nullptr, nullptr, nullptr, L.dhead, 2 * p->z_dim, p->beta};
+    hd.kl_mode = p->kl_mode;
     PV_TRY(pv_dec1d_bwd(p->dec, p->n_dec_ops, L.d1_wt, (int)B, L.ds[0].H, L.ds[0].C, L.da, L.dlda, L.dg, s, dz_done ? &lf : nullptr,
                         head_done ? &hd : nullptr));
     PV_TRY(pvcs::stack_wgrads(p->params, p->grads, p->dec, p->n_dec_ops, p->ndim_out, (int)B, L.da, L.ds, L.dlda, L.dg, L.sc, s, 1));
@@ -383,7 +386,7 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
   // ---- reparameterised sample + sampled KL -> head ----
   PvHeadBwd hb{};
   hb.dzc = L.dzc; hb.ldzc = z; hb.z = L.z; hb.z_scale = L.z_scale; hb.eps = p->eps; hb.head = L.head; hb.dhead = L.dhead;
-  hb.B = (int)B; hb.z_dim = (int)z; hb.coord_dim = 0; hb.beta = p->beta;
+  hb.B = (int)B; hb.z_dim = (int)z; hb.coord_dim = 0; hb.beta = p->beta; hb.kl_mode = p->kl_mode;
   if (!head_done) PV_TRY(pv_head_bwd(hb, s));
   const Shape& fe = L.es[p->n_enc_ops];
   const pv_op& last = p->enc[p->n_enc_ops - 1];

@@ -26,7 +26,13 @@ from .nets.conv import convEncoderNet
 from ._convplan import UnsupportedModel, conv_ops, fill_ops, bn_modules
 
 ALIGN = 64      # floats: every tensor starts on a 256-byte boundary of the flat buffer
-N_SCALARS = 4   # loss, ll, beta*log p(z), beta*log q(z|x)
+N_SCALARS = 4   # loss, ll, beta*log p(z), beta*log q(z|x)  (kl="analytic": the last two are those terms' expectations under q)
+
+
+def _kl_name(kl) -> str:
+    if kl not in _abi.KL:
+        raise ValueError("kl must be 'sampled' or 'analytic' (got %r)" % (kl,))
+    return kl
 
 
 def _linears(seq: nn.Sequential) -> List[nn.Linear]:
@@ -49,9 +55,12 @@ class IVAEEngine:
     enc_per_image = True             # the guide of a training step as one workgroup per image (False: PV_PLAN_ENC_TILED, the tiled one-launch encoder)
     conv_x3 = False                  # PV_PLAN_CONV_X3 / conv_bf16 = 0: fp32-class kernel-3 convolutions with both operands as two fp16 pieces
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
+    kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
+                                     # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
 
-    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2):
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled"):
         self.model = model
+        self.kl = _kl_name(kl)
         self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.fused = int(fused)         # 0 layered kernels, 1 fused f32-MFMA decoder, 2 fused bf16x3 decoder, 3 fused plain-bf16 decoder
         self.adam_t = 0                 # number of optimizer steps taken (incl. evaluate()'s, see SVItrainer)
@@ -99,6 +108,7 @@ class IVAEEngine:
             raise UnsupportedModel("the HIP SVI path needs encoder_z to be pyroved_amd.nets.fcEncoderNet / "
                                    "jfcEncoderNet / convEncoderNet (got %s)" % type(enc).__name__)
         self.K = int(getattr(m, "discrete_dim", 0)) if isinstance(enc, jfcEncoderNet) else 0
+        self._check_kl()
         if self.ext_enc and self.ext_dec:
             return                                   # both user modules: the library keeps the reparameterisation + KL
         if self.ext_enc and isinstance(dec, (sDecoderNet, fcDecoderNet)):
@@ -217,7 +227,12 @@ class IVAEEngine:
                 self._enc_opt = torch.optim.Adam(self._enc_params, lr=self.lr, betas=self.betas, eps=self.adam_eps)
         self._static = self._static_plan()
 
-    def configure(self, lr=None, betas=None, eps=None, fused=None):
+    def _check_kl(self):
+        if self.kl == "analytic" and getattr(self, "K", 0) > 0:
+            raise ValueError("kl='analytic' (TraceMeanField_ELBO) is not defined for models with a discrete latent (jiVAE): "
+                             "their objective enumerates or samples the class (TraceEnum_ELBO / Trace_ELBO)")
+
+    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them)."""
         if lr is not None:
@@ -229,6 +244,13 @@ class IVAEEngine:
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
             self.ws = None
+        if kl is not None:
+            old, self.kl = self.kl, _kl_name(kl)
+            try:
+                self._check_kl()
+            except ValueError:
+                self.kl = old
+                raise
         if self.flat is not None:
             self._static = self._static_plan()
         return self
@@ -457,6 +479,7 @@ class IVAEEngine:
         p.conv_wide = int(self.wide_weights)
         p.flags = self._plan_flags()
         p.dec_kernel = int(getattr(self, "dec_kernel", 0))     # 0: the library picks the decoder-kernel build by size (ABI v15)
+        p.kl_mode = _abi.KL[self.kl]                            # (ABI v17)
         p.x = p.y = p.eps = p.z_loc = p.z_scale = p.loc = p.alpha = p.ext_head = p.ext_dhead = None
         p.row_w = p.row_elbo = p.dy = None
         p.ext_z = p.ext_dz = p.ext_ll = None
@@ -489,7 +512,7 @@ class IVAEEngine:
                        row_w: Optional[torch.Tensor] = None, row_elbo: Optional[torch.Tensor] = None,
                        dy: Optional[torch.Tensor] = None, step: bool = False,
                        class_onehot: Optional[torch.Tensor] = None, comm=None, hist_out: Optional[torch.Tensor] = None):
-        """Enqueues Trace_ELBO.loss_and_grads on the current stream.  Results land in
+        """Enqueues Trace_ELBO.loss_and_grads (self.kl == "analytic": TraceMeanField_ELBO's) on the current stream.  Results land in
         self.scalars (device, 4 floats) and self.grad[:n_flat]; nothing is synchronised.
         row_w (B): per-sample weights of the ELBO terms; row_elbo (B) / dy (B, c_dim): extra outputs
         (include/pyroved_amd.h: pv_ivae_plan.row_w / row_elbo / dy).

@@ -95,6 +95,7 @@ class VEDEngine(IVAEEngine):
         p.conv_bf16 = ((1 if self.wide_weights else 3) if self.fused == 3 else
                        (2 if self.wide_weights else (0 if self.conv_x3 else 4)))
         p.flags = self._plan_flags()
+        p.kl_mode = _abi.KL[self.kl]
         p.x = p.y = p.eps = p.z_loc = p.z_scale = p.loc = None
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)

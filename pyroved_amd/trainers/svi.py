@@ -31,8 +31,11 @@ class SVItrainer:
         model: initialized model (pyroved_amd.models.iVAE)
         optimizer: None (Adam, lr 1e-3) or a dict of Adam arguments {"lr", "betas", "eps"} — the fused HIP route; a
             pyro.optim object (needs pyro-ppl) selects the generic Pyro route over model.model / model.guide
-        loss: None / "Trace_ELBO" (the one-particle ELBO the reference defaults to); a pyro.infer ELBO object
-            (needs pyro-ppl) selects the generic Pyro route
+        loss: None / "Trace_ELBO" (the one-particle ELBO the reference defaults to: log q(z|x) - log p(z) at the drawn z)
+            or "TraceMeanField_ELBO" (the same ELBO with the KL between the encoder's Normal and the N(0, 1) prior in
+            closed form — lower gradient variance; what pyro.infer.TraceMeanField_ELBO computes for these models) — both
+            run in the HIP library and compose with every keyword below; not for models.jiVAE, whose objective
+            enumerates or samples the class.  A pyro.infer ELBO object (needs pyro-ppl) selects the generic Pyro route
         enumerate_parallel: exact enumeration of the discrete latent of models.jiVAE (False, the reference's default:
             the class is drawn by the guide — vanilla jiVAE only, as in the reference)
         seed: enforces reproducibility
@@ -53,6 +56,9 @@ class SVItrainer:
         mirror_evaluate_update: keep the reference's behaviour of stepping the optimizer inside
             evaluate() (svi.py:126-135 calls svi.step under no_grad) — default True
     """
+    # the objectives the HIP library evaluates -> the engines' `kl` setting (pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode)
+    _LOSSES = {None: "sampled", "Trace_ELBO": "sampled", "TraceMeanField_ELBO": "analytic"}
+
     def __init__(self,
                  model: Type[torch.nn.Module],
                  optimizer=None,
@@ -81,8 +87,14 @@ class SVItrainer:
         self.engine, self.group, self._hist, self._feed_cache = None, kwargs.get("process_group", None), None, None
         self.loss_history = {"training_loss": [], "test_loss": []}
         self.current_epoch = 0
-        pyro_objects = (optimizer is not None and not isinstance(optimizer, dict)) or \
-                       (loss is not None and loss != "Trace_ELBO")
+        if isinstance(loss, str) and loss not in self._LOSSES:
+            raise ValueError("loss must be one of the strings %s (or a pyro.infer ELBO object); got %r"
+                             % (" / ".join(repr(k) for k in self._LOSSES if k), loss))
+        kl = self._LOSSES[loss] if (loss is None or isinstance(loss, str)) else None
+        if kl == "analytic" and is_joint:
+            raise ValueError("loss='TraceMeanField_ELBO' is not defined for models.jiVAE: the discrete latent is enumerated "
+                             "(TraceEnum_ELBO) or sampled (Trace_ELBO), and neither has a mean-field form")
+        pyro_objects = (optimizer is not None and not isinstance(optimizer, dict)) or kl is None
         if pyro_objects:
             # Pyro optimizer / ELBO OBJECTS (the reference's signature, svi.py:66-67): the generic Pyro route —
             # pyro.infer.SVI over model.model / model.guide (models/_pyro_programs.py), the networks as differentiable
@@ -108,6 +120,8 @@ class SVItrainer:
             if loss is None or loss == "Trace_ELBO":
                 loss = (infer.TraceEnum_ELBO(max_plate_nesting=1, strict_enumeration_warning=False)
                         if enumerate_parallel else infer.Trace_ELBO())
+            elif loss == "TraceMeanField_ELBO":      # (named by its string next to a Pyro optimizer object)
+                loss = infer.TraceMeanField_ELBO()
             guide = infer.config_enumerate(model.guide, "parallel", expand=True) if enumerate_parallel else model.guide
             self.svi = infer.SVI(model.model, guide, opt, loss=loss)
             self.loss_history = {"training_loss": [], "test_loss": []}
@@ -125,12 +139,13 @@ class SVItrainer:
         if kwargs.get("engine") is not None:
             # test hook: a stand-in engine (tests drive the data-parallel host logic on CPU/gloo with it)
             self.engine = kwargs["engine"]
+            self.engine.kl = kl
         else:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
-                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)))
+                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl)
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
