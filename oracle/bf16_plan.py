@@ -31,7 +31,7 @@ code path is unchanged.  The rounding points, from the kernel sources (pyroved_a
     transcendentals); the per-workgroup fp32 vectors (db1, db2, d(wo), dbo, dWc, dbc); the guide (encoder, fc_latent) folded
     into the prologue or run as its own launch — fp32 in another summation order.
   * model.decode() does NOT run this kernel: pv_ivae_decode launches the split-precision (fp32-class) build whatever the
-    training precision (pv_plan.hip:1217-1218, x3 = true) — the plain oracle is its reference.
+    training precision (pv_plan.hip: decode_fused_run, x3 = true) — the plain oracle is its reference.
 
 4-wave kernel, plain-bf16 build `pv_sdec_fused_bf16_kernel<., ., FB_P_BF16>` (kernel="w4"; fused == 3 on small problems,
 pv_sdec_fused_bf16.hip):

@@ -163,17 +163,11 @@ struct Scratch {
   int ev_op = -1;
   // two-stream steps (pv_side.h).  side != null: the split-operand weight gradients of stack_bwd are enqueued there (each
   // after the launches on the main stream that produce its g; the CALLER joins before the finish) — needs per-op gradient
-  // buffers (stack_bwd's gown), since nothing on the main stream waits for them.  wt_join != null && *wt_join: the step's
-  // weight tilings are still running on `side`; stack_fwd joins before the first op that reads them.
+  // buffers (stack_bwd's gown), since nothing on the main stream waits for them.
   hipStream_t side = nullptr;
-  bool* wt_join = nullptr;
   bool fork_after = false;       // stack_bwd: the stack's LAST input-gradient launch carries a fork event (the caller calls pv_fork_to)
   bool* side_joined = nullptr;   // stack_bwd sets it when it has joined the side stream itself (after its flush of the reductions)
 };
-inline int join_tilings(const Scratch& sc, hipStream_t s) {
-  if (sc.wt_join && *sc.wt_join) { *sc.wt_join = false; return pv_stream_after(s, sc.side); }
-  return 0;
-}
 // recorded (batched) weight gradients are flushed onto the side stream every k1_chunk() problems, next to the rest of the
 // input-gradient chain (PV_K1_CHUNK=n; 0: one launch after the chain)
 inline int k1_chunk() {
@@ -200,6 +194,15 @@ inline int heaviest_conv(const pv_op* ops, int n, int nd, int B, const Shape* sh
   }
   if (flops) *flops = bf;
   return best;
+}
+// measurement (plan->conv_ev_*): events around the heaviest convolution of stack 0's forward, its FLOPs to the caller
+inline void time_heaviest_conv(Scratch& sc, const pv_op* ops, int n, int nd, int B, const Shape* sh, void* ev_start, void* ev_stop,
+                               double* flops_out) {
+  if (!ev_start || !ev_stop) return;
+  double fl = 0.0;
+  sc.ev_op = heaviest_conv(ops, n, nd, B, sh, &fl);
+  sc.ev_start = ev_start; sc.ev_stop = ev_stop;
+  if (flops_out) *flops_out = fl;
 }
 inline const void* wt_ready(const Scratch& sc, int slot, int flip) {
   if (!sc.wt || !sc.wtp || sc.wtp->off[2 * slot + flip] < 0) return nullptr;
@@ -473,7 +476,6 @@ inline int stack_fwd(const float* params, const pv_op* ops, int n, int nd, int B
                               ops[0].cout, ops[0].act, a[2], sc.code, s));
     i0 = 2;
   }
-  PV_TRY(join_tilings(sc, s));                         // (the fused first block reads the raw weights)
   for (int i = i0; i < n; ++i) {
     const bool timed = stack_id == 0 && i == sc.ev_op && sc.ev_start && sc.ev_stop;
     struct EvGuard {                     // start event now, stop event when the op's launches are enqueued
@@ -597,6 +599,50 @@ inline int stack_wgrads(const float* params, float* grads, const pv_op* ops, int
                   PV_ACT_NONE, nullptr, g_up));
   }
   return 0;
+}
+
+// ---- the Linear behind a conv encoder (features2latent: flattened (C, spatial) features -> [mu | softplus input]) ----
+// wt != null: the kernels of pv_convhead.hip on the weight re-indexed channels-last (the step's tiling launch wrote it); null: the
+// features transposed to channels-first (feat) and the GEMMs of pv_linear.h
+struct ConvHead {
+  const pv_layer& l; const float* params; float* grads;
+  const float* a; Shape fe;                            // the stack's last activation (B, H, W, C) and its shape
+  int B; float* wt; float* feat; float* head; float* dhead; void* ws; int64_t ws_bytes;
+  int64_t F() const { return (int64_t)fe.H * fe.W * fe.C; }
+};
+// part != null: the head's partial sums only, where that form exists — the caller's next launch sums them (*part stays null otherwise)
+inline int conv_head_fwd(const ConvHead& h, hipStream_t s, const float** part = nullptr, int* nseg = nullptr) {
+  const float* bias = bias_of(h.params, h.l);
+  if (h.wt && part && pv_convhead_fwd_partials(h.a, h.wt, h.B, h.F(), h.l.out_dim, h.ws, h.ws_bytes, s, part, nseg) == 0) return 0;
+  if (h.wt) return pv_convhead_fwd(h.a, h.wt, bias, h.head, h.B, h.F(), h.l.out_dim, h.ws, h.ws_bytes, s);
+  PV_TRY(pv_nsc_to_ncs(h.a, h.feat, h.B, h.fe.C, (int64_t)h.fe.H * h.fe.W, s));
+  return linear_fwd(h.feat, h.F(), h.params + h.l.w_off, bias, h.head, nullptr, h.l.out_dim, h.B, h.F(), h.l.out_dim, PV_ACT_NONE,
+                    h.ws, h.ws_bytes, s);
+}
+// weight gradient, then dL/d(a) channels-last into a ping-pong buffer (*g; pp = the first free one, before and after), with the
+// last convolution's activation derivative folded in where the kernel can (*g_is_pre).
+// The re-indexed form only — wgrad_stream: where its weight gradient runs (it needs dhead only); behind_wgrad(): what the caller
+// enqueues right behind it; arm: the input-gradient launch carries a fork event (the last convolution's weight gradient forks off it)
+template <class Behind>
+inline int conv_head_bwd(const ConvHead& h, const pv_op& last, hipStream_t wgrad_stream, bool arm, float* const* gbuf, int& pp, float** g,
+                         bool* g_is_pre, hipStream_t s, Behind&& behind_wgrad) {
+  float* dw = h.grads + h.l.w_off;
+  float* db = bias_of(h.grads, h.l);
+  if (h.wt) {
+    *g_is_pre = last.kind == PV_OP_CONV && last.act != PV_ACT_GELU;
+    PV_TRY(pv_convhead_wgrad(h.dhead, h.a, dw, db, h.B, h.fe.H * h.fe.W, h.fe.C, h.l.out_dim, h.ws, h.ws_bytes, wgrad_stream));
+    PV_TRY(behind_wgrad());
+    *g = gbuf[pp]; pp ^= 1;
+    if (arm) pv_fork_arm();
+    return pv_convhead_bwd(h.dhead, h.wt, h.a, *g_is_pre ? last.act : PV_ACT_NONE, *g, h.B, h.F(), h.l.out_dim, s);
+  }
+  *g_is_pre = false;
+  PV_TRY(linear_wgrad(h.dhead, h.l.out_dim, h.feat, h.F(), dw, db, h.B, h.F(), h.l.out_dim, h.ws, h.ws_bytes, s));
+  float* dfeat = gbuf[pp];
+  *g = gbuf[pp ^ 1];
+  PV_TRY(linear_dgrad(h.dhead, h.l.out_dim, h.params + h.l.w_off, dfeat, h.F(), nullptr, nullptr, 0, PV_ACT_NONE, h.B, h.F(), h.l.out_dim,
+                      h.ws, h.ws_bytes, s));
+  return pv_ncs_to_nsc(dfeat, *g, h.B, h.fe.C, (int64_t)h.fe.H * h.fe.W, s);
 }
 
 }  // namespace pvcs

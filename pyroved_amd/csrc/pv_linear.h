@@ -1,6 +1,9 @@
-// pv_linear.h — the generic nn.Linear building blocks (GEMM + fused epilogues, pv_plan.hip) for other translation units.
+// pv_linear.h — the generic nn.Linear / kernel-3 convolution building blocks (GEMM + fused epilogues, pv_linear.hip).
 #pragma once
 #include "pv_common.h"
+
+// a layer's (pv_layer, pv_op) bias in the flat parameter / gradient buffer `base`; null: the layer has none
+template <class T, class Layer> inline T* bias_of(T* base, const Layer& l) { return l.b_off >= 0 ? base + l.b_off : nullptr; }
 
 int64_t gemm_ws_need(int64_t M, int64_t N, int64_t K);
 // y[M,N] = act(x[M,K] W[N,K]^T + b)

@@ -26,15 +26,6 @@ struct Carver {
   }
 };
 
-}  // namespace
-
-int64_t gemm_ws_need(int64_t M, int64_t N, int64_t K) {
-  const int s = pv_gemm_pick_splits((int)M, (int)N, (int)K);
-  return s > 1 ? (int64_t)s * M * (N + 1) * (int64_t)sizeof(float) : 0;     // + row-sum partials
-}
-
-namespace {
-
 struct Layout {
   // encoder
   float* xin; float* eact[PV_MAX_LAYERS]; float* epre[PV_MAX_LAYERS];
@@ -42,7 +33,6 @@ struct Layout {
   float* edp[PV_MAX_LAYERS];               // dL/d(pre-activation) of every encoder hidden layer
   bool enc_compact; float* kl_part; int kl_blocks;   // compact encoder kernels (pv_encoder.hip)
   unsigned* enc_flags;                               // ... their merged launch's tile flags (8 per row block; any content)
-  unsigned* coop_flags;                              // the shared first layer's hand-off tags (PvEncFold::coop_flags; any content)
   // decoder
   float* hz; float* h0; float* dact[PV_MAX_LAYERS]; float* dpre_[PV_MAX_LAYERS];
   float* logits; float* llrow; float* llb; float* dbuf[2];
@@ -171,7 +161,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.kl_blocks = (int)((B + 15) / 16);
   L.kl_part = c.take(2 * (B > L.kl_blocks ? B : L.kl_blocks));   // (per 16-row block — or per sample when the guide rides in the decoder launch)
   L.enc_flags = reinterpret_cast<unsigned*>(c.take(8 * L.kl_blocks));     // (the merged encoder launch's tile flags)
-  L.coop_flags = reinterpret_cast<unsigned*>(c.take(1024 + 16));
+  c.take(1024 + 16);                                 // (PvEncFold::coop_flags of the experiments-only shared first layer: the workspace size stays)
   int64_t maxd = 0;
   L.fused = p->fused && pv_sdec_fused_supported(p) && !(K > 0 && !L.enc_compact);   // (jiVAE + generic encoder: layered)
   L.f_grid = L.f_kmax = 0;
@@ -272,132 +262,43 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.total = c.off;
 }
 
-}  // namespace
-
-// ---- generic nn.Linear building blocks (exported to other translation units through pv_linear.h) ----
-// y = act(x W^T + b)
-int linear_fwd(const float* x, int64_t ldx, const float* W, const float* b, float* y, float* pre, int64_t ldy,
-               int64_t M, int64_t K, int64_t N, int act, void* ws, int64_t wsb, hipStream_t s) {
-  PvGemm g{};
-  g.A = x; g.a_rs = ldx; g.a_cs = 1;
-  g.B = W; g.b_rs = 1; g.b_cs = K;            // B(k,n) = W[n][k]
-  g.C = y; g.ldc = ldy; g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.bias = b; g.act = act; g.pre = pre;
-  return pv_gemm(g, pv_gemm_pick_splits((int)M, (int)N, (int)K), ws, wsb, s);
-}
-
-// dx = (dpre W) * act'(xact)
-int linear_dgrad(const float* dpre, int64_t lddp, const float* W, float* dx, int64_t lddx, const float* xact,
-                 const float* xpre, int64_t ldxa, int act_prev, int64_t M, int64_t K, int64_t N, void* ws, int64_t wsb,
-                 hipStream_t s) {
-  PvGemm g{};
-  g.A = dpre; g.a_rs = lddp; g.a_cs = 1;      // (M, N)
-  g.B = W; g.b_rs = K; g.b_cs = 1;            // B(n,k) = W[n][k]
-  g.C = dx; g.ldc = lddx; g.M = (int)M; g.N = (int)K; g.K = (int)N;
-  g.act = PV_ACT_NONE;
-  if (act_prev != PV_ACT_NONE) { g.aux = xact; g.auxpre = xpre; g.ldaux = ldxa; g.act_aux = act_prev; }
-  return pv_gemm(g, pv_gemm_pick_splits((int)M, (int)K, (int)N), ws, wsb, s);
-}
-
-// dw = dpre^T x ; db = colsum(dpre)
-int linear_wgrad(const float* dpre, int64_t lddp, const float* x, int64_t ldx, float* dw, float* db, int64_t M,
-                 int64_t K, int64_t N, void* ws, int64_t wsb, hipStream_t s) {
-  if (dw) {
-    PvGemm g{};
-    g.A = dpre; g.a_rs = 1; g.a_cs = lddp;    // A(n, row) = dpre[row][n]
-    g.B = x; g.b_rs = ldx; g.b_cs = 1;        // B(row, k) = x[row][k]
-    g.C = dw; g.ldc = K; g.M = (int)N; g.N = (int)K; g.K = (int)M;
-    g.act = PV_ACT_NONE;
-    g.rowsumA = db;                            // db[n] = sum_rows dpre[row][n], fused into the same pass
-    PV_TRY(pv_gemm(g, pv_gemm_pick_splits((int)N, (int)K, (int)M), ws, wsb, s));
-    return 0;
+// the conv encoder as pv_convstack.h takes it: the activations (a[0] = x: one input channel, (B, 1, H, W) is already channels-last),
+// the scratch with the step's tiled weights (both orientations: the backward reuses what the forward's launch tiled) and the head
+struct ConvEnc {
+  float* a[PV_MAX_OPS + 1];
+  pvcs::Scratch sc;
+  bool hfused;                                      // the head on the kernels of pv_convhead.hip (its weight re-indexed channels-last)
+  ConvEnc(const pv_ivae_plan* p, const Layout& L)
+      : sc{L.ccol, L.scratch, L.scratch_bytes, L.cbn, L.cbn_maxC, p->bn_eval, plan_conv_mode(p)},
+        hfused(pv_convhead_supported(L.cF, p->head.out_dim) && L.chead_wt) {
+    a[0] = const_cast<float*>(p->x);
+    for (int i = 1; i <= p->n_enc_ops; ++i) a[i] = L.cea[i];
+    sc.wt = L.cwt; sc.wtp = &L.cwtp;
+    sc.code = L.ccode; sc.code2 = L.ccode2;
   }
-  if (db) PV_TRY(pv_colsum(dpre, lddp, M, (int)N, db, ws, wsb, s));
-  return 0;
-}
-
-// ---- convolutions (kernel 3, padding 1, stride 1; channels-last) as GEMMs over an IMPLICIT im2col operand ----
-// y[(b,y,x)][co] = act(sum_j patch[(b,y,x)][j] W[co][j] + b[co]),  j = ci*KK + tap;  W = the torch weight as it lies
-int conv3_fwd(const float* in, int B, int H, int W_, int C, int nd, const float* W, const float* b, float* y, int Cout,
-              int act, void* ws, int64_t wsb, hipStream_t s) {
-  const int64_t rows = (int64_t)B * H * W_, K = (int64_t)C * (nd == 2 ? 9 : 3);
-  PvGemm g{};
-  g.A = in; g.a_rs = K; g.a_cs = 1; g.conv_a = 1; g.cH = H; g.cW = W_; g.cC = C; g.cnd = nd;
-  g.B = W; g.b_rs = 1; g.b_cs = K;
-  g.C = y; g.ldc = Cout; g.M = (int)rows; g.N = Cout; g.K = (int)K;
-  g.bias = b; g.act = act;
-  return pv_gemm(g, pv_gemm_pick_splits((int)rows, Cout, (int)K), ws, wsb, s);
-}
-
-// dw[co][j] = sum_rows dpre[row][co] patch[row][j] ; db[co] = sum_rows dpre[row][co]
-int conv3_wgrad(const float* dpre, const float* in, int B, int H, int W_, int C, int nd, float* dw, float* db, int Cout,
-                void* ws, int64_t wsb, hipStream_t s) {
-  const int64_t rows = (int64_t)B * H * W_, K = (int64_t)C * (nd == 2 ? 9 : 3);
-  PvGemm g{};
-  g.A = dpre; g.a_rs = 1; g.a_cs = Cout;
-  g.B = in; g.b_rs = K; g.b_cs = 1; g.conv_b = 1; g.cH = H; g.cW = W_; g.cC = C; g.cnd = nd;
-  g.C = dw; g.ldc = K; g.M = Cout; g.N = (int)K; g.K = (int)rows;
-  g.act = PV_ACT_NONE;
-  g.rowsumA = db;
-  return pv_gemm(g, pv_gemm_pick_splits(Cout, (int)K, (int)rows), ws, wsb, s);
-}
-
-namespace {
+  pvcs::ConvHead head(const pv_ivae_plan* p, const Layout& L) const {
+    return {p->head, p->params, p->grads, L.cea[p->n_enc_ops], L.ces[p->n_enc_ops], (int)p->batch, hfused ? L.chead_wt : nullptr,
+            L.cfeat, L.head, L.dhead, L.scratch, L.scratch_bytes};
+  }
+};
 
 // convolutional encoder: x viewed as (B, 1, *enc_in_dim) -> op sequence -> flatten (C, spatial) -> L.head
 // prep != null: the spatial decoder's weight images are written by the same tiling launch (pv_conv_wprep_table)
-// hp != null: the caller's next launch (pv_head_fwd) sums the conv head's partial sums itself — *hp is filled when that form ran
+// hp != null: the caller's next launch (pv_head_fwd_blocks) sums the conv head's partial sums itself — *hp is filled when that form ran
 struct PvHeadPart { const float* part = nullptr; const float* bias = nullptr; int nseg = 0, out = 0; };
 int conv_encoder_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbPrep* prep = nullptr, PvHeadPart* hp = nullptr) {
-  const int64_t B = p->batch;
   if (L.cF < 0 || p->head.in_dim != L.cF) return PV_EINVAL;
-  float* a[PV_MAX_OPS + 1];
-  a[0] = const_cast<float*>(p->x);                  // one input channel: (B, 1, H, W) is already channels-last
-  for (int i = 1; i <= p->n_enc_ops; ++i) a[i] = L.cea[i];
-  pvcs::Scratch sc{L.ccol, L.scratch, L.scratch_bytes, L.cbn, L.cbn_maxC, p->bn_eval, plan_conv_mode(p)};
-  sc.wt = L.cwt; sc.wtp = &L.cwtp;                  // (both orientations: the backward of the same step reuses them)
-  sc.code = L.ccode; sc.code2 = L.ccode2;
-  if (p->conv_ev_start && p->conv_ev_stop) {
-    double fl = 0.0;
-    sc.ev_op = pvcs::heaviest_conv(p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)p->batch, L.ces, &fl);
-    sc.ev_start = p->conv_ev_start; sc.ev_stop = p->conv_ev_stop;
-    if (p->conv_ev_flops) *p->conv_ev_flops = fl;
-  }
-  const pvcs::Shape& fe0 = L.ces[p->n_enc_ops];
-  const bool hfused = pv_convhead_supported(L.cF, p->head.out_dim) && L.chead_wt;
-  const PvWprepEntry he = pvcs::head_entry(p->params + p->head.w_off, L.chead_wt, p->head.out_dim, fe0.C, (int64_t)fe0.H * fe0.W);
-  // the weight tilings next to the fused first block (raw weights) on the side stream; stack_fwd joins before its first tiled op
-  hipStream_t side = pv_side_stream_for(s, p->flags);
-  bool wt_join = false;
-  static const int wprep_side = pv_exp_int("PV_SIDE_WPREP", 0) ? 1 : 0;   // (measured: the join costs more than the overlap returns)
-  if (wprep_side && side && sc.code && pvcs::c1pool_fusable(p->enc_ops, p->n_enc_ops, p->enc_ndim, L.ces[0])) {
-    PV_TRY(pv_stream_after(side, s));
-    PV_TRY(pvcs::wt_prep(p->params, p->enc_ops, p->n_enc_ops, p->enc_ndim, 0, plan_conv_mode(p), L.cwtp, L.cwt, true, side, &he,
-                         hfused ? 1 : 0, prep));
-    wt_join = true;
-    sc.side = side; sc.wt_join = &wt_join;
-  } else {
-    PV_TRY(pvcs::wt_prep(p->params, p->enc_ops, p->n_enc_ops, p->enc_ndim, 0, plan_conv_mode(p), L.cwtp, L.cwt, true, s, &he,
-                         hfused ? 1 : 0, prep));
-  }
-  PV_TRY(pvcs::stack_fwd(p->params, p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)B, a, L.ces, sc, s));
-  if (wt_join) { wt_join = false; PV_TRY(pv_stream_after(s, side)); }
+  ConvEnc ce(p, L);
+  pvcs::time_heaviest_conv(ce.sc, p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)p->batch, L.ces, p->conv_ev_start, p->conv_ev_stop,
+                           p->conv_ev_flops);
   const pvcs::Shape& fe = L.ces[p->n_enc_ops];
-  if (hfused && hp) {
-    const float* part = nullptr;
-    int nseg = 0;
-    if (pv_convhead_fwd_partials(L.cea[p->n_enc_ops], L.chead_wt, (int)B, L.cF, p->head.out_dim, L.scratch, L.scratch_bytes, s, &part,
-                                 &nseg) == 0) {
-      hp->part = part; hp->bias = p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr; hp->nseg = nseg; hp->out = p->head.out_dim;
-      return 0;
-    }
-  }
-  if (hfused)      // (the weight is re-indexed channels-last, not the feature map: pv_convhead.hip)
-    return pv_convhead_fwd(L.cea[p->n_enc_ops], L.chead_wt, p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr, L.head,
-                           (int)B, L.cF, p->head.out_dim, L.scratch, L.scratch_bytes, s);
-  PV_TRY(pv_nsc_to_ncs(L.cea[p->n_enc_ops], L.cfeat, B, fe.C, (int64_t)fe.H * fe.W, s));
-  return linear_fwd(L.cfeat, L.cF, p->params + p->head.w_off, p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr,
-                    L.head, nullptr, p->head.out_dim, B, L.cF, p->head.out_dim, PV_ACT_NONE, L.scratch, L.scratch_bytes, s);
+  const PvWprepEntry he = pvcs::head_entry(p->params + p->head.w_off, L.chead_wt, p->head.out_dim, fe.C, (int64_t)fe.H * fe.W);
+  PV_TRY(pvcs::wt_prep(p->params, p->enc_ops, p->n_enc_ops, p->enc_ndim, 0, plan_conv_mode(p), L.cwtp, L.cwt, true, s, &he,
+                       ce.hfused ? 1 : 0, prep));
+  PV_TRY(pvcs::stack_fwd(p->params, p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)p->batch, ce.a, L.ces, ce.sc, s));
+  PV_TRY(pvcs::conv_head_fwd(ce.head(p, L), s, hp ? &hp->part : nullptr, hp ? &hp->nseg : nullptr));
+  if (hp && hp->part) { hp->bias = bias_of(p->params, p->head); hp->out = p->head.out_dim; }
+  return 0;
 }
 
 int encoder_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbPrep* prep = nullptr, PvHeadPart* hp = nullptr) {
@@ -413,14 +314,14 @@ int encoder_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvF
   for (int i = 0; i < p->n_enc; ++i) {
     const pv_layer& l = p->enc[i];
     if (l.in_dim != ldin) return PV_EINVAL;
-    PV_TRY(linear_fwd(in, ldin, p->params + l.w_off, l.b_off >= 0 ? p->params + l.b_off : nullptr, L.eact[i],
-                      L.epre[i], l.out_dim, B, l.in_dim, l.out_dim, l.act, L.scratch, L.scratch_bytes, s));
+    PV_TRY(linear_fwd(in, ldin, p->params + l.w_off, bias_of(p->params, l), L.eact[i], L.epre[i], l.out_dim, B, l.in_dim, l.out_dim, l.act,
+                      L.scratch, L.scratch_bytes, s));
     in = L.eact[i]; ldin = l.out_dim;
   }
   const pv_layer& h = p->head;
   if (h.in_dim != ldin) return PV_EINVAL;
-  return linear_fwd(in, ldin, p->params + h.w_off, h.b_off >= 0 ? p->params + h.b_off : nullptr, L.head, nullptr,
-                    h.out_dim, B, h.in_dim, h.out_dim, PV_ACT_NONE, L.scratch, L.scratch_bytes, s);
+  return linear_fwd(in, ldin, p->params + h.w_off, bias_of(p->params, h), L.head, nullptr, h.out_dim, B, h.in_dim, h.out_dim, PV_ACT_NONE,
+                    L.scratch, L.scratch_bytes, s);
 }
 
 // decoder forward from the decoder's latent input zin (B, lat_in); tp must be filled for coord_dim > 0.
@@ -452,14 +353,14 @@ int decoder_hidden_fwd(const pv_ivae_plan* p, const Layout& L, const float* zin,
     // instrumentation: the last hidden layer's forward GEMM is the layered path's representative kernel
     const bool timed = (i == p->n_dec - 1) && p->ev_start && p->ev_stop;
     if (timed) (void)hipEventRecord((hipEvent_t)p->ev_start, s);
-    PV_TRY(linear_fwd(in, ldin, p->params + l.w_off, l.b_off >= 0 ? p->params + l.b_off : nullptr, L.dact[i],
+    PV_TRY(linear_fwd(in, ldin, p->params + l.w_off, bias_of(p->params, l), L.dact[i],
                       L.dpre_[i], l.out_dim, R, l.in_dim, l.out_dim, l.act, L.scratch, L.scratch_bytes, s));
     if (timed) (void)hipEventRecord((hipEvent_t)p->ev_stop, s);
     in = L.dact[i]; ldin = l.out_dim;
   }
   if (p->out.in_dim != ldin) return PV_EINVAL;
   if (p->coord_dim == 0) {
-    PV_TRY(linear_fwd(in, ldin, p->params + p->out.w_off, p->out.b_off >= 0 ? p->params + p->out.b_off : nullptr,
+    PV_TRY(linear_fwd(in, ldin, p->params + p->out.w_off, bias_of(p->params, p->out),
                       L.logits, nullptr, p->n_pix, R, p->out.in_dim, p->n_pix, PV_ACT_NONE, L.scratch,
                       L.scratch_bytes, s));
   }
@@ -478,10 +379,107 @@ PvGemm wgrad_problem(const float* dpre, int64_t lddp, const float* x, int64_t ld
   return g;
 }
 
+typedef PvFinishArgs PvFinish;
+inline int finish_scalars(const PvFinish& f, hipStream_t s) {
+  return pv_finish_scalars(f.llb, f.B, f.scalars, f.kl_part, f.n_part, f.beta, s);
+}
+
+// one-tile-per-workgroup weight gradients, four problems a launch: the loss scalars (fin) ride in the first launch, the optimizer
+// update (adam; *adam_done set) in the last, which must be the one that finalises the step's last gradient
+int wgrad_small_chunks(const PvGemm* g, int n, hipStream_t s, const PvFinish* fin = nullptr, const PvAdamFuse* adam = nullptr,
+                       bool* adam_done = nullptr) {
+  for (int i = 0; i < n; i += 4) {
+    const bool last = i + 4 >= n;
+    PV_TRY(pv_wgrad_small(g + i, n - i < 4 ? n - i : 4, s, last ? adam : nullptr, i == 0 ? fin : nullptr));
+    if (last && adam) *adam_done = true;
+  }
+  return 0;
+}
+
+// a long contraction over a few output tiles (jiVAE's fc_latent: K*B decoder samples onto 128 x lat_in) would sit on a handful of
+// workgroups in the one-tile-per-workgroup launch: such a problem wants the split-K GEMM
+bool wants_split_k(const PvGemm& e) {
+  const int64_t tiles = (int64_t)((e.M + 15) / 16) * ((e.N + 15) / 16);
+  return e.K > 1024 && tiles < 128 && pv_gemm_pick_splits(e.M, e.N, e.K) > 1;
+}
+
+// the fc encoder's weight-gradient problems: the head's, then the hidden layers' from the last to the first (1 + n_enc of them)
+int encoder_wgrad_problems(const pv_ivae_plan* p, const Layout& L, PvGemm* probs) {
+  const int64_t B = p->batch;
+  const int ne = p->n_enc;
+  float* G = p->grads;
+  const pv_layer& hd = p->head;
+  int np = 0;
+  probs[np++] = wgrad_problem(L.dhead, hd.out_dim, L.eact[ne - 1], hd.in_dim, G + hd.w_off, bias_of(G, hd), B, hd.in_dim, hd.out_dim);
+  const float* xin = p->c_dim > 0 ? L.xin : p->x;
+  const int64_t ldx = p->n_pix + p->c_dim;
+  for (int i = ne - 1; i >= 0; --i) {
+    const pv_layer& l = p->enc[i];
+    probs[np++] = wgrad_problem(L.edp[i], l.out_dim, i > 0 ? L.eact[i - 1] : xin, i > 0 ? p->enc[i - 1].out_dim : ldx, G + l.w_off,
+                                bias_of(G, l), B, l.in_dim, l.out_dim);
+  }
+  return np;
+}
+
+// `extra` and the compact (fc) encoder's problems as ONE one-tile-per-workgroup launch (the launch that closes an own-sample step);
+// -1 when one of them wants the split-K GEMM or they are more than that launch takes
+int one_launch_wgrad_problems(const pv_ivae_plan* p, const Layout& L, const PvGemm* extra, int n_extra, PvGemm (&probs)[4]) {
+  if (p->batch > 4096 || n_extra + 1 + p->n_enc > 4) return -1;
+  for (int i = 0; i < n_extra; ++i) {
+    if (wants_split_k(extra[i])) return -1;
+    probs[i] = extra[i];
+  }
+  return n_extra + encoder_wgrad_problems(p, L, probs + n_extra);
+}
+
+// conv encoder backward from L.dhead: the head (features2latent), then the op sequence in reverse — input gradients on s, kernel-3
+// weight gradients on the side stream, joined before their one finish launch; the caller's small weight gradients (`extra`) ride along
+int conv_encoder_bwd(const pv_ivae_plan* p, const Layout& L, const PvGemm* extra, int n_extra, hipStream_t s, const PvFinish* fin,
+                     const PvAdamFuse* adam, bool* adam_done, bool head_side) {
+  const int64_t B = p->batch;
+  ConvEnc ce(p, L);
+  hipStream_t side = pv_side_stream_for(s, p->flags);
+  PvSideJoin sj;                                    // joins the side stream on an early return
+  // the head's weight gradient needs dhead only: on the side stream (forked off the launch that wrote dhead) next to the input gradient
+  hipStream_t hs = s;
+  if (ce.hfused) {
+    if (head_side && side) { PV_TRY(pv_fork_to(side, s)); sj.fork(s, side); hs = side; }
+    else pv_fork_disarm();
+  }
+  // ... and so do the small weight gradients the caller hands over (fc_latent's: they need the latent-backward launch's results
+  // only) with the loss scalars riding: behind the head's on the side stream instead of at the very end of the step.
+  // The optimizer update is then a launch of its own after the last reduction (round 5: the closing launch 13.6 -> ~6 us).
+  auto extra_early = [&]() -> int {
+    if (hs != side || !side || n_extra < 1 || n_extra > 4) return 0;
+    PV_TRY(pv_wgrad_small(extra, n_extra, side, nullptr, fin));
+    n_extra = 0; fin = nullptr;
+    return 0;
+  };
+  float* g = nullptr;
+  bool g_is_pre = false;
+  int pp = ce.hfused ? 1 : 0;                       // (dL/d(features) lands in cg[1] in either form; first free ping-pong buffer: cg[0])
+  PV_TRY(pvcs::conv_head_bwd(ce.head(p, L), p->enc_ops[p->n_enc_ops - 1], hs, side != nullptr, L.cg, pp, &g, &g_is_pre, s, extra_early));
+  PvFinishList wfin{};                              // the weight gradients' reductions: one launch after the stack
+  wfin.base = L.cfin_ws; wfin.cap = L.cfin_bytes;
+  ce.sc.fin = &wfin;
+  // kernel-3 weight gradients on the side stream, the input-gradient chain on s (every op's gradient in its own buffer);
+  // joined before the finish
+  bool joined = false;
+  sj.fork(s, side);
+  ce.sc.side = side; ce.sc.side_joined = &joined;
+  PV_TRY(pvcs::stack_bwd(p->params, p->grads, p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)B, ce.a, L.ces, g, L.cg, pp, false,
+                         nullptr, ce.sc, s, 0, g_is_pre, side ? L.ceg : nullptr));
+  if (side && !joined) PV_TRY(pv_stream_after(s, side));
+  sj.joined();
+  PV_TRY(pv_wgrad_finish_all(&wfin, s));
+  if (fin && n_extra < 1) PV_TRY(finish_scalars(*fin, s));
+  // (the loss scalars ride in the first of these launches; every other gradient is final by now, so pv_ivae_step's Adam update
+  //  rides in the last one: its own outputs in its epilogue, the rest of the flat buffer by guest workgroups)
+  return wgrad_small_chunks(extra, n_extra, s, fin, (adam_done && B <= 4096) ? adam : nullptr, adam_done);
+}
+
 // encoder backward from dL/d(head pre-activations) (L.dhead): the dgrad chain through the hidden layers, then
 // every weight gradient of the encoder (plus `extra`, e.g. fc_latent's) in one multi-GEMM launch per 4 problems
-typedef PvFinishArgs PvFinish;
-
 // adam / adam_done: pv_ivae_step's optimizer update, applied inside the weight-gradient launch when that single launch
 // finalises every encoder gradient (compact encoder, <= 4 problems); *adam_done tells the caller whether it was
 // dgrad_done: the compact encoder's dgrad chain already ran (inside pv_latent_bwd_reduce); the loss scalars then ride
@@ -490,84 +488,15 @@ int encoder_bwd(const pv_ivae_plan* p, const Layout& L, const PvGemm* extra, int
                 const PvFinish* fin = nullptr, const PvAdamFuse* adam = nullptr, bool* adam_done = nullptr,
                 bool dgrad_done = false, bool head_side = false) {
   const int64_t B = p->batch;
-  float* G = p->grads;
   void* ws = L.scratch;
   const int64_t wsb = L.scratch_bytes;
   const int ne = p->n_enc;
   const pv_layer& hd = p->head;
   if (L.enc_ext) {                                   // dhead already sits in the caller's ext_dhead
-    if (fin) PV_TRY(pv_finish_scalars(fin->llb, fin->B, fin->scalars, fin->kl_part, fin->n_part, fin->beta, s));
-    for (int i = 0; i < n_extra; i += 4) PV_TRY(pv_wgrad_small(extra + i, n_extra - i < 4 ? n_extra - i : 4, s));
-    return 0;
+    if (fin) PV_TRY(finish_scalars(*fin, s));
+    return wgrad_small_chunks(extra, n_extra, s);
   }
-  if (L.enc_conv) {
-    // head (features2latent.fc_latent) backward, then the op sequence in reverse; the other small wgrads ride along
-    const pvcs::Shape& fe = L.ces[p->n_enc_ops];
-    const pv_op& last = p->enc_ops[p->n_enc_ops - 1];
-    bool g_is_pre = false;
-    hipStream_t side = pv_side_stream_for(s, p->flags);
-    PvSideJoin sj;                                    // joins the side stream on an early return
-    if (pv_convhead_supported(L.cF, hd.out_dim) && L.chead_wt) {
-      // dL/d(features) straight in channels-last order into cg[1], the last convolution's activation derivative folded in
-      g_is_pre = last.kind == PV_OP_CONV && last.act != PV_ACT_GELU;
-      // the head's weight gradient needs dhead only: on the side stream (forked off the launch that wrote dhead) next to the
-      // input gradient below
-      hipStream_t hs = s;
-      if (head_side && side) { PV_TRY(pv_fork_to(side, s)); sj.fork(s, side); hs = side; }
-      else pv_fork_disarm();
-      PV_TRY(pv_convhead_wgrad(L.dhead, L.cea[p->n_enc_ops], G + hd.w_off, hd.b_off >= 0 ? G + hd.b_off : nullptr, (int)B,
-                               fe.H * fe.W, fe.C, hd.out_dim, ws, wsb, hs));
-      // ... and so do the small weight gradients the caller hands over (fc_latent's: they need the latent-backward launch's
-      // results only) with the loss scalars riding: behind the head's on the side stream instead of at the very end of the step.
-      // The optimizer update is then a launch of its own after the last reduction (round 5: the closing launch 13.6 -> ~6 us).
-      static const int ab_early = pv_exp_int("PV_EXTRA_EARLY", 1);
-      if (ab_early && hs == side && side && n_extra > 0 && n_extra <= 4) {
-        PV_TRY(pv_wgrad_small(extra, n_extra, side, nullptr, fin));
-        n_extra = 0; fin = nullptr;
-      }
-      if (side) pv_fork_arm();                                        // (the last convolution's weight gradient forks off this launch)
-      PV_TRY(pv_convhead_bwd(L.dhead, L.chead_wt, L.cea[p->n_enc_ops], g_is_pre ? last.act : PV_ACT_NONE, L.cg[1], (int)B, L.cF,
-                             hd.out_dim, s));
-    } else {
-      PV_TRY(linear_wgrad(L.dhead, hd.out_dim, L.cfeat, L.cF, G + hd.w_off, hd.b_off >= 0 ? G + hd.b_off : nullptr, B, L.cF,
-                          hd.out_dim, ws, wsb, s));
-      PV_TRY(linear_dgrad(L.dhead, hd.out_dim, p->params + hd.w_off, L.cg[0], L.cF, nullptr, nullptr, 0, PV_ACT_NONE, B,
-                          L.cF, hd.out_dim, ws, wsb, s));
-      PV_TRY(pv_ncs_to_nsc(L.cg[0], L.cg[1], B, fe.C, (int64_t)fe.H * fe.W, s));
-    }
-    float* a[PV_MAX_OPS + 1];
-    a[0] = const_cast<float*>(p->x);
-    for (int i = 1; i <= p->n_enc_ops; ++i) a[i] = L.cea[i];
-    pvcs::Scratch sc{L.ccol, ws, wsb, L.cbn, L.cbn_maxC, p->bn_eval, plan_conv_mode(p)};
-    sc.wt = L.cwt; sc.wtp = &L.cwtp;                  // tiled by this step's conv_encoder_fwd
-    sc.code = L.ccode; sc.code2 = L.ccode2;
-    PvFinishList wfin{};                              // the weight gradients' reductions: one launch after the stack
-    wfin.base = L.cfin_ws; wfin.cap = L.cfin_bytes;
-    sc.fin = &wfin;
-    int pp = 0;                                       // g = cg[1]; first free ping-pong buffer = cg[0]
-    // kernel-3 weight gradients on the side stream, the input-gradient chain on s (every op's gradient in its own buffer);
-    // joined before the finish
-    bool joined = false;
-    sj.fork(s, side);
-    sc.side = side; sc.side_joined = &joined;
-    PV_TRY(pvcs::stack_bwd(p->params, G, p->enc_ops, p->n_enc_ops, p->enc_ndim, (int)B, a, L.ces, L.cg[1], L.cg, pp, false,
-                           nullptr, sc, s, 0, g_is_pre, side ? L.ceg : nullptr));
-    if (side && !joined) PV_TRY(pv_stream_after(s, side));
-    sj.joined();
-    PV_TRY(pv_wgrad_finish_all(&wfin, s));
-    if (fin && n_extra < 1) PV_TRY(pv_finish_scalars(fin->llb, fin->B, fin->scalars, fin->kl_part, fin->n_part, fin->beta, s));
-    // (the loss scalars ride in the first of these launches; every other gradient is final by now, so pv_ivae_step's Adam update
-    //  rides in the last one: its own outputs in its epilogue, the rest of the flat buffer by guest workgroups)
-    static const int ab_adam = pv_exp_int("PV_CONV_ADAM_RIDE", 1);
-    for (int i = 0; i < n_extra; i += 4) {
-      const bool last = i + 4 >= n_extra;
-      const bool ride = last && adam && adam_done && ab_adam && B <= 4096;
-      PV_TRY(pv_wgrad_small(extra + i, n_extra - i < 4 ? n_extra - i : 4, s, ride ? adam : nullptr, i == 0 ? fin : nullptr));
-      if (ride) *adam_done = true;
-    }
-    return 0;
-  }
-  const float* elast = L.eact[ne - 1];
+  if (L.enc_conv) return conv_encoder_bwd(p, L, extra, n_extra, s, fin, adam, adam_done, head_side);
   if (L.enc_compact && dgrad_done) {
     // nothing to launch here
   } else if (L.enc_compact) {
@@ -575,85 +504,73 @@ int encoder_bwd(const pv_ivae_plan* p, const Layout& L, const PvGemm* extra, int
     d.params = p->params; d.n_enc = ne; d.B = (int)B; d.head = hd; d.dhead = L.dhead;
     for (int i = 0; i < ne; ++i) { d.enc[i] = p->enc[i]; d.eact[i] = L.eact[i]; d.edp[i] = L.edp[i]; }
     if (fin) {
-      d.fin_llb = fin->llb; d.fin_scalars = fin->scalars; d.fin_kl_part = fin->kl_part; d.fin_n_part = fin->n_part;
-      d.fin_beta = fin->beta;
+      d.fin_llb = fin->llb; d.fin_scalars = fin->scalars; d.fin_kl_part = fin->kl_part; d.fin_n_part = fin->n_part; d.fin_beta = fin->beta;
     }
     PV_TRY(pv_enc_dgrad(d, s));
   } else {
-    PV_TRY(linear_dgrad(L.dhead, hd.out_dim, p->params + hd.w_off, L.edp[ne - 1], hd.in_dim, elast, L.epre[ne - 1],
+    PV_TRY(linear_dgrad(L.dhead, hd.out_dim, p->params + hd.w_off, L.edp[ne - 1], hd.in_dim, L.eact[ne - 1], L.epre[ne - 1],
                         hd.in_dim, p->enc[ne - 1].act, B, hd.in_dim, hd.out_dim, ws, wsb, s));
     for (int i = ne - 1; i > 0; --i) {
       const pv_layer& l = p->enc[i];
       PV_TRY(linear_dgrad(L.edp[i], l.out_dim, p->params + l.w_off, L.edp[i - 1], l.in_dim, L.eact[i - 1],
-                          L.epre[i - 1], p->enc[i - 1].out_dim, p->enc[i - 1].act, B, l.in_dim, l.out_dim, ws, wsb,
-                          s));
+                          L.epre[i - 1], p->enc[i - 1].out_dim, p->enc[i - 1].act, B, l.in_dim, l.out_dim, ws, wsb, s));
     }
   }
-  // (the same list, as a pure function, for the launch that closes an own-sample step: compact_wgrad_problems below — keep the two in step)
   PvGemm probs[PV_MAX_LAYERS + 4];
   int np = 0;
   for (int i = 0; i < n_extra; ++i) {
-    // a long contraction over a few output tiles (jiVAE's fc_latent: K*B decoder samples onto 128 x lat_in) would sit on
-    // a handful of workgroups in the one-tile-per-workgroup launch: split-K GEMM instead, finished before that launch
-    // so that its fused Adam guests see the final gradient
+    // split-K GEMM where the workspace has the room, finished before the one-tile-per-workgroup launch so that its fused Adam
+    // guests see the final gradient
     const PvGemm& e = extra[i];
-    const int64_t tiles = (int64_t)((e.M + 15) / 16) * ((e.N + 15) / 16);
-    const int sp = pv_gemm_pick_splits(e.M, e.N, e.K);
-    if (e.K > 1024 && tiles < 128 && sp > 1 &&
-        (int64_t)sp * e.M * (e.N + 1) * (int64_t)sizeof(float) <= wsb) PV_TRY(pv_gemm(e, sp, ws, wsb, s));
+    if (wants_split_k(e) && gemm_ws_need(e.M, e.N, e.K) <= wsb) PV_TRY(pv_gemm(e, pv_gemm_pick_splits(e.M, e.N, e.K), ws, wsb, s));
     else probs[np++] = e;
   }
-  probs[np++] = wgrad_problem(L.dhead, hd.out_dim, elast, hd.in_dim, G + hd.w_off,
-                              hd.b_off >= 0 ? G + hd.b_off : nullptr, B, hd.in_dim, hd.out_dim);
-  const float* xin = p->c_dim > 0 ? L.xin : p->x;
-  const int64_t ldx = p->n_pix + p->c_dim;
-  for (int i = ne - 1; i >= 0; --i) {
-    const pv_layer& l = p->enc[i];
-    const float* in = i > 0 ? L.eact[i - 1] : xin;
-    const int64_t ldin = i > 0 ? p->enc[i - 1].out_dim : ldx;
-    probs[np++] = wgrad_problem(L.edp[i], l.out_dim, in, ldin, G + l.w_off, l.b_off >= 0 ? G + l.b_off : nullptr, B,
-                                l.in_dim, l.out_dim);
-  }
+  np += encoder_wgrad_problems(p, L, probs + np);
   const PvFinish* fin_w = (L.enc_compact && dgrad_done) ? fin : nullptr;     // (otherwise pv_enc_dgrad hosted it)
-  if (B <= 4096 && np <= 4 && adam && adam_done && L.enc_compact) {
-    PV_TRY(pv_wgrad_small(probs, np, s, adam, fin_w));
-    *adam_done = true;
-  } else if (B <= 4096) {
-    for (int i = 0; i < np; i += 4)
-      PV_TRY(pv_wgrad_small(probs + i, np - i < 4 ? np - i : 4, s, nullptr, i == 0 ? fin_w : nullptr));
-  } else {                                   // long contractions: split-K GEMMs, one launch pair each
-    if (fin_w) PV_TRY(pv_finish_scalars(fin_w->llb, fin_w->B, fin_w->scalars, fin_w->kl_part, fin_w->n_part, fin_w->beta, s));
-    for (int i = 0; i < np; ++i)
-      PV_TRY(pv_gemm(probs[i], pv_gemm_pick_splits(probs[i].M, probs[i].N, probs[i].K), ws, wsb, s));
+  if (B <= 4096) {
+    const bool ride = np <= 4 && adam_done && L.enc_compact;
+    return wgrad_small_chunks(probs, np, s, fin_w, ride ? adam : nullptr, adam_done);
   }
+  // long contractions: split-K GEMMs, one launch pair each
+  if (fin_w) PV_TRY(finish_scalars(*fin_w, s));
+  for (int i = 0; i < np; ++i)
+    PV_TRY(pv_gemm(probs[i], pv_gemm_pick_splits(probs[i].M, probs[i].N, probs[i].K), ws, wsb, s));
   return 0;
 }
 
-// the compact (fc) encoder's weight-gradient problems behind `extra` — what encoder_bwd hands its one-tile-per-workgroup launch;
-// -1 when one of them wants the split-K GEMM or they are more than that launch takes
-int compact_wgrad_problems(const pv_ivae_plan* p, const Layout& L, const PvGemm* extra, int n_extra, PvGemm (&probs)[4]) {
-  const int64_t B = p->batch;
-  const int ne = p->n_enc;
-  if (B > 4096 || n_extra + 1 + ne > 4) return -1;
-  float* G = p->grads;
-  const pv_layer& hd = p->head;
-  int np = 0;
-  for (int i = 0; i < n_extra; ++i) {
-    const PvGemm& e = extra[i];
-    const int64_t tiles = (int64_t)((e.M + 15) / 16) * ((e.N + 15) / 16);
-    if (e.K > 1024 && tiles < 128 && pv_gemm_pick_splits(e.M, e.N, e.K) > 1) return -1;
-    probs[np++] = e;
-  }
-  probs[np++] = wgrad_problem(L.dhead, hd.out_dim, L.eact[ne - 1], hd.in_dim, G + hd.w_off, hd.b_off >= 0 ? G + hd.b_off : nullptr, B,
-                              hd.in_dim, hd.out_dim);
-  const float* xin = p->c_dim > 0 ? L.xin : p->x;
-  const int64_t ldx = p->n_pix + p->c_dim;
-  for (int i = ne - 1; i >= 0; --i) {
-    const pv_layer& l = p->enc[i];
-    probs[np++] = wgrad_problem(L.edp[i], l.out_dim, i > 0 ? L.eact[i - 1] : xin, i > 0 ? p->enc[i - 1].out_dim : ldx, G + l.w_off,
-                                l.b_off >= 0 ? G + l.b_off : nullptr, B, l.in_dim, l.out_dim);
-  }
-  return np;
+// ---- the plan's latent description, written once for every argument block that carries it ----
+// the latent geometry (which of z's leading columns are rotation / translation / scale, their priors, the KL weight and form) on
+// PvHead, PvHeadBwd, PvEncFwd or PvEncFold — kl_mode where the block has it (PvEncFold's launches take it as an argument)
+template <class D> auto set_kl_mode(D& d, int m, int) -> decltype((void)(d.kl_mode = m)) { d.kl_mode = m; }
+template <class D> void set_kl_mode(D&, int, long) {}
+template <class D> void latent_geometry(D& d, const pv_ivae_plan* p) {
+  d.z_dim = p->z_dim; d.coord_dim = p->coord_dim;
+  d.has_r = p->has_r; d.has_t = p->has_t; d.has_s = p->has_s;
+  d.tp0 = p->t_prior[0]; d.tp1 = p->t_prior[1]; d.sc_prior = p->sc_prior; d.beta = p->beta;
+  set_kl_mode(d, p->kl_mode, 0);
+}
+// where the head lives: the encoder's merged [mu | softplus input (| class logits)] rows in the workspace, or the caller's
+// (z_loc, z_scale) of an external encoder
+template <class D> void head_source(D& d, const pv_ivae_plan* p, const Layout& L) {
+  d.head = L.enc_ext ? p->ext_head : L.head; d.scale_direct = L.enc_ext ? 1 : 0;
+  d.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
+  d.w = p->row_w;
+}
+// the head's backward (reparameterised sample + KL terms -> L.dhead) without its inputs from the decoder (dzc, dtp)
+PvHeadBwd head_bwd_desc(const pv_ivae_plan* p, const Layout& L) {
+  PvHeadBwd hb{};
+  latent_geometry(hb, p);
+  head_source(hb, p, L);
+  hb.z = L.z; hb.z_scale = L.z_scale; hb.eps = p->eps; hb.B = p->batch;
+  hb.dhead = L.enc_ext ? p->ext_dhead : L.dhead;
+  return hb;
+}
+// the fused spatial decoder's weights (pv_sdec_fused.h: coord_latent, two hidden layers of 128, the output layer)
+void fused_weights(PvFused& f, const pv_ivae_plan* p) {
+  f.Wc = p->params + p->fc_coord.w_off; f.bc = p->params + p->fc_coord.b_off;
+  f.W1 = p->params + p->dec[0].w_off; f.b1 = p->params + p->dec[0].b_off;
+  f.W2 = p->params + p->dec[1].w_off; f.b2 = p->params + p->dec[1].b_off;
+  f.wo = p->params + p->out.w_off; f.bo = p->params + p->out.b_off;
 }
 
 // plan->row_w / row_elbo on the paths that form ll_b with pv_segsum: keep the unweighted ll_b, weight what the loss sums
@@ -691,15 +608,8 @@ int extra_outputs(const pv_ivae_plan* p, const Layout& L, const float* dzc, int6
 // dL/dz from the decoder (dzc: content/y columns; dtp: phi, scale, tx, ty) -> head -> encoder
 int latent_encoder_bwd(const pv_ivae_plan* p, const Layout& L, int64_t lat_in, int dtp_sb, int dtp_sc,
                        hipStream_t s) {
-  PvHeadBwd hb{};
+  PvHeadBwd hb = head_bwd_desc(p, L);
   hb.dzc = L.dzc; hb.ldzc = lat_in; hb.dtp = L.dtp; hb.dtp_sb = dtp_sb; hb.dtp_sc = dtp_sc;
-  hb.z = L.z; hb.z_scale = L.z_scale; hb.eps = p->eps;
-  hb.head = L.enc_ext ? p->ext_head : L.head; hb.dhead = L.enc_ext ? p->ext_dhead : L.dhead;
-  hb.scale_direct = L.enc_ext ? 1 : 0; hb.B = p->batch; hb.z_dim = p->z_dim; hb.coord_dim = p->coord_dim;
-  hb.has_r = p->has_r; hb.has_t = p->has_t; hb.has_s = p->has_s;
-  hb.tp0 = p->t_prior[0]; hb.tp1 = p->t_prior[1]; hb.sc_prior = p->sc_prior; hb.beta = p->beta;
-  hb.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
-  hb.w = p->row_w; hb.kl_mode = p->kl_mode;
   PV_TRY(pv_head_bwd(hb, s));
   PV_TRY(encoder_bwd(p, L, nullptr, 0, s));
   return extra_outputs(p, L, L.dzc, lat_in, s);
@@ -725,15 +635,14 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
     e.eps = p->eps; e.y = p->y; e.head_out = L.head; e.z = L.z; e.z_scale = L.z_scale;
     e.z_loc_out = p->z_loc; e.z_scale_out = p->z_scale;
     e.tp = p->coord_dim > 0 ? L.tp : nullptr; e.zy = L.zy; e.kl_part = L.kl_part;
-    e.beta = p->beta; e.beta_disc = p->beta_disc; e.K = (int)plan_K(p); e.alpha = L.alpha; e.sw = L.sw;
-    e.w = p->row_w; e.kl_mode = p->kl_mode;
+    e.beta_disc = p->beta_disc; e.K = (int)plan_K(p); e.alpha = L.alpha; e.sw = L.sw;
+    e.w = p->row_w;
     if (p->coord_dim > 0) { e.hz = L.hz; e.Wz = p->params + p->fc_latent.w_off; e.H0 = p->fc_coord.out_dim; }
     e.hz_scale = hz_scale;
     e.flags = (p->flags & PV_PLAN_ENC_TWO_LAUNCH) ? nullptr : L.enc_flags;
     e.spin_limit = (p->flags & PV_PLAN_ENC_NO_WAIT) ? 0 : 256;
-    e.B = p->batch; e.z_dim = p->z_dim; e.c_dim = p->c_dim; e.coord_dim = p->coord_dim;
-    e.has_r = p->has_r; e.has_t = p->has_t; e.has_s = p->has_s;
-    e.tp0 = p->t_prior[0]; e.tp1 = p->t_prior[1]; e.sc_prior = p->sc_prior;
+    e.B = p->batch; e.c_dim = p->c_dim;
+    latent_geometry(e, p);
     return pv_enc_fwd(e, s);
   }
   if (prep && !L.enc_conv) return PV_EINVAL;      // (stand-alone preparation on this path)
@@ -752,22 +661,18 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
       hzr->done = true;
     }
   }
-  h.head = L.enc_ext ? p->ext_head : L.head; h.scale_direct = L.enc_ext ? 1 : 0; h.eps = p->eps; h.y = p->y; h.z = L.z; h.z_scale = L.z_scale;
+  latent_geometry(h, p);
+  head_source(h, p, L);
+  h.eps = p->eps; h.y = p->y; h.z = L.z; h.z_scale = L.z_scale;
   h.z_loc_out = p->z_loc; h.z_scale_out = p->z_scale;
   h.tp = p->coord_dim > 0 ? L.tp : nullptr; h.zy = L.zy; h.scalars = p->scalars;
-  h.B = p->batch; h.z_dim = p->z_dim; h.c_dim = p->c_dim; h.coord_dim = p->coord_dim;
-  h.has_r = p->has_r; h.has_t = p->has_t; h.has_s = p->has_s;
-  h.tp0 = p->t_prior[0]; h.tp1 = p->t_prior[1]; h.sc_prior = p->sc_prior; h.beta = p->beta;
-  h.w = p->row_w; h.kl_mode = p->kl_mode;
-  h.ldh = L.enc_ext ? 0 : (int)plan_head_w(p);
+  h.B = p->batch; h.c_dim = p->c_dim;
   const int64_t K = plan_K(p);
   if (K > 0) h.zy = nullptr;                      // (written per decoder sample below)
   if (blocks) PV_TRY(pv_head_fwd_blocks(h, s));
   else PV_TRY(pv_head_fwd(h, s));
   if (K > 0) {
-    const int coord = p->z_dim - p->latent_dim;
     const int n_content = p->coord_dim > 0 ? p->latent_dim : p->z_dim;
-    (void)coord;
     PV_TRY(pv_jiv_expand(L.head, (int)plan_head_w(p), L.z, p->z_dim, n_content, p->coord_dim > 0 ? L.tp : nullptr, L.zy,
                          L.alpha, L.sw, p->scalars, p->beta_disc, p->batch, (int)K, s));
   }
@@ -796,35 +701,39 @@ static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L) {
          ((uintptr_t)p->params & 15) == 0 && ((uintptr_t)p->x & 15) == 0;
 }
 
-// loss_and_grads with the fused persistent spatial-decoder kernel (pv_sdec_fused.hip)
-int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s,
-                         const PvAdamFuse* adam = nullptr, bool* adam_done = nullptr) {
-  const int64_t B = p->batch, N = p->n_pix, R = L.rows, z = p->z_dim;
-  const int64_t K = plan_K(p), S = plan_S(p);        // jiVAE: S = K*B decoder samples, rows R = S*N
-  const int64_t lat_in = plan_lat_in(p);
-  const int H = FD_H;
-  float* G = p->grads;
-  const int coord = (int)(z - p->latent_dim);
-  const bool cat_in = p->c_dim > 0 || K > 0;         // the decoder's latent input is a materialised concatenation
-  const float* zin = cat_in ? L.zy : L.z + coord;
-  const int64_t ldz = cat_in ? lat_in : z;
-  if (p->fc_latent.in_dim != lat_in) return PV_EINVAL;
-  if (K > 0 && !L.enc_compact) return PV_EINVAL;
-  PvFused f{};
+// ---- loss_and_grads with the fused persistent spatial-decoder kernel (pv_sdec_fused.hip), step by step ----
+// what the steps hand to one another
+struct FusedStep {
+  const pv_ivae_plan* p; const Layout& L; bool grads; hipStream_t s;
+  const float* zin; int64_t ldz;                     // the decoder's latent input: z's content columns, or the materialised concatenation
+  int rec_fmt;                                       // the record format the decoder launch writes (pv_sdec_fused.h PV_REC_*)
+  PvFused f{};                                       // the decoder launch's arguments
+  PvEncFold ef{};                                    // one image's guide per workgroup: hosted by the decoder launch (fold), the per-image guide
+                                                     // launch, and the latent backward + encoder chain in a decoder launch's epilogue (own chain)
+  bool fold = false;                                 // the guide rides in the decoder launch
+  bool kl_part = false;                              // the guide left the KL sums of scalars[2], [3] as partials in L.kl_part ...
+  int kl_n = 0;                                      // ... that many: per sample when a workgroup runs an image's guide, else per 16-row block
+  // the closing form
+  PvLatentBwd lb{};                                  // latent backward + record sums, followed by the encoder backward
+  bool chain = false;                                // compact encoder: every sample's dgrad chain runs in its latent-backward workgroup
+  PvGemm wz;                                         // fc_latent: dWz = dhz^T zin; its row sums are fc_coord's bias gradient (dbc = sum_b dhz[b])
+                                                     // (jiVAE: over the K*B decoder samples, zin = [z content | onehot(k)])
+  PvGemm tail[4]; int tail_np = -1;                  // own chain: the ONE closing launch's weight-gradient problems
+  bool own_chain() const { return tail_np > 0; }
+};
+
+void fused_decoder_args(FusedStep& st) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L;
+  const int64_t B = p->batch, N = p->n_pix, R = L.rows, K = plan_K(p), S = plan_S(p);   // jiVAE: S = K*B decoder samples, rows R = S*N
+  PvFused& f = st.f;
+  fused_weights(f, p);
   f.x = p->x; f.grid = p->grid; f.tp = L.tp; f.hz = L.hz;
-  f.Wc = p->params + p->fc_coord.w_off; f.bc = p->params + p->fc_coord.b_off;
-  f.W1 = p->params + p->dec[0].w_off; f.b1 = p->params + p->dec[0].b_off;
-  f.W2 = p->params + p->dec[1].w_off; f.b2 = p->params + p->dec[1].b_off;
-  f.wo = p->params + p->out.w_off; f.bo = p->params + p->out.b_off;
   f.llrow = L.llrow; f.loc = p->loc; f.rowtp = L.f_rowtp; f.part_hz = L.f_part_hz; f.part = L.f_part;
   // (round 6) training launches of the 4-wave kernels (pv_sdec_fused_bf16.hip: the ones that write PV_REC_LANE_F32 records) hand
   // over per-slot row sums instead of rows.  NOT the 8-wave throughput kernel: it has no registers for five running sums, and
   // keeping them in LDS cost its in-order waves what the next launch saved (read-modify-write: +-0 on the step; ds_add_f32: +1.4 us
   // on the kernel — profiles/r06h_row_sums_ab.txt)
-  static const int ab_row_sums = pv_exp_int("PV_ROW_SUMS", 1);      // (experiments build: 0 = per-row outputs from the 4-wave kernels too)
-  f.part_rs = (want_grads && p->fused >= 2 && H == FD_H && ab_row_sums &&
-               pv_sdec_fused_bf16_record_fmt(p->fused == 2, R / FD_UNIT, p->dec_kernel) == PV_REC_LANE_F32)
-                  ? L.f_part_hz + S * L.f_kmax * H : nullptr;
+  f.part_rs = (st.grads && st.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
   f.wimg = L.f_wimg; f.park = L.f_park;
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
   f.sw = K > 0 ? L.sw : p->row_w; f.x_units = K > 0 ? B * N / FD_UNIT : 0;
@@ -837,126 +746,124 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
     (void)frexpf(p->decoder_sig * p->decoder_sig, &e2);      // sig^2 = m 2^e2, m in [0.5, 1)
     f.dl_exp = e2 < -40 ? -40 : (e2 > 40 ? 40 : e2);
   }
-  PvHzReq hzr{zin, ldz, (int)lat_in, H, p->params + p->fc_latent.w_off, L.hz, false, false};
+}
+
+void fold_args(PvEncFold& ef, const pv_ivae_plan* p, const Layout& L) {
+  ef.params = p->params; ef.enc0 = p->enc[0]; ef.enc1 = p->enc[1]; ef.head = p->head;
+  ef.x = p->x; ef.ldx = p->n_pix; ef.eps = p->eps;
+  ef.eact0 = L.eact[0]; ef.eact1 = L.eact[1]; ef.head_out = L.head;
+  ef.z = L.z; ef.z_scale = L.z_scale; ef.z_loc_out = p->z_loc; ef.z_scale_out = p->z_scale;
+  ef.tp = L.tp; ef.kl_part = L.kl_part; ef.hz = L.hz; ef.Wz = p->params + p->fc_latent.w_off;
+  ef.lat_in = (int)plan_lat_in(p);
+  latent_geometry(ef, p);
+}
+
+// the guide, in the cheapest form the plan allows: folded into the decoder launch (nothing to launch here), one workgroup per
+// image, the compact encoder's tiled launch, or the generic / conv encoder followed by the head — each with the preparation of the
+// bf16 decoder's weight images where fused >= 2
+int fused_guide(FusedStep& st) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
+  PvFused& f = st.f;
+  const int64_t B = p->batch, lat_in = plan_lat_in(p);
+  const float* Wz = p->params + p->fc_latent.w_off;
+  st.kl_n = L.kl_blocks;
+  st.kl_part = L.enc_compact;
   // ---- the guide folded into the decoder launch (pv_sdec_fused.h PvEncFold): the plain-bf16 8-wave kernel, a workgroup's units a
   // whole number of images, the plain fc encoder of two hidden layers — BASELINE's headline config is exactly this.  No encoder
   // launch, no weight-image copy, no hand-off: the step is decoder launch -> latent backward + record sums -> small weight gradients.
-  PvEncFold ef{};
-  bool fold = false;
-  auto fill_fold = [&]() {
-    ef.params = p->params; ef.enc0 = p->enc[0]; ef.enc1 = p->enc[1]; ef.head = p->head;
-    ef.x = p->x; ef.ldx = N; ef.eps = p->eps;
-    ef.eact0 = L.eact[0]; ef.eact1 = L.eact[1]; ef.head_out = L.head;
-    ef.z = L.z; ef.z_scale = L.z_scale; ef.z_loc_out = p->z_loc; ef.z_scale_out = p->z_scale;
-    ef.tp = L.tp; ef.kl_part = L.kl_part; ef.hz = L.hz; ef.Wz = p->params + p->fc_latent.w_off;
-    ef.lat_in = (int)lat_in; ef.z_dim = (int)z; ef.coord_dim = p->coord_dim;
-    ef.has_r = p->has_r; ef.has_t = p->has_t; ef.has_s = p->has_s;
-    ef.tp0 = p->t_prior[0]; ef.tp1 = p->t_prior[1]; ef.sc_prior = p->sc_prior; ef.beta = p->beta;
-  };
   if (plan_guide_may_fold(p, L)) {       // (no cross-workgroup hand-off in it: fine under stream capture too)
     f.hz_scale = 2.8853900817779268f;
-    fold = pv_sdec_fused_fold_ok(f, L.f_grid, p->fused == 2);
-    if (fold) fill_fold();
-    else f.hz_scale = 0.0f;
-    // (the hosting launch owns whole images: it sums their per-row outputs itself in its epilogue — PvFused::part_rs, first slot)
-    static const int ab_fold_rs = pv_exp_int("PV_FOLD_RS", 1);      // (experiments build: 0 = the latent backward reduces the rows)
-    if (fold && want_grads && H == FD_H && f.llrow && ab_fold_rs) f.part_rs = L.f_part_hz + S * L.f_kmax * H;
-    // ... and its dL/d(hz): the eight waves' partials summed next to the other column sums (PvFused::dhz_out)
-    static const int ab_fold_dhz = pv_exp_int("PV_FOLD_DHZ", 1);
-    if (fold && want_grads && H == FD_H && ab_fold_dhz) {
-      f.dhz_out = L.dhz;
-      if (ab_fold_dhz > 1 || ab_fold_dhz == 1) f.dzc_out = (ab_fold_dhz == 2) ? nullptr : L.dzc;      // (PV_FOLD_DHZ=2: dhz only, A/B)
-    }
+    st.fold = pv_sdec_fused_fold_ok(f, L.f_grid, p->fused == 2);
+    if (!st.fold) f.hz_scale = 0.0f;
   }
-  int kl_n = fold ? (int)B : L.kl_blocks;            // KL partial sums in L.kl_part: per sample when a workgroup runs an image's guide, else per 16-row block
-  if (fold) {
-    // (nothing to launch before the decoder kernel)
-  } else if (p->fused >= 2 && L.enc_compact) {
-    const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, want_grads != 0, p->fused == 2);
+  if (st.fold) {
+    fold_args(st.ef, p, L);
+    st.kl_n = (int)B;
+    if (st.grads) {
+      // the hosting launch owns whole images: it sums their per-row outputs itself in its epilogue (PvFused::part_rs, first slot),
+      // and its dL/d(hz): the eight waves' partials summed next to the other column sums (PvFused::dhz_out)
+      f.part_rs = L.f_part_hz + plan_S(p) * L.f_kmax * FD_H;
+      f.dhz_out = L.dhz; f.dzc_out = L.dzc;
+    }
+    return 0;
+  }
+  if (p->fused >= 2 && L.enc_compact) {
+    const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2);
     f.hz_scale = prep.scale;                          // the compact encoder's last launch writes scale * hz directly
     // (round 6) the guide as one workgroup per image (pv_guide_img.hip: no tile hand-offs, 11-13 us where the tiled one-launch
     // encoder takes 18-19) for the minibatch sizes where every image streaming the first-layer matrix from L2 is still cheaper
     // than that latency; the flags that are about the tiled encoder's launch form keep the tiled encoder
-    fill_fold();
-    const bool per_image = plan_guide_one_image(p, L) && pv_guide_img_ok(ef, (int)B) &&
-                           !(p->flags & (PV_PLAN_ENC_TILED | PV_PLAN_ENC_TWO_LAUNCH | PV_PLAN_ENC_NO_WAIT));
-    if (per_image) {
-      PV_TRY(pv_guide_img_launch(ef, &prep, f.hz_scale, (int)B, s, p->kl_mode));
-      kl_n = (int)B;
-    } else {
-      PV_TRY(guide_fwd(p, L, s, &prep, f.hz_scale));
+    fold_args(st.ef, p, L);
+    if (plan_guide_one_image(p, L) && pv_guide_img_ok(st.ef, (int)B) &&
+        !(p->flags & (PV_PLAN_ENC_TILED | PV_PLAN_ENC_TWO_LAUNCH | PV_PLAN_ENC_NO_WAIT))) {
+      st.kl_n = (int)B;
+      return pv_guide_img_launch(st.ef, &prep, f.hz_scale, (int)B, s, p->kl_mode);
     }
-  } else {
-    // conv encoder: the decoder's weight images ride in its weight-tiling launch; generic encoders: a launch of their own
-    const bool prep_in_enc = p->fused >= 2 && L.enc_conv;
-    const PvFbPrep prep = p->fused >= 2 ? pv_sdec_fused_bf16_prep_args(f, want_grads != 0, p->fused == 2) : PvFbPrep{};
-    PV_TRY(guide_fwd(p, L, s, prep_in_enc ? &prep : nullptr, 0.0f, &hzr));
-    if (p->fused >= 2 && !prep_in_enc) {
-      PV_TRY(pv_sdec_fused_bf16_prep(f, want_grads != 0, p->fused == 2, s));
-    } else if (p->fused >= 2) {
-      // (done)
-    } else if (want_grads) {
-      hipError_t e = hipMemsetAsync(L.f_part_hz, 0, (size_t)(S * L.f_kmax * H) * sizeof(float), s);
-      if (e != hipSuccess) return (int)e;
-    }
+    return guide_fwd(p, L, s, &prep, f.hz_scale);
   }
-  if (!L.enc_compact && !hzr.done) {
-    if (lat_in <= 16) PV_TRY(pv_smallk_linear(zin, ldz, p->params + p->fc_latent.w_off, L.hz, B, (int)lat_in, (int)H, s));
-    else PV_TRY(linear_fwd(zin, ldz, p->params + p->fc_latent.w_off, nullptr, L.hz, nullptr, H, B, lat_in, H, PV_ACT_NONE,
-                           L.scratch, L.scratch_bytes, s));
+  // conv encoder: the decoder's weight images ride in its weight-tiling launch; generic encoders: a launch of their own
+  PvHzReq hzr{st.zin, st.ldz, (int)lat_in, FD_H, Wz, L.hz, false, false};
+  const bool prep_in_enc = p->fused >= 2 && L.enc_conv;
+  const PvFbPrep prep = p->fused >= 2 ? pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2) : PvFbPrep{};
+  PV_TRY(guide_fwd(p, L, s, prep_in_enc ? &prep : nullptr, 0.0f, &hzr));
+  if (p->fused >= 2 && !prep_in_enc) {
+    PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, p->fused == 2, s));
+  } else if (p->fused < 2 && st.grads) {
+    hipError_t e = hipMemsetAsync(L.f_part_hz, 0, (size_t)(plan_S(p) * L.f_kmax * FD_H) * sizeof(float), s);
+    if (e != hipSuccess) return (int)e;
   }
-  PvFusedOffsets o{p->dec[0].w_off, p->dec[0].b_off, p->dec[1].w_off, p->dec[1].b_off,
-                   p->fc_coord.w_off, p->out.w_off, p->out.b_off};
-  // per sample: ll_b, d(phi, scale, tx, ty), dL/d(hz), dL/d(z content), head backward -> L.dhead ; in the same
-  // launch: the per-workgroup gradient records summed into the flat gradient
-  PvLatentBwd lb{};
-  lb.llrow = L.llrow; lb.rowtp = L.f_rowtp; lb.part_hz = L.f_part_hz; lb.Wz = p->params + p->fc_latent.w_off;
-  // (round 6) the 4-wave kernels too, wherever every workgroup's units are exactly one sample (batch == grid, e.g. C2's 256 on 256 CUs)
-  static const int ab_own = pv_exp_int("PV_OWN_SAMPLE", 1);
-  if (ab_own && !f.dhz_out && f.part_rs && K == 0 && lat_in <= 16 && S == L.f_grid && f.units == S * (N / FD_UNIT) &&
-      !p->dy && pv_sdec_fused_bf16_record_fmt(p->fused == 2, R / FD_UNIT, p->dec_kernel) == PV_REC_LANE_F32) {
-    f.dhz_out = L.dhz; f.dzc_out = L.dzc; f.Wz = p->params + p->fc_latent.w_off; f.lat_in = (int)lat_in;
+  st.kl_part = L.enc_compact || hzr.kl;
+  if (!L.enc_compact && !hzr.done) {                 // fc_latent did not ride in the head launch
+    if (lat_in <= 16) PV_TRY(pv_smallk_linear(st.zin, st.ldz, Wz, L.hz, B, (int)lat_in, FD_H, s));
+    else PV_TRY(linear_fwd(st.zin, st.ldz, Wz, nullptr, L.hz, nullptr, FD_H, B, lat_in, FD_H, PV_ACT_NONE, L.scratch, L.scratch_bytes, s));
   }
+  return 0;
+}
+
+// how the step closes after the decoder launch: (a) pv_latent_bwd_reduce (per sample: ll_b, d(phi, scale, tx, ty), dL/d(hz),
+// dL/d(z content), head backward -> L.dhead; in the same launch the per-workgroup gradient records summed into the flat gradient)
+// followed by the encoder backward, or (b) the own chain: every workgroup of the decoder launch owns one image and runs its latent
+// backward and encoder chain in its epilogue, and ONE launch of workgroups that need nothing from each other closes the step
+void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L;
+  PvFused& f = st.f;
+  const int64_t N = p->n_pix, R = L.rows, z = p->z_dim, K = plan_K(p), S = plan_S(p), lat_in = plan_lat_in(p);
+  const int H = FD_H;
+  const float* Wz = p->params + p->fc_latent.w_off;
+  // (round 6) the 4-wave kernels too hand over dL/d(hz) and dL/dz, wherever every workgroup's units are exactly one sample
+  // (batch == grid, e.g. C2's 256 on 256 CUs)
+  if (!f.dhz_out && f.part_rs && K == 0 && lat_in <= 16 && S == L.f_grid && f.units == S * (N / FD_UNIT) && !p->dy &&
+      st.rec_fmt == PV_REC_LANE_F32) {
+    f.dhz_out = L.dhz; f.dzc_out = L.dzc; f.Wz = Wz; f.lat_in = (int)lat_in;
+  }
+  PvLatentBwd& lb = st.lb;
+  lb.llrow = L.llrow; lb.rowtp = L.f_rowtp; lb.part_hz = L.f_part_hz; lb.Wz = Wz;
   lb.part_rs = f.part_rs;
   lb.dhz_ready = f.dhz_out ? 1 : 0;
   lb.dzc_in = f.dzc_out;
   lb.llb = L.llb; lb.dhz = L.dhz; lb.M = R; lb.N = (int)N; lb.kmax = L.f_kmax; lb.H = H; lb.lat_in = (int)lat_in;
-  PvHeadBwd& hb = lb.hb;
-  hb.z = L.z; hb.z_scale = L.z_scale; hb.eps = p->eps;
-  hb.head = L.enc_ext ? p->ext_head : L.head; hb.dhead = L.enc_ext ? p->ext_dhead : L.dhead;
-  hb.scale_direct = L.enc_ext ? 1 : 0;
-  hb.B = (int)B; hb.z_dim = (int)z; hb.coord_dim = p->coord_dim;
-  hb.has_r = p->has_r; hb.has_t = p->has_t; hb.has_s = p->has_s;
-  hb.tp0 = p->t_prior[0]; hb.tp1 = p->t_prior[1]; hb.sc_prior = p->sc_prior; hb.beta = p->beta;
-  hb.ldh = L.enc_ext ? 0 : (int)plan_head_w(p); hb.kl_mode = p->kl_mode;
+  lb.hb = head_bwd_desc(p, L);
   lb.K = (int)K; lb.alpha = L.alpha; lb.beta_disc = p->beta_disc;
-  hb.w = p->row_w; lb.row_ll = p->row_elbo ? L.row_ll : nullptr; lb.dzc_out = p->dy ? L.dzc : nullptr;
+  lb.row_ll = p->row_elbo ? L.row_ll : nullptr; lb.dzc_out = p->dy ? L.dzc : nullptr;
   // compact encoder: every sample's dgrad chain runs in its latent_bwd workgroup (one dependent launch less)
-  static const int chain_env = pv_exp_int("PV_CHAIN", 1) ? 1 : 0;          // PV_CHAIN=0: keep pv_enc_dgrad as its own launch (A/B timing, experiments build)
-  const bool chain = chain_env && L.enc_compact && !L.enc_ext && 2 * z + K <= 256;
-  if (chain) {
+  st.chain = L.enc_compact && !L.enc_ext && 2 * z + K <= 256;
+  if (st.chain) {
     lb.enc_n = p->n_enc; lb.enc_params = p->params; lb.enc_head = p->head;
     for (int i = 0; i < p->n_enc; ++i) { lb.enc_l[i] = p->enc[i]; lb.enc_act[i] = L.eact[i]; lb.enc_dp[i] = L.edp[i]; }
   }
-  // (round 6, third cut) where every workgroup of the decoder launch owns one image — the launch that hosts the guide, or a 4-wave
-  // launch at batch == grid — it also runs the image's latent backward and encoder chain in its epilogue (PvEncFold::chain), and the
-  // step closes with ONE launch of workgroups that need
-  // nothing from each other: record sums, small weight gradients, loss scalars (pv_elementwise.hip: pv_rec_wgrad_kernel).
-  // Needs what that epilogue is written for (the plain iVAE step: no per-sample weights / extra outputs, a head of <= 16 outputs)
-  // and — with the optimizer riding — records + tiles covering every parameter.
-  static const int ab_tail = pv_exp_int("PV_FOLD_CHAIN", 1);
-  const int rec_fmt = p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, R / FD_UNIT, p->dec_kernel) : PV_REC_ROWMAJOR;
-  const PvGemm wz = wgrad_problem(L.dhz, H, zin, ldz, G + p->fc_latent.w_off, G + p->fc_coord.b_off, S, lat_in, H);
-  PvGemm tail_probs[4];
-  int tail_np = -1;
-  // (f.dhz_out / dzc_out / part_rs together: the hosting 8-wave launch, or a 4-wave launch whose workgroups own one sample each)
-  // (the decoder launches' epilogue differentiates the sampled KL form only: the analytic form takes the latent-backward launch)
-  if (ab_tail && want_grads && chain && f.part_rs && f.dhz_out && f.dzc_out && K == 0 && H == FD_H && !p->row_w &&
-      p->kl_mode == PV_KL_SAMPLED &&
-      !p->row_elbo && !p->dy && p->head.out_dim <= 16 && p->n_enc == 2 && p->enc[0].out_dim == FD_H && p->enc[1].in_dim == FD_H &&
-      p->enc[1].out_dim == FD_H && p->head.in_dim == FD_H) {      // (the epilogue's chain is written for two hidden layers of width 128)
-    tail_np = compact_wgrad_problems(p, L, &wz, 1, tail_probs);
-    if (tail_np > 0 && adam) {
+  st.wz = wgrad_problem(L.dhz, H, st.zin, st.ldz, p->grads + p->fc_latent.w_off, p->grads + p->fc_coord.b_off, S, lat_in, H);
+  // (round 6, third cut) the own chain: where every workgroup of the decoder launch owns one image — the launch that hosts the
+  // guide, or a 4-wave launch at batch == grid (f.dhz_out / dzc_out / part_rs together) — it also runs the image's latent backward
+  // and encoder chain in its epilogue (PvEncFold::chain), and the step closes with record sums, small weight gradients and loss
+  // scalars in one launch (pv_elementwise.hip: pv_rec_wgrad_kernel).
+  // Needs what that epilogue is written for — the plain iVAE step: no per-sample weights / extra outputs, a head of <= 16 outputs,
+  // two hidden layers of width 128, the sampled KL form (the analytic form takes the latent-backward launch) — and, with the
+  // optimizer riding, records + tiles covering every parameter.
+  if (st.chain && f.part_rs && f.dhz_out && f.dzc_out && K == 0 && !p->row_w && p->kl_mode == PV_KL_SAMPLED && !p->row_elbo &&
+      !p->dy && p->head.out_dim <= 16 && p->n_enc == 2 && p->enc[0].out_dim == FD_H && p->enc[1].in_dim == FD_H &&
+      p->enc[1].out_dim == FD_H && p->head.in_dim == FD_H) {
+    st.tail_np = one_launch_wgrad_problems(p, L, &st.wz, 1, st.tail);
+    if (st.tail_np > 0 && adam) {
       // every PARAMETER must be finalised by a record block or a tile (the launch has no Adam guests): the plan's layers, counted,
       // against what the records and the tiles cover.  What else the flat buffer holds — alignment padding, batch-norm statistics —
       // never has a gradient or a moment, and Adam leaves such an element where it is.
@@ -965,59 +872,82 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
       for (int i = 0; i < p->n_enc; ++i) want += lsz(p->enc[i]);
       for (int i = 0; i < p->n_dec; ++i) want += lsz(p->dec[i]);
       int64_t cov = 2 * (int64_t)H * H + (int64_t)H * (3 + p->coord_dim) + 1;
-      for (int i = 0; i < tail_np; ++i) cov += (int64_t)tail_probs[i].M * tail_probs[i].N + (tail_probs[i].rowsumA ? tail_probs[i].M : 0);
-      if (cov != want || !adam_done || p->n_dec != 2) tail_np = -1;
+      for (int i = 0; i < st.tail_np; ++i) cov += (int64_t)st.tail[i].M * st.tail[i].N + (st.tail[i].rowsumA ? st.tail[i].M : 0);
+      if (cov != want || !adam_done || p->n_dec != 2) st.tail_np = -1;
     }
   }
-  const bool own_chain = tail_np > 0;
-  if (own_chain) {
+  if (st.own_chain()) {
+    PvEncFold& ef = st.ef;
     ef.chain = 1; ef.dhead = L.dhead; ef.ldh = (int)plan_head_w(p); ef.edp0 = L.edp[0]; ef.edp1 = L.edp[1]; ef.llb = L.llb;
-    // ... and, in the hosting launch, the guide's first layer shared among the workgroups of a group (pv_sdec_fused_w8.hip, build 3):
-    // its hand-off tags live in coop_flags, whose last word this step's closing launch increments
-    static const int ab_coop = pv_exp_int("PV_COOP_L0", 0);          // (experiments build only; measured slower than every workgroup for itself)
-    if (fold && ab_coop && L.f_grid <= 1024) { ef.coop = 1; ef.coop_flags = L.coop_flags; }
   }
-  if (p->ev_start && p->ev_stop) (void)hipEventRecord((hipEvent_t)p->ev_start, s);
-  if (p->fused >= 2) PV_TRY(pv_sdec_fused_bf16_launch(f, L.f_grid, want_grads != 0, p->fused == 2, s, fold ? &ef : nullptr,
-                                                      (own_chain && !fold) ? &ef : nullptr));
-  else PV_TRY(pv_sdec_fused_launch(f, L.f_grid, want_grads != 0, s));
-  if (p->ev_start && p->ev_stop) (void)hipEventRecord((hipEvent_t)p->ev_stop, s);
-  if (!want_grads && K > 0) {                        // llb[b] = sum_k alpha_bk ll_kb
+}
+
+int fused_decoder_launch(FusedStep& st) {
+  const pv_ivae_plan* p = st.p;
+  const bool timed = p->ev_start && p->ev_stop;
+  if (timed) (void)hipEventRecord((hipEvent_t)p->ev_start, st.s);
+  if (p->fused >= 2) PV_TRY(pv_sdec_fused_bf16_launch(st.f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
+                                                      (st.own_chain() && !st.fold) ? &st.ef : nullptr));
+  else PV_TRY(pv_sdec_fused_launch(st.f, st.L.f_grid, st.grads, st.s));
+  if (timed) (void)hipEventRecord((hipEvent_t)p->ev_stop, st.s);
+  return 0;
+}
+
+// no gradients: ll_b from the decoder's rows, the loss scalars, the extra outputs
+int fused_close_forward(const FusedStep& st) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
+  const int64_t B = p->batch, N = p->n_pix, K = plan_K(p);
+  if (K > 0) {                                       // llb[b] = sum_k alpha_bk ll_kb
     PvLatentBwd lf{};
-    lf.llrow = L.llrow; lf.llb = L.llb; lf.M = R; lf.N = (int)N; lf.H = 0; lf.K = (int)K; lf.alpha = L.alpha;
+    lf.llrow = L.llrow; lf.llb = L.llb; lf.M = L.rows; lf.N = (int)N; lf.H = 0; lf.K = (int)K; lf.alpha = L.alpha;
     lf.hb.B = (int)B; lf.fwd_only = 1;
     PV_TRY(pv_latent_bwd(lf, s));
     return pv_finish_scalars(L.llb, (int)B, p->scalars, L.kl_part, L.kl_blocks, 1.0f, s);
   }
-  if (!want_grads) {
-    PV_TRY(pv_segsum(L.llrow, B, N, L.llb, s));
-    PV_TRY(weigh_llb(p, L, s));
-    PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, (L.enc_compact || hzr.kl) ? L.kl_part : nullptr, kl_n, 1.0f /* partials come scaled */, s));
-    return extra_outputs(p, L, nullptr, lat_in, s);
-  }
-  // conv encoder with a side stream: the head's weight gradient forks off this launch (encoder_bwd)
+  PV_TRY(pv_segsum(L.llrow, B, N, L.llb, s));
+  PV_TRY(weigh_llb(p, L, s));
+  PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, st.kl_part ? L.kl_part : nullptr, st.kl_n, 1.0f /* partials come scaled */, s));
+  return extra_outputs(p, L, nullptr, plan_lat_in(p), s);
+}
+
+int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
+  const PvFusedOffsets o{p->dec[0].w_off, p->dec[0].b_off, p->dec[1].w_off, p->dec[1].b_off,
+                         p->fc_coord.w_off, p->out.w_off, p->out.b_off};
+  // conv encoder with a side stream: the head's weight gradient forks off the closing launch (conv_encoder_bwd)
   static const int ab_side = pv_exp_int("PV_HEAD_SIDE", 1);
   static const int ab_fin = pv_exp_int("PV_FIN_RIDE", 1);
   const bool head_side = ab_side && L.enc_conv && !L.enc_ext && pv_side_stream_for(s, p->flags) && !pv_convhead_wgrad_uses_ws() &&
                          pv_convhead_supported(L.cF, p->head.out_dim) && L.chead_wt;
   if (head_side) pv_fork_arm();
-  if (own_chain) {
-    const PvFinish fin{L.llb, (int)B, p->scalars, L.kl_part, kl_n, 1.0f /* scaled */};
-    PV_TRY(pv_rec_wgrad(L.f_part, L.f_grid, G, o, p->coord_dim, rec_fmt, tail_probs, tail_np, adam, &fin, s,
-                        (fold && ef.coop) ? L.coop_flags + L.f_grid : nullptr));
+  PvFinish fin{L.llb, (int)p->batch, p->scalars, st.kl_part ? L.kl_part : nullptr, st.kl_n, 1.0f /* partials come scaled */};
+  if (st.own_chain()) {
+    PV_TRY(pv_rec_wgrad(L.f_part, L.f_grid, p->grads, o, p->coord_dim, st.rec_fmt, st.tail, st.tail_np, adam, &fin, s));
     if (adam) *adam_done = true;
-    return extra_outputs(p, L, L.dzc, lat_in, s);
+    return extra_outputs(p, L, L.dzc, plan_lat_in(p), s);
   }
-  // (rec_fmt: the record format the decoder launch above wrote: pv_sdec_fused.h PV_REC_*)
-  PV_TRY(pv_latent_bwd_reduce(lb, L.f_part, L.f_grid, G, o, p->coord_dim, s, rec_fmt));
+  PV_TRY(pv_latent_bwd_reduce(st.lb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
   // the loss scalars ride in the encoder dgrad launch (compact encoder), in the last weight-gradient launch (conv encoder) or get their own
-  PvFinish fin{L.llb, (int)B, p->scalars, (L.enc_compact || hzr.kl) ? L.kl_part : nullptr, kl_n, 1.0f /* scaled */};
   const bool fin_rides = L.enc_compact || (ab_fin && L.enc_conv && !L.enc_ext);
-  if (!fin_rides) PV_TRY(pv_finish_scalars(fin.llb, fin.B, fin.scalars, fin.kl_part, fin.n_part, fin.beta, s));
-  // fc_latent: dWz = dhz^T zin; its row sums are fc_coord's bias gradient (dbc = sum_b dhz[b])
-  // (jiVAE: over the K*B decoder samples, zin = [z content | onehot(k)])
-  PV_TRY(encoder_bwd(p, L, &wz, 1, s, fin_rides ? &fin : nullptr, adam, adam_done, chain, head_side));
-  return extra_outputs(p, L, L.dzc, lat_in, s);
+  if (!fin_rides) PV_TRY(finish_scalars(fin, s));
+  PV_TRY(encoder_bwd(p, L, &st.wz, 1, s, fin_rides ? &fin : nullptr, adam, adam_done, st.chain, head_side));
+  return extra_outputs(p, L, L.dzc, plan_lat_in(p), s);
+}
+
+// the step's launch sequence
+int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s,
+                         const PvAdamFuse* adam = nullptr, bool* adam_done = nullptr) {
+  const int64_t K = plan_K(p), lat_in = plan_lat_in(p);
+  if (p->fc_latent.in_dim != lat_in) return PV_EINVAL;
+  if (K > 0 && !L.enc_compact) return PV_EINVAL;
+  const bool cat_in = p->c_dim > 0 || K > 0;         // the decoder's latent input is a materialised concatenation
+  FusedStep st{p, L, want_grads != 0, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
+               p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, p->dec_kernel) : PV_REC_ROWMAJOR};
+  fused_decoder_args(st);
+  PV_TRY(fused_guide(st));
+  if (want_grads) fused_closing_form(st, adam, adam_done);
+  PV_TRY(fused_decoder_launch(st));
+  return want_grads ? fused_close(st, adam, adam_done) : fused_close_forward(st);
 }
 
 int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s) {
@@ -1050,7 +980,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   if (p->coord_dim > 0) {
     PvOutLik o{};
     o.h = hlast; o.hpre = L.dpre_[nd - 1]; o.ldh = Hl; o.wo = p->params + p->out.w_off;
-    o.bo = p->out.b_off >= 0 ? p->params + p->out.b_off : nullptr; o.x = p->x; o.loc = p->loc; o.llrow = L.llrow;
+    o.bo = bias_of(p->params, p->out); o.x = p->x; o.loc = p->loc; o.llrow = L.llrow;
     o.dpre = want_grads ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = K > 0 ? L.sw : p->row_w; o.N = (int)N; o.xmod = K > 0 ? B * N : 0;
@@ -1089,7 +1019,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     if (p->out.b_off >= 0) PV_TRY(pv_reduce_partials(L.part_dbo, (int)ob, 1, G + p->out.b_off, 1, s));
   } else {
     // out layer of the vanilla decoder: logits = hlast Wout^T + bout
-    PV_TRY(linear_wgrad(oth, N, hlast, Hl, G + p->out.w_off, p->out.b_off >= 0 ? G + p->out.b_off : nullptr, R, Hl, N,
+    PV_TRY(linear_wgrad(oth, N, hlast, Hl, G + p->out.w_off, bias_of(G, p->out), R, Hl, N,
                         ws, wsb, s));
     PV_TRY(linear_dgrad(oth, N, p->params + p->out.w_off, cur, Hl, hlast, L.dpre_[nd - 1], Hl, p->dec[nd - 1].act, R,
                         Hl, N, ws, wsb, s));
@@ -1100,7 +1030,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     if (i > 0) { in = L.dact[i - 1]; inpre = L.dpre_[i - 1]; ldin = p->dec[i - 1].out_dim; act_in = p->dec[i - 1].act; }
     else if (p->coord_dim > 0) { in = L.h0; inpre = nullptr; ldin = p->fc_coord.out_dim; act_in = PV_ACT_TANH; }
     else { in = zin; inpre = nullptr; ldin = ldz; act_in = PV_ACT_NONE; }
-    PV_TRY(linear_wgrad(cur, l.out_dim, in, ldin, G + l.w_off, l.b_off >= 0 ? G + l.b_off : nullptr, R, l.in_dim,
+    PV_TRY(linear_wgrad(cur, l.out_dim, in, ldin, G + l.w_off, bias_of(G, l), R, l.in_dim,
                         l.out_dim, ws, wsb, s));
     if (i > 0 || p->coord_dim > 0) {
       PV_TRY(linear_dgrad(cur, l.out_dim, p->params + l.w_off, oth, l.in_dim, in, inpre, ldin, act_in, R, l.in_dim,
@@ -1209,10 +1139,7 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   PvFused f{};
   f.x = D.xdummy; f.x_units = 1;                       // (no observations: every unit reads the same 16 zeros)
   f.grid = lay->grid; f.tp = D.tp; f.hz = D.hz;
-  f.Wc = lay->params + lay->fc_coord.w_off; f.bc = lay->params + lay->fc_coord.b_off;
-  f.W1 = lay->params + lay->dec[0].w_off; f.b1 = lay->params + lay->dec[0].b_off;
-  f.W2 = lay->params + lay->dec[1].w_off; f.b2 = lay->params + lay->dec[1].b_off;
-  f.wo = lay->params + lay->out.w_off; f.bo = lay->params + lay->out.b_off;
+  fused_weights(f, lay);
   f.llrow = nullptr; f.loc = loc; f.wimg = D.wimg;
   f.M = B * N; f.units = f.M / FD_UNIT; f.N = (int)N; f.cd = lay->coord_dim; f.B = (int)B;
   f.lik = PV_LIK_GAUSSIAN; f.sigmoid_out = lay->sigmoid_out; f.sig = 1.0f;      // loc = sigmoid(a) or a
@@ -1430,45 +1357,11 @@ extern "C" int pv_ivae_decode(const pv_ivae_plan* plan, const float* z, float an
   if (plan->coord_dim > 0) {
     PvOutLik o{};
     o.h = L.dact[nd - 1]; o.ldh = plan->dec[nd - 1].out_dim; o.wo = plan->params + plan->out.w_off;
-    o.bo = plan->out.b_off >= 0 ? plan->params + plan->out.b_off : nullptr;
+    o.bo = bias_of(plan->params, plan->out);
     o.x = L.llrow /* unused for loc */; o.loc = loc; o.llrow = nullptr; o.dpre = nullptr; o.M = R;
     o.H = plan->dec[nd - 1].out_dim; o.lik = PV_LIK_GAUSSIAN; o.sigmoid_out = plan->sigmoid_out; o.sig = 1.0f;
     o.act_last = plan->dec[nd - 1].act;
     return pv_out_lik(o, s);
   }
   return pv_lik_elem(L.logits, L.logits, B * N, PV_LIK_GAUSSIAN, plan->sigmoid_out, 1.0f, loc, nullptr, nullptr, s);
-}
-
-// ---- building blocks -------------------------------------------------------------------------
-extern "C" int64_t pv_linear_workspace_bytes(int64_t M, int64_t K, int64_t N) {
-  if (M < 0 || K <= 0 || N <= 0) return PV_EINVAL;
-  int64_t need = gemm_ws_need(M, N, K);
-  const int64_t a = gemm_ws_need(M, K, N), b = gemm_ws_need(N, K, M), c = pv_colsum_ws(M, (int)N);
-  if (a > need) need = a;
-  if (b > need) need = b;
-  if (c > need) need = c;
-  return pv_align_up(need, 256);
-}
-
-extern "C" int pv_linear_fwd(const float* x, int64_t ldx, const float* w, const float* b, float* y, float* pre,
-                             int64_t ldy, int64_t M, int64_t K, int64_t N, int act, void* ws, int64_t ws_bytes,
-                             void* stream) {
-  if (!x || !w || !y || M < 0 || K <= 0 || N <= 0) return PV_EINVAL;
-  return linear_fwd(x, ldx, w, b, y, pre, ldy, M, K, N, act, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int pv_linear_bwd(const float* dpre, int64_t lddp, const float* x, int64_t ldx, const float* w, float* dx,
-                             int64_t lddx, const float* xact, const float* xpre, int64_t ldxa, int act_prev, float* dw,
-                             float* db, int64_t M, int64_t K, int64_t N, void* ws, int64_t ws_bytes, void* stream) {
-  if (!dpre || M < 0 || K <= 0 || N <= 0) return PV_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dx) {
-    if (!w) return PV_EINVAL;
-    PV_TRY(linear_dgrad(dpre, lddp, w, dx, lddx, xact, xpre, ldxa, act_prev, M, K, N, ws, ws_bytes, s));
-  }
-  if (dw || db) {
-    if (dw && !x) return PV_EINVAL;
-    PV_TRY(linear_wgrad(dpre, lddp, x, ldx, dw, db, M, K, N, ws, ws_bytes, s));
-  }
-  return 0;
 }

@@ -147,7 +147,13 @@ bool dec1d_active(const pv_ved_plan* p, const VLayout& L) {
 
 // the head (reparameterised sample, its KL terms, its backward) in the decoder's launches: with latent_to_features there
 bool head_folded(const pv_ved_plan* p, const VLayout& L) {
-  return dec1d_active(p, L) && L.l2f_wt && pv_dec1d_l2f_ok(p->z_dim) && !pv_exp_str("PV_NO_HEADFOLD");
+  return dec1d_active(p, L) && L.l2f_wt && pv_dec1d_l2f_ok(p->z_dim);
+}
+
+// features2latent behind the encoder stack (pvcs::conv_head_fwd / conv_head_bwd)
+pvcs::ConvHead ved_head(const pv_ved_plan* p, const VLayout& L) {
+  return {p->head, p->params, p->grads, L.ea[p->n_enc_ops], L.es[p->n_enc_ops], (int)p->batch, L.head_wt, L.feat, L.head, L.dhead,
+          L.sc.ws, L.sc.ws_bytes};
 }
 
 // tile the conv weights the coming launches need: stack 0 / 1 / both, with or without the input-gradient orientation
@@ -181,30 +187,15 @@ int ved_encoder_fwd(const pv_ved_plan* p, VLayout& L, float* z_loc_out, float* z
   const float* x = p->x;
   if (p->in_ch > 1) { PV_TRY(pv_ncs_to_nsc(p->x, L.x_nsc, B, p->in_ch, (int64_t)s0.H * s0.W, s)); x = L.x_nsc; }
   L.ea[0] = const_cast<float*>(x);
-  if (p->conv_ev_start && p->conv_ev_stop) {          // measurement: events around the heaviest kernel-3 convolution
-    double fl = 0.0;
-    L.sc.ev_op = pvcs::heaviest_conv(p->enc, p->n_enc_ops, p->ndim_in, (int)B, L.es, &fl);
-    L.sc.ev_start = p->conv_ev_start; L.sc.ev_stop = p->conv_ev_stop;
-    if (p->conv_ev_flops) *p->conv_ev_flops = fl;
-  }
+  pvcs::time_heaviest_conv(L.sc, p->enc, p->n_enc_ops, p->ndim_in, (int)B, L.es, p->conv_ev_start, p->conv_ev_stop, p->conv_ev_flops);
   PV_TRY(pvcs::stack_fwd(p->params, p->enc, p->n_enc_ops, p->ndim_in, (int)B, L.ea, L.es, L.sc, s));
   L.sc.ev_op = -1;
-  const Shape& fe = L.es[p->n_enc_ops];
-  // torch flattens (C, spatial): features2latent sees channels-first order — the weight is re-indexed, not the features
+  // torch flattens (C, spatial): features2latent sees channels-first order — the weight is re-indexed, not the features.
+  // Head folded into the decoder's launch: the partial sums meet there (it writes L.head), where that form of the head exists
+  const bool folded = with_kl && head_folded(p, L);
   L.head_part = nullptr;
-  if (L.head_wt && with_kl && head_folded(p, L) && !pv_exp_str("PV_NO_HEADPART") &&
-      pv_convhead_fwd_partials(L.ea[p->n_enc_ops], L.head_wt, (int)B, L.F, 2 * p->z_dim, L.sc.ws, L.sc.ws_bytes, s, &L.head_part,
-                               &L.head_nseg) == 0) {
-    // (the partial sums meet in the decoder's launch, which writes L.head)
-  } else if (L.head_wt) {
-    PV_TRY(pv_convhead_fwd(L.ea[p->n_enc_ops], L.head_wt, p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr, L.head,
-                           (int)B, L.F, 2 * p->z_dim, L.sc.ws, L.sc.ws_bytes, s));
-  } else {
-    PV_TRY(pv_nsc_to_ncs(L.ea[p->n_enc_ops], L.feat, B, fe.C, (int64_t)fe.H * fe.W, s));
-    PV_TRY(linear_fwd(L.feat, L.F, p->params + p->head.w_off, p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr,
-                      L.head, nullptr, 2 * p->z_dim, B, L.F, 2 * p->z_dim, PV_ACT_NONE, L.sc.ws, L.sc.ws_bytes, s));
-  }
-  if (with_kl && head_folded(p, L)) return 0;          // (z is drawn in the decoder's launch: ved_decoder_fwd)
+  PV_TRY(pvcs::conv_head_fwd(ved_head(p, L), s, folded ? &L.head_part : nullptr, &L.head_nseg));
+  if (folded) return 0;                                // (z is drawn in the decoder's launch: ved_decoder_fwd)
   PvHead h{};
   h.head = L.head; h.eps = with_kl ? p->eps : L.z_scale; h.z = L.z; h.z_scale = L.z_scale;
   h.z_loc_out = z_loc_out; h.z_scale_out = z_scale_out;
@@ -221,20 +212,20 @@ int ved_decoder_fwd(const pv_ved_plan* p, VLayout& L, const float* z, hipStream_
   const Shape& d0 = L.ds[0];
   const int64_t F0 = (int64_t)d0.H * d0.W * d0.C;
   if (L.l2f_wt && dec1d_active(p, L) && pv_dec1d_l2f_ok(p->z_dim)) {       // the Linear rides in the decoder's launch
-    const PvD1L2f lf{z, L.l2f_wt, p->l2f.b_off >= 0 ? p->params + p->l2f.b_off : nullptr, nullptr, p->z_dim};
+    const PvD1L2f lf{z, L.l2f_wt, bias_of(p->params, p->l2f), nullptr, p->z_dim};
     PvD1Head hd{L.head, p->eps, L.z, L.z_scale, p->z_loc, p->z_scale, L.kl_part, nullptr, 2 * p->z_dim, p->beta};
     hd.kl_mode = p->kl_mode;
-    if (L.head_part) { hd.part = L.head_part; hd.bias = p->head.b_off >= 0 ? p->params + p->head.b_off : nullptr; hd.head_out = L.head; hd.nseg = L.head_nseg; }
+    if (L.head_part) { hd.part = L.head_part; hd.bias = bias_of(p->params, p->head); hd.head_out = L.head; hd.nseg = L.head_nseg; }
     if (lik_done) *lik_done = lk != nullptr;
     if (arm_fork) pv_fork_arm();
     return pv_dec1d_fwd(p->params, p->dec, p->n_dec_ops, L.d1_wt, (int)B, d0.H, d0.C, L.da, s, &lf, lk,
                         with_head && head_folded(p, L) ? &hd : nullptr);
   }
   if (L.l2f_wt) {                                      // Linear + view(-1, C0, *dims), written channels-last directly
-    PV_TRY(pv_l2f_fwd(z, L.l2f_wt, p->l2f.b_off >= 0 ? p->params + p->l2f.b_off : nullptr, L.da[0], (int)B, d0.H * d0.W, d0.C,
+    PV_TRY(pv_l2f_fwd(z, L.l2f_wt, bias_of(p->params, p->l2f), L.da[0], (int)B, d0.H * d0.W, d0.C,
                       p->z_dim, s));
   } else {
-    PV_TRY(linear_fwd(z, p->z_dim, p->params + p->l2f.w_off, p->l2f.b_off >= 0 ? p->params + p->l2f.b_off : nullptr,
+    PV_TRY(linear_fwd(z, p->z_dim, p->params + p->l2f.w_off, bias_of(p->params, p->l2f),
                       L.f0, nullptr, F0, B, p->z_dim, F0, PV_ACT_NONE, L.sc.ws, L.sc.ws_bytes, s));
     PV_TRY(pv_ncs_to_nsc(L.f0, L.da[0], B, d0.C, (int64_t)d0.H * d0.W, s));     // view(-1, C0, *dims) -> channels-last
   }
@@ -274,31 +265,17 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
   const int64_t B = p->batch, z = p->z_dim;
   pv_fork_disarm();                                    // (no fork state of an earlier, failed call)
   PvSideJoin sj;                                       // joins the side stream on every return path
-  // The step's weight tilings run on the side stream next to the fused first block (which reads the raw weights); the
-  // encoder's stack joins before its first tiled convolution.
-  hipStream_t side = pv_side_stream_for(s, p->flags);
-  bool wt_join = false;
-  static const int wprep_side = pv_exp_int("PV_SIDE_WPREP", 0) ? 1 : 0;   // (measured: the join costs more than the overlap returns)
-  if (wprep_side && side && pvcs::c1pool_fusable(p->enc, p->n_enc_ops, p->ndim_in, L.es[0]) && L.sc.code) {
-    PV_TRY(pv_stream_after(side, s));                  // (the previous step's Adam wrote the weights on s)
-    PV_TRY(ved_wt_prep(p, L, true, true, want_grads != 0, side));
-    wt_join = true;
-    L.sc.side = side; L.sc.wt_join = &wt_join;
-  } else {
-    PV_TRY(ved_wt_prep(p, L, true, true, want_grads != 0, s));
-  }
+  PV_TRY(ved_wt_prep(p, L, true, true, want_grads != 0, s));
   PV_TRY(ved_encoder_fwd(p, L, p->z_loc, p->z_scale, true, s));
-  if (wt_join) { wt_join = false; PV_TRY(pv_stream_after(s, side)); }    // (a stack that never joined)
-  L.sc.wt_join = nullptr; L.sc.side = nullptr;
   // ---- decoder + likelihood of the target (ved.py:141-145); one output channel: the likelihood rides in the decoder's launch ----
   const Shape& od = L.ds[p->n_dec_ops];
   const int64_t OUT = od.elems(B), per = OUT / B, S = (int64_t)od.H * od.W;
   const PvD1Lik lk{p->y, p->loc, want_grads ? L.dlda : nullptr, L.llb, p->lik, p->sigmoid_out, p->decoder_sig};
   bool lik_done = false;
   // a step with gradients and a side stream: the loss scalars are summed there, next to the backward's first launch
-  static const int fin_side_env = pv_exp_int("PV_FIN_SIDE", 1);
-  hipStream_t side_f = (want_grads != 0 && fin_side_env != 0) ? pv_side_stream_for(s, p->flags) : nullptr;
-  PV_TRY(ved_decoder_fwd(p, L, L.z, s, p->out_ch == 1 ? &lk : nullptr, &lik_done, true, side_f != nullptr));
+  hipStream_t side = want_grads ? pv_side_stream_for(s, p->flags) : nullptr;
+  const bool two = side != nullptr;
+  PV_TRY(ved_decoder_fwd(p, L, L.z, s, p->out_ch == 1 ? &lk : nullptr, &lik_done, true, two));
   const float* y = p->y;
   if (!lik_done && p->out_ch > 1) { PV_TRY(pv_ncs_to_nsc(p->y, L.y_nsc, B, p->out_ch, S, s)); y = L.y_nsc; }
   float* loc = p->loc ? (p->out_ch > 1 ? L.loc_nsc : p->loc) : nullptr;
@@ -315,7 +292,7 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
     PV_TRY(pv_segsum(L.llrow, B, per, L.llb, s));
   }
   hipStream_t sf = s;
-  if (side_f && lik_done && pv_fork_taken()) { PV_TRY(pv_fork_to(side_f, s)); sj.fork(s, side_f); sf = side_f; }
+  if (two && lik_done && pv_fork_taken()) { PV_TRY(pv_fork_to(side, s)); sj.fork(s, side); sf = side; }
   else pv_fork_disarm();
   if (head_folded(p, L)) PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, L.kl_part, (int)B, 1.0f /* partials come scaled */, sf));
   else PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, nullptr, 0, p->beta, sf));
@@ -328,15 +305,13 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
   float* g = nullptr;                                  // (dlda = dL/d(output of the last op), loss = -ELBO)
   int pp = 0;
   // the decoder's register-fed weight gradients (kernel-1 family, Conv1d kernel 3) are recorded and run as ONE launch after
-  // the input-gradient chain: every layer keeps its own gradient buffer (L.dg) until then.  PV_NO_K1BATCH=1: one launch each.
-  static const int k1b_env = pv_exp_int("PV_NO_K1BATCH", 0) ? 0 : 1;
+  // the input-gradient chain: every layer keeps its own gradient buffer (L.dg) until then.
   PvK1Batch k1b{};
-  if (k1b_env) fin.k1b = &k1b;
-  hipStream_t side2 = k1b_env ? pv_side_stream_for(s, p->flags) : nullptr;      // (k1b_env: every decoder gradient has its own buffer)
+  fin.k1b = &k1b;
   bool dz_done = false, head_done = false;
-  if (k1b_env && dec1d_active(p, L)) {
+  if (dec1d_active(p, L)) {
     // every input gradient of the decoder in one launch (the fork event rides on it), then the weight gradients are recorded
-    if (side2) pv_fork_arm();
+    if (two) pv_fork_arm();
     dz_done = L.l2f_wt && pv_dec1d_l2f_ok(p->z_dim);   // the latent gradient rides in the same launch
     const PvD1L2f lf{nullptr, L.l2f_wt, nullptr, L.dzc, p->z_dim};
     head_done = dz_done && head_folded(p, L);          // ... and the head's backward
@@ -347,23 +322,19 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
     PV_TRY(pvcs::stack_wgrads(p->params, p->grads, p->dec, p->n_dec_ops, p->ndim_out, (int)B, L.da, L.ds, L.dlda, L.dg, L.sc, s, 1));
     g = L.dg[0];
   } else {
-    L.sc.fork_after = side2 != nullptr;
-    L.sc.side = side2;                                 // (chunks of the recorded weight gradients run next to the chain)
+    L.sc.fork_after = two;
+    L.sc.side = side;                                  // (chunks of the recorded weight gradients run next to the chain)
     PV_TRY(pvcs::stack_bwd(p->params, p->grads, p->dec, p->n_dec_ops, p->ndim_out, (int)B, L.da, L.ds, L.dlda, L.g, pp, true,
-                           &g, L.sc, s, 1, false, k1b_env ? L.dg : nullptr));
+                           &g, L.sc, s, 1, false, L.dg));
     L.sc.fork_after = false; L.sc.side = nullptr;
   }
   // The recorded decoder weight gradients and everything else off the dependent chain from here on (latent_to_features'
   // weight gradient, the encoder's kernel-3 weight gradients) go to the side stream; the chain — latent gradient, head,
   // the encoder's input gradients — stays on s.  Joined before the finish.
-  const bool two = side2 != nullptr;
-  side = side2;
   if (two) sj.fork(s, side);
   // the decoder's recorded weight gradients on a stream of their own: the encoder's kernel-3 weight gradients then start as
-  // soon as their dL/dy exists instead of queueing behind them (round 5, `gpurun_out/r05y`: VED at batch 256 0.806-0.812 ->
-  // 0.792 ms; PV_K1_STREAM3=0 in the experiments build: both families on the one side stream)
-  static const int k1_own_env = pv_exp_int("PV_K1_STREAM3", 1);
-  hipStream_t side3 = (two && k1_own_env) ? pv_side_stream2() : nullptr;
+  // soon as their dL/dy exists instead of queueing behind them (round 5: VED at batch 256 0.806-0.812 -> 0.792 ms)
+  hipStream_t side3 = two ? pv_side_stream2() : nullptr;
   struct Join3 { hipStream_t m, s3; ~Join3() { if (s3) (void)pv_stream_after(m, s3); } } j3{s, side3};
   hipStream_t sw = two ? (side3 ? side3 : side) : s;
   if (two) PV_TRY(pv_fork_to(side, s, side3));         // after the chain's last launch (its stop event when it took one)
@@ -373,13 +344,11 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
   const Shape& d0 = L.ds[0];
   const int64_t F0 = (int64_t)d0.H * d0.W * d0.C;
   if (L.l2f_wt) {                                      // straight from the channels-last gradient
-    PV_TRY(pv_l2f_wgrad(g, L.z, p->grads + p->l2f.w_off, p->l2f.b_off >= 0 ? p->grads + p->l2f.b_off : nullptr, (int)B,
-                        d0.H * d0.W, d0.C, (int)z, sw));
+    PV_TRY(pv_l2f_wgrad(g, L.z, p->grads + p->l2f.w_off, bias_of(p->grads, p->l2f), (int)B, d0.H * d0.W, d0.C, (int)z, sw));
     if (!dz_done) PV_TRY(pv_convhead_fwd(g, L.l2f_wt, nullptr, L.dzc, (int)B, F0, (int)z, L.sc.ws, L.sc.ws_bytes, s));
   } else {
     PV_TRY(pv_nsc_to_ncs(g, L.df0, B, d0.C, (int64_t)d0.H * d0.W, s));
-    PV_TRY(linear_wgrad(L.df0, F0, L.z, z, p->grads + p->l2f.w_off, p->l2f.b_off >= 0 ? p->grads + p->l2f.b_off : nullptr, B,
-                        z, F0, L.sc.ws, L.sc.ws_bytes, s));
+    PV_TRY(linear_wgrad(L.df0, F0, L.z, z, p->grads + p->l2f.w_off, bias_of(p->grads, p->l2f), B, z, F0, L.sc.ws, L.sc.ws_bytes, s));
     PV_TRY(linear_dgrad(L.df0, F0, p->params + p->l2f.w_off, L.dzc, z, nullptr, nullptr, 0, PV_ACT_NONE, B, z, F0,
                         L.sc.ws, L.sc.ws_bytes, s));
   }
@@ -388,43 +357,18 @@ extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void*
   hb.dzc = L.dzc; hb.ldzc = z; hb.z = L.z; hb.z_scale = L.z_scale; hb.eps = p->eps; hb.head = L.head; hb.dhead = L.dhead;
   hb.B = (int)B; hb.z_dim = (int)z; hb.coord_dim = 0; hb.beta = p->beta; hb.kl_mode = p->kl_mode;
   if (!head_done) PV_TRY(pv_head_bwd(hb, s));
-  const Shape& fe = L.es[p->n_enc_ops];
-  const pv_op& last = p->enc[p->n_enc_ops - 1];
+  // the head's weight gradient needs dhead only: when the decoder's backward launch wrote it (the side streams already wait for
+  // that launch) it runs on the side stream next to the head's input gradient instead of in front of it on the chain
   bool g_is_pre = false;
-  if (L.head_wt) {
-    // dL/d(features) straight in channels-last order, with the last convolution's activation derivative folded in
-    const bool fold = last.kind == PV_OP_CONV && last.act != PV_ACT_GELU;
-    // the head's weight gradient needs dhead only: when the decoder's backward launch wrote it (the side streams already wait for
-    // that launch) it runs on the side stream next to the input gradient below instead of in front of it on the chain
-    static const int head_side_env = pv_exp_int("PV_VED_HEAD_SIDE", 1);
-    hipStream_t hs = (two && head_done && head_side_env && !pv_convhead_wgrad_uses_ws()) ? side : s;
-    PV_TRY(pv_convhead_wgrad(L.dhead, L.ea[p->n_enc_ops], p->grads + p->head.w_off,
-                             p->head.b_off >= 0 ? p->grads + p->head.b_off : nullptr, (int)B, fe.H * fe.W, fe.C, (int)(2 * z),
-                             L.sc.ws, L.sc.ws_bytes, hs));
-    g = L.g[pp];
-    if (two) pv_fork_arm();                            // (the last convolution's weight gradient forks off this launch)
-    PV_TRY(pv_convhead_bwd(L.dhead, L.head_wt, L.ea[p->n_enc_ops], fold ? last.act : PV_ACT_NONE, g, (int)B, L.F, (int)(2 * z), s));
-    pp ^= 1;
-    g_is_pre = fold;
-  } else {
-    PV_TRY(linear_wgrad(L.dhead, 2 * z, L.feat, L.F, p->grads + p->head.w_off,
-                        p->head.b_off >= 0 ? p->grads + p->head.b_off : nullptr, B, L.F, 2 * z, L.sc.ws, L.sc.ws_bytes, s));
-    float* dfeat = L.g[pp];
-    PV_TRY(linear_dgrad(L.dhead, 2 * z, p->params + p->head.w_off, dfeat, L.F, nullptr, nullptr, 0, PV_ACT_NONE, B, L.F,
-                        2 * z, L.sc.ws, L.sc.ws_bytes, s));
-    pp ^= 1;
-    g = L.g[pp];
-    PV_TRY(pv_ncs_to_nsc(dfeat, g, B, fe.C, (int64_t)fe.H * fe.W, s));
-    pp ^= 1;
-  }
+  hipStream_t hs = (two && head_done && !pv_convhead_wgrad_uses_ws()) ? side : s;
+  PV_TRY(pvcs::conv_head_bwd(ved_head(p, L), p->enc[p->n_enc_ops - 1], hs, two, L.g, pp, &g, &g_is_pre, s, [] { return 0; }));
   // ---- encoder ops in reverse (no input gradient for the first one) ----
   bool joined = false;
-  L.sc.side = two ? side : nullptr; L.sc.side_joined = &joined;
+  L.sc.side = side; L.sc.side_joined = &joined;
   PV_TRY(pvcs::stack_bwd(p->params, p->grads, p->enc, p->n_enc_ops, p->ndim_in, (int)B, L.ea, L.es, g, L.g, pp, false,
                          nullptr, L.sc, s, 0, g_is_pre, two ? L.eg : nullptr));
   L.sc.side = nullptr; L.sc.side_joined = nullptr;
   if (two && !joined) PV_TRY(pv_stream_after(s, side));
-  else if (!two && sf != s) PV_TRY(pv_stream_after(s, sf));   // (no second fork: the loss scalars alone ran on the side stream)
   sj.joined();
   if (side3) { PV_TRY(pv_stream_after(s, side3)); j3.s3 = nullptr; }
   return pv_wgrad_finish_all(&fin, s);

@@ -291,7 +291,7 @@ def test_bf16_forward_only_vs_emulated_reference(gpu_device, name):
     print("\n[bf16-emulated] forward %s: loss %.3e, loc %.3e (vs float64 %.3e)" % (name, le, lo, lo64))
     assert le < BARS[name][1] and lo < 4.5e-5       # measured loc 1.03e-5 / 1.10e-5 (ceiling LOC_CEIL)
     # model.decode(): pv_ivae_decode launches the split-precision (fp32-class) build whatever the training precision
-    # (pv_plan.hip:1217-1218) — not the plain-bf16 kernel — so its reference is the plain float64 oracle
+    # (pv_plan.hip: decode_fused_run) — not the plain-bf16 kernel — so its reference is the plain float64 oracle
     dname = _kernel_name(b * n_pix // 16, LIK["gaussian"], fused=2, grads=0)
     assert "pv_sdec_w8_kernel" not in dname and "0>(PvFused, PvEncFold)" not in dname, dname
     z = torch.randn(b, 2, generator=torch.Generator().manual_seed(2))
