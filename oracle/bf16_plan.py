@@ -4,16 +4,17 @@ oracle/bf16_plan.py — a rounding plan for the oracle's spatial decoder: the bf
 TEST INFRASTRUCTURE, NOT PRODUCT (like the rest of oracle/).  `Config.bf16_plan = Bf16Plan(...)` makes `sdecoder_forward`
 compute the decoder's hidden layers with the operand values the HIP kernel feeds its matrix cores, bit for bit; only the
 accumulation stays exact (the dtype of the caller, float64 in the tests).  With the field unset (the default) the oracle's
-code path is unchanged.  The rounding points, from the kernel sources (pyroved_amd/csrc/):
+code path is unchanged.  The rounding points, from the kernel sources (pyroved_amd/csrc/; bare `:NNN` line numbers are those of
+the sources when this module was written — the names next to them are what to search for):
 
 8-wave kernel, `pv_sdec_w8_kernel` (kernel="w8"; pv_sdec_fused_w8.hip):
   * weight images hold bf16(C W), C = 2 log2(e), the product C W formed in fp32 (pv_fb_layout.h:94 `s1 = p.scale`,
-    pv_sdec_fused_bf16.hip:1826 `p.scale`); the biases enter as fp32 C b (WO_VEC, pv_sdec_fused_w8.hip:48, filled at :802-803).
+    `p.scale` in pv_sdec_fused_bf16.hip's launcher); the biases enter as fp32 C b (WO_VEC in pv_sdec_fused_w8.hip, filled as `SD_C * b`).
     The MFMAs deliver C * pre-activation: emulated as h_b @ bf16(C W)^T + fp32(C b), never as bf16(W).
   * the coordinate layer is one MFMA per block on (hi, lo) bf16 pairs (fb_split, pv_fb_layout.h:14): C Wc, C bc and x' split,
     three products wh xh + wh xl + wl xh per coordinate (lo x lo dropped) plus bh + bl, on top of the fp32 C hz
     (A table :805-819, B operand :998-1005, the MFMA :1023).  Emulated as written.
-  * tanh of the scaled pre-activation is 1 - 2 rcp(exp2(C x) + 1) in fp32 (w8_tanhc :81, w8_tanh8 :246); restated here
+  * tanh of the scaled pre-activation is 1 - 2 rcp(exp2(C x) + 1) in fp32 (w8_tanhc :81, sd_tanh8 in pv_sdec_prims.h); restated here
     in fp32 (exact division and exp2 in place of the 1-ulp hardware approximations).  Its cancellation near 0 is kept.
   * h0, h1 -> bf16 (w8_cvt8 :295 at :1026 and :1034; the tail's w8_cvt4 :461); h2 stays fp32 for the logit (:1039-1044)
     and goes to bf16 for the d(wo) column sum (pA at :1047, consumed at :1102; the tail's h2b at :1315).
@@ -22,10 +23,10 @@ code path is unchanged.  The rounding points, from the kernel sources (pyroved_a
     carries -C dpre1, rounded to bf16 (:1123 / tail :1330), after layer 1 C^2 dpre0, rounded to bf16 (:1128 / tail :1336).
     dW1 / db1 are un-scaled by -1/C where the record is written (:1489-1490, :1500), dpre0 by 1/C^2 where it leaves the
     kernel (dL/d(hz) :896, the row-local coordinate backward :1143, dWc / dbc).
-  * records: each workgroup's partial dW1 / dW2 is rounded to bf16 once, round to nearest even (`pack2` :1464-1467, of the
+  * records: each workgroup's partial dW1 / dW2 is rounded to bf16 once, round to nearest even (`pack2` in pv_sdec_w8_kernel, of the
     fp32 value accW1 * -1/C and accW2), and pv_latent_bwd_reduce sums the partials in fp32 in a fixed order.  Partition:
-    units of 16 rows, workgroup g of G = pv_sdec_fused_grid(units) = min(units, CUs) (pv_sdec_fused.hip:504) owns units
-    [g units / G, (g + 1) units / G) (:905), the last of which is a column-parallel tail when the range is 1 mod 8 (:920).
+    units of 16 rows, workgroup g of G = pv_sdec_fused_grid(units) = min(units, CUs) (pv_sdec_fused.hip) owns units
+    [g units / G, (g + 1) units / G) (`u_lo`, `u_hi`), the last of which is a column-parallel tail when the range is 1 mod 8 (`has_tail`).
   * NOT emulated (fp32-class): the row-local coordinate backward (table of Wc hi / lo, :1141), the column sums of dlda h2 /
     dpre0 / dpre0 x' against hi / lo B operands (:1102, :1168); the logit, the likelihood and dL/dlogit (fp32
     transcendentals); the per-workgroup fp32 vectors (db1, db2, d(wo), dbo, dWc, dbc); the guide (encoder, fc_latent) folded
@@ -78,7 +79,7 @@ def tanh_c(cx: torch.Tensor) -> torch.Tensor:
 
 
 def partition(units: int, grid: int) -> List[Tuple[int, int, bool]]:
-    """The 8-wave kernel's work split: (u_lo, u_hi, has_tail) per workgroup (pv_sdec_fused_w8.hip:905, :920)."""
+    """The 8-wave kernel's work split: (u_lo, u_hi, has_tail) per workgroup (`u_lo`, `u_hi`, `has_tail` in pv_sdec_w8_kernel, pv_sdec_fused_w8.hip)."""
     out = []
     for g in range(grid):
         lo, hi = g * units // grid, (g + 1) * units // grid
@@ -87,7 +88,7 @@ def partition(units: int, grid: int) -> List[Tuple[int, int, bool]]:
 
 
 def grid_of(units: int, cus: int) -> int:
-    """pv_sdec_fused_grid (pv_sdec_fused.hip:504)."""
+    """pv_sdec_fused_grid (pv_sdec_fused.hip)."""
     return max(1, min(units, cus))
 
 

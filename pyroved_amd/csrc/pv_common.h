@@ -7,6 +7,9 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+#define LOG_SQRT_2PI 0.91893853320467274178f
+#define BERN_EPS 1.1920928955078125e-07f   // torch.finfo(float32).eps used by clamp_probs
+
 #define PV_LAUNCH_CHECK()                      \
   do {                                         \
     hipError_t e__ = hipGetLastError();        \

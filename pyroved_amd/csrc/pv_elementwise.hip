@@ -12,8 +12,6 @@
 #include "pv_side.h"
 #include "pv_sdec_fused.h"
 
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f   // torch.finfo(float32).eps used by clamp_probs
 
 // deterministic block-wide sum (blockDim.x == 256); result valid in every thread
 __device__ __forceinline__ float block_sum_256(float v, float* sm /* >= 4 floats */) {

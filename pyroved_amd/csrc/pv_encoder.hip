@@ -21,7 +21,6 @@
 #define EN_ROWS 16
 #define EN_LD 132
 #define EN_THREADS 512
-#define LOG_SQRT_2PI 0.91893853320467274178f
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ float en_block_sum(float v, float* sm /* 8 floats */) {

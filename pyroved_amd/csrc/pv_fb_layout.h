@@ -26,7 +26,7 @@ __device__ __forceinline__ int fb_pcol(int k) {
 }
 // q-swapped form (PvFbPrep::qswap, round 6; the 4-wave kernel's images): the half a column block sits in is h ^ (q >> 1) — chunks
 // q = 2, 3 hold [h = 1 | h = 0].  The forward's operand stays one ds_read_b128 (its lanes of groups q >= 2 feed the activation
-// pieces in the same swapped order: fb_catq); the dgrad's transposing read of column block 2m + h now takes pieces q' = 0, 1 from
+// pieces in the same swapped order: sd_catq); the dgrad's transposing read of column block 2m + h now takes pieces q' = 0, 1 from
 // half h and q' = 2, 3 from the other one, so its 32 lanes (8 rows x 4 pieces) cover 16 chunks x BOTH halves = all 64 banks
 // once: conflict-free, where the plain form has every lane on the same half (2-way).
 // ... and every row R of an image has its sixteen 16-byte chunks XOR-swizzled by fb_swz(R) = 4*(R&3) + SL[(R>>2)&3],

@@ -20,7 +20,6 @@
 #define GI_WAVES 8
 #define GI_THREADS (64 * GI_WAVES)
 #define GI_P_WAVE (64 * 17)                           // floats of a wave's partial-sum transpose buffer (pv_gemv16.h)
-#define GI_LOG_SQRT_2PI 0.91893853320467274178f
 
 __global__ __launch_bounds__(GI_THREADS) void pv_guide_img_kernel(PvEncFold e, PvFbPrep prep, float hz_mul, int n_img, int has_prep,
                                                                   int kl_mode) {
@@ -118,8 +117,8 @@ __global__ __launch_bounds__(GI_THREADS) void pv_guide_img_kernel(PvEncFold e, P
       if (e.z_scale_out) e.z_scale_out[b * zd + lane] = sig;
       const float d = z - mu;
       if (kl_mode == PV_KL_SAMPLED) {
-        lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - GI_LOG_SQRT_2PI;
-        lp = -(z * z) / 2.0f - GI_LOG_SQRT_2PI;
+        lq = -(d * d) / (2.0f * (sig * sig)) - logf(sig) - LOG_SQRT_2PI;
+        lp = -(z * z) / 2.0f - LOG_SQRT_2PI;
       } else {
         pv_kl_analytic_terms(mu, sig, lq, lp);     // the analytic-KL objective: the terms' expectations under q
       }

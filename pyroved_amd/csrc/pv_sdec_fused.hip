@@ -24,6 +24,7 @@
 //     pv_sdec_fused_reduce (no float atomics: bit-reproducible).
 // LDS: W1, W2 (2 x 66 KiB), staging (18 KiB), small vectors: 157.5 KiB of the CU's 160 KiB.
 #include "pv_sdec_fused.h"
+#include "pv_sdec_prims.h"     // sd_exp / sd_log / sd_rcp (the rest of it is for the bf16-family kernels)
 #include <stdlib.h>
 
 #define LDW 132        // LDS row stride of the weight images (floats): conflict-free ds_read_b128 over 16 rows
@@ -44,8 +45,6 @@
 #define FD_LDS_FLOATS (OFF_RED + 64)
 #define FD_THREADS (64 * FD_WAVES)
 
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f
 
 // keeps the machine scheduler from hoisting a whole layer's LDS operand loads ahead of its MFMAs
 // (which would need hundreds of VGPRs); the partner wave on the SIMD hides the ds_read latency instead
@@ -154,9 +153,6 @@ __device__ __forceinline__ void fd_mul_dtanh(f32x4 (&out)[8], const f32x4 (&h)[8
 }
 
 // raw-instruction transcendental helpers (v_exp_f32 / v_log_f32 / v_rcp_f32: 1 ulp)
-__device__ __forceinline__ float fd_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float fd_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float fd_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 __device__ __forceinline__ void fd_stage_write(float* __restrict__ st, const f32x4 (&v)[8], int r, int q) {
 #pragma unroll
@@ -308,19 +304,20 @@ __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_kernel(PvFused f)
       float ll, dlda, locv;
       if (f.lik == PV_LIK_BERNOULLI) {
         // torch Bernoulli(probs=sigmoid(a)).log_prob(x): clamp_probs -> logits -> -BCEWithLogits
-        const float pr = fd_rcp(1.0f + fd_exp(-a));
+        // (not sd_pixel_lik: this kernel keeps the literal softplus and sigmoid(lg) — seven transcendentals — and a run-time f.lik)
+        const float pr = sd_rcp(1.0f + sd_exp(-a));
         const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        const float lg = fd_log(pc) - fd_log(1.0f - pc);
-        ll = -(fmaxf(lg, 0.0f) - lg * xv + fd_log(1.0f + fd_exp(-fabsf(lg))));
+        const float lg = sd_log(pc) - sd_log(1.0f - pc);
+        ll = -(fmaxf(lg, 0.0f) - lg * xv + sd_log(1.0f + sd_exp(-fabsf(lg))));
         const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
-        dlda = (fd_rcp(1.0f + fd_exp(-lg)) - xv) * mask;
+        dlda = (sd_rcp(1.0f + sd_exp(-lg)) - xv) * mask;
         locv = pr;
       } else if (f.lik == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
       } else {
-        const float pr = f.sigmoid_out ? fd_rcp(1.0f + fd_exp(-a)) : a;
+        const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - fd_log(f.sig) - LOG_SQRT_2PI;
+        ll = -(d * d) / (2.0f * f.sig * f.sig) - sd_log(f.sig) - LOG_SQRT_2PI;
         dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
         locv = pr;
       }

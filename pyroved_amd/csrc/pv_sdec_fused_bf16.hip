@@ -35,19 +35,16 @@
 //     transposes through the wave's own rows of whichever staging area is dead at that moment (fb_colsum).
 #include "pv_sdec_fused.h"
 #include "pv_fb_layout.h"
+#include "pv_sdec_prims.h"
 #include "pv_kernels.h"        // PvHeadBwd, pv_head_dz / pv_head_bwd_math: the own-sample epilogue's latent backward
 #include <stdlib.h>
 #include <stdio.h>
 
-typedef short short4_ __attribute__((ext_vector_type(4)));
-typedef short short8_ __attribute__((ext_vector_type(8)));
 typedef int int4_ __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4_ lds_short4;
 
 #define FB_WAVES 4               // waves per workgroup (one per SIMD), one 16-row unit each
 #define TILE_UNITS FB_WAVES      // units per workgroup tile
 #define TILE_ROWS (TILE_UNITS * FD_UNIT)
-#define LDS2 144                 // staging arrays: 72-dword rows -> the 4x16 transposing reads are conflict-free
 #define ST_ARR (TILE_ROWS * LDS2)          // elements of one staging array (64 rows)
 #define ST_BYTES (2 * ST_ARR)              // 18,432
 // byte offsets in dynamic LDS:  [ weight images and staging areas (FbLds<PREC>) | vectors ... ]
@@ -143,8 +140,6 @@ template <int P> struct FbLds {
 static_assert(IMG_BYTES % (FB_WAVES * 1024) == 0, "image reload: whole 1 KB LDS-DMA pieces per wave");
 static_assert(FB_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f
 // The stage fences of the elementwise phases and layer loops: __builtin_amdgcn_sched_barrier(mask), mask 0 = nothing crosses.
 // NOT to be relaxed under the iterative-ILP strategy this file is compiled with (Makefile): masks 0x2 / 0x6 (VALU, SALU may cross)
 // measure another 0.9-1.4 % faster there and produce WRONG gradients in the H231 builds (35 parity tests fail; the same masks
@@ -182,8 +177,6 @@ static_assert(FB_LDS_BYTES <= 160 * 1024, "LDS budget");
 #define FB_FENCE_B2() __builtin_amdgcn_sched_barrier(FB_FENCE_MASK_B2)      // dgrad loop: behind the MFMA group
 #define FB_FENCE_C() __builtin_amdgcn_sched_barrier(FB_FENCE_MASK_C)
 #define FB_FENCE_D() __builtin_amdgcn_sched_barrier(FB_FENCE_MASK_D)
-typedef _Float16 half4_ __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_ __attribute__((ext_vector_type(8)));
 // 16-bit operands travel as bf16x4 / bf16x8 bit containers in every mode; F16 picks the instruction that reads them
 template <bool F16> __device__ __forceinline__ f32x4 fb_mma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_, a), __builtin_bit_cast(half8_, b), c, 0, 0, 0);
@@ -193,55 +186,6 @@ template <bool F16> __device__ __forceinline__ f32x4 fb_mma(const bf16x8& a, con
 __device__ __forceinline__ float fb_tanh(float x) {
   const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-__device__ __forceinline__ float fb_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float fb_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float fb_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-
-__device__ __forceinline__ bf16x8 fb_cat(const bf16x4& a, const bf16x4& b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// the forward's activation operand under the q-swapped image layout (pv_fb_layout.h): lanes of groups q >= 2 hold their weight
-// chunk's halves in the other order (sw: per lane, loop-invariant)
-__device__ __forceinline__ bf16x8 fb_catq(bf16x4 a, bf16x4 b, bool sw) {
-  typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
-  const u32x2_ ua = __builtin_bit_cast(u32x2_, a), ub = __builtin_bit_cast(u32x2_, b);
-  const u32x2_ lo = {sw ? ub[0] : ua[0], sw ? ub[1] : ua[1]}, hi = {sw ? ua[0] : ub[0], sw ? ua[1] : ub[1]};
-  return fb_cat(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi));
-}
-
-// a zero the compiler cannot see through: lane-address arithmetic that depends on it is redone where it is used
-// instead of being hoisted out of the tile loop and held in (or spilled from) registers for the whole kernel
-__device__ __forceinline__ int fb_opaque0() { int z = 0; asm volatile("" : "+v"(z)); return z; }
-
-__device__ __forceinline__ bf16x4 fb_tr(const __bf16* p) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-
-// ---- LDS-DMA: 16 B per lane from global straight into LDS at (wave-uniform byte address) + 16 * lane.  hipcc
-// does not count these in its s_waitcnt bookkeeping: fb_wait_vm0() before the landed data is read, and no
-// compiler-visible global load may be pending when one is issued (the callers drain first).
-__device__ __forceinline__ void fb_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void fb_glds4(const void* gsrc, unsigned lds_dst) {     // 4 B per lane, 256 B per wave
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void fb_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// BYTES of weight images (whole 32 KB images) from their global copy: BYTES / 4 KB one-KB pieces per wave
-template <int BYTES>
-__device__ __forceinline__ void fb_reload(const char* __restrict__ gimg, unsigned lds_dst, int wave, int lane) {
-  constexpr int PIECES = BYTES / (FB_WAVES * 1024);
-#pragma unroll
-  for (int c = 0; c < PIECES; ++c) {
-    const int off = (wave * PIECES + c) * 1024;
-    fb_glds16(gimg + off + lane * 16, lds_dst + off);
-  }
 }
 
 // forward layer of the wave's unit: out = bias + W in (pre-activation on return; times the images' scale in the fp16
@@ -257,7 +201,7 @@ __device__ __forceinline__ void fb_layer_fwd(const __bf16* __restrict__ Wh, cons
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) out[ob] = *reinterpret_cast<const f32x4*>(bs + 16 * ob + 4 * q);
   // row 16*ob + r, logical chunk 4m + q  ->  physical chunk 4*(m ^ (r&3)) + (q ^ SL[r>>2])
-  r |= fb_opaque0();
+  r |= sd_opaque0();
   const int lbase = r * LDB + 8 * (q ^ fb_sl(r >> 2));
   const __bf16* ah = Wh + lbase;
   const __bf16* al = Wl + lbase;
@@ -280,13 +224,13 @@ __device__ __forceinline__ void fb_layer_fwd(const __bf16* __restrict__ Wh, cons
     const int m = g / FB_GPM, op = (g % FB_GPM) * FB_GB;
     if (g + 1 < 4 * FB_GPM) load(g + 1, wh[(g + 1) & 1], wl[(g + 1) & 1]);
     FB_FENCE_A();
-    const bf16x8 bh = fb_catq(ih[2 * m], ih[2 * m + 1], sw);
+    const bf16x8 bh = sd_catq(ih[2 * m], ih[2 * m + 1], sw);
     const bf16x8(&h)[FB_GB] = wh[g & 1];
     const bf16x8(&l)[FB_GB] = wl[g & 1];
 #pragma unroll
     for (int o = 0; o < FB_GB; ++o) out[op + o] = fb_mma<F16>(h[o], bh, out[op + o]);
     if (AL) {
-      const bf16x8 bl = fb_catq(il[2 * m], il[2 * m + 1], sw);
+      const bf16x8 bl = sd_catq(il[2 * m], il[2 * m + 1], sw);
 #pragma unroll
       for (int o = 0; o < FB_GB; ++o) out[op + o] = fb_mma<F16>(h[o], bl, out[op + o]);
     }
@@ -309,7 +253,7 @@ __device__ __forceinline__ void fb_layer_dgrad(const __bf16* __restrict__ Wh, co
   // lane i of 16-lane group q points at W[j0 + i/4][16*kb + 4*(i%4)], j0 = 32m + 4q (+16): after the transpose
   // lane k' holds W[j0 .. j0+3][16*kb + k']
   // (rows j0 + r/4 with j0 = 32m + 4q (+16): swizzle 4*(r>>2) + SL[q]; logical chunk 4*kk + (r&3), kk = kb/2)
-  r |= fb_opaque0();
+  r |= sd_opaque0();
   // (q-swapped images: piece r&3 of column block 2 kk + h sits in half h ^ ((r&3) >> 1))
   const int toff = (4 * q + (r >> 2)) * LDB + 8 * ((r & 3) ^ fb_sl(q));
   const int hs = qs ? 4 * ((r >> 1) & 1) : 0;
@@ -326,8 +270,8 @@ __device__ __forceinline__ void fb_layer_dgrad(const __bf16* __restrict__ Wh, co
       const int off = 32 * m * LDB + xk[(kp + o) >> 1];
       const __bf16* ah = ahx[(kp + o) & 1];
       const __bf16* al = alx[(kp + o) & 1];
-      h[o] = fb_cat(fb_tr(ah + off), fb_tr(ah + off + 16 * LDB));
-      if (WL) l[o] = fb_cat(fb_tr(al + off), fb_tr(al + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(ah + off), sd_tr(ah + off + 16 * LDB));
+      if (WL) l[o] = sd_cat(sd_tr(al + off), sd_tr(al + off + 16 * LDB));
     }
   };
 #pragma unroll
@@ -337,13 +281,13 @@ __device__ __forceinline__ void fb_layer_dgrad(const __bf16* __restrict__ Wh, co
     const int m = g / FB_GPM, kp = (g % FB_GPM) * FB_GB;
     if (g + FB_DGD < 4 * FB_GPM) load(g + FB_DGD, wh[(g + FB_DGD) % (FB_DGD + 1)], wl[(g + FB_DGD) % (FB_DGD + 1)]);
     FB_FENCE_B1();
-    const bf16x8 bh = fb_cat(ih[2 * m], ih[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]);
     const bf16x8(&h)[FB_GB] = wh[g % (FB_DGD + 1)];
     const bf16x8(&l)[FB_GB] = wl[g % (FB_DGD + 1)];
 #pragma unroll
     for (int o = 0; o < FB_GB; ++o) out[kp + o] = fb_mma<F16>(h[o], bh, out[kp + o]);
     if (AL) {
-      const bf16x8 bl = fb_cat(il[2 * m], il[2 * m + 1]);
+      const bf16x8 bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
       for (int o = 0; o < FB_GB; ++o) out[kp + o] = fb_mma<F16>(h[o], bl, out[kp + o]);
     }
@@ -358,8 +302,8 @@ __device__ __forceinline__ void fb_layer_dgrad(const __bf16* __restrict__ Wh, co
 // Written as STAGES over all 32 values of a lane with scheduling fences in between (round 2): left alone, hipcc walks the
 // values two at a time through the dependent chain mul -> exp -> add -> rcp -> fma, and the one wave of a SIMD then pays
 // every instruction's latency (~10 cycles each instead of ~6.5; scripts/ubench/valu_rates.hip).
-#define FB_C 2.8853900817779268f           // 2 log2(e): tanh(x) = 1 - 2 / (exp2(C x) + 1)
-__device__ __forceinline__ void fb_tanh8(f32x4 (&v)[8], float c = FB_C) {       // c: C / (scale carried by v)
+// (sd_tanh8 is this without the leading multiply: its callers' operands arrive pre-scaled by C)
+__device__ __forceinline__ void fb_tanh8(f32x4 (&v)[8], float c = SD_C) {       // c: C / (scale carried by v)
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) v[ob] = v[ob] * c;
   FB_FENCE_C();
@@ -423,13 +367,14 @@ __device__ __forceinline__ void fb_zero8(bf16x4 (&h)[8], bf16x4 (&l)[8]) {
 // the wave's 16 rows (row = 16 * wave + r) of one staged tensor: hi and lo arrays, row-major [64][LDS2].  Inside
 // every 16-column block the four 8-byte pieces are XOR-swizzled by (row>>2)&3: ds_write_b64 is banked mod 32 and
 // serviced 16 lanes (16 rows, one q) at a time, and 72-dword rows alone would put rows r and r+4 on the same banks
-// (4-way); the transposing reads (fb_stage_toff) undo the swizzle and stay conflict-free.
+// (4-way); the transposing reads (sd_stage_toff) undo the swizzle and stay conflict-free.
+// (sd_stage_store is the one-array, unscaled form of this; h8_stage_store one array with SCALED)
 // SCALED (fp16 modes, the activation operand): every piece times the row's power of two ph (exact), and the row's ph itself
 // into column block 8 (the rows' padding) of the hi array: the bias gradient contracts against it (fb_wgrad_consume)
 template <bool LO, bool SCALED>
 __device__ __forceinline__ void fb_stage_store(__bf16* __restrict__ sh, __bf16* __restrict__ sl, const bf16x4 (&h)[8],
                                                const bf16x4 (&l)[8], int row, int q, half4_ ph = half4_{}) {
-  row |= fb_opaque0();
+  row |= sd_opaque0();
   const int e = row * LDS2 + 4 * (q ^ ((row >> 2) & 3));
 #pragma unroll
   for (int jb = 0; jb < 8; ++jb) {
@@ -443,8 +388,6 @@ __device__ __forceinline__ void fb_stage_store(__bf16* __restrict__ sh, __bf16* 
   }
   if constexpr (SCALED) *reinterpret_cast<half4_*>(sh + e + 16 * 8) = ph;
 }
-// lane offset of the transposing read of staged rows R0 + 4q .. 4q+3 (R0 a multiple of 16), columns 16*blk ..
-__device__ __forceinline__ int fb_stage_toff(int r, int q) { return (4 * q + (r >> 2)) * LDS2 + 4 * ((r & 3) ^ q); }
 
 // wgrad of the wave's two 16-row slices (rows 16*(2*wave + s) ..) over the staged tile's 64 rows:
 //   dW[j][k] += sum_rows dpre[row][j] h[row][k];   db[j] += sum_rows dpre[row][j]  (MFMA against ones)
@@ -453,11 +396,12 @@ __device__ __forceinline__ int fb_stage_toff(int r, int q) { return (4 * q + (r 
 // (fp16 modes: the bias gradient's second operand is the rows' own factor — column block 8 of the staged activations — the
 //  product then being what the weight gradient's is: dpre_n[row][j] * 2^(e_row + dl_exp); BIAS_LO: dL/dpre's lo pieces are
 //  staged for this product alone)
+// (the 4-wave, per-precision-mode form; w8_wgrad_consume owns one 32 x 64 block per wave with one bf16 piece per operand)
 template <int P>
 __device__ __forceinline__ void fb_wgrad_consume(const __bf16* st, f32x4 (&accW)[2][8], f32x4 (&accB)[2], int wave,
                                                  int r, int q, int ksteps) {
   constexpr bool F16 = FbP<P>::F16, WG3 = FbP<P>::WG3, AL = WG3 || FbP<P>::BIAS_LO;
-  const int toff = fb_stage_toff(r | fb_opaque0(), q);
+  const int toff = sd_stage_toff(r | sd_opaque0(), q);
   const short one = 0x3f80;                           // bf16 1.0
   const short8_ ones_s = {one, one, one, one, one, one, one, one};
   const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
@@ -476,20 +420,20 @@ __device__ __forceinline__ void fb_wgrad_consume(const __bf16* st, f32x4 (&accW)
     bf16x8 a_h[2], a_l[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      a_h[s] = fb_cat(tr_at(la + 32u * s), tr_at(la + 32u * s + ROW16));
-      if (AL) a_l[s] = fb_cat(tr_at(la + ARR + 32u * s), tr_at(la + ARR + 32u * s + ROW16));
+      a_h[s] = sd_cat(tr_at(la + 32u * s), tr_at(la + 32u * s + ROW16));
+      if (AL) a_l[s] = sd_cat(tr_at(la + ARR + 32u * s), tr_at(la + ARR + 32u * s + ROW16));
     }
     bf16x8 bh[2][2], bl[2][2];
     auto load = [&](int kp, bf16x8 (&h)[2], bf16x8 (&l)[2]) {
 #pragma unroll
       for (int o = 0; o < 2; ++o) {
         const unsigned off = 32u * (unsigned)(kp + o);
-        h[o] = fb_cat(tr_at(lb + off), tr_at(lb + off + ROW16));
-        if (WG3) l[o] = fb_cat(tr_at(lb + ARR + off), tr_at(lb + ARR + off + ROW16));
+        h[o] = sd_cat(tr_at(lb + off), tr_at(lb + off + ROW16));
+        if (WG3) l[o] = sd_cat(tr_at(lb + ARR + off), tr_at(lb + ARR + off + ROW16));
       }
     };
     load(0, bh[0], bl[0]);
-    const bf16x8 bias_b = F16 ? fb_cat(tr_at(lb + 32u * 8), tr_at(lb + 32u * 8 + ROW16)) : ones;
+    const bf16x8 bias_b = F16 ? sd_cat(tr_at(lb + 32u * 8), tr_at(lb + 32u * 8 + ROW16)) : ones;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       accB[s] = fb_mma<F16>(a_h[s], bias_b, accB[s]);
@@ -522,6 +466,7 @@ __device__ __forceinline__ void fb_wgrad_consume(const __bf16* st, f32x4 (&accW)
   }
 }
 
+// (the permlane form, as w8_sum_q; x3_sum_q / h8_sum_q are two __shfl_xor)
 __device__ __forceinline__ float fb_sum_q(float v) {
   return pv_sum_rows(v);                             // (pv_common.h: v_permlane16/32_swap, the bits of the two shfl_xor sums)
 }
@@ -675,7 +620,7 @@ __device__ __forceinline__ void fb_tail_fwd(const __bf16* __restrict__ Wh, const
     }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    const bf16x8 bh = fb_catq(ih[2 * m], ih[2 * m + 1], sw);
+    const bf16x8 bh = sd_catq(ih[2 * m], ih[2 * m + 1], sw);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[o] = fb_mma<F16>(wh[m][o], bh, out[o]);
     if (WL) {
@@ -700,14 +645,14 @@ __device__ __forceinline__ void fb_tail_dgrad(const __bf16* __restrict__ Wh, con
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const int off = toff + 32 * m * LDB + (o ? 4 - hs : hs);
-      h[o] = fb_cat(fb_tr(Wh + off), fb_tr(Wh + off + 16 * LDB));
-      if (WL) l[o] = fb_cat(fb_tr(Wl + off), fb_tr(Wl + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(Wh + off), sd_tr(Wh + off + 16 * LDB));
+      if (WL) l[o] = sd_cat(sd_tr(Wl + off), sd_tr(Wl + off + 16 * LDB));
     }
-    const bf16x8 bh = fb_cat(ih[2 * m], ih[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[o] = fb_mma<F16>(h[o], bh, out[o]);
     if (AL) {
-      const bf16x8 bl = fb_cat(il[2 * m], il[2 * m + 1]);
+      const bf16x8 bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
       for (int o = 0; o < 2; ++o) out[o] = fb_mma<F16>(h[o], bl, out[o]);
     }
@@ -724,8 +669,8 @@ template <int P>
 __device__ __forceinline__ void fb_wgrad_consume16(const __bf16* sd, const __bf16* sa, f32x4 (&accW)[2][8], f32x4 (&accB)[2],
                                                    int wave, int r, int q) {
   static_assert(FbP<P>::F16 && FbP<P>::BIAS_LO && !FbP<P>::WG3, "H231");
-  const int toff = fb_stage_toff(r, q);
-  auto tr4 = [](const __bf16* p_) { return __builtin_bit_cast(half4_, fb_tr(p_)); };
+  const int toff = sd_stage_toff(r, q);
+  auto tr4 = [](const __bf16* p_) { return __builtin_bit_cast(half4_, sd_tr(p_)); };
   half4_ a_h[2], a_l[2];
 #pragma unroll
   for (int s_ = 0; s_ < 2; ++s_) {
@@ -834,21 +779,21 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
   // the vectors, the first unit's observations and its prefetch slots — and land under the first tile's coordinate layer and
   // forward of layer 1.
   constexpr bool LATE_W2 = OV && GRADS;
-  fb_reload<IMG_BYTES>(gimg, lds0 + LL::W1H, wave, lane);
-  if (!LATE_W2) fb_reload<IMG_BYTES>(gimg + 2 * IMG_BYTES, lds0 + LL::W2H, wave, lane);
+  sd_reload<IMG_BYTES, FB_WAVES>(gimg, lds0 + LL::W1H, wave, lane);
+  if (!LATE_W2) sd_reload<IMG_BYTES, FB_WAVES>(gimg + 2 * IMG_BYTES, lds0 + LL::W2H, wave, lane);
   if (PP::WP == 2) {
-    fb_reload<IMG_BYTES>(gimg + IMG_BYTES, lds0 + LL::W1L, wave, lane);
-    if (!LATE_W2) fb_reload<IMG_BYTES>(gimg + 3 * IMG_BYTES, lds0 + LL::W2L, wave, lane);
+    sd_reload<IMG_BYTES, FB_WAVES>(gimg + IMG_BYTES, lds0 + LL::W1L, wave, lane);
+    if (!LATE_W2) sd_reload<IMG_BYTES, FB_WAVES>(gimg + 3 * IMG_BYTES, lds0 + LL::W2L, wave, lane);
   }
   // fp16 modes: the images' power-of-two scales (written by the preparation, pv_fb_layout.h); everything derived from them
   // is wave-uniform.  The forward un-scales in tanh's multiply (c1, c2); the backward carries kso * m down the dgrad chain
   // and removes uw2 / uw1 / u0 where a gradient leaves the kernel.
-  float s1 = 1.0f, s2 = 1.0f, kso = 1.0f, c1 = FB_C, c2 = FB_C, uw2 = 1.0f, uw1 = 1.0f, u0 = 1.0f;
+  float s1 = 1.0f, s2 = 1.0f, kso = 1.0f, c1 = SD_C, c2 = SD_C, uw2 = 1.0f, uw1 = 1.0f, u0 = 1.0f;
   if (F16) {
     const float* sc = reinterpret_cast<const float*>(gimg + FB_SCALE_OFF);
     s1 = __builtin_amdgcn_readfirstlane(sc[0]); s2 = __builtin_amdgcn_readfirstlane(sc[1]);
     kso = FB_KAPPA * __builtin_amdgcn_readfirstlane(sc[2]);
-    c1 = FB_C / s1; c2 = FB_C / s2;
+    c1 = SD_C / s1; c2 = SD_C / s2;
     uw2 = __builtin_amdgcn_ldexpf(1.0f / kso, -f.dl_exp);
     uw1 = uw2 / s2;
     u0 = 1.0f / (kso * s1 * s2);
@@ -862,7 +807,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     vec[5 * FD_H + j] = f.b2[j] * s2;
   }
   if (!LATE_W2) {
-    fb_wait_vm0();
+    sd_wait_vm0();
     __syncthreads();
   }
   const float bo = f.bo[0];
@@ -957,20 +902,20 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
   auto fetch_unit_inputs = [&](const Pos& p_) {
     const int b_ = p_.b;
     const int n0 = p_.loc * FD_UNIT;
-    fb_glds4(f.hz + (int64_t)b_ * FD_H + lane, lds0 + BO_CHZ + wave * (FD_H * 4));
-    fb_glds4(f.hz + (int64_t)b_ * FD_H + 64 + lane, lds0 + BO_CHZ + wave * (FD_H * 4) + 256);
-    fb_glds4(f.tp + (int64_t)b_ * 8 + (lane & 7), lds0 + BO_CTP + wave * 256);
-    fb_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + BO_CGR + wave * 256);
+    sd_glds4(f.hz + (int64_t)b_ * FD_H + lane, lds0 + BO_CHZ + wave * (FD_H * 4));
+    sd_glds4(f.hz + (int64_t)b_ * FD_H + 64 + lane, lds0 + BO_CHZ + wave * (FD_H * 4) + 256);
+    sd_glds4(f.tp + (int64_t)b_ * 8 + (lane & 7), lds0 + BO_CTP + wave * 256);
+    sd_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + BO_CGR + wave * 256);
   };
   fetch_unit_inputs(pos_cur);
   if (LATE_W2) {
     // everything requested so far lands (W1's images, the first unit's observations and slots) — the observation registers are
     // touched here so that the compiler's own wait for them stands HERE and not at their first use inside the tile, where it
     // would drain W2's requests as well — then W2's images are requested and the tile loop starts without waiting for them
-    fb_wait_vm0();
+    sd_wait_vm0();
     asm volatile("" : "+v"(xv_next), "+v"(sw_next));
-    fb_reload<IMG_BYTES>(gimg + 2 * IMG_BYTES, lds0 + LL::W2H, wave, lane);
-    fb_reload<IMG_BYTES>(gimg + 3 * IMG_BYTES, lds0 + LL::W2L, wave, lane);
+    sd_reload<IMG_BYTES, FB_WAVES>(gimg + 2 * IMG_BYTES, lds0 + LL::W2H, wave, lane);
+    sd_reload<IMG_BYTES, FB_WAVES>(gimg + 3 * IMG_BYTES, lds0 + LL::W2L, wave, lane);
     __syncthreads();
   }
   int tile_no = -1;
@@ -1003,7 +948,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     const int64_t row = (int64_t)unit * FD_UNIT + r;
     float x0, x1, u0c, u1c, sc;
     // this wave's LDS-DMA of the tile's inputs (issued a tile ago; first tile: in front of W2's images, which stay in flight)
-    if (!(LATE_W2 && tile_no == 0)) fb_wait_vm0();
+    if (!(LATE_W2 && tile_no == 0)) sd_wait_vm0();
     {
       const float* t = ctp + opq;
       const float* gr = cgr + opq;
@@ -1048,8 +993,8 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     if (OV && GRADS && tile_no > 0) {
       // W2's images were the previous tile's staging area: bring them back under the forward of layer 1.
       // (every compiler-visible load above has been consumed; none is issued before the barrier below)
-      fb_wait_vm0();
-      fb_reload<LL::RL_BYTES>(gimg + LL::RL2_SRC, lds0 + LL::RL2_LDS, wave, lane);
+      sd_wait_vm0();
+      sd_reload<LL::RL_BYTES, FB_WAVES>(gimg + LL::RL2_SRC, lds0 + LL::RL2_LDS, wave, lane);
     }
     {
       fb_layer_fwd<PREC>(W1h, W1l, b1s, pBh, pBl, tB, r, q, qsw);
@@ -1058,7 +1003,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     }
     FB_STAMP(2);
     if (OV && GRADS) {
-      fb_wait_vm0();
+      sd_wait_vm0();
       __syncthreads();      // W2 landed everywhere; every wave is past its reads of W1 (staging may overwrite it)
     }
     FB_STAMP(3);
@@ -1081,13 +1026,11 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
       }
       const float a = fb_sum_q((part4[0] + part4[1]) + (part4[2] + part4[3])) + bo;
       float ll, locv;
+      // (sd_pixel_lik<LIK> written out: called as the function, this site compiles to other code — same math, see its comment)
       if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = fb_rcp(1.0f + fb_exp(-a));
+        const float pr = sd_rcp(1.0f + sd_exp(-a));
         const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        // -BCEWithLogits(lg, x) with lg = logit(pc) (torch: probs_to_logits, then binary_cross_entropy_with_logits), written with
-        // the identities 1 + exp(-|lg|) = 1 / max(pc, 1 - pc) and sigmoid(lg) = pc: the two logarithms lg is made of serve the
-        // softplus term too, and the row's dependent chain is exp -> rcp -> 2 log instead of seven transcendentals (round 5)
-        const float lpc = fb_log(pc), l1pc = fb_log(1.0f - pc);
+        const float lpc = sd_log(pc), l1pc = sd_log(1.0f - pc);
         const float lg = lpc - l1pc;
         ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
         const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
@@ -1096,9 +1039,9 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
       } else {
-        const float pr = f.sigmoid_out ? fb_rcp(1.0f + fb_exp(-a)) : a;
+        const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - fb_log(f.sig) - LOG_SQRT_2PI;
+        ll = -(d * d) / (2.0f * f.sig * f.sig) - sd_log(f.sig) - LOG_SQRT_2PI;
         dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
         locv = pr;
       }
@@ -1160,8 +1103,8 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     if (OV) {
       __syncthreads();
       FB_STAMP(6);
-      fb_wait_vm0();                                   // (stores only: nothing the compiler still waits for)
-      fb_reload<LL::RL_BYTES>(gimg + LL::RL1_SRC, lds0 + LL::RL1_LDS, wave, lane);   // W1 comes back under the dgrad of layer 2
+      sd_wait_vm0();                                   // (stores only: nothing the compiler still waits for)
+      sd_reload<LL::RL_BYTES, FB_WAVES>(gimg + LL::RL1_SRC, lds0 + LL::RL1_LDS, wave, lane);   // W1 comes back under the dgrad of layer 2
     }
     {
       fb_layer_dgrad<PREC, PP::DGR2_LO>(W2h, W2l, pAh, pAl, tA, r, q, qsw);
@@ -1170,7 +1113,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
     }
     FB_STAMP(7);
     if (OV) {
-      fb_wait_vm0();
+      sd_wait_vm0();
       __syncthreads();      // W1 landed everywhere; every wave is past its reads of W2
     }
     FB_STAMP(8);
@@ -1246,7 +1189,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
       const int bu = pos_cur.b;                          // (every wave's prefetch slots hold the tail unit's inputs)
       const int64_t row = (int64_t)u_end * FD_UNIT + r;
       float x0, x1, u0c, u1c, sc;
-      fb_wait_vm0();
+      sd_wait_vm0();
       if (f.cd == 2) {
         const float gx = cgr[2 * r], gy = cgr[2 * r + 1];
         u0c = gx * ctp[0] - gy * ctp[1];
@@ -1273,12 +1216,12 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
 #pragma unroll
         for (int i = 0; i < 4; ++i) h0o[o][i] = w0[i] * x0 + w1[i] * x1 + bc[i] + hz[i];
       }
-      fb_tanh2(h0o, FB_C);
+      fb_tanh2(h0o, SD_C);
       fb_presplit2<false>(h0o, oh, ol);
       fb_xchg_put(smb, TL::E, oh, wave, lane);
       if (tile_no > 0) {                                  // W2's lo image was the previous tile's staging area
-        fb_wait_vm0();
-        fb_reload<LL::RL_BYTES>(gimg + LL::RL2_SRC, lds0 + LL::RL2_LDS, wave, lane);
+        sd_wait_vm0();
+        sd_reload<LL::RL_BYTES, FB_WAVES>(gimg + LL::RL2_SRC, lds0 + LL::RL2_LDS, wave, lane);
       }
       FB_TSTAMP(1);
       __syncthreads();                                                   // exchange 0: h0
@@ -1289,7 +1232,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
       fb_presplit2<false>(h1o, oh, ol);
       fb_xchg_put(smb, TL::E + 4096, oh, wave, lane);
       FB_TSTAMP(3);
-      fb_wait_vm0();
+      sd_wait_vm0();
       FB_TSTAMP(4);
       __syncthreads();                                                   // exchange 1: h1; W2 landed
       FB_TSTAMP(5);
@@ -1309,24 +1252,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
       FB_TSTAMP(7);
       const float a = ((rp[r] + rp[16 + r]) + (rp[32 + r] + rp[48 + r])) + bo;
       float ll, locv, dlda;
-      if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = fb_rcp(1.0f + fb_exp(-a));
-        const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        const float lpc = fb_log(pc), l1pc = fb_log(1.0f - pc);
-        const float lg = lpc - l1pc;
-        ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
-        const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
-        dlda = (pc - xv) * mask;
-        locv = pr;
-      } else if (LIK == PV_LIK_CBERNOULLI) {
-        pv_cbern(a, xv, ll, dlda, locv);
-      } else {
-        const float pr = f.sigmoid_out ? fb_rcp(1.0f + fb_exp(-a)) : a;
-        const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - fb_log(f.sig) - LOG_SQRT_2PI;
-        dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
-        locv = pr;
-      }
+      sd_pixel_lik<LIK>(a, xv, f.sig, f.sigmoid_out, ll, dlda, locv);
       dlda *= swv;
       if (wave == 0) {
         // (the tail's row sums ride in wave 0's slot: its sample check first — the tile loop's, at the top of the tile)

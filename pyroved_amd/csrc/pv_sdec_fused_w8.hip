@@ -28,17 +28,13 @@
 // | per-wave prefetch slots.  Four workgroup barriers per 128-row tile.
 #include "pv_sdec_fused.h"
 #include "pv_fb_layout.h"
+#include "pv_sdec_prims.h"
 #include "pv_kernels.h"        // PvHeadBwd, pv_head_dz / pv_head_bwd_math: the image's latent backward in the hosting launch's epilogue
 #include <stdlib.h>
-
-typedef short short4_ __attribute__((ext_vector_type(4)));
-typedef short short8_ __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) short4_ lds_short4;
 
 #define W8_WAVES 8
 #define W8_ROWS (W8_WAVES * FD_UNIT)       // 128
 #define W8_THREADS (64 * W8_WAVES)
-#define LDS2 144                           // staging rows: 72 dwords -> conflict-free 4x16 transposing reads
 #define W8_ARR (W8_ROWS * LDS2)            // elements of one staging array
 #define W8_ARR_BYTES (2 * W8_ARR)          // 36,864
 #define WO_W1 0
@@ -63,28 +59,16 @@ static_assert(WO_TLOG + W8_WAVES * 16 * 4 <= WO_SB + W8_ARR_BYTES, "tail exchang
 static_assert(W8_LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(2 * IMG_BYTES % (W8_WAVES * 1024) == 0, "image load: whole 1 KB LDS-DMA pieces per wave");
 
-#define W8_C 2.8853900817779268f           // 2 log2(e): tanh(x) = 1 - 2 / (exp2(C x) + 1)
-#define W8_RC (1.0f / W8_C)
-#define W8_RC2 (W8_RC * W8_RC)
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f
 #ifndef W8_FENCE_MASK
 #define W8_FENCE_MASK 0          // __builtin_amdgcn_sched_barrier's mask: 0 = nothing crosses a stage fence
 #endif
 #define W8_FENCE() __builtin_amdgcn_sched_barrier(W8_FENCE_MASK)
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ f32x4 w8_mfma16(const bf16x4& a, const bf16x4& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(short4_, a), __builtin_bit_cast(short4_, b), c, 0, 0, 0);
-}
 // tanh of x given C*x
 __device__ __forceinline__ float w8_tanhc(float cx) {
   const float e = __builtin_amdgcn_exp2f(cx);
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
-__device__ __forceinline__ float w8_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float w8_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float w8_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 #ifndef W8_HSWAP
 #define W8_HSWAP 0            // (A/B build only)
 #endif
@@ -92,40 +76,11 @@ __device__ __forceinline__ float w8_rcp(float x) { return __builtin_amdgcn_rcpf(
 #define W8_QSWAP 1            // the weight images' column order (below, at w8_addr)
 #endif
 bool pv_sdec_fused_w8_qswap() { return W8_QSWAP != 0; }
-__device__ __forceinline__ bf16x8 w8_cat(const bf16x4& a, const bf16x4& b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// the forward's activation operand: sd_catq under the q-swapped column order, plain otherwise (W8_QSWAP is this file's A/B switch)
 __device__ __forceinline__ bf16x8 w8_catq(const bf16x4& a, const bf16x4& b, int q) {
-#if W8_QSWAP
-  typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
-  const bool sw = q >= 2;
-  const u32x2_ ua = __builtin_bit_cast(u32x2_, a), ub = __builtin_bit_cast(u32x2_, b);
-  const u32x2_ lo = {sw ? ub[0] : ua[0], sw ? ub[1] : ua[1]}, hi = {sw ? ua[0] : ub[0], sw ? ua[1] : ub[1]};
-  return w8_cat(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi));
-#else
-  (void)q;
-  return w8_cat(a, b);
-#endif
+  return W8_QSWAP ? sd_catq(a, b, q >= 2) : sd_cat(a, b);
 }
-__device__ __forceinline__ int w8_opaque0() { int z = 0; asm volatile("" : "+v"(z)); return z; }
-__device__ __forceinline__ bf16x4 w8_tr(const __bf16* p) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-__device__ __forceinline__ bf16x4 w8_zero4() { const short4_ z = {0, 0, 0, 0}; return __builtin_bit_cast(bf16x4, z); }
-// LDS-DMA (see pv_sdec_fused_bf16.hip: not in hipcc's waitcnt bookkeeping; drain explicitly)
-__device__ __forceinline__ void w8_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void w8_glds4(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void w8_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void w8_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
+// (the permlane form, as fb_sum_q; x3_sum_q / h8_sum_q are two __shfl_xor)
 __device__ __forceinline__ float w8_sum_q(float v) {
   return pv_sum_rows(v);                             // (pv_common.h: v_permlane16/32_swap, the bits of the two shfl_xor sums)
 }
@@ -156,15 +111,13 @@ __device__ __forceinline__ float w8_sum_q(float v) {
 // the forward keeps its ONE ds_read_b128: lanes of groups q >= 2 feed the activation pieces in the swapped order instead (w8_catq:
 // 4 v_cndmask per k-block).  Images written by the kernel itself (FOLD) and by pv_fb_prep (PvFbPrep::qswap) alike.
 
-struct W8Addr { int fb, fx[4], db, dx[4], fs, hs; };
+// SdAddr plus which half of a chunk comes first for this lane's rows under W8_HSWAP / W8_QSWAP
+struct W8Addr : SdAddr { int fs, hs; };
 __device__ __forceinline__ W8Addr w8_addr(int r, int q) {
   W8Addr a;
   a.fs = W8_HSWAP ? ((r >> 2) & 1) : 0;               // forward: rows 16 ob + r
   a.hs = W8_HSWAP ? (q & 1) : (W8_QSWAP ? ((r >> 1) & 1) : 0);   // dgrad: rows 32 m + 4 q (+ 16) + r / 4, piece r & 3
-  a.fb = r * LDB + 8 * (q ^ fb_sl(r >> 2));
-  a.db = (4 * q + (r >> 2)) * LDB + 8 * ((r & 3) ^ fb_sl(q));
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { a.fx[m] = 32 * (m ^ (r & 3)); a.dx[m] = 32 * (m ^ (r >> 2)); }
+  static_cast<SdAddr&>(a) = sd_addr(r, q);
   return a;
 }
 
@@ -191,7 +144,7 @@ __device__ __forceinline__ void w8_layer_fwd(const __bf16* __restrict__ Wh, cons
       typedef const volatile bf16x4* vp4;
       const bf16x4 lo4 = *reinterpret_cast<vp4>(ah0 + 16 * (op + o) * LDB + xm[m]);
       const bf16x4 hi4 = *reinterpret_cast<vp4>(ah1 + 16 * (op + o) * LDB + xm[m]);
-      h[o] = w8_cat(lo4, hi4);
+      h[o] = sd_cat(lo4, hi4);
 #else
       h[o] = *reinterpret_cast<const bf16x8*>(ah + 16 * (op + o) * LDB + xm[m]);
 #endif
@@ -223,7 +176,7 @@ __device__ __forceinline__ void w8_layer_dgrad(const __bf16* __restrict__ Wh, co
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const int off = 32 * m * LDB + xk[(kp + o) >> 1] + (((kp + o) & 1) ? 4 - 4 * ad.hs : 4 * ad.hs);
-      h[o] = w8_cat(w8_tr(ah + off), w8_tr(ah + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(ah + off), sd_tr(ah + off + 16 * LDB));
     }
   };
   load(0, wh[0]);
@@ -232,7 +185,7 @@ __device__ __forceinline__ void w8_layer_dgrad(const __bf16* __restrict__ Wh, co
     const int m = g >> 2, kp = (g & 3) * 2;
     if (g + 1 < 16 && W8_ABL_LOADS(2, g + 1)) load(g + 1, wh[W8_ABL_BUF(2, g + 1)]);
     W8_FENCE();
-    const bf16x8 bh = w8_cat(ih[2 * m], ih[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[kp + o] = MFMA32(wh[W8_ABL_BUF(2, g)][o], bh, out[kp + o]);
     W8_FENCE();
@@ -243,34 +196,6 @@ __device__ __forceinline__ void w8_layer_dgrad(const __bf16* __restrict__ Wh, co
 // the compiler (at the 256-register limit) walks the values two at a time through the whole dependent chain
 // (exp -> add -> rcp -> fma -> cvt), and an in-order wave then pays every instruction's latency (~10 cycles each).
 // tanh of x given C*x, in place: 1 - 2 rcp(exp2(.) + 1)
-__device__ __forceinline__ void w8_tanh8(f32x4 (&v)[8]) {
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[jb][i] = __builtin_amdgcn_exp2f(v[jb][i]);
-  W8_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) v[jb] = v[jb] + 1.0f;
-  W8_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[jb][i] = __builtin_amdgcn_rcpf(v[jb][i]);
-  W8_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) v[jb] = 1.0f - 2.0f * v[jb];
-  W8_FENCE();
-}
-__device__ __forceinline__ f32x4 w8_f32_of(const bf16x4& h) {
-  typedef unsigned uint2_ __attribute__((ext_vector_type(2)));
-  const uint2_ u = __builtin_bit_cast(uint2_, h);
-  f32x4 f;
-  f[0] = __builtin_bit_cast(float, u[0] << 16);
-  f[1] = __builtin_bit_cast(float, u[0] & 0xffff0000u);
-  f[2] = __builtin_bit_cast(float, u[1] << 16);
-  f[3] = __builtin_bit_cast(float, u[1] & 0xffff0000u);
-  return f;
-}
 // d *= h^2 - 1 = -(1 - h^2) with h saved as bf16, four blocks at a time.  The SIGN is deliberate: `1 - t t` costs a v_xor per value
 // in front of the packed fma (its operand negation is not used by the compiler: 64 instructions per tile), `t t - 1` is the
 // packed fma alone.  Everything downstream is linear, so after layer 2's call the kernel carries -C dpre1 (the wgrad of layer 1
@@ -281,7 +206,7 @@ __device__ __forceinline__ void w8_mul_dtanh(f32x4 (&d)[8], const bf16x4 (&hb)[8
   for (int half = 0; half < 2; ++half) {
     f32x4 t[4];
 #pragma unroll
-    for (int jb = 0; jb < 4; ++jb) t[jb] = w8_f32_of(hb[4 * half + jb]);
+    for (int jb = 0; jb < 4; ++jb) t[jb] = sd_f32_of(hb[4 * half + jb]);
     W8_FENCE();
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) t[jb] = t[jb] * t[jb] - 1.0f;
@@ -300,26 +225,16 @@ __device__ __forceinline__ void w8_cvt8(const f32x4 (&v)[8], bf16x4 (&h)[8]) {
 }
 // the wave's 16 rows (row = 16 * wave + r) of a staged tensor, row-major [128][LDS2]; inside every 16-column block the
 // four 8-byte pieces are XOR-swizzled by (row>>2)&3 (pv_sdec_fused_bf16.hip: fb_stage_store)
-__device__ __forceinline__ void w8_stage_store(__bf16* __restrict__ sh, const bf16x4 (&h)[8], int row, int q) {
-  row |= w8_opaque0();
-  const int e = row * LDS2 + 4 * (q ^ ((row >> 2) & 3));
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) *reinterpret_cast<bf16x4*>(sh + e + 16 * jb) = h[jb];
-}
 // lane offset of the transposing read of staged rows R0 + 4q .. 4q+3 (R0 a multiple of 16), columns 16*blk ..
-__device__ __forceinline__ int w8_stage_toff(int r, int q) { return (4 * q + (r >> 2)) * LDS2 + 4 * ((r & 3) ^ q); }
 
 // wgrad over the staged tile.  Wave (jp = wave >> 1, kh = wave & 1) owns the 32 x 64 block dW[32jp .. +31][64kh .. +63]
 // (2 A operands x 4 B operands per 32 staged rows: 12 transposing reads per 8 MFMAs; a 16 x 128 slice per wave needs
 // 18) and the bias sums of rows 32jp + 16kh .. +15 (an MFMA against ones):
 //   dW[j][k] += sum_rows dpre[row][j] h[row][k];   db[j] += sum_rows dpre[row][j]
-__device__ __forceinline__ bf16x4 w8_tr_at(unsigned lds_byte_addr) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)lds_byte_addr);
-  return __builtin_bit_cast(bf16x4, v);
-}
+// (twins: h8_wgrad_consume contracts the bias against the rows' own factor, x3_wgrad_consume hi + lo arrays in three products, fb_wgrad_consume two 16-row slices per wave)
 __device__ __forceinline__ void w8_wgrad_consume(const __bf16* sa, const __bf16* sb, f32x4 (&accW)[2][4], f32x4& accB,
                                                  int wave, int r, int q, int ksteps) {
-  const int toff = w8_stage_toff(r | w8_opaque0(), q);
+  const int toff = sd_stage_toff(r | sd_opaque0(), q);
   const int jp = wave >> 1, kh = wave & 1;
   const short one = 0x3f80;                           // bf16 1.0
   const short8_ ones_s = {one, one, one, one, one, one, one, one};
@@ -344,10 +259,10 @@ __device__ __forceinline__ void w8_wgrad_consume(const __bf16* sa, const __bf16*
     bf16x8 a[2], b[4];
     {
 #endif
-    a[0] = w8_cat(w8_tr_at(la0), w8_tr_at(la0 + ROW16));
-    a[1] = w8_cat(w8_tr_at(la1), w8_tr_at(la1 + ROW16));
+    a[0] = sd_cat(sd_tr_at(la0), sd_tr_at(la0 + ROW16));
+    a[1] = sd_cat(sd_tr_at(la1), sd_tr_at(la1 + ROW16));
 #pragma unroll
-    for (int o = 0; o < 4; ++o) b[o] = w8_cat(w8_tr_at(lb + 32u * o), w8_tr_at(lb + 32u * o + ROW16));
+    for (int o = 0; o < 4; ++o) b[o] = sd_cat(sd_tr_at(lb + 32u * o), sd_tr_at(lb + 32u * o + ROW16));
     }
     W8_FENCE();
     accB = MFMA32(a[0], ones, accB);
@@ -363,16 +278,17 @@ __device__ __forceinline__ void w8_wgrad_consume(const __bf16* sa, const __bf16*
 // wave-local column sums on the matrix cores: accS[jb][.] (D[j][n]) += sum over the unit's 16 rows of t[row][j] * Bn[row][n].
 // The wave stages its bf16 tile `t` in its own rows of `sc` (nobody else reads them at this point of the tile), reads it
 // back transposed as the A operand and contracts against `bop` (lane (n, kq): B[4kq..4kq+3][n]).
+// (twins: h8_colsum_mfma is the fp16 instruction and drains its own reads, x3_colsum_mfma contracts hi and lo pieces)
 __device__ __forceinline__ void w8_colsum_mfma(__bf16* __restrict__ sc, const bf16x4 (&t)[8], const bf16x4& bop,
                                                f32x4 (&accS)[8], int wave, int r, int q) {
-  w8_stage_store(sc, t, 16 * wave + r, q);
-  w8_wait_lgkm0();
-  const __bf16* base = sc + (16 * wave) * LDS2 + w8_stage_toff(r | w8_opaque0(), q);
+  sd_stage_store(sc, t, 16 * wave + r, q);
+  sd_wait_lgkm0();
+  const __bf16* base = sc + (16 * wave) * LDS2 + sd_stage_toff(r | sd_opaque0(), q);
   bf16x4 a[8];
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) a[jb] = w8_tr(base + 16 * jb);
+  for (int jb = 0; jb < 8; ++jb) a[jb] = sd_tr(base + 16 * jb);
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) accS[jb] = w8_mfma16(a[jb], bop, accS[jb]);
+  for (int jb = 0; jb < 8; ++jb) accS[jb] = sd_mfma16(a[jb], bop, accS[jb]);
 }
 
 // phase-timing trace (profiling builds only: -DW8_TRACE): shader-clock stamps of workgroup 0, waves 0 and 7, first tiles
@@ -432,7 +348,7 @@ __device__ __forceinline__ f32x4 w8_tail_fwd(const __bf16* __restrict__ Wh, cons
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
 #if W8_HSWAP
-    wh[m] = w8_cat(*reinterpret_cast<const bf16x4*>(ah + ad.fx[m] + 4 * ad.fs), *reinterpret_cast<const bf16x4*>(ah + ad.fx[m] + 4 - 4 * ad.fs));
+    wh[m] = sd_cat(*reinterpret_cast<const bf16x4*>(ah + ad.fx[m] + 4 * ad.fs), *reinterpret_cast<const bf16x4*>(ah + ad.fx[m] + 4 - 4 * ad.fs));
 #else
     wh[m] = *reinterpret_cast<const bf16x8*>(ah + ad.fx[m]);
 #endif
@@ -448,9 +364,9 @@ __device__ __forceinline__ f32x4 w8_tail_dgrad(const __bf16* __restrict__ Wh, co
   const __bf16* ah = Wh + ad.db + 32 * ((wave >> 1) ^ (r >> 2)) + ((wave & 1) ? 4 - 4 * ad.hs : 4 * ad.hs);
   bf16x8 wh[4];
 #pragma unroll
-  for (int m = 0; m < 4; ++m) wh[m] = w8_cat(w8_tr(ah + 32 * m * LDB), w8_tr(ah + 32 * m * LDB + 16 * LDB));
+  for (int m = 0; m < 4; ++m) wh[m] = sd_cat(sd_tr(ah + 32 * m * LDB), sd_tr(ah + 32 * m * LDB + 16 * LDB));
 #pragma unroll
-  for (int m = 0; m < 4; ++m) out = MFMA32(wh[m], w8_cat(ih[2 * m], ih[2 * m + 1]), out);
+  for (int m = 0; m < 4; ++m) out = MFMA32(wh[m], sd_cat(ih[2 * m], ih[2 * m + 1]), out);
   return out;
 }
 __device__ __forceinline__ f32x4 w8_tanh4(f32x4 v) {
@@ -466,7 +382,7 @@ __device__ __forceinline__ bf16x4 w8_cvt4(const f32x4& v) {
 }
 // d * (h^2 - 1) for one block (w8_mul_dtanh's sign convention)
 __device__ __forceinline__ f32x4 w8_mul_dtanh4(const f32x4& d, const bf16x4& hb) {
-  const f32x4 t = w8_f32_of(hb);
+  const f32x4 t = sd_f32_of(hb);
   return d * (t * t - 1.0f);
 }
 
@@ -567,8 +483,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
 #pragma unroll
     for (int c = 0; c < PIECES; ++c) {
       const int off = (wave * PIECES + c) * 1024;
-      w8_glds16(gimg + off + lane * 16, lds0 + WO_W1 + off);
-      w8_glds16(gimg + 2 * IMG_BYTES + off + lane * 16, lds0 + WO_W2 + off);
+      sd_glds16(gimg + off + lane * 16, lds0 + WO_W1 + off);
+      sd_glds16(gimg + 2 * IMG_BYTES + off + lane * 16, lds0 + WO_W2 + off);
     }
   } else {
     // FOLD: the images straight from the fp32 weights (pv_fb_layout.h pv_fb_prep, mode 0: bf16(C w), permuted columns,
@@ -792,28 +708,28 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         const float* wz = e.Wz + (int64_t)tid * e.lat_in;
         float v = 0.0f;
         for (int i = 0; i < e.lat_in; ++i) v += zs[coord + i] * (i < 4 ? pwz[i] : wz[i]);
-        e.hz[b * FD_H + tid] = v * W8_C;
+        e.hz[b * FD_H + tid] = v * SD_C;
       }
       W8_STAMP_K(7);
     }
   }
   if (tid < FD_H) {
     vec[tid] = FOLD ? pt_v[0] : f.wo[tid];
-    vec[FD_H + tid] = W8_C * (FOLD ? pt_v[1] : f.b1[tid]);
-    vec[2 * FD_H + tid] = W8_C * (FOLD ? pt_v[2] : f.b2[tid]);
+    vec[FD_H + tid] = SD_C * (FOLD ? pt_v[1] : f.b1[tid]);
+    vec[2 * FD_H + tid] = SD_C * (FOLD ? pt_v[2] : f.b2[tid]);
   }
   {
     // coordinate layer A operands (v_mfma_f32_16x16x16_bf16: lane (m, kq) holds A[m][4kq .. 4kq+3]), k slots:
     //   kq 0: [wh0 wh0 wl0 0] x [xh0 xl0 xh0 0]   kq 1: the same for coordinate 1   kq 2: [bch bcl 0 0] x [1 1 0 0]
     const int jb = tid >> 6, m = lane & 15, kq = lane >> 4, j = 16 * jb + m;
     float v = 0.0f;
-    if (FOLD) v = W8_C * pt_a;
-    else if (kq == 0) v = W8_C * f.Wc[j * f.cd];
-    else if (kq == 1) v = f.cd == 2 ? W8_C * f.Wc[j * 2 + 1] : 0.0f;
-    else if (kq == 2) v = W8_C * f.bc[j];
+    if (FOLD) v = SD_C * pt_a;
+    else if (kq == 0) v = SD_C * f.Wc[j * f.cd];
+    else if (kq == 1) v = f.cd == 2 ? SD_C * f.Wc[j * 2 + 1] : 0.0f;
+    else if (kq == 2) v = SD_C * f.bc[j];
     __bf16 hi, lo;
     fb_split(v, hi, lo);
-    bf16x4 a = w8_zero4();
+    bf16x4 a = sd_zero4();
     if (kq < 2) { a[0] = hi; a[1] = hi; a[2] = lo; }
     else if (kq == 2) { a[0] = hi; a[1] = lo; }
     reinterpret_cast<bf16x4*>(smb + WO_ATAB)[tid] = a;
@@ -847,15 +763,15 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       us4 h1, h2;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        h1[i] = __builtin_bit_cast(unsigned short, (__bf16)(w1v[u][i] * W8_C));
-        h2[i] = __builtin_bit_cast(unsigned short, (__bf16)(w2v[u][i] * W8_C));
+        h1[i] = __builtin_bit_cast(unsigned short, (__bf16)(w1v[u][i] * SD_C));
+        h2[i] = __builtin_bit_cast(unsigned short, (__bf16)(w2v[u][i] * SD_C));
       }
       const int el = fb_wel(row, fb_pcol(4 * c4)) ^ (W8_HSWAP ? 4 * ((row >> 2) & 1) : 0) ^ (W8_QSWAP ? 4 * ((c4 >> 1) & 1) : 0);
       *reinterpret_cast<us4*>(i1 + el) = h1;
       *reinterpret_cast<us4*>(i2 + el) = h2;
     }
   }
-  w8_wait_vm0();
+  sd_wait_vm0();
   __syncthreads();
   W8_STAMP_K(1);
   const float bo = f.bo[0];
@@ -892,7 +808,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     gfloat* dst = a_part_hz + ((int64_t)b * f.kmax + (g - gfirst) * W8_WAVES + wave) * FD_H + 4 * q;
     if (r == 0) {
 #pragma unroll
-      for (int jb = 0; jb < 8; ++jb) *(__attribute__((address_space(1))) f32x4*)(dst + 16 * jb) = accS[jb] * W8_RC2;
+      for (int jb = 0; jb < 8; ++jb) *(__attribute__((address_space(1))) f32x4*)(dst + 16 * jb) = accS[jb] * SD_RC2;
     }
 #pragma unroll
     for (int jb = 0; jb < 8; ++jb)
@@ -933,10 +849,10 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   float* cgr = reinterpret_cast<float*>(smb + WO_CGR) + wave * 64;
   auto fetch_unit_inputs = [&](const Pos& p_) {
     const int n0 = p_.loc * FD_UNIT;
-    w8_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + WO_CHZ + wave * (FD_H * 4));
-    w8_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + WO_CHZ + wave * (FD_H * 4) + 256);
-    w8_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + WO_CTP + wave * 256);
-    w8_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + WO_CGR + wave * 256);
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + WO_CHZ + wave * (FD_H * 4));
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + WO_CHZ + wave * (FD_H * 4) + 256);
+    sd_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + WO_CTP + wave * 256);
+    sd_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + WO_CGR + wave * 256);
   };
   fetch_unit_inputs(pos_cur);
   const W8Addr wad = w8_addr(r, q);
@@ -963,7 +879,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     const int bu = pos_cur.b;
     const int64_t row = (int64_t)unit * FD_UNIT + r;
     float x0, x1, u0c, u1c, sc;
-    w8_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
+    sd_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
     {
       const float* t = ctp;
       const float* gr = cgr;
@@ -995,7 +911,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     // the merges they create cost register copies of the 104 accumulators' neighbours in every tile.
     {
       // ---- coordinate layer on the matrix cores: C h0pre = (C Wc) x' + C bc + C hz[b] ----
-      bf16x4 bx = w8_zero4();
+      bf16x4 bx = sd_zero4();
       {
         const float v = q == 0 ? x0 : x1;
         __bf16 vh, vl;
@@ -1016,13 +932,13 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       W8_FENCE();
       if (f.hz_scale == 0.0f) {                  // hz arrives unscaled only when the generic encoder path produced it
 #pragma unroll
-        for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * W8_C;
+        for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * SD_C;
       }
       W8_FENCE();
 #pragma unroll
-      for (int jb = 0; jb < 8; ++jb) tC[jb] = w8_mfma16(aop[jb], bx, tC[jb]);
+      for (int jb = 0; jb < 8; ++jb) tC[jb] = sd_mfma16(aop[jb], bx, tC[jb]);
       W8_FENCE();
-      w8_tanh8(tC);
+      sd_tanh8<W8_FENCE_MASK>(tC);
       w8_cvt8(tC, h0b);
     }
     asm volatile("; W8_P1_coord_done");
@@ -1030,13 +946,13 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     fetch_unit_inputs(pos_nx);                 // the slots were consumed by the coordinate layer above
     {
       w8_layer_fwd(W1h, b1s, h0b, tC, wad, q);
-      w8_tanh8(tC);
+      sd_tanh8<W8_FENCE_MASK>(tC);
       w8_cvt8(tC, h1b);                                             // feeds layer 2 and its wgrad
       asm volatile("; W8_P2_l1_done");
     W8_STAMP(2);
       w8_layer_fwd(W2h, b2s, h1b, tC, wad, q);
       // ---- h2, output layer + likelihood (fp32); tC <- g = wo (1 - h2^2), pA <- bf16(h2) ----
-      w8_tanh8(tC);                                                // tC = h2
+      sd_tanh8<W8_FENCE_MASK>(tC);                                                // tC = h2
       f32x4 part4 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
       for (int jb = 0; jb < 8; ++jb) {
@@ -1051,27 +967,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       }
       const float a = w8_sum_q((part4[0] + part4[1]) + (part4[2] + part4[3])) + bo;
       float ll, locv;
-      if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = w8_rcp(1.0f + w8_exp(-a));
-        const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        // -BCEWithLogits(lg, x) with lg = logit(pc) (torch: probs_to_logits, then binary_cross_entropy_with_logits), written with
-        // the identities 1 + exp(-|lg|) = 1 / max(pc, 1 - pc) and sigmoid(lg) = pc: the two logarithms lg is made of serve the
-        // softplus term too, and the row's dependent chain is exp -> rcp -> 2 log instead of seven transcendentals (round 5)
-        const float lpc = w8_log(pc), l1pc = w8_log(1.0f - pc);
-        const float lg = lpc - l1pc;
-        ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
-        const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
-        dlda = (pc - xv) * mask;
-        locv = pr;
-      } else if (LIK == PV_LIK_CBERNOULLI) {
-        pv_cbern(a, xv, ll, dlda, locv);
-      } else {
-        const float pr = f.sigmoid_out ? w8_rcp(1.0f + w8_exp(-a)) : a;
-        const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - w8_log(f.sig) - LOG_SQRT_2PI;
-        dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
-        locv = pr;
-      }
+      sd_pixel_lik<LIK>(a, xv, f.sig, f.sigmoid_out, ll, dlda, locv);
       dlda *= act ? swv : 0.0f;
       if (q == 0) {
         if (act) {
@@ -1090,9 +986,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     {
       // ---- d(wo) += sum_rows dlda h2 : wave-local MFMA through the wave's own rows of staging A (free: every wave
       // passed barrier 4 of the previous tile); B = dlda of rows 4q..4q+3 in columns 3 (hi) and 4 (lo)
-      w8_wait_lgkm0();
+      sd_wait_lgkm0();
       const f32x4 d4 = *reinterpret_cast<const f32x4*>(inf_dl + 4 * q);
-      bf16x4 bw = w8_zero4();
+      bf16x4 bw = sd_zero4();
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         __bf16 hi, lo;
@@ -1108,8 +1004,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     asm volatile("; W8_P4_dwo_done");
     W8_STAMP(4);
     // ---- wgrad of layer 2: stage (dpre2, h1) of all 128 rows, one pass ----
-    w8_stage_store(sA, pA, 16 * wave + r, q);
-    w8_stage_store(sB, h1b, 16 * wave + r, q);
+    sd_stage_store(sA, pA, 16 * wave + r, q);
+    sd_stage_store(sB, h1b, 16 * wave + r, q);
     __syncthreads();                                                // barrier 1
     asm volatile("; W8_P5_bar1");
     W8_STAMP(5);
@@ -1138,9 +1034,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       f32x4 dd = {0.0f, 0.0f, 0.0f, 0.0f};
       const bf16x8* ttab = reinterpret_cast<const bf16x8*>(smb + WO_TTAB) + lane;
 #pragma unroll
-      for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], w8_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
+      for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], sd_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
       if (q == 0 && act) {
-        const float d0 = (dd[0] + dd[1]) * W8_RC2, d1 = (dd[2] + dd[3]) * W8_RC2;
+        const float d0 = (dd[0] + dd[1]) * SD_RC2, d1 = (dd[2] + dd[3]) * SD_RC2;
         a_rowtp[row] = sc * (d1 * u0c - d0 * u1c);
         a_rowtp[a_M + row] = d0 * u0c + d1 * u1c;
         a_rowtp[2 * a_M + row] = d0;
@@ -1154,7 +1050,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       // B columns: 0 ones | 1, 5 x0 (hi, lo) | 2, 6 x1 (hi, lo)
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(inf_x0 + 4 * q);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(inf_x1 + 4 * q);
-      bf16x4 bc_ = w8_zero4();
+      bf16x4 bc_ = sd_zero4();
       const bool use1 = r == 2 || r == 6, lo_col = r >= 5;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1166,13 +1062,13 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         bc_[i] = v;
       }
       w8_colsum_mfma(sA, p0, bc_, accS, wave, r, q);
-      w8_wait_lgkm0();                                              // (own reads done before the rows are re-staged)
+      sd_wait_lgkm0();                                              // (own reads done before the rows are re-staged)
     }
     asm volatile("; W8_P12_rowlocal");
     W8_STAMP(12);
     // ---- wgrad of layer 1: stage (C dpre1, h0) ----
-    w8_stage_store(sA, pA, 16 * wave + r, q);
-    w8_stage_store(sB, h0b, 16 * wave + r, q);
+    sd_stage_store(sA, pA, 16 * wave + r, q);
+    sd_stage_store(sB, h0b, 16 * wave + r, q);
     __syncthreads();                                                // barrier 3
     asm volatile("; W8_P10_bar3");
     W8_STAMP(10);
@@ -1196,7 +1092,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     const int unit = u_end, bu = pos_cur.b;            // (every wave's prefetch slots hold the tail unit's inputs: pos_lo)
     const int64_t row = (int64_t)unit * FD_UNIT + r;
     float x0, x1, u0c, u1c, sc;
-    w8_wait_vm0();
+    sd_wait_vm0();
     {
       const float* t = ctp;
       const float* gr = cgr;
@@ -1219,7 +1115,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     bf16x4 h0b[8], h1b[8], own0, own1;
     {
       // ---- coordinate layer, block `wave` ----
-      bf16x4 bx = w8_zero4();
+      bf16x4 bx = sd_zero4();
       {
         const float v = q == 0 ? x0 : x1;
         __bf16 vh, vl;
@@ -1229,10 +1125,10 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         else if (q == 2) { bx[0] = one; bx[1] = one; }
       }
       f32x4 t0 = *reinterpret_cast<const f32x4*>(chz + 16 * wave + 4 * q);
-      if (f.hz_scale == 0.0f) t0 = t0 * W8_C;
+      if (f.hz_scale == 0.0f) t0 = t0 * SD_C;
       const bf16x4 aop = (reinterpret_cast<const bf16x4*>(smb + WO_ATAB) + lane)[64 * wave];
       if (GRADS && q == 0) { inf_x0[r] = x0; inf_x1[r] = x1; }
-      t0 = w8_mfma16(aop, bx, t0);
+      t0 = sd_mfma16(aop, bx, t0);
       own0 = w8_cvt4(w8_tanh4(t0));
       w8_xchg_put(smb, 0, own0, wave, lane);
     }
@@ -1264,13 +1160,11 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         a += sacc;
       }
       float ll, locv;
+      // (sd_pixel_lik<LIK> written out: called as the function, this site compiles to other code — same math, see its comment)
       if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = w8_rcp(1.0f + w8_exp(-a));
+        const float pr = sd_rcp(1.0f + sd_exp(-a));
         const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        // -BCEWithLogits(lg, x) with lg = logit(pc) (torch: probs_to_logits, then binary_cross_entropy_with_logits), written with
-        // the identities 1 + exp(-|lg|) = 1 / max(pc, 1 - pc) and sigmoid(lg) = pc: the two logarithms lg is made of serve the
-        // softplus term too, and the row's dependent chain is exp -> rcp -> 2 log instead of seven transcendentals (round 5)
-        const float lpc = w8_log(pc), l1pc = w8_log(1.0f - pc);
+        const float lpc = sd_log(pc), l1pc = sd_log(1.0f - pc);
         const float lg = lpc - l1pc;
         ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
         const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
@@ -1279,9 +1173,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
       } else {
-        const float pr = f.sigmoid_out ? w8_rcp(1.0f + w8_exp(-a)) : a;
+        const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - w8_log(f.sig) - LOG_SQRT_2PI;
+        ll = -(d * d) / (2.0f * f.sig * f.sig) - sd_log(f.sig) - LOG_SQRT_2PI;
         dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
         locv = pr;
       }
@@ -1302,21 +1196,21 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       __syncthreads();                                             // exchange 3: dpre2
       w8_xchg_get(smb, 3, pA, lane);
       if (wave == 0) {                                             // rows 0 .. 15 of the weight-gradient staging
-        w8_stage_store(sA, pA, r, q);
-        w8_stage_store(sB, h1b, r, q);
+        sd_stage_store(sA, pA, r, q);
+        sd_stage_store(sB, h1b, r, q);
       } else if (wave == 1) {                                      // rows 16 .. 31: zero gradient rows (one k-step is 32 rows)
         bf16x4 z8[8];
 #pragma unroll
-        for (int jb = 0; jb < 8; ++jb) z8[jb] = w8_zero4();
-        w8_stage_store(sA, z8, 16 + r, q);
-        w8_stage_store(sB, h1b, 16 + r, q);
+        for (int jb = 0; jb < 8; ++jb) z8[jb] = sd_zero4();
+        sd_stage_store(sA, z8, 16 + r, q);
+        sd_stage_store(sB, h1b, 16 + r, q);
       } else if (wave == 3) {
         // d(wo) += sum_rows dlda h2 in this wave's own rows of staging A (rows 48 .. 63: unused by the tail's staging)
         bf16x4 h2b[8];
         w8_xchg_get(smb, 2, h2b, lane);
-        w8_wait_lgkm0();
+        sd_wait_lgkm0();
         const f32x4 d4 = *reinterpret_cast<const f32x4*>(inf_dl + 4 * q);
-        bf16x4 bw = w8_zero4();
+        bf16x4 bw = sd_zero4();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           __bf16 hi, lo;
@@ -1336,14 +1230,14 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       w8_xchg_put(smb, 5, w8_cvt4(d0), wave, lane);
       __syncthreads();                                             // exchange 5: dpre0; round 1 consumed everywhere
       if (wave == 0) {
-        w8_stage_store(sA, pA, r, q);
-        w8_stage_store(sB, h0b, r, q);
+        sd_stage_store(sA, pA, r, q);
+        sd_stage_store(sB, h0b, r, q);
       } else if (wave == 1) {
         bf16x4 z8[8];
 #pragma unroll
-        for (int jb = 0; jb < 8; ++jb) z8[jb] = w8_zero4();
-        w8_stage_store(sA, z8, 16 + r, q);
-        w8_stage_store(sB, h0b, 16 + r, q);
+        for (int jb = 0; jb < 8; ++jb) z8[jb] = sd_zero4();
+        sd_stage_store(sA, z8, 16 + r, q);
+        sd_stage_store(sB, h0b, 16 + r, q);
       } else if (wave == 2) {
         // coordinate layer backward, row-local part
         bf16x4 p0[8];
@@ -1351,9 +1245,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         f32x4 dd = {0.0f, 0.0f, 0.0f, 0.0f};
         const bf16x8* ttab = reinterpret_cast<const bf16x8*>(smb + WO_TTAB) + lane;
 #pragma unroll
-        for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], w8_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
+        for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], sd_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
         if (q == 0) {
-          const float d0_ = (dd[0] + dd[1]) * W8_RC2, d1_ = (dd[2] + dd[3]) * W8_RC2;
+          const float d0_ = (dd[0] + dd[1]) * SD_RC2, d1_ = (dd[2] + dd[3]) * SD_RC2;
           a_rowtp[row] = sc * (d1_ * u0c - d0_ * u1c);
           a_rowtp[a_M + row] = d0_ * u0c + d1_ * u1c;
           a_rowtp[2 * a_M + row] = d0_;
@@ -1369,7 +1263,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         }
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(inf_x0 + 4 * q);
         const f32x4 a1 = *reinterpret_cast<const f32x4*>(inf_x1 + 4 * q);
-        bf16x4 bc_ = w8_zero4();
+        bf16x4 bc_ = sd_zero4();
         const bool use1 = r == 2 || r == 6, lo_col = r >= 5;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1475,7 +1369,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
           for (int i = 0; i < 4; ++i) {
             // C/D layout: lane (col = r, q), reg i -> dW[32jp + 16 (s ^ kh) + 4q + i][64kh + 16o + r]  (w8_wgrad_consume's rotation)
             const int e = (32 * jp + 16 * (s_ ^ kh) + 4 * q + i) * FD_H + 64 * kh + 16 * o + r;
-            rec[e] = accW1[s_][o][i] * -W8_RC;                        // (accW1 / accB1 hold -C dW1 / -C db1)
+            rec[e] = accW1[s_][o][i] * -SD_RC;                        // (accW1 / accB1 hold -C dW1 / -C db1)
             rec[FD_H * FD_H + e] = accW2[s_][o][i];
           }
     } else {
@@ -1486,8 +1380,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
           u32x4_ v;
-          v[0] = pack2(accW1[s_][o][0] * -W8_RC, accW1[s_][o][1] * -W8_RC);   // (accW1 / accB1 hold -C dW1 / -C db1)
-          v[1] = pack2(accW1[s_][o][2] * -W8_RC, accW1[s_][o][3] * -W8_RC);
+          v[0] = pack2(accW1[s_][o][0] * -SD_RC, accW1[s_][o][1] * -SD_RC);   // (accW1 / accB1 hold -C dW1 / -C db1)
+          v[1] = pack2(accW1[s_][o][2] * -SD_RC, accW1[s_][o][3] * -SD_RC);
           v[2] = pack2(accW2[s_][o][0], accW2[s_][o][1]);
           v[3] = pack2(accW2[s_][o][2], accW2[s_][o][3]);
           rec4[((wave * 2 + s_) * 4 + o) * 64 + lane] = v;
@@ -1497,7 +1391,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       const int j0 = 32 * jp + 16 * kh;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        rec[2 * FD_H * FD_H + j0 + 4 * q + i] = accB1[i] * -W8_RC;
+        rec[2 * FD_H * FD_H + j0 + 4 * q + i] = accB1[i] * -SD_RC;
         rec[2 * FD_H * FD_H + FD_H + j0 + 4 * q + i] = accB2[i];
       }
     }
@@ -1530,10 +1424,10 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       v1 += s_[2 * FD_H] + s_[6 * FD_H];
       vo += s_[3 * FD_H] + s_[4 * FD_H];
     }
-    dhz_j = vh * W8_RC2;
+    dhz_j = vh * SD_RC2;
     if (own_dhz) f.dhz_out[(int64_t)g * FD_H + tid] = dhz_j;
-    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = v0 * W8_RC2;
-    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = v1 * W8_RC2;
+    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = v0 * SD_RC2;
+    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = v1 * SD_RC2;
     rec[2 * FD_H * FD_H + 4 * FD_H + tid] = vo;
   }
   const bool own_dzc = own_dhz && f.dzc_out != nullptr;

@@ -23,17 +23,12 @@
 // pv_sdec_fused_bf16.hip / pv_sdec_fused_w8.hip (pv_fb_layout.h), so the rest of the step is unchanged.
 #include "pv_sdec_fused.h"
 #include "pv_fb_layout.h"
+#include "pv_sdec_prims.h"
 #include <stdlib.h>
-
-typedef short short4_ __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4_ lds_short4;
-typedef _Float16 half4_ __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_ __attribute__((ext_vector_type(8)));
 
 #define H8_WAVES 8
 #define H8_ROWS (H8_WAVES * FD_UNIT)       // 128
 #define H8_THREADS (64 * H8_WAVES)
-#define LDS2 144                           // staging rows: 72 dwords -> conflict-free 4x16 transposing reads
 #define H8_ARR (H8_ROWS * LDS2)            // elements of one staging array
 #define H8_ARR_BYTES (2 * H8_ARR)          // 36,864
 #define H8_GAP (2 * H8_ARR_BYTES - 2 * IMG_BYTES)      // 8,192
@@ -57,35 +52,17 @@ static_assert(HO_ST2 + 2 * H8_ARR_BYTES <= HO_W2H && HO_ST1 + 2 * H8_ARR_BYTES <
 static_assert(H8_LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(2 * IMG_BYTES % (H8_WAVES * 1024) == 0, "image load: whole 1 KB LDS-DMA pieces per wave");
 
-#define H8_C 2.8853900817779268f           // 2 log2(e): tanh(x) = 1 - 2 / (exp2(C x) + 1)
 #define H8_KAPPA 16.0f                     // dL/dpre2 operands are kappa * s_o * mantissa(dL/dlogit) * wo * (1 - h2^2)
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f
 #define H8_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // 16-bit operands travel as bf16x4 / bf16x8 bit containers (pv_fb_layout.h's types); the instructions read them as fp16
 __device__ __forceinline__ f32x4 h8_mma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_, a), __builtin_bit_cast(half8_, b), c, 0, 0, 0);
 }
+// (sd_mfma16 is the bf16 instruction; this is the fp16 one)
 __device__ __forceinline__ f32x4 h8_mma16(const bf16x4& a, const bf16x4& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(half4_, a), __builtin_bit_cast(half4_, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ float h8_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float h8_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float h8_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ bf16x8 h8_cat(const bf16x4& a, const bf16x4& b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ int h8_opaque0() { int z = 0; asm volatile("" : "+v"(z)); return z; }
-__device__ __forceinline__ bf16x4 h8_tr(const __bf16* p) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-__device__ __forceinline__ bf16x4 h8_tr_at(unsigned lds_byte_addr) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)lds_byte_addr);
-  return __builtin_bit_cast(bf16x4, v);
-}
-__device__ __forceinline__ bf16x4 h8_zero4() { const short4_ z = {0, 0, 0, 0}; return __builtin_bit_cast(bf16x4, z); }
 __device__ __forceinline__ unsigned short h8_bits(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
 __device__ __forceinline__ void h8_put(bf16x4& v, int i, _Float16 x) { v[i] = __builtin_bit_cast(__bf16, x); }
 // x -> (hi, lo) fp16 with hi + lo = x to 2^-22 (lo subnormal below |x| ~ 0.125: 2^-25 absolute)
@@ -93,43 +70,11 @@ __device__ __forceinline__ void h8_split(float x, _Float16& hi, _Float16& lo) {
   hi = (_Float16)x;
   lo = (_Float16)(x - (float)hi);
 }
-// LDS-DMA (see pv_sdec_fused_bf16.hip: not in hipcc's waitcnt bookkeeping; drain explicitly)
-__device__ __forceinline__ void h8_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void h8_glds4(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void h8_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void h8_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
+// (two __shfl_xor, as x3_sum_q; w8_sum_q / fb_sum_q are the permlane form)
 __device__ __forceinline__ float h8_sum_q(float v) {
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;
-}
-// one layer's hi + lo images (64 KB, adjacent in LDS and in the global copy): 8 one-KB pieces per wave
-__device__ __forceinline__ void h8_reload(const char* __restrict__ gimg, unsigned lds_dst, int wave, int lane) {
-  constexpr int PIECES = 2 * IMG_BYTES / (H8_WAVES * 1024);
-#pragma unroll
-  for (int c = 0; c < PIECES; ++c) {
-    const int off = (wave * PIECES + c) * 1024;
-    h8_glds16(gimg + off + lane * 16, lds_dst + off);
-  }
-}
-
-// lane offsets (elements) of the weight reads (pv_sdec_fused_w8.hip: W8Addr)
-struct H8Addr { int fb, fx[4], db, dx[4]; };
-__device__ __forceinline__ H8Addr h8_addr(int r, int q) {
-  H8Addr a;
-  a.fb = r * LDB + 8 * (q ^ fb_sl(r >> 2));
-  a.db = (4 * q + (r >> 2)) * LDB + 8 * ((r & 3) ^ fb_sl(q));
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { a.fx[m] = 32 * (m ^ (r & 3)); a.dx[m] = 32 * (m ^ (r >> 2)); }
-  return a;
 }
 
 #ifndef H8_PF
@@ -137,7 +82,7 @@ __device__ __forceinline__ H8Addr h8_addr(int r, int q) {
 #endif
 // forward layer of the wave's unit: out = bias + W in (times C s): two products per block, hi x in and lo x in
 __device__ __forceinline__ void h8_layer_fwd(const __bf16* __restrict__ Wh, const float* __restrict__ bs, const bf16x4 (&ih)[8],
-                                             f32x4 (&out)[8], const H8Addr& ad, int q) {
+                                             f32x4 (&out)[8], const SdAddr& ad, int q) {
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) out[ob] = *reinterpret_cast<const f32x4*>(bs + 16 * ob + 4 * q);
   const __bf16* ah = Wh + ad.fb;
@@ -160,7 +105,7 @@ __device__ __forceinline__ void h8_layer_fwd(const __bf16* __restrict__ Wh, cons
     const int m = g >> 2, op = (g & 3) * 2, cur = g % (H8_PF + 1);
     if (g + H8_PF < 16) load(g + H8_PF, wh[(g + H8_PF) % (H8_PF + 1)], wl[(g + H8_PF) % (H8_PF + 1)]);
     H8_FENCE();
-    const bf16x8 bh = h8_cat(ih[2 * m], ih[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[op + o] = h8_mma(wh[cur][o], bh, out[op + o]);
 #pragma unroll
@@ -172,7 +117,7 @@ __device__ __forceinline__ void h8_layer_fwd(const __bf16* __restrict__ Wh, cons
 // dgrad of the wave's unit: out[k] = sum_j (C s W)[j][k] dp[j]; A = W^T via the transposing LDS read; DS: dp arrives split
 template <bool DS>
 __device__ __forceinline__ void h8_layer_dgrad(const __bf16* __restrict__ Wh, const bf16x4 (&ih)[8], const bf16x4 (&il)[8],
-                                               f32x4 (&out)[8], const H8Addr& ad) {
+                                               f32x4 (&out)[8], const SdAddr& ad) {
 #pragma unroll
   for (int kb = 0; kb < 8; ++kb) out[kb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   const __bf16* ah = Wh + ad.db;
@@ -184,8 +129,8 @@ __device__ __forceinline__ void h8_layer_dgrad(const __bf16* __restrict__ Wh, co
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const int off = 32 * m * LDB + xk[(kp + o) >> 1] + 4 * ((kp + o) & 1);
-      h[o] = h8_cat(h8_tr(ah + off), h8_tr(ah + off + 16 * LDB));
-      l[o] = h8_cat(h8_tr(al + off), h8_tr(al + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(ah + off), sd_tr(ah + off + 16 * LDB));
+      l[o] = sd_cat(sd_tr(al + off), sd_tr(al + off + 16 * LDB));
     }
   };
 #pragma unroll
@@ -195,11 +140,11 @@ __device__ __forceinline__ void h8_layer_dgrad(const __bf16* __restrict__ Wh, co
     const int m = g >> 2, kp = (g & 3) * 2, cur = g % (H8_PF + 1);
     if (g + H8_PF < 16) load(g + H8_PF, wh[(g + H8_PF) % (H8_PF + 1)], wl[(g + H8_PF) % (H8_PF + 1)]);
     H8_FENCE();
-    const bf16x8 bh = h8_cat(ih[2 * m], ih[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[kp + o] = h8_mma(wh[cur][o], bh, out[kp + o]);
     if (DS) {
-      const bf16x8 bl = h8_cat(il[2 * m], il[2 * m + 1]);
+      const bf16x8 bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
       for (int o = 0; o < 2; ++o) out[kp + o] = h8_mma(wh[cur][o], bl, out[kp + o]);
     }
@@ -209,7 +154,7 @@ __device__ __forceinline__ void h8_layer_dgrad(const __bf16* __restrict__ Wh, co
   }
 }
 
-// tanh of x given C s x (MUL: s != 1, rc = 1 / s), in place, written as stages (pv_sdec_fused_w8.hip)
+// tanh of x given C s x (MUL: s != 1, rc = 1 / s), in place, written as stages: sd_tanh8 plus the optional un-scaling multiply
 template <bool MUL>
 __device__ __forceinline__ void h8_tanh8(f32x4 (&v)[8], float rc) {
   if (MUL) {
@@ -264,11 +209,11 @@ __device__ __forceinline__ void h8_mul_d(f32x4 (&t)[8], const bf16x4 (&d)[8]) {
   }
 }
 // the wave's 16 rows (row = 16 * wave + r) of a staged tensor, row-major [128][LDS2]; inside every 16-column block the
-// four 8-byte pieces are XOR-swizzled by (row>>2)&3 (pv_sdec_fused_bf16.hip: fb_stage_store).  SCALED: every piece times the
+// four 8-byte pieces are XOR-swizzled by (row>>2)&3: sd_stage_store with an optional scale (fb_stage_store also has lo arrays).  SCALED: every piece times the
 // row's power of two ph (exact), and ph itself into column block 8 (the rows' padding): the bias gradient's operand
 template <bool SCALED>
 __device__ __forceinline__ void h8_stage_store(__bf16* __restrict__ sh, const bf16x4 (&h)[8], int row, int q, half4_ ph = half4_{}) {
-  row |= h8_opaque0();
+  row |= sd_opaque0();
   const int e = row * LDS2 + 4 * (q ^ ((row >> 2) & 3));
 #pragma unroll
   for (int jb = 0; jb < 8; ++jb) {
@@ -277,14 +222,13 @@ __device__ __forceinline__ void h8_stage_store(__bf16* __restrict__ sh, const bf
   }
   if constexpr (SCALED) *reinterpret_cast<half4_*>(sh + e + 16 * 8) = ph;
 }
-__device__ __forceinline__ int h8_stage_toff(int r, int q) { return (4 * q + (r >> 2)) * LDS2 + 4 * ((r & 3) ^ q); }
 
 // wgrad over the staged tile (pv_sdec_fused_w8.hip: w8_wgrad_consume): wave (jp = wave >> 1, kh = wave & 1) owns the 32 x 64
 // block dW[32jp .. +31][64kh .. +63] and the bias sums of rows 32jp + 16kh .. +15 — contracted against the rows' own
 // factor (column block 8 of the staged activations) instead of ones
 __device__ __forceinline__ void h8_wgrad_consume(const __bf16* sa, const __bf16* sb, f32x4 (&accW)[2][4], f32x4& accB,
                                                  int wave, int r, int q, int ksteps) {
-  const int toff = h8_stage_toff(r | h8_opaque0(), q);
+  const int toff = sd_stage_toff(r | sd_opaque0(), q);
   const int jp = wave >> 1, kh = wave & 1;
   unsigned la0 = (unsigned)(size_t)sa + 2u * (unsigned)(toff + 32 * jp + 16 * kh);
   unsigned la1 = (unsigned)(size_t)sa + 2u * (unsigned)(toff + 32 * jp + 16 * (1 ^ kh));
@@ -294,11 +238,11 @@ __device__ __forceinline__ void h8_wgrad_consume(const __bf16* sa, const __bf16*
   constexpr unsigned ROW16 = 2u * 16 * LDS2;         // bytes of 16 staged rows
   for (int ks = 0; ks < ksteps; ++ks) {
     bf16x8 a[2], b[4];
-    a[0] = h8_cat(h8_tr_at(la0), h8_tr_at(la0 + ROW16));
-    a[1] = h8_cat(h8_tr_at(la1), h8_tr_at(la1 + ROW16));
-    const bf16x8 bp = h8_cat(h8_tr_at(lp), h8_tr_at(lp + ROW16));
+    a[0] = sd_cat(sd_tr_at(la0), sd_tr_at(la0 + ROW16));
+    a[1] = sd_cat(sd_tr_at(la1), sd_tr_at(la1 + ROW16));
+    const bf16x8 bp = sd_cat(sd_tr_at(lp), sd_tr_at(lp + ROW16));
 #pragma unroll
-    for (int o = 0; o < 4; ++o) b[o] = h8_cat(h8_tr_at(lb + 32u * o), h8_tr_at(lb + 32u * o + ROW16));
+    for (int o = 0; o < 4; ++o) b[o] = sd_cat(sd_tr_at(lb + 32u * o), sd_tr_at(lb + 32u * o + ROW16));
     H8_FENCE();
     accB = h8_mma(a[0], bp, accB);
 #pragma unroll
@@ -313,17 +257,18 @@ __device__ __forceinline__ void h8_wgrad_consume(const __bf16* sa, const __bf16*
 // wave-local column sums on the matrix cores: accS[jb][.] (D[j][n]) += sum over the unit's 16 rows of t[row][j] * Bn[row][n].
 // The wave stages its fp16 tile `t` in its own rows of `sc` (nobody else reads them at this point of the tile), reads it
 // back transposed as the A operand and contracts against `bop` (lane (n, kq): B[4kq..4kq+3][n]).
+// (w8_colsum_mfma with the fp16 instruction and a second drain: its rows are written again right after)
 __device__ __forceinline__ void h8_colsum_mfma(__bf16* __restrict__ sc, const bf16x4 (&t)[8], const bf16x4& bop,
                                                f32x4 (&accS)[8], int wave, int r, int q) {
   h8_stage_store<false>(sc, t, 16 * wave + r, q);
-  h8_wait_lgkm0();
-  const __bf16* base = sc + (16 * wave) * LDS2 + h8_stage_toff(r | h8_opaque0(), q);
+  sd_wait_lgkm0();
+  const __bf16* base = sc + (16 * wave) * LDS2 + sd_stage_toff(r | sd_opaque0(), q);
   bf16x4 a[8];
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) a[jb] = h8_tr(base + 16 * jb);
+  for (int jb = 0; jb < 8; ++jb) a[jb] = sd_tr(base + 16 * jb);
 #pragma unroll
   for (int jb = 0; jb < 8; ++jb) accS[jb] = h8_mma16(a[jb], bop, accS[jb]);
-  h8_wait_lgkm0();                                   // (own reads done before the rows are written again)
+  sd_wait_lgkm0();                                   // (own reads done before the rows are written again)
 }
 
 // LIK: the likelihood is a compile-time choice; DS: dL/dpre split in both dgrads (H231) or one piece everywhere (H221)
@@ -346,8 +291,8 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
   const char* gimg = reinterpret_cast<const char*>(f.wimg);
 
   // ---- prologue: weight images by LDS-DMA, scales, vectors and tables ----
-  h8_reload(gimg, lds0 + HO_W1H, wave, lane0);
-  h8_reload(gimg + 2 * IMG_BYTES, lds0 + HO_W2H, wave, lane0);
+  sd_reload<2 * IMG_BYTES, H8_WAVES>(gimg, lds0 + HO_W1H, wave, lane0);
+  sd_reload<2 * IMG_BYTES, H8_WAVES>(gimg + 2 * IMG_BYTES, lds0 + HO_W2H, wave, lane0);
   const float* scg = reinterpret_cast<const float*>(gimg + FB_SCALE_OFF);
   const float s1 = __builtin_amdgcn_readfirstlane(scg[0]), s2 = __builtin_amdgcn_readfirstlane(scg[1]);
   const float kso = H8_KAPPA * __builtin_amdgcn_readfirstlane(scg[2]);
@@ -356,25 +301,25 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
   // what the backward's carried scales amount to where a gradient leaves the kernel (all powers of two but C):
   //   dW2, db2: kappa s_o 2^dl_exp ; dW1, db1: that times C s2 ; dpre0 (per row, with 2^e): kappa s_o C^2 s1 s2
   const float uw2 = __builtin_amdgcn_ldexpf(1.0f / kso, -f.dl_exp);
-  const float uw1 = uw2 / (H8_C * s2);
-  const float u0 = 1.0f / (kso * s1 * s2 * H8_C * H8_C);          // times 2^e per row
+  const float uw1 = uw2 / (SD_C * s2);
+  const float u0 = 1.0f / (kso * s1 * s2 * SD_C * SD_C);          // times 2^e per row
   const float u0p = __builtin_amdgcn_ldexpf(u0, -f.dl_exp);       // ... for sums weighted by the row's staged factor 2^(e + dl_exp)
   if (tid < FD_H) {
     vec[tid] = f.wo[tid];
-    vec[FD_H + tid] = H8_C * s1 * f.b1[tid];
-    vec[2 * FD_H + tid] = H8_C * s2 * f.b2[tid];
+    vec[FD_H + tid] = SD_C * s1 * f.b1[tid];
+    vec[2 * FD_H + tid] = SD_C * s2 * f.b2[tid];
   }
   {
     // coordinate layer A operands (v_mfma_f32_16x16x16_f16: lane (m, kq) holds A[m][4kq .. 4kq+3]), k slots:
     //   kq 0: [wh0 wh0 wl0 0] x [xh0 xl0 xh0 0]   kq 1: the same for coordinate 1   kq 2: [bch bcl 0 0] x [1 1 0 0]
     const int jb = tid >> 6, m = lane0 & 15, kq = lane0 >> 4, j = 16 * jb + m;
     float v = 0.0f;
-    if (kq == 0) v = H8_C * f.Wc[j * f.cd];
-    else if (kq == 1) v = f.cd == 2 ? H8_C * f.Wc[j * 2 + 1] : 0.0f;
-    else if (kq == 2) v = H8_C * f.bc[j];
+    if (kq == 0) v = SD_C * f.Wc[j * f.cd];
+    else if (kq == 1) v = f.cd == 2 ? SD_C * f.Wc[j * 2 + 1] : 0.0f;
+    else if (kq == 2) v = SD_C * f.bc[j];
     _Float16 hi, lo;
     h8_split(v, hi, lo);
-    bf16x4 a = h8_zero4();
+    bf16x4 a = sd_zero4();
     if (kq < 2) { h8_put(a, 0, hi); h8_put(a, 1, hi); h8_put(a, 2, lo); }
     else if (kq == 2) { h8_put(a, 0, hi); h8_put(a, 1, lo); }
     reinterpret_cast<bf16x4*>(smb + HO_ATAB)[tid] = a;
@@ -396,7 +341,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
     }
     reinterpret_cast<bf16x8*>(smb + HO_TTAB)[tid] = a;
   }
-  h8_wait_vm0();
+  sd_wait_vm0();
   __syncthreads();
   const float bo = f.bo[0];
   typedef __attribute__((address_space(1))) float gfloat;         // (explicitly global: an opaque pointer would be stored through flat_*)
@@ -463,14 +408,14 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
   float* cgr = reinterpret_cast<float*>(smb + HO_CGR) + wave * 64;
   auto fetch_unit_inputs = [&](const Pos& p_) {
     const int n0 = p_.loc * FD_UNIT;
-    h8_glds4(f.hz + (int64_t)p_.b * FD_H + lane0, lds0 + HO_CHZ + wave * (FD_H * 4));
-    h8_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane0, lds0 + HO_CHZ + wave * (FD_H * 4) + 256);
-    h8_glds4(f.tp + (int64_t)p_.b * 8 + (lane0 & 7), lds0 + HO_CTP + wave * 256);
-    h8_glds4(f.grid + (int64_t)n0 * f.cd + (lane0 & (16 * f.cd - 1)), lds0 + HO_CGR + wave * 256);
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + lane0, lds0 + HO_CHZ + wave * (FD_H * 4));
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane0, lds0 + HO_CHZ + wave * (FD_H * 4) + 256);
+    sd_glds4(f.tp + (int64_t)p_.b * 8 + (lane0 & 7), lds0 + HO_CTP + wave * 256);
+    sd_glds4(f.grid + (int64_t)n0 * f.cd + (lane0 & (16 * f.cd - 1)), lds0 + HO_CGR + wave * 256);
   };
   fetch_unit_inputs(pos_cur);
-  const H8Addr wad = h8_addr(lane0 & 15, lane0 >> 4);
-  const float hzs = f.hz_scale == 0.0f ? H8_C : 1.0f;             // (hz arrives as C hz when the compact encoder produced it)
+  const SdAddr wad = sd_addr(lane0 & 15, lane0 >> 4);
+  const float hzs = f.hz_scale == 0.0f ? SD_C : 1.0f;             // (hz arrives as C hz when the compact encoder produced it)
   int tile_no = -1;
   for (int ut = u_lo; ut < u_hi; ut += H8_WAVES) {
     ++tile_no;
@@ -488,7 +433,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
     const int bu = pos_cur.b;
     const int64_t row = (int64_t)unit * FD_UNIT + r;
     float x0, x1, u0c, u1c, sc;
-    h8_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
+    sd_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
     {
       const float* t = ctp;
       const float* gr = cgr;
@@ -516,7 +461,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
     half4_ ph4 = half4_{};
     {
       // ---- coordinate layer on the matrix cores: C h0pre = (C Wc) x' + C bc + C hz[b] ----
-      bf16x4 bx = h8_zero4();
+      bf16x4 bx = sd_zero4();
       {
         const float v = q == 0 ? x0 : x1;
         _Float16 vh, vl;
@@ -548,8 +493,8 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
     if (tile_no > 0) {
       // W2's images were the previous tile's staging area: bring them back under the forward of layer 1
       // (every compiler-visible load above has been consumed; none is issued before the barrier below)
-      h8_wait_vm0();
-      h8_reload(gimg + 2 * IMG_BYTES, lds0 + HO_W2H, wave, lane);
+      sd_wait_vm0();
+      sd_reload<2 * IMG_BYTES, H8_WAVES>(gimg + 2 * IMG_BYTES, lds0 + HO_W2H, wave, lane);
     }
     {
       h8_layer_fwd(W1h, b1s, h0h, tC, wad, q);
@@ -557,7 +502,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
       h8_save8(tC, h1h, d1);
     }
     asm volatile("; H8_P2_l1");
-    h8_wait_vm0();
+    sd_wait_vm0();
     __syncthreads();      // barrier (a): W2 landed everywhere; every wave is past its reads of W1 (staging may overwrite it)
     {
       h8_layer_fwd(W2h, b2s, h1h, tC, wad, q);
@@ -574,27 +519,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
       }
       const float a = h8_sum_q((part4[0] + part4[1]) + (part4[2] + part4[3])) + bo;
       float ll, locv;
-      if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = h8_rcp(1.0f + h8_exp(-a));
-        const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        // -BCEWithLogits(lg, x) with lg = logit(pc) (torch: probs_to_logits, then binary_cross_entropy_with_logits), written with
-        // the identities 1 + exp(-|lg|) = 1 / max(pc, 1 - pc) and sigmoid(lg) = pc: the two logarithms lg is made of serve the
-        // softplus term too, and the row's dependent chain is exp -> rcp -> 2 log instead of seven transcendentals (round 5)
-        const float lpc = h8_log(pc), l1pc = h8_log(1.0f - pc);
-        const float lg = lpc - l1pc;
-        ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
-        const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
-        dlda = (pc - xv) * mask;
-        locv = pr;
-      } else if (LIK == PV_LIK_CBERNOULLI) {
-        pv_cbern(a, xv, ll, dlda, locv);
-      } else {
-        const float pr = f.sigmoid_out ? h8_rcp(1.0f + h8_exp(-a)) : a;
-        const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - h8_log(f.sig) - LOG_SQRT_2PI;
-        dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
-        locv = pr;
-      }
+      sd_pixel_lik<LIK>(a, xv, f.sig, f.sigmoid_out, ll, dlda, locv);
       dlda *= act ? swv : 0.0f;
       // dL/dlogit = m 2^e: the mantissa (times kappa s_o) goes down the dgrad chain, the exponent into the staged rows
       const int e = __builtin_amdgcn_frexp_expf(dlda);
@@ -615,9 +540,9 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
       {
         // ---- d(wo) += sum_rows dlda h2 : wave-local MFMA through the wave's own rows of the layer-2 staging area (W1's
         // images are dead since barrier (a)); B = dlda of rows 4q..4q+3 in columns 3 (hi) and 4 (lo)
-        h8_wait_lgkm0();
+        sd_wait_lgkm0();
         const f32x4 d4 = *reinterpret_cast<const f32x4*>(inf_dl + 4 * q);
-        bf16x4 bw = h8_zero4();
+        bf16x4 bw = sd_zero4();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           _Float16 hi, lo;
@@ -642,15 +567,15 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
     h8_wgrad_consume(sA2, sB2, accW2, accB2, wave, r, q, ksteps);
     asm volatile("; H8_P5_cons2");
     __syncthreads();                                                // barrier (c): consumed everywhere
-    h8_wait_vm0();                                                  // (stores only: nothing the compiler still waits for)
-    h8_reload(gimg, lds0 + HO_W1H, wave, lane);                     // W1 comes back under the dgrad of layer 2
+    sd_wait_vm0();                                                  // (stores only: nothing the compiler still waits for)
+    sd_reload<2 * IMG_BYTES, H8_WAVES>(gimg, lds0 + HO_W1H, wave, lane);                     // W1 comes back under the dgrad of layer 2
     {
       h8_layer_dgrad<DS>(W2h, pA, pAl, tC, wad);                    // tC = (carried scales) dL/dh1
       h8_mul_d(tC, d1);
       if (DS) h8_split8(tC, pA, pAl); else h8_cvt8(tC, pA);        // dpre1: feeds the dgrad and the wgrad of layer 1
     }
     asm volatile("; H8_P6_dgrad2");
-    h8_wait_vm0();
+    sd_wait_vm0();
     __syncthreads();      // barrier (d): W1 landed everywhere; every wave is past its reads of W2
     bf16x4 p0h[8], p0l[8];
     {
@@ -665,8 +590,8 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
 #pragma unroll
       for (int mm = 0; mm < 4; ++mm) {
         const bf16x8 ta = ttab[64 * mm];
-        dd = h8_mma(ta, h8_cat(p0h[2 * mm], p0h[2 * mm + 1]), dd);
-        dd = h8_mma(ta, h8_cat(p0l[2 * mm], p0l[2 * mm + 1]), dd);
+        dd = h8_mma(ta, sd_cat(p0h[2 * mm], p0h[2 * mm + 1]), dd);
+        dd = h8_mma(ta, sd_cat(p0l[2 * mm], p0l[2 * mm + 1]), dd);
       }
       if (q == 0 && act) {
         const float d0_ = (dd[0] + dd[1]) * frow, d1_ = (dd[2] + dd[3]) * frow;
@@ -685,7 +610,7 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(inf_x0 + 4 * q);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(inf_x1 + 4 * q);
       const f32x4 ap = *reinterpret_cast<const f32x4*>(inf_ph + 4 * q);
-      bf16x4 bc_ = h8_zero4();
+      bf16x4 bc_ = sd_zero4();
       const bool use1 = r == 2 || r == 6, lo_col = r >= 5;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {

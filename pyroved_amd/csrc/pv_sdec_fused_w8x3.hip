@@ -32,18 +32,15 @@
 // pv_sdec_fused_bf16.hip / pv_sdec_fused_w8.hip (pv_fb_layout.h), so the rest of the step is unchanged.
 #include "pv_sdec_fused.h"
 #include "pv_fb_layout.h"
+#include "pv_sdec_prims.h"
 #include <stdlib.h>
 
-typedef short short4_ __attribute__((ext_vector_type(4)));
-typedef short short8_ __attribute__((ext_vector_type(8)));
 typedef unsigned uint4_ __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4_ lds_short4;
 
 #define X3_WAVES 8                         // the LDS map is laid out for the 8-wave form (NW = 4 leaves slots unused)
 #define X3_ROWS (X3_WAVES * FD_UNIT)       // 128 rows per tile
 #define X3_HALF 64                         // rows per staged half
 #define X3_THREADS (64 * X3_WAVES)
-#define LDS2 144                           // staging rows: 72 dwords -> conflict-free 4x16 transposing reads
 #define X3_ARR (X3_HALF * LDS2)            // elements of one staging array (64 rows)
 #define X3_ARR_BYTES (2 * X3_ARR)          // 18,432
 #define X3_GAP_BYTES (4 * X3_ARR_BYTES - 2 * IMG_BYTES)   // 8,192
@@ -68,67 +65,13 @@ static_assert(2 * X3_ROWS * LDS2 * 2 <= 4 * X3_ARR_BYTES, "column-sum scratch (h
 // per wave and tile: the parked h0 (8 blocks x 64 lanes x 16 B)
 #define X3_PARK_BYTES_PER_WAVE (8 * 64 * 16)
 
-#define X3_C 2.8853900817779268f           // 2 log2(e): tanh(x) = 1 - 2 / (exp2(C x) + 1)
-#define X3_RC (1.0f / X3_C)
-#define X3_RC2 (X3_RC * X3_RC)
-#define LOG_SQRT_2PI 0.91893853320467274178f
-#define BERN_EPS 1.1920928955078125e-07f
 #define X3_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ f32x4 x3_mfma16(const bf16x4& a, const bf16x4& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(short4_, a), __builtin_bit_cast(short4_, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float x3_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float x3_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float x3_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ bf16x8 x3_cat(const bf16x4& a, const bf16x4& b) {
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ int x3_opaque0() { int z = 0; asm volatile("" : "+v"(z)); return z; }
-__device__ __forceinline__ bf16x4 x3_tr(const __bf16* p) {
-  const short4_ v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-__device__ __forceinline__ bf16x4 x3_zero4() { const short4_ z = {0, 0, 0, 0}; return __builtin_bit_cast(bf16x4, z); }
-// LDS-DMA (see pv_sdec_fused_bf16.hip: not in hipcc's waitcnt bookkeeping; drain explicitly)
-__device__ __forceinline__ void x3_glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void x3_glds4(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void x3_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void x3_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
+// (two __shfl_xor, as h8_sum_q; w8_sum_q / fb_sum_q are the permlane form)
 __device__ __forceinline__ float x3_sum_q(float v) {
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;
-}
-// one layer's hi + lo images (64 KB) from their global copy: 8 one-KB pieces per wave
-template <int NW>
-__device__ __forceinline__ void x3_reload(const char* __restrict__ gimg, unsigned lds_dst, int wave, int lane) {
-  constexpr int PIECES = 2 * IMG_BYTES / (NW * 1024);
-#pragma unroll
-  for (int c = 0; c < PIECES; ++c) {
-    const int off = (wave * PIECES + c) * 1024;
-    x3_glds16(gimg + off + lane * 16, lds_dst + off);
-  }
-}
-
-// lane offsets (elements) of the weight reads (pv_sdec_fused_w8.hip: W8Addr)
-struct X3Addr { int fb, fx[4], db, dx[4]; };
-__device__ __forceinline__ X3Addr x3_addr(int r, int q) {
-  X3Addr a;
-  a.fb = r * LDB + 8 * (q ^ fb_sl(r >> 2));
-  a.db = (4 * q + (r >> 2)) * LDB + 8 * ((r & 3) ^ fb_sl(q));
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { a.fx[m] = 32 * (m ^ (r & 3)); a.dx[m] = 32 * (m ^ (r >> 2)); }
-  return a;
 }
 
 #ifndef X3_PF4
@@ -147,7 +90,7 @@ struct X3NoEpi { __device__ __forceinline__ void operator()(int) const {} };
 template <int PF, class Epi = X3NoEpi>
 __device__ __forceinline__ void x3_layer_fwd(const __bf16* __restrict__ Wh, const float* __restrict__ bs,
                                              const bf16x4 (&ih)[8], const bf16x4 (&il)[8], f32x4 (&out)[8],
-                                             const X3Addr& ad, int q, Epi epi = Epi()) {
+                                             const SdAddr& ad, int q, Epi epi = Epi()) {
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) out[ob] = *reinterpret_cast<const f32x4*>(bs + 16 * ob + 4 * q);
   const __bf16* ah = Wh + ad.fb;
@@ -171,7 +114,7 @@ __device__ __forceinline__ void x3_layer_fwd(const __bf16* __restrict__ Wh, cons
     const int cur = g % (PF + 1);
     if (g + PF < 16) load(g + PF, wh[(g + PF) % (PF + 1)], wl[(g + PF) % (PF + 1)]);
     X3_FENCE();
-    const bf16x8 bh = x3_cat(ih[2 * m], ih[2 * m + 1]), bl = x3_cat(il[2 * m], il[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]), bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[op + o] = MFMA32(wh[cur][o], bh, out[op + o]);
 #pragma unroll
@@ -189,7 +132,7 @@ __device__ __forceinline__ void x3_layer_fwd(const __bf16* __restrict__ Wh, cons
 // PF: operand prefetch distance in groups (0 with 8 waves: the 256-register limit)
 template <int PF>
 __device__ __forceinline__ void x3_layer_dgrad_half(const __bf16* __restrict__ Wh, const bf16x4 (&ih)[8],
-                                                    const bf16x4 (&il)[8], f32x4 (&out)[4], int hf, const X3Addr& ad) {
+                                                    const bf16x4 (&il)[8], f32x4 (&out)[4], int hf, const SdAddr& ad) {
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb) out[kb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   const __bf16* ah = Wh + ad.db;
@@ -201,8 +144,8 @@ __device__ __forceinline__ void x3_layer_dgrad_half(const __bf16* __restrict__ W
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const int off = 32 * m * LDB + xk[(kp + o) >> 1] + 4 * ((kp + o) & 1);
-      h[o] = x3_cat(x3_tr(ah + off), x3_tr(ah + off + 16 * LDB));
-      l[o] = x3_cat(x3_tr(al + off), x3_tr(al + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(ah + off), sd_tr(ah + off + 16 * LDB));
+      l[o] = sd_cat(sd_tr(al + off), sd_tr(al + off + 16 * LDB));
     }
   };
 #pragma unroll
@@ -213,7 +156,7 @@ __device__ __forceinline__ void x3_layer_dgrad_half(const __bf16* __restrict__ W
     const int cur = g % (PF + 1);
     if (g + PF < 8) load(g + PF, wh[(g + PF) % (PF + 1)], wl[(g + PF) % (PF + 1)]);
     X3_FENCE();
-    const bf16x8 bh = x3_cat(ih[2 * m], ih[2 * m + 1]), bl = x3_cat(il[2 * m], il[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]), bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[kq + o] = MFMA32(wh[cur][o], bh, out[kq + o]);
 #pragma unroll
@@ -227,7 +170,7 @@ __device__ __forceinline__ void x3_layer_dgrad_half(const __bf16* __restrict__ W
 // dgrad of the wave's unit, all 8 output blocks (the 4-wave form: registers are no concern), with an epilogue functor
 template <int PF, class Epi = X3NoEpi>
 __device__ __forceinline__ void x3_layer_dgrad(const __bf16* __restrict__ Wh, const bf16x4 (&ih)[8], const bf16x4 (&il)[8],
-                                               f32x4 (&out)[8], const X3Addr& ad, Epi epi = Epi()) {
+                                               f32x4 (&out)[8], const SdAddr& ad, Epi epi = Epi()) {
 #pragma unroll
   for (int kb = 0; kb < 8; ++kb) out[kb] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   const __bf16* ah = Wh + ad.db;
@@ -239,8 +182,8 @@ __device__ __forceinline__ void x3_layer_dgrad(const __bf16* __restrict__ Wh, co
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const int off = 32 * m * LDB + xk[(kp + o) >> 1] + 4 * ((kp + o) & 1);
-      h[o] = x3_cat(x3_tr(ah + off), x3_tr(ah + off + 16 * LDB));
-      l[o] = x3_cat(x3_tr(al + off), x3_tr(al + off + 16 * LDB));
+      h[o] = sd_cat(sd_tr(ah + off), sd_tr(ah + off + 16 * LDB));
+      l[o] = sd_cat(sd_tr(al + off), sd_tr(al + off + 16 * LDB));
     }
   };
 #pragma unroll
@@ -251,7 +194,7 @@ __device__ __forceinline__ void x3_layer_dgrad(const __bf16* __restrict__ Wh, co
     const int cur = g % (PF + 1);
     if (g + PF < 16) load(g + PF, wh[(g + PF) % (PF + 1)], wl[(g + PF) % (PF + 1)]);
     X3_FENCE();
-    const bf16x8 bh = x3_cat(ih[2 * m], ih[2 * m + 1]), bl = x3_cat(il[2 * m], il[2 * m + 1]);
+    const bf16x8 bh = sd_cat(ih[2 * m], ih[2 * m + 1]), bl = sd_cat(il[2 * m], il[2 * m + 1]);
 #pragma unroll
     for (int o = 0; o < 2; ++o) out[kp + o] = MFMA32(wh[cur][o], bh, out[kp + o]);
 #pragma unroll
@@ -289,35 +232,6 @@ __device__ __forceinline__ void x3_dtanh_split_chunk(const f32x4 (&d)[8], const 
   x3_split2(t0, t1, oh[jb], ol[jb], e0);
 }
 
-// tanh of x given C*x, in place, written as stages (pv_sdec_fused_w8.hip)
-__device__ __forceinline__ void x3_tanh8(f32x4 (&v)[8]) {
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[jb][i] = __builtin_amdgcn_exp2f(v[jb][i]);
-  X3_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) v[jb] = v[jb] + 1.0f;
-  X3_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[jb][i] = __builtin_amdgcn_rcpf(v[jb][i]);
-  X3_FENCE();
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) v[jb] = 1.0f - 2.0f * v[jb];
-  X3_FENCE();
-}
-__device__ __forceinline__ f32x4 x3_f32_of(const bf16x4& h) {
-  typedef unsigned uint2_ __attribute__((ext_vector_type(2)));
-  const uint2_ u = __builtin_bit_cast(uint2_, h);
-  f32x4 f;
-  f[0] = __builtin_bit_cast(float, u[0] << 16);
-  f[1] = __builtin_bit_cast(float, u[0] & 0xffff0000u);
-  f[2] = __builtin_bit_cast(float, u[1] << 16);
-  f[3] = __builtin_bit_cast(float, u[1] & 0xffff0000u);
-  return f;
-}
 // v -> (hi, lo) per C/D block, staged: all hi converts, then the residuals, then the lo converts
 __device__ __forceinline__ void x3_split8(const f32x4 (&v)[8], bf16x4 (&h)[8], bf16x4 (&l)[8]) {
 #pragma unroll
@@ -329,7 +243,7 @@ __device__ __forceinline__ void x3_split8(const f32x4 (&v)[8], bf16x4 (&h)[8], b
       for (int i = 0; i < 4; ++i) h[4 * half + jb][i] = (__bf16)v[4 * half + jb][i];
     X3_FENCE();
 #pragma unroll
-    for (int jb = 0; jb < 4; ++jb) t[jb] = v[4 * half + jb] - x3_f32_of(h[4 * half + jb]);
+    for (int jb = 0; jb < 4; ++jb) t[jb] = v[4 * half + jb] - sd_f32_of(h[4 * half + jb]);
     X3_FENCE();
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb)
@@ -342,7 +256,7 @@ __device__ __forceinline__ void x3_split8(const f32x4 (&v)[8], bf16x4 (&h)[8], b
 __device__ __forceinline__ void x3_dtanh_split4(f32x4 (&d)[4], const bf16x4* hh, const bf16x4* hl, bf16x4* oh, bf16x4* ol) {
   f32x4 t[4];
 #pragma unroll
-  for (int jb = 0; jb < 4; ++jb) t[jb] = x3_f32_of(hh[jb]) + x3_f32_of(hl[jb]);
+  for (int jb = 0; jb < 4; ++jb) t[jb] = sd_f32_of(hh[jb]) + sd_f32_of(hl[jb]);
   X3_FENCE();
 #pragma unroll
   for (int jb = 0; jb < 4; ++jb) t[jb] = 1.0f - t[jb] * t[jb];
@@ -356,7 +270,7 @@ __device__ __forceinline__ void x3_dtanh_split4(f32x4 (&d)[4], const bf16x4* hh,
     for (int i = 0; i < 4; ++i) oh[jb][i] = (__bf16)d[jb][i];
   X3_FENCE();
 #pragma unroll
-  for (int jb = 0; jb < 4; ++jb) t[jb] = d[jb] - x3_f32_of(oh[jb]);
+  for (int jb = 0; jb < 4; ++jb) t[jb] = d[jb] - sd_f32_of(oh[jb]);
   X3_FENCE();
 #pragma unroll
   for (int jb = 0; jb < 4; ++jb)
@@ -370,7 +284,7 @@ __device__ __forceinline__ void x3_mul_dtanh(f32x4 (&d)[8], const bf16x4 (&hh)[8
   for (int half = 0; half < 2; ++half) {
     f32x4 t[4];
 #pragma unroll
-    for (int jb = 0; jb < 4; ++jb) t[jb] = x3_f32_of(hh[4 * half + jb]) + x3_f32_of(hl[4 * half + jb]);
+    for (int jb = 0; jb < 4; ++jb) t[jb] = sd_f32_of(hh[4 * half + jb]) + sd_f32_of(hl[4 * half + jb]);
     X3_FENCE();
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) t[jb] = 1.0f - t[jb] * t[jb];
@@ -381,17 +295,6 @@ __device__ __forceinline__ void x3_mul_dtanh(f32x4 (&d)[8], const bf16x4 (&hh)[8
   }
 }
 
-// 16 rows (row0 + r) of a staged tensor, row-major [rows][LDS2]; inside every 16-column block the four 8-byte pieces
-// are XOR-swizzled by (row>>2)&3 (pv_sdec_fused_bf16.hip: fb_stage_store)
-__device__ __forceinline__ void x3_stage_store(__bf16* __restrict__ sh, const bf16x4 (&h)[8], int row, int q) {
-  row |= x3_opaque0();
-  const int e = row * LDS2 + 4 * (q ^ ((row >> 2) & 3));
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) *reinterpret_cast<bf16x4*>(sh + e + 16 * jb) = h[jb];
-}
-// lane offset of the transposing read of staged rows R0 + 4q .. 4q+3 (R0 a multiple of 16), columns 16*blk ..
-__device__ __forceinline__ int x3_stage_toff(int r, int q) { return (4 * q + (r >> 2)) * LDS2 + 4 * ((r & 3) ^ q); }
-
 // wgrad over one staged exchange (64 rows = up to 2 k-steps).  Region: [dpre hi | dpre lo | h hi | h lo], 64 x LDS2 each.
 // Wave (jp = wave >> 1, kh = wave & 1) owns the (16 SB) x 64 block dW[16 SB jp .. ][64kh .. +63] (SB = 16 / NW: 32 rows
 // with 8 waves, 64 with 4) and the bias sums of its 16 NB rows 16 SB jp + 16 NB kh .. (NB = 8 / NW; an MFMA against ones):
@@ -399,6 +302,7 @@ __device__ __forceinline__ int x3_stage_toff(int r, int q) { return (4 * q + (r 
 // The wave holds its SB row blocks ROTATED by NB kh — accW[s] is row block (s + NB kh) mod SB — so that its bias blocks are
 // always operands 0 .. NB-1: a wave-uniform choice between REGISTER operands (kh ? a[NB + t] : a[t]) made hipcc put the
 // operand arrays in scratch memory and index them there (14 scratch transfers per k-step: 8.7 k cycles per exchange).
+// (w8_wgrad_consume takes one bf16 piece per operand and a fixed 32 x 64 block per wave)
 template <int NW>
 __device__ __forceinline__ void x3_wgrad_consume(const __bf16* st, f32x4 (&accW)[16 / NW][4], f32x4 (&accB)[8 / NW], int wave,
                                                  int r, int q, int ksteps) {
@@ -407,7 +311,7 @@ __device__ __forceinline__ void x3_wgrad_consume(const __bf16* st, f32x4 (&accW)
   const __bf16* sal = st + X3_ARR;
   const __bf16* sbh = st + 2 * X3_ARR;
   const __bf16* sbl = st + 3 * X3_ARR;
-  const int toff = x3_stage_toff(r | x3_opaque0(), q);
+  const int toff = sd_stage_toff(r | sd_opaque0(), q);
   const int jp = wave >> 1, kh = wave & 1;
   const short one = 0x3f80;                           // bf16 1.0
   const short8_ ones_s = {one, one, one, one, one, one, one, one};
@@ -418,14 +322,14 @@ __device__ __forceinline__ void x3_wgrad_consume(const __bf16* st, f32x4 (&accW)
 #pragma unroll
     for (int s_ = 0; s_ < SB; ++s_) {
       const int off = koff + 16 * SB * jp + 16 * ((s_ + NB * kh) & (SB - 1));
-      ah[s_] = x3_cat(x3_tr(sah + off), x3_tr(sah + off + 16 * LDS2));
-      al[s_] = x3_cat(x3_tr(sal + off), x3_tr(sal + off + 16 * LDS2));
+      ah[s_] = sd_cat(sd_tr(sah + off), sd_tr(sah + off + 16 * LDS2));
+      al[s_] = sd_cat(sd_tr(sal + off), sd_tr(sal + off + 16 * LDS2));
     }
     bf16x8 bh[2], bl[2];
     auto load = [&](int o, bf16x8& h, bf16x8& l) {
       const int off = koff + 64 * kh + 16 * o;
-      h = x3_cat(x3_tr(sbh + off), x3_tr(sbh + off + 16 * LDS2));
-      l = x3_cat(x3_tr(sbl + off), x3_tr(sbl + off + 16 * LDS2));
+      h = sd_cat(sd_tr(sbh + off), sd_tr(sbh + off + 16 * LDS2));
+      l = sd_cat(sd_tr(sbl + off), sd_tr(sbl + off + 16 * LDS2));
     };
     load(0, bh[0], bl[0]);
     X3_FENCE();
@@ -453,22 +357,23 @@ __device__ __forceinline__ void x3_wgrad_consume(const __bf16* st, f32x4 (&accW)
 //   t_hi[row][j] * b1[row][n] + t_lo[row][j] * b2[row][n].
 // The wave stages its tile (hi at `sc`, lo 128 rows further) in its own 16 rows of a region nobody else touches at this
 // point, reads it back transposed as the A operand and contracts against the B operands (lane (n, kq): B[4kq..4kq+3][n]).
+// (w8_colsum_mfma is the one-piece form)
 __device__ __forceinline__ void x3_colsum_mfma(__bf16* __restrict__ sc, const bf16x4 (&th)[8], const bf16x4 (&tl)[8],
                                                const bf16x4& b1, const bf16x4& b2, f32x4 (&accS)[8], int wave, int r, int q) {
   __bf16* sl = sc + X3_ROWS * LDS2;
-  x3_stage_store(sc, th, 16 * wave + r, q);
-  x3_stage_store(sl, tl, 16 * wave + r, q);
-  x3_wait_lgkm0();
-  const int toff = (16 * wave) * LDS2 + x3_stage_toff(r | x3_opaque0(), q);
+  sd_stage_store(sc, th, 16 * wave + r, q);
+  sd_stage_store(sl, tl, 16 * wave + r, q);
+  sd_wait_lgkm0();
+  const int toff = (16 * wave) * LDS2 + sd_stage_toff(r | sd_opaque0(), q);
   bf16x4 a[8];
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) a[jb] = x3_tr(sc + toff + 16 * jb);
+  for (int jb = 0; jb < 8; ++jb) a[jb] = sd_tr(sc + toff + 16 * jb);
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) accS[jb] = x3_mfma16(a[jb], b1, accS[jb]);
+  for (int jb = 0; jb < 8; ++jb) accS[jb] = sd_mfma16(a[jb], b1, accS[jb]);
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) a[jb] = x3_tr(sl + toff + 16 * jb);
+  for (int jb = 0; jb < 8; ++jb) a[jb] = sd_tr(sl + toff + 16 * jb);
 #pragma unroll
-  for (int jb = 0; jb < 8; ++jb) accS[jb] = x3_mfma16(a[jb], b2, accS[jb]);
+  for (int jb = 0; jb < 8; ++jb) accS[jb] = sd_mfma16(a[jb], b2, accS[jb]);
 }
 
 #ifdef X3_TRACE
@@ -506,12 +411,12 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
   const char* gimg = reinterpret_cast<const char*>(f.wimg);
 
   // ---- prologue: weight images by LDS-DMA (prepared set: W1h W1l W2h W2l), vectors and tables ----
-  x3_reload<NW>(gimg, lds0 + XO_R1, wave, lane);
-  x3_reload<NW>(gimg + 2 * IMG_BYTES, lds0 + XO_R2, wave, lane);
+  sd_reload<2 * IMG_BYTES, NW>(gimg, lds0 + XO_R1, wave, lane);
+  sd_reload<2 * IMG_BYTES, NW>(gimg + 2 * IMG_BYTES, lds0 + XO_R2, wave, lane);
   if (tid < FD_H) {
     vec[tid] = f.wo[tid];
-    vec[FD_H + tid] = X3_C * f.b1[tid];
-    vec[2 * FD_H + tid] = X3_C * f.b2[tid];
+    vec[FD_H + tid] = SD_C * f.b1[tid];
+    vec[2 * FD_H + tid] = SD_C * f.b2[tid];
   }
   {
     // coordinate layer A operands (v_mfma_f32_16x16x16_bf16: lane (m, kq) holds A[m][4kq .. 4kq+3]), k slots:
@@ -519,12 +424,12 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     for (int jb = tid >> 6; jb < 8; jb += NW) {
       const int m = lane & 15, kq = lane >> 4, j = 16 * jb + m;
       float v = 0.0f;
-      if (kq == 0) v = X3_C * f.Wc[j * f.cd];
-      else if (kq == 1) v = f.cd == 2 ? X3_C * f.Wc[j * 2 + 1] : 0.0f;
-      else if (kq == 2) v = X3_C * f.bc[j];
+      if (kq == 0) v = SD_C * f.Wc[j * f.cd];
+      else if (kq == 1) v = f.cd == 2 ? SD_C * f.Wc[j * 2 + 1] : 0.0f;
+      else if (kq == 2) v = SD_C * f.bc[j];
       __bf16 hi, lo;
       fb_split(v, hi, lo);
-      bf16x4 a = x3_zero4();
+      bf16x4 a = sd_zero4();
       if (kq < 2) { a[0] = hi; a[1] = hi; a[2] = lo; }
       else if (kq == 2) { a[0] = hi; a[1] = lo; }
       reinterpret_cast<bf16x4*>(smb + XO_ATAB)[64 * jb + lane] = a;
@@ -547,7 +452,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     }
     reinterpret_cast<bf16x8*>(smb + XO_TTAB)[tid] = a;
   }
-  x3_wait_vm0();
+  sd_wait_vm0();
   __syncthreads();
   const float bo = f.bo[0];
 
@@ -571,7 +476,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
   //  pair per access point — per-lane pointers hoisted out of the tile loop were what the first build spilled)
   char* const park_base = reinterpret_cast<char*>(f.park) + ((int64_t)g * NW + wave) * X3_PARK_BYTES_PER_WAVE;   // (NW = 8 only)
   auto park_at = [&](int jb) -> uint4_* {
-    return reinterpret_cast<uint4_*>(park_base + (unsigned)((lane0 | x3_opaque0()) * 16 + 1024 * jb));
+    return reinterpret_cast<uint4_*>(park_base + (unsigned)((lane0 | sd_opaque0()) * 16 + 1024 * jb));
   };
 
   auto flush_hz = [&](int b) {
@@ -580,7 +485,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     float* dst = f.part_hz + ((int64_t)b * f.kmax + (g - gfirst) * NW + wave) * FD_H + 4 * q;
     if (r == 0) {
 #pragma unroll
-      for (int jb = 0; jb < 8; ++jb) *reinterpret_cast<f32x4*>(dst + 16 * jb) = accS[jb] * X3_RC2;
+      for (int jb = 0; jb < 8; ++jb) *reinterpret_cast<f32x4*>(dst + 16 * jb) = accS[jb] * SD_RC2;
     }
 #pragma unroll
     for (int jb = 0; jb < 8; ++jb)
@@ -615,14 +520,14 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
   float* cgr = reinterpret_cast<float*>(smb + XO_CGR) + wave * 64;
   auto fetch_unit_inputs = [&](const Pos& p_) {
     const int n0 = p_.loc * FD_UNIT;
-    x3_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + XO_CHZ + wave * (FD_H * 4));
-    x3_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + XO_CHZ + wave * (FD_H * 4) + 256);
-    x3_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + XO_CTP + wave * 256);
-    x3_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + XO_CGR + wave * 256);
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + XO_CHZ + wave * (FD_H * 4));
+    sd_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + XO_CHZ + wave * (FD_H * 4) + 256);
+    sd_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + XO_CTP + wave * 256);
+    sd_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + XO_CGR + wave * 256);
   };
-  x3_wait_vm0();                                        // (the observation load above: nothing compiler-visible in flight)
+  sd_wait_vm0();                                        // (the observation load above: nothing compiler-visible in flight)
   fetch_unit_inputs(pos_cur);
-  const X3Addr wad0 = x3_addr(r, q);
+  const SdAddr wad0 = sd_addr(r, q);
   (void)wad0;
   int tile_no = -1;
   for (int ut = u_lo; ut < u_hi; ut += NW) {
@@ -637,9 +542,9 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     asm volatile("" : "+v"(opq));
     const int lane = lane0 | opq, r = lane & 15, q = lane >> 4;
 #if X3_WAD_LOCAL
-#define wad x3_addr((lane0 | x3_opaque0()) & 15, (lane0 | x3_opaque0()) >> 4)
+#define wad sd_addr((lane0 | sd_opaque0()) & 15, (lane0 | sd_opaque0()) >> 4)
 #else
-    const X3Addr& wad = wad0;
+    const SdAddr& wad = wad0;
 #endif
     const float* wos = vec;
     const float* b1s = vec + FD_H;
@@ -649,7 +554,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     const int bu = pos_cur.b;
     const unsigned rowb = ((unsigned)unit * FD_UNIT + (unsigned)r) * 4u;      // byte offset of the lane's row (rows < 2^30)
     float x0, x1, u0c, u1c, sc;
-    x3_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
+    sd_wait_vm0();                        // this wave's LDS-DMA of the tile's inputs (issued a tile ago)
     {
       const float* t = ctp;
       const float* gr = cgr;
@@ -675,7 +580,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     float dlda = 0.0f;
     {
       // ---- coordinate layer on the matrix cores: C h0pre = (C Wc) x' + C bc + C hz[b] ----
-      bf16x4 bx = x3_zero4();
+      bf16x4 bx = sd_zero4();
       {
         const float v = q == 0 ? x0 : x1;
         __bf16 vh, vl;
@@ -696,24 +601,24 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       X3_FENCE();
       if (f.hz_scale == 0.0f) {                  // hz arrives unscaled only when the generic encoder path produced it
 #pragma unroll
-        for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * X3_C;
+        for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * SD_C;
       }
       X3_FENCE();
 #pragma unroll
-      for (int jb = 0; jb < 8; ++jb) tC[jb] = x3_mfma16(aop[jb], bx, tC[jb]);
+      for (int jb = 0; jb < 8; ++jb) tC[jb] = sd_mfma16(aop[jb], bx, tC[jb]);
       X3_FENCE();
       if (NW == 4 && X3_FOLD) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) x3_tanh_split_chunk(tC, h0h, h0l, c);      // (k-block 0; the rest rides in layer 1's loop)
       } else {
-        x3_tanh8(tC);
+        sd_tanh8(tC);
         x3_split8(tC, h0h, h0l);
       }
     }
     asm volatile("; X3_P1_coord_done");
     X3_STAMP(1);
     fetch_unit_inputs(pos_nx);                 // the slots were consumed by the coordinate layer above
-    if (GRADS && tile_no > 0) x3_reload<NW>(gimg + 2 * IMG_BYTES, lds0 + XO_R2, wave, lane);   // W2 was the previous tile's staging area
+    if (GRADS && tile_no > 0) sd_reload<2 * IMG_BYTES, NW>(gimg + 2 * IMG_BYTES, lds0 + XO_R2, wave, lane);   // W2 was the previous tile's staging area
     {
       if (NW == 4 && X3_FOLD) {
         x3_layer_fwd<X3_PF4>(W1h, b1s, h0h, h0l, tD, wad, q, [&](int g_) { if (g_ < 12) x3_tanh_split_chunk(tC, h0h, h0l, 4 + g_); });
@@ -732,14 +637,14 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
         }
       }
       if (!(NW == 4 && X3_FOLD)) {
-        x3_tanh8(tC);
+        sd_tanh8(tC);
         x3_split8(tC, h1h, h1l);                                   // feeds layer 2 and its wgrad
       }
     }
     asm volatile("; X3_P2_l1_done");
     X3_STAMP(2);
     if (GRADS) {
-      x3_wait_vm0();
+      sd_wait_vm0();
       __syncthreads();      // barrier 0: W2 landed everywhere; every wave is past its reads of W1 (region ST2 is free)
     }
     X3_STAMP(3);
@@ -749,7 +654,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       else
         x3_layer_fwd<(NW == 4 ? X3_PF4 : 1)>(W2h, b2s, h1h, h1l, tC, wad, q);
       // ---- h2, output layer + likelihood (fp32); tC <- g = wo (1 - h2^2), pA <- split(h2) ----
-      x3_tanh8(tC);                                                // tC = h2
+      sd_tanh8(tC);                                                // tC = h2
       if (GRADS) x3_split8(tC, pAh, pAl);
       f32x4 part4 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -763,13 +668,11 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       }
       const float a = x3_sum_q((part4[0] + part4[1]) + (part4[2] + part4[3])) + bo;
       float ll, locv;
+      // (sd_pixel_lik<LIK> written out: called as the function, this site compiles to other code — same math, see its comment)
       if (LIK == PV_LIK_BERNOULLI) {
-        const float pr = x3_rcp(1.0f + x3_exp(-a));
+        const float pr = sd_rcp(1.0f + sd_exp(-a));
         const float pc = fminf(fmaxf(pr, BERN_EPS), 1.0f - BERN_EPS);
-        // -BCEWithLogits(lg, x) with lg = logit(pc) (torch: probs_to_logits, then binary_cross_entropy_with_logits), written with
-        // the identities 1 + exp(-|lg|) = 1 / max(pc, 1 - pc) and sigmoid(lg) = pc: the two logarithms lg is made of serve the
-        // softplus term too, and the row's dependent chain is exp -> rcp -> 2 log instead of seven transcendentals (round 5)
-        const float lpc = x3_log(pc), l1pc = x3_log(1.0f - pc);
+        const float lpc = sd_log(pc), l1pc = sd_log(1.0f - pc);
         const float lg = lpc - l1pc;
         ll = -(fmaxf(lg, 0.0f) - lg * xv - fmaxf(lpc, l1pc));
         const float mask = (pr >= BERN_EPS && pr <= 1.0f - BERN_EPS) ? 1.0f : 0.0f;
@@ -778,9 +681,9 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
       } else {
-        const float pr = f.sigmoid_out ? x3_rcp(1.0f + x3_exp(-a)) : a;
+        const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
-        ll = -(d * d) / (2.0f * f.sig * f.sig) - x3_log(f.sig) - LOG_SQRT_2PI;
+        ll = -(d * d) / (2.0f * f.sig * f.sig) - sd_log(f.sig) - LOG_SQRT_2PI;
         dlda = -d / (f.sig * f.sig) * (f.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
         locv = pr;
       }
@@ -803,9 +706,9 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     {
       // ---- d(wo) += sum_rows dlda h2 : wave-local MFMAs through the wave's own scratch rows of region ST2;
       // B = dlda of rows 4q..4q+3 in columns 3 (hi) and 4 (lo) for h2_hi, column 3 (hi) for h2_lo
-      x3_wait_lgkm0();
+      sd_wait_lgkm0();
       const f32x4 d4 = *reinterpret_cast<const f32x4*>(inf_dl + 4 * q);
-      bf16x4 bw1 = x3_zero4(), bw2 = x3_zero4();
+      bf16x4 bw1 = sd_zero4(), bw2 = sd_zero4();
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         __bf16 hi, lo;
@@ -818,7 +721,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
 #pragma unroll
       for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * dlda;
       x3_split8(tC, pAh, pAl);                                    // feeds the wgrad and the dgrad of layer 2
-      x3_wait_lgkm0();                                            // (own scratch reads done)
+      sd_wait_lgkm0();                                            // (own scratch reads done)
     }
     asm volatile("; X3_P4_dwo_done");
     X3_STAMP(5);
@@ -831,10 +734,10 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       if (ks_of(h) == 0) break;                                   // (workgroup-uniform)
       if (h > 0) __syncthreads();
       if ((wave >> 2) == h) {
-        x3_stage_store(st2, pAh, 16 * (wave & 3) + r, q);
-        x3_stage_store(st2 + X3_ARR, pAl, 16 * (wave & 3) + r, q);
-        x3_stage_store(st2 + 2 * X3_ARR, h1h, 16 * (wave & 3) + r, q);
-        x3_stage_store(st2 + 3 * X3_ARR, h1l, 16 * (wave & 3) + r, q);
+        sd_stage_store(st2, pAh, 16 * (wave & 3) + r, q);
+        sd_stage_store(st2 + X3_ARR, pAl, 16 * (wave & 3) + r, q);
+        sd_stage_store(st2 + 2 * X3_ARR, h1h, 16 * (wave & 3) + r, q);
+        sd_stage_store(st2 + 3 * X3_ARR, h1l, 16 * (wave & 3) + r, q);
       }
       __syncthreads();
       X3_STAMP(6 + h);
@@ -843,8 +746,8 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     __syncthreads();                                              // region ST2 consumed everywhere
     asm volatile("; X3_P6_cons2");
     X3_STAMP(8);
-    x3_wait_vm0();                                                // (nothing compiler-visible may be in flight)
-    x3_reload<NW>(gimg, lds0 + XO_R1, wave, lane);                // W1 comes back under the dgrad of layer 2
+    sd_wait_vm0();                                                // (nothing compiler-visible may be in flight)
+    sd_reload<2 * IMG_BYTES, NW>(gimg, lds0 + XO_R1, wave, lane);                // W1 comes back under the dgrad of layer 2
     bf16x4 p0h[8], p0l[8], d1h[8], d1l[8];
     if (NW == 4 && X3_FOLD) {
       // 4 waves: dgrad of layer 2 in one piece; its epilogue C dpre1 = (C dL/dh1)(1 - h1^2) -> (hi, lo) rides in the k-loop
@@ -854,7 +757,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       for (int c = 0; c < 4; ++c) x3_dtanh_split_chunk(tC, h1h, h1l, d1h, d1l, c);
       asm volatile("; X3_P7_dgrad2");
       X3_STAMP(9);
-      x3_wait_vm0();
+      sd_wait_vm0();
       __syncthreads();      // W1 landed everywhere; every wave is past its reads of W2 (region ST1 is free)
       X3_STAMP(10);
       x3_layer_dgrad<X3_PF4>(W1h, d1h, d1l, tD, wad, [&](int g_) { if (g_ < 12) x3_dtanh_split_chunk(tC, h1h, h1l, d1h, d1l, 4 + g_); });
@@ -876,7 +779,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
     }
     asm volatile("; X3_P7_dgrad2");
     X3_STAMP(9);
-    x3_wait_vm0();
+    sd_wait_vm0();
     __syncthreads();        // W1 landed everywhere; every wave is past its reads of W2 (region ST1 is free)
     X3_STAMP(10);
     {
@@ -921,11 +824,11 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
 #pragma unroll
       for (int mm = 0; mm < 4; ++mm) {
         const bf16x8 tt = ttab[64 * mm];
-        dd = MFMA32(tt, x3_cat(p0h[2 * mm], p0h[2 * mm + 1]), dd);
-        dd = MFMA32(tt, x3_cat(p0l[2 * mm], p0l[2 * mm + 1]), dd);
+        dd = MFMA32(tt, sd_cat(p0h[2 * mm], p0h[2 * mm + 1]), dd);
+        dd = MFMA32(tt, sd_cat(p0l[2 * mm], p0l[2 * mm + 1]), dd);
       }
       if (q == 0 && act) {
-        const float d0 = (dd[0] + dd[1]) * X3_RC2, d1 = (dd[2] + dd[3]) * X3_RC2;
+        const float d0 = (dd[0] + dd[1]) * SD_RC2, d1 = (dd[2] + dd[3]) * SD_RC2;
         char* const tp0 = reinterpret_cast<char*>(f.rowtp);
         *reinterpret_cast<float*>(tp0 + rowb) = sc * (d1 * u0c - d0 * u1c);
         *reinterpret_cast<float*>(tp0 + f.M * 4 + rowb) = d0 * u0c + d1 * u1c;
@@ -940,7 +843,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       // B columns: 0 ones | 1, 5 x0 (hi, lo) | 2, 6 x1 (hi, lo) for dpre0_hi; 0 | 1 | 2 (hi) for dpre0_lo
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(inf_x0 + 4 * q);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(inf_x1 + 4 * q);
-      bf16x4 bc1 = x3_zero4(), bc2 = x3_zero4();
+      bf16x4 bc1 = sd_zero4(), bc2 = sd_zero4();
       const bool use1 = r == 2 || r == 6, lo_col = r >= 5;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -953,7 +856,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
         bc2[i] = r <= 2 ? v : (__bf16)0.0f;
       }
       x3_colsum_mfma(st1, p0h, p0l, bc1, bc2, accS, wave, r, q);
-      x3_wait_lgkm0();                                              // (own reads done before the rows are re-staged)
+      sd_wait_lgkm0();                                              // (own reads done before the rows are re-staged)
     }
     asm volatile("; X3_P12_rowlocal");
     X3_STAMP(12);
@@ -964,10 +867,10 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       if (ks_of(h) == 0) break;
       if (h > 0) __syncthreads();
       if ((wave >> 2) == h) {
-        x3_stage_store(st1, d1h, 16 * (wave & 3) + r, q);
-        x3_stage_store(st1 + X3_ARR, d1l, 16 * (wave & 3) + r, q);
-        x3_stage_store(st1 + 2 * X3_ARR, h0h, 16 * (wave & 3) + r, q);
-        x3_stage_store(st1 + 3 * X3_ARR, h0l, 16 * (wave & 3) + r, q);
+        sd_stage_store(st1, d1h, 16 * (wave & 3) + r, q);
+        sd_stage_store(st1 + X3_ARR, d1l, 16 * (wave & 3) + r, q);
+        sd_stage_store(st1 + 2 * X3_ARR, h0h, 16 * (wave & 3) + r, q);
+        sd_stage_store(st1 + 3 * X3_ARR, h0l, 16 * (wave & 3) + r, q);
       }
       __syncthreads();
       X3_STAMP(13 + h);
@@ -992,7 +895,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
         for (int i = 0; i < 4; ++i) {
           // C/D layout: lane (col = r, q), reg i -> dW[16 SB jp + 16 blk + 4q + i][64kh + 16o + r], blk = (s + NB kh) mod SB
           const int e = (16 * SB * jp + 16 * ((s_ + NB * kh) & (SB - 1)) + 4 * q + i) * FD_H + 64 * kh + 16 * o + r;
-          rec[e] = accW1[s_][o][i] * X3_RC;
+          rec[e] = accW1[s_][o][i] * SD_RC;
           rec[FD_H * FD_H + e] = accW2[s_][o][i];
         }
     if (r == 0) {
@@ -1001,7 +904,7 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
         const int j0 = 16 * SB * jp + 16 * (NB * kh + t);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          rec[2 * FD_H * FD_H + j0 + 4 * q + i] = accB1[t][i] * X3_RC;
+          rec[2 * FD_H * FD_H + j0 + 4 * q + i] = accB1[t][i] * SD_RC;
           rec[2 * FD_H * FD_H + FD_H + j0 + 4 * q + i] = accB2[t][i];
         }
       }
@@ -1029,8 +932,8 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
       v1 += s_[2 * FD_H] + s_[6 * FD_H];
       vo += s_[3 * FD_H] + s_[4 * FD_H];
     }
-    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = v0 * X3_RC2;
-    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = v1 * X3_RC2;
+    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = v0 * SD_RC2;
+    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = v1 * SD_RC2;
     rec[2 * FD_H * FD_H + 4 * FD_H + tid] = vo;
   }
   if (tid == 0) {

@@ -10,7 +10,6 @@
 #include "pv_kernels.h"
 #include "pv_linear.h"
 
-#define LOG_SQRT_2PI 0.91893853320467274178f
 
 namespace {
 

@@ -112,8 +112,8 @@ def test_bf16_helper_is_round_to_nearest_even():
 @pytest.mark.parametrize("units,grid", [(12544, 256), (6272, 256), (25088, 256), (50176, 256), (1536, 256), (3072, 256),
                                         (392, 256), (12, 12), (5, 5), (1, 1), (1568, 256), (12544, 304), (999, 77)])
 def test_partition_covers_units_and_flags_tails(units, grid):
-    """u_lo = g units / G (pv_sdec_fused_w8.hip:905): the ranges tile [0, units) in order without gaps or overlaps, and a range
-    of 8 n + 1 units (and only such a range) ends with a column-parallel tail (:920)."""
+    """u_lo = g units / G (`u_lo` in pv_sdec_w8_kernel, pv_sdec_fused_w8.hip): the ranges tile [0, units) in order without gaps or overlaps, and a range
+    of 8 n + 1 units (and only such a range) ends with a column-parallel tail (`has_tail`, same kernel)."""
     parts = bp.partition(units, grid)
     assert len(parts) == grid and parts[0][0] == 0 and parts[-1][1] == units
     for (lo, hi, tail), nxt in zip(parts, parts[1:] + [(units, None, None)]):
