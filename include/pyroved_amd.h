@@ -343,6 +343,30 @@ int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, void* strea
  * so plan->grads holds the zeroed gradients of pyro's zero_grads afterwards.  Needs adam_m / adam_v / adam_step. */
 int pv_ivae_step(const pv_ivae_plan* plan, void* stream);
 
+/* ---- (v17, added without a layout change) the multi-particle ELBO ------------------------------------------------------------
+ * pyro.infer.Trace_ELBO(num_particles=P) / TraceMeanField_ELBO(num_particles=P): for images x_b, b < B, and draws eps_pb, p < P,
+ *   z_pb = mu_b + sigma_b eps_pb
+ *   e_pb = log p(x_b | z_pb) + beta (log p(z_pb) - log q(z_pb | x_b))          (PV_KL_SAMPLED)
+ *   e_pb = log p(x_b | z_pb) - beta KL(N(mu_b, sigma_b) || N(0, 1))            (PV_KL_ANALYTIC: the KL does not depend on p)
+ *   loss = -(1 / P) sum_p sum_b e_pb,   gradients those of loss.
+ * The plan is the one-particle step's, with these differences:
+ *   eps    (P*B, z_dim), rows ordered [p][b] (particle-major: the order jiVAE's enumerated decoder samples have);
+ *   loc    optional, (P*B, n_pix) in the same order;
+ *   z_loc, z_scale   stay (B, z_dim): the encoder runs ONCE over the B images, the decoder over the P*B samples;
+ *   scalars keep their slots and scalars[0] = -(scalars[1] + scalars[2] - scalars[3]): each holds the mean over particles of
+ *          the term it holds in the one-particle step;
+ *   ws     sized by pv_ivae_particles_workspace_bytes (the PV_WS_STEP layout for P particles).
+ * num_particles == 1 forwards to pv_ivae_workspace_bytes_for(plan, PV_WS_STEP) / pv_ivae_loss_and_grads / pv_ivae_step (the same
+ * launches, the guide folded into the decoder launch where pv_ivae_guide_folds says so); num_particles < 1 is PV_EINVAL.
+ * For P > 1 the guide never folds into the decoder launch, and every sum over particles runs in a fixed order (no float
+ * atomics): a step is bit-reproducible run to run.
+ * Scope for P > 1: the fc-encoder iVAE (spatial 1-D / 2-D or vanilla decoder, with or without c_dim, every likelihood, both
+ * kl_mode values) with fused = 0, 2 or 3.  PV_EINVAL — from the workspace query too — for discrete_dim > 0 (jiVAE), a
+ * convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 1. */
+int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles);   /* PV_WS_STEP layout; <0 unsupported */
+int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream);
+int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream);    /* + Adam, as pv_ivae_step */
+
 /* ---- (v16) the data-parallel step with its collective INSIDE the library --------------------------------------------------
  * The reference has no distributed code.  What is sharded is trainers/svi.py:104-113 (`self.svi.step(x)` per
  * minibatch): the loss is a SUM over the data plate (models/ivae.py:177,215), so every replica computes its contiguous slice of

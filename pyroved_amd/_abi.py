@@ -150,6 +150,10 @@ SIGNATURES = {
                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "pv_ivae_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p]),
+    # the multi-particle ELBO (v17, added without a layout change)
+    "pv_ivae_particles_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan), C.c_int32]),
+    "pv_ivae_particles_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_int, C.c_void_p]),
+    "pv_ivae_particles_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_void_p]),
     "pv_dist_load": (C.c_int, [C.c_char_p]),
     "pv_dist_library": (C.c_char_p, []),
     "pv_dist_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -1,0 +1,56 @@
+// pv_particles.h — the multi-particle ELBO (Trace_ELBO / TraceMeanField_ELBO with num_particles = P > 1; pv_particles.hip).
+// One encoder pass over the B images, P decoder samples per image ordered [p][b] (sample s = p * B + b — the order jiVAE's
+// enumerated decoder samples already have), each weighted sw[s] = 1 / P; their dL/dz is reduced over p, in ascending p, into the
+// image's head gradient.
+#pragma once
+#include "pv_common.h"
+#include "pv_kernels.h"
+#include "pv_sdec_fused.h"
+
+// guide side, after the head: per decoder sample (p, b) the reparameterised z, the transform parameters, the decoder's latent
+// input and (spatial decoder on the fused path) fc_latent; per image the KL partial sums
+struct PvParticleExpand {
+  const float* head; int ldh;       // (B, ldh): [mu | softplus input]
+  const float* eps;                 // (P*B, z_dim), rows [p][b]
+  const float* y;                   // (B, c_dim) or null
+  float* z;                         // (P*B, z_dim)
+  float* z_scale;                   // (B, z_dim)
+  float* z_loc_out; float* z_scale_out;   // optional (B, z_dim) copies for the caller
+  float* tp;                        // (P*B, 8): cos, sin, scale, tx, ty (null when coord_dim == 0)
+  float* zy;                        // (P*B, lat_in) = [z content | y_b] when c_dim > 0, else null
+  float* hz; const float* Wz; int H0;     // (P*B, H0) = fc_latent(decoder latent input), or null: not wanted here
+  float hz_scale;                   // hz is stored multiplied by this (0: unscaled); see PvFused::hz_scale
+  float* sw;                        // (P*B) <- 1 / P
+  float* kl_part;                   // (B, 2): beta * {log p, log q} — sampled form: the mean over p; analytic form: once per image
+  int B, P, z_dim, c_dim, coord_dim, has_r, has_t, has_s;
+  float tp0, tp1, sc_prior, beta;
+  int kl_mode;
+};
+int pv_particle_expand(const PvParticleExpand& e, hipStream_t s);
+
+// the particle-reducing latent backward: one workgroup per image b, its P samples in ascending p
+//   llb[b]   = sum_p sw[s] ll_s
+//   dhead[b] = sum_p pv_head_bwd_math_kl(dz_s, ..., beta * sw[s])        (the decoder's dz_s arrives weighted by sw[s])
+// fused form (llkb == null): gathers ll_s, d(phi, scale, tx, ty) and dL/d(hz_s) from the fused decoder launch's outputs as
+// pv_latent_bwd does per sample (dhz[s] is written for fc_latent's weight gradient), dL/dz_s = dhz_s Wz;
+// layered form: reads ll_s, dL/d(decoder latent input) and d(phi, scale, tx, ty) the layer-by-layer backward left.
+// enc_n > 0: the image's encoder dgrad chain follows in the same workgroup (PvLatentBwd::enc_*).
+struct PvParticleBwd {
+  const float* llrow; const float* rowtp; const float* part_hz; const float* part_rs; const float* Wz; float* dhz;
+  int64_t M; int N, kmax, H, lat_in;
+  const float* llkb; const float* dzc; int64_t ldzc; const float* dtp;     // (P*B), (P*B, ldzc), (P*B, 4)
+  const float* sw;                  // (P*B)
+  float* llb;                       // (B)
+  int P, fwd_only;
+  PvHeadBwd hb;                     // z, eps: (P*B, z_dim); z_scale, head, dhead: per image; dzc / dtp fields unused
+  int enc_n;
+  const float* enc_params;
+  pv_layer enc_l[PV_MAX_LAYERS];
+  pv_layer enc_head;
+  const float* enc_act[PV_MAX_LAYERS];
+  float* enc_dp[PV_MAX_LAYERS];
+};
+int pv_particle_bwd(const PvParticleBwd& p, hipStream_t s);
+// ... in one launch with the sums of the fused decoder's gradient records (as pv_latent_bwd_reduce)
+int pv_particle_bwd_reduce(const PvParticleBwd& p, const float* part, int grid, float* G, const PvFusedOffsets& o, int cd,
+                           hipStream_t s, int rec_fmt);

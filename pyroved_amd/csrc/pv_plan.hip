@@ -13,6 +13,7 @@
 #include "pv_convstack.h"
 #include "pv_side.h"
 #include "pv_conv.h"
+#include "pv_particles.h"
 
 namespace {
 
@@ -57,6 +58,9 @@ struct Layout {
   // fused persistent decoder path
   bool fused; int f_grid, f_kmax;
   float* f_part; float* f_part_hz; float* f_rowtp; float* f_wimg; float* f_park;
+  // multi-particle ELBO (pv_ivae_particles_*): P decoder samples per image ordered [p][b]; z, tp, zy, hz, sw, llkb hold P*B rows.
+  // The count travels here, not in the ABI struct; 1 everywhere else
+  int P;
   int64_t total;
 };
 
@@ -73,6 +77,8 @@ static inline int plan_conv_mode(const pv_ivae_plan* p) {
   return pvcs::conv_mode_for(4, p->enc_ops, p->n_enc_ops, p->enc_ndim, p->batch, 1, p->enc_in_dim);
 }
 static inline int64_t plan_S(const pv_ivae_plan* p) { return (plan_K(p) > 0 ? plan_K(p) : 1) * (int64_t)p->batch; }
+// decoder samples of a training step: jiVAE's K per input or the multi-particle ELBO's P (never both)
+static inline int64_t step_S(const pv_ivae_plan* p, const Layout& L) { return plan_S(p) * L.P; }
 static inline int64_t plan_head_w(const pv_ivae_plan* p) { return 2 * (int64_t)p->z_dim + plan_K(p); }
 static inline int64_t plan_lat_in(const pv_ivae_plan* p) {
   return (p->coord_dim > 0 ? p->latent_dim : p->z_dim) + p->c_dim + plan_K(p);
@@ -102,10 +108,13 @@ bool valid_plan(const pv_ivae_plan* p) {
 
 // inference_only: encode / decode process B samples (jiVAE's K-fold enumeration exists only in the training step)
 // encode_only (with inference_only): none of the decoder's per-row buffers is touched, so they get no room
-void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false) {
+// P > 1 (training step only): the multi-particle ELBO's layout; P == 1 is byte for byte the one-particle layout
+void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1) {
   Carver c{base, 0};
+  L.P = inference_only ? 1 : P;
   const int64_t B = p->batch, N = encode_only ? 0 : p->n_pix, z = p->z_dim;
-  const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p), hw = plan_head_w(p);
+  const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
+  const bool multi = K > 0 || L.P > 1;              // several decoder samples per input
   L.rows = p->coord_dim > 0 ? S * N : S;
   const int64_t R = L.rows;
   L.xin = p->c_dim > 0 ? c.take(B * (p->n_pix + p->c_dim)) : nullptr;
@@ -150,12 +159,12 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   }
   L.head = c.take(B * hw);
   L.dhead = c.take(B * hw);
-  L.z = c.take(B * z);
+  L.z = c.take((L.P > 1 ? S : B) * z);
   L.z_scale = c.take(B * z);
   L.tp = c.take(S * 8);
   L.zy = (p->c_dim > 0 || K > 0) ? c.take(S * lat_in) : nullptr;
   L.alpha = K > 0 ? c.take(B * K) : nullptr;
-  L.sw = K > 0 ? c.take(S) : nullptr;
+  L.sw = multi ? c.take(S) : nullptr;
   for (int i = 0; i < n_enc; ++i) L.edp[i] = c.take(B * p->enc[i].out_dim);
   L.enc_compact = !L.enc_conv && !L.enc_ext && pv_enc_compact_supported(p);
   L.kl_blocks = (int)((B + 15) / 16);
@@ -227,7 +236,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   }
   L.llb = c.take(B);
   L.row_ll = c.take(B);
-  L.llkb = K > 0 ? c.take(S) : nullptr;
+  L.llkb = multi ? c.take(S) : nullptr;
   L.jfix = K > 0 ? c.take(4) : nullptr;
   L.dbuf[0] = L.fused ? nullptr : c.take(R * maxd);
   L.dbuf[1] = L.fused ? nullptr : c.take(R * maxd);
@@ -679,6 +688,46 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
   return 0;
 }
 
+// ---- multi-particle ELBO (L.P > 1; pv_particles.h) ----
+// The guide: the encoder ONCE over the B images, then one launch that expands the head into the P*B decoder samples [p][b].
+// The compact encoder's launch also samples with the first B rows of eps — particle 0's — into the rows the expansion then writes
+// for every particle (and hosts `prep`, the bf16 decoder's weight images); a generic fc encoder stops at the head.
+// hz != null: fc_latent per sample rides in the expansion (the fused decoder's input), stored multiplied by hz_scale
+// img != null: the encoder as one workgroup per image (pv_guide_img.hip) where the one-particle step would run it so
+int particle_guide(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbPrep* prep, float hz_scale, float* hz,
+                   const PvEncFold* img = nullptr) {
+  // (the expansion and the particle backward derive the content columns from the invariance flags: they must be the plan's)
+  const int ncoord = p->coord_dim == 1 ? (p->has_t ? 1 : 0)
+                                       : p->coord_dim == 2 ? (p->has_r ? 1 : 0) + (p->has_t ? 2 : 0) + (p->has_s ? 1 : 0) : 0;
+  if (p->coord_dim > 0 && p->z_dim - ncoord != p->latent_dim) return PV_EINVAL;
+  if (img) PV_TRY(pv_guide_img_launch(*img, prep, hz_scale, (int)p->batch, s, p->kl_mode));
+  else if (L.enc_compact) PV_TRY(guide_fwd(p, L, s, prep, hz_scale));
+  else if (prep) return PV_EINVAL;
+  else PV_TRY(encoder_fwd(p, L, s));
+  PvParticleExpand e{};
+  latent_geometry(e, p);
+  e.head = L.head; e.ldh = (int)plan_head_w(p); e.eps = p->eps; e.y = p->y;
+  e.z = L.z; e.z_scale = L.z_scale; e.z_loc_out = p->z_loc; e.z_scale_out = p->z_scale;
+  e.tp = p->coord_dim > 0 ? L.tp : nullptr; e.zy = p->c_dim > 0 ? L.zy : nullptr;
+  if (hz) { e.hz = hz; e.Wz = p->params + p->fc_latent.w_off; e.H0 = p->fc_coord.out_dim; e.hz_scale = hz_scale; }
+  e.sw = L.sw; e.kl_part = L.kl_part;
+  e.B = (int)p->batch; e.P = L.P; e.c_dim = p->c_dim;
+  return pv_particle_expand(e, s);
+}
+// the particle-reducing latent backward without its inputs from the decoder
+PvParticleBwd particle_bwd_desc(const pv_ivae_plan* p, const Layout& L) {
+  PvParticleBwd pb{};
+  pb.hb = head_bwd_desc(p, L);
+  pb.sw = L.sw; pb.llb = L.llb; pb.P = L.P;
+  return pb;
+}
+// the scopes of pv_ivae_particles_*: the fc-encoder iVAE (spatial or vanilla decoder, with or without c_dim), layered or on the
+// bf16-class fused decoder kernels
+static bool particles_supported(const pv_ivae_plan* p) {
+  return p->discrete_dim == 0 && p->n_enc_ops == 0 && !p->ext_encoder && !p->ext_decoder && !p->row_w && !p->row_elbo && !p->dy &&
+         !p->class_onehot && p->fused != 1;
+}
+
 // the plan-side conditions of the folded guide (PvEncFold): plain-bf16 fused decoder, the plain two-hidden-layer fc encoder, no
 // conditioning vector / discrete latent / per-sample weights; the launch-side ones are pv_sdec_fused_fold_ok's
 // (plan_guide_one_image: the architecture one workgroup can run a whole image's guide for — the fold in the decoder launch and the
@@ -686,7 +735,9 @@ int guide_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvFbP
 static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L);
 static bool plan_guide_may_fold(const pv_ivae_plan* p, const Layout& L) {
   // (the hosting launch computes the sampled KL form only: it sits at the register ceiling — the analytic form runs the guide as its own launch)
-  return p->fused == 3 && !(p->flags & PV_PLAN_NO_ENC_FOLD) && p->kl_mode == PV_KL_SAMPLED && plan_guide_one_image(p, L);
+  // (multi-particle: one image's guide feeds P samples that sit in P different workgroups' unit ranges — decided on (B, P), never
+  //  on the sample count alone: B = 128, P = 2 has the 256 samples of a foldable batch)
+  return p->fused == 3 && L.P == 1 && !(p->flags & PV_PLAN_NO_ENC_FOLD) && p->kl_mode == PV_KL_SAMPLED && plan_guide_one_image(p, L);
 }
 static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L) {
   const int64_t z = p->z_dim;
@@ -715,6 +766,7 @@ struct FusedStep {
   int kl_n = 0;                                      // ... that many: per sample when a workgroup runs an image's guide, else per 16-row block
   // the closing form
   PvLatentBwd lb{};                                  // latent backward + record sums, followed by the encoder backward
+  PvParticleBwd pb{};                                // ... its particle-reducing form (L.P > 1)
   bool chain = false;                                // compact encoder: every sample's dgrad chain runs in its latent-backward workgroup
   PvGemm wz;                                         // fc_latent: dWz = dhz^T zin; its row sums are fc_coord's bias gradient (dbc = sum_b dhz[b])
                                                      // (jiVAE: over the K*B decoder samples, zin = [z content | onehot(k)])
@@ -724,7 +776,8 @@ struct FusedStep {
 
 void fused_decoder_args(FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
-  const int64_t B = p->batch, N = p->n_pix, R = L.rows, K = plan_K(p), S = plan_S(p);   // jiVAE: S = K*B decoder samples, rows R = S*N
+  const int64_t B = p->batch, N = p->n_pix, R = L.rows, K = plan_K(p), S = step_S(p, L);   // jiVAE: S = K*B decoder samples, rows R = S*N
+  const bool multi = K > 0 || L.P > 1;               // (multi-particle: S = P*B, each weighted 1/P against the same B observations)
   PvFused& f = st.f;
   fused_weights(f, p);
   f.x = p->x; f.grid = p->grid; f.tp = L.tp; f.hz = L.hz;
@@ -736,7 +789,7 @@ void fused_decoder_args(FusedStep& st) {
   f.part_rs = (st.grads && st.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
   f.wimg = L.f_wimg; f.park = L.f_park;
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
-  f.sw = K > 0 ? L.sw : p->row_w; f.x_units = K > 0 ? B * N / FD_UNIT : 0;
+  f.sw = multi ? L.sw : p->row_w; f.x_units = multi ? B * N / FD_UNIT : 0;
   f.sigmoid_out = p->sigmoid_out; f.kmax = L.f_kmax; f.sig = p->decoder_sig; f.sel = p->dec_kernel;
   // fp16 builds of the fp32-class kernel: where the per-row exponent of dL/dlogit is centred (|dL/dlogit| <= 1 for the Bernoulli
   // likelihoods; ~ residual / sig^2 for the Gaussian): exact powers of two either way, only the representable RANGE moves
@@ -768,6 +821,24 @@ int fused_guide(FusedStep& st) {
   const float* Wz = p->params + p->fc_latent.w_off;
   st.kl_n = L.kl_blocks;
   st.kl_part = L.enc_compact;
+  if (L.P > 1) {
+    // multi-particle: the guide never rides in the decoder launch; the encoder once, the expansion writes hz for the P*B samples
+    if (p->fused < 2) return PV_EINVAL;
+    if (L.enc_compact) {
+      const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2);
+      f.hz_scale = prep.scale;
+      fold_args(st.ef, p, L);
+      const bool img = plan_guide_one_image(p, L) && pv_guide_img_ok(st.ef, (int)B) &&
+                       !(p->flags & (PV_PLAN_ENC_TILED | PV_PLAN_ENC_TWO_LAUNCH | PV_PLAN_ENC_NO_WAIT));
+      PV_TRY(particle_guide(p, L, s, &prep, f.hz_scale, L.hz, img ? &st.ef : nullptr));
+    } else {
+      PV_TRY(particle_guide(p, L, s, nullptr, 0.0f, L.hz));
+      PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, p->fused == 2, s));
+    }
+    st.kl_n = (int)B;
+    st.kl_part = true;
+    return 0;
+  }
   // ---- the guide folded into the decoder launch (pv_sdec_fused.h PvEncFold): the plain-bf16 8-wave kernel, a workgroup's units a
   // whole number of images, the plain fc encoder of two hidden layers — BASELINE's headline config is exactly this.  No encoder
   // launch, no weight-image copy, no hand-off: the step is decoder launch -> latent backward + record sums -> small weight gradients.
@@ -827,12 +898,12 @@ int fused_guide(FusedStep& st) {
 void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
   PvFused& f = st.f;
-  const int64_t N = p->n_pix, R = L.rows, z = p->z_dim, K = plan_K(p), S = plan_S(p), lat_in = plan_lat_in(p);
+  const int64_t N = p->n_pix, R = L.rows, z = p->z_dim, K = plan_K(p), S = step_S(p, L), lat_in = plan_lat_in(p);
   const int H = FD_H;
   const float* Wz = p->params + p->fc_latent.w_off;
   // (round 6) the 4-wave kernels too hand over dL/d(hz) and dL/dz, wherever every workgroup's units are exactly one sample
   // (batch == grid, e.g. C2's 256 on 256 CUs)
-  if (!f.dhz_out && f.part_rs && K == 0 && lat_in <= 16 && S == L.f_grid && f.units == S * (N / FD_UNIT) && !p->dy &&
+  if (!f.dhz_out && f.part_rs && K == 0 && L.P == 1 && lat_in <= 16 && S == L.f_grid && f.units == S * (N / FD_UNIT) && !p->dy &&
       st.rec_fmt == PV_REC_LANE_F32) {
     f.dhz_out = L.dhz; f.dzc_out = L.dzc; f.Wz = Wz; f.lat_in = (int)lat_in;
   }
@@ -850,6 +921,16 @@ void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) 
   if (st.chain) {
     lb.enc_n = p->n_enc; lb.enc_params = p->params; lb.enc_head = p->head;
     for (int i = 0; i < p->n_enc; ++i) { lb.enc_l[i] = p->enc[i]; lb.enc_act[i] = L.eact[i]; lb.enc_dp[i] = L.edp[i]; }
+  }
+  if (L.P > 1) {
+    PvParticleBwd& pb = st.pb;
+    pb = particle_bwd_desc(p, L);
+    pb.llrow = L.llrow; pb.rowtp = L.f_rowtp; pb.part_hz = L.f_part_hz; pb.part_rs = f.part_rs; pb.Wz = Wz; pb.dhz = L.dhz;
+    pb.M = R; pb.N = (int)N; pb.kmax = L.f_kmax; pb.H = H; pb.lat_in = (int)lat_in;
+    if (st.chain) {
+      pb.enc_n = p->n_enc; pb.enc_params = p->params; pb.enc_head = p->head;
+      for (int i = 0; i < p->n_enc; ++i) { pb.enc_l[i] = p->enc[i]; pb.enc_act[i] = L.eact[i]; pb.enc_dp[i] = L.edp[i]; }
+    }
   }
   st.wz = wgrad_problem(L.dhz, H, st.zin, st.ldz, p->grads + p->fc_latent.w_off, p->grads + p->fc_coord.b_off, S, lat_in, H);
   // (round 6, third cut) the own chain: where every workgroup of the decoder launch owns one image — the launch that hosts the
@@ -904,6 +985,12 @@ int fused_close_forward(const FusedStep& st) {
     PV_TRY(pv_latent_bwd(lf, s));
     return pv_finish_scalars(L.llb, (int)B, p->scalars, L.kl_part, L.kl_blocks, 1.0f, s);
   }
+  if (L.P > 1) {                                     // llb[b] = sum_p sw ll_pb
+    PvParticleBwd pf = particle_bwd_desc(p, L);
+    pf.llrow = L.llrow; pf.M = L.rows; pf.N = (int)N; pf.kmax = 1; pf.fwd_only = 1;
+    PV_TRY(pv_particle_bwd(pf, s));
+    return pv_finish_scalars(L.llb, (int)B, p->scalars, L.kl_part, st.kl_n, 1.0f, s);
+  }
   PV_TRY(pv_segsum(L.llrow, B, N, L.llb, s));
   PV_TRY(weigh_llb(p, L, s));
   PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, st.kl_part ? L.kl_part : nullptr, st.kl_n, 1.0f /* partials come scaled */, s));
@@ -926,7 +1013,8 @@ int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
     if (adam) *adam_done = true;
     return extra_outputs(p, L, L.dzc, plan_lat_in(p), s);
   }
-  PV_TRY(pv_latent_bwd_reduce(st.lb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
+  if (L.P > 1) PV_TRY(pv_particle_bwd_reduce(st.pb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
+  else PV_TRY(pv_latent_bwd_reduce(st.lb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
   // the loss scalars ride in the encoder dgrad launch (compact encoder), in the last weight-gradient launch (conv encoder) or get their own
   const bool fin_rides = L.enc_compact || (ab_fin && L.enc_conv && !L.enc_ext);
   if (!fin_rides) PV_TRY(finish_scalars(fin, s));
@@ -953,7 +1041,9 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
 int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s) {
   const int64_t K = plan_K(p);
   const int64_t B = p->batch, N = p->n_pix, R = L.rows, z = p->z_dim;
-  const int64_t S = plan_S(p);                       // decoder samples (jiVAE: K per input, ordered [k][b])
+  const int64_t S = step_S(p, L);                    // decoder samples (jiVAE: K per input, ordered [k][b]; multi-particle: [p][b])
+  const int P = L.P;
+  const int64_t reps = K > 0 ? K : P;                // decoder passes against the same B observations
   const int64_t lat_in = plan_lat_in(p);
   float* G = p->grads;
   void* ws = L.scratch;
@@ -961,7 +1051,8 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   const int nd = p->n_dec;
 
   // ---------------- forward ----------------
-  PV_TRY(guide_fwd(p, L, s));
+  if (P > 1) PV_TRY(particle_guide(p, L, s, nullptr, 0.0f, nullptr));
+  else PV_TRY(guide_fwd(p, L, s));
   const bool sampled = K > 0 && p->class_onehot != nullptr;       // jiVAE without enumeration (plan->class_onehot)
   if (sampled) {
     if (p->coord_dim > 0) return PV_EINVAL;
@@ -983,15 +1074,16 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     o.bo = bias_of(p->params, p->out); o.x = p->x; o.loc = p->loc; o.llrow = L.llrow;
     o.dpre = want_grads ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
-    o.sw = K > 0 ? L.sw : p->row_w; o.N = (int)N; o.xmod = K > 0 ? B * N : 0;
+    o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
     PV_TRY(pv_out_lik(o, s));
   } else {
     // oth <- dL/dlogits (R, N); jiVAE: one pass per enumerated class against the same observations, rows then
     // weighted by alpha (the decoder's gradients become the enumerated expectation)
-    for (int64_t k = 0; k < (K > 0 ? K : 1); ++k)
+    // (multi-particle: one pass per particle, rows weighted 1/P)
+    for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
                          p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s));
-    if (K > 0 && want_grads) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
+    if (reps > 1 && want_grads) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
   if (K > 0) {
@@ -1001,6 +1093,11 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
                                     (int)K, p->beta, p->beta_disc, 0, nullptr, nullptr, nullptr, s));
     else if (!want_grads) PV_TRY(pv_jiv_combine(L.llkb, L.alpha, L.llb, nullptr, 0, 0, nullptr, 0, (int)z, (int)B, (int)K,
                                            p->beta_disc, 0, s));
+  } else if (P > 1) {                                // llb[b] = sum_p sw ll_pb
+    PV_TRY(pv_segsum(L.llrow, S, N, L.llkb, s));
+    PvParticleBwd pf = particle_bwd_desc(p, L);
+    pf.llkb = L.llkb; pf.fwd_only = 1;
+    PV_TRY(pv_particle_bwd(pf, s));
   } else {
     PV_TRY(pv_segsum(L.llrow, B, N, L.llb, s));
     PV_TRY(weigh_llb(p, L, s));
@@ -1008,7 +1105,8 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   if (K > 0 && want_grads) {
     // (llb is formed by pv_jiv_combine at the end of the decoder backward; the scalars are finished there)
   } else
-  PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, L.enc_compact ? L.kl_part : nullptr, L.kl_blocks, 1.0f /* partials come scaled */, s));
+  PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, (L.enc_compact || P > 1) ? L.kl_part : nullptr, P > 1 ? (int)B : L.kl_blocks,
+                           1.0f /* partials come scaled */, s));
   if (!want_grads && sampled) PV_TRY(pv_jiv_sampled_fix(p->scalars, L.jfix, s));
   if (!want_grads) return extra_outputs(p, L, nullptr, lat_in, s);
 
@@ -1073,6 +1171,12 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
                           (int)B, (int)K, p->beta_disc, 1, s, p->coord_dim > 0 ? L.dtp : nullptr));
     PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, L.enc_compact ? L.kl_part : nullptr, L.kl_blocks, 1.0f, s));
     if (sampled) PV_TRY(pv_jiv_sampled_fix(p->scalars, L.jfix, s));
+  }
+  if (P > 1) {                                       // the P samples' dL/dz reduced into the image's head gradient, then the encoder
+    PvParticleBwd pb = particle_bwd_desc(p, L);
+    pb.llkb = L.llkb; pb.dzc = L.dzc; pb.ldzc = lat_in; pb.dtp = p->coord_dim > 0 ? L.dtp : nullptr;
+    PV_TRY(pv_particle_bwd(pb, s));
+    return encoder_bwd(p, L, nullptr, 0, s);
   }
   return latent_encoder_bwd(p, L, lat_in, 4, 1, s);
 }
@@ -1218,15 +1322,16 @@ extern "C" int pv_debug_ivae_conv_trace(const pv_ivae_plan* plan, int64_t* out) 
   return 0;
 }
 
-extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, void* stream) {
-  PV_RANGE("pv_ivae_loss_and_grads");
+// P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
+static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream) {
   if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
   if (!valid_plan(plan) || !plan->params || !plan->x || !plan->eps || !plan->scalars || !plan->ws) return PV_EINVAL;
   if (want_grads && !plan->grads) return PV_EINVAL;
   if (plan->ext_encoder && (!plan->ext_head || (want_grads && !plan->ext_dhead))) return PV_EINVAL;
   if (plan->coord_dim > 0 && !plan->grid) return PV_EINVAL;
+  if (P < 1 || (P > 1 && !particles_supported(plan))) return PV_EINVAL;
   Layout L;
-  carve(plan, (char*)plan->ws, L);
+  carve(plan, (char*)plan->ws, L, false, false, P);
   if (plan->ws_bytes < L.total) return PV_EWS;
   hipStream_t s = (hipStream_t)stream;
   // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
@@ -1234,6 +1339,10 @@ extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, 
   if (plan->class_onehot && (L.fused || plan->coord_dim > 0)) return PV_EINVAL;
   if (L.fused) return loss_and_grads_fused(plan, L, want_grads, s);
   return loss_and_grads_layered(plan, L, want_grads, s);
+}
+extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_loss_and_grads");
+  return loss_and_grads_impl(plan, 1, want_grads, stream);
 }
 
 // ---- external decoder (plan->ext_decoder): the library's half of the step works on a copy of the plan whose decoder is
@@ -1284,8 +1393,8 @@ extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, 
 // SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
 // gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
 // pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
-extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
-  PV_RANGE("pv_ivae_step");
+static int step_impl(const pv_ivae_plan* plan, int P, void* stream) {
+  if (P < 1 || (P > 1 && !(valid_plan(plan) && particles_supported(plan)))) return PV_EINVAL;
   if (plan && !plan->ext_decoder && valid_plan(plan) && plan->params && plan->x && plan->eps && plan->scalars && plan->ws &&
       plan->grads && plan->adam_m && plan->adam_v && plan->adam_step >= 1 && plan->n_params > 0 &&
       !(plan->coord_dim > 0 && !plan->grid) && !plan->ext_encoder &&
@@ -1293,7 +1402,7 @@ extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
       // riding in that launch they would see the updated weights — such plans take the two-call sequence below
       !plan->dy && !plan->row_elbo) {
     Layout L;
-    carve(plan, (char*)plan->ws, L);
+    carve(plan, (char*)plan->ws, L, false, false, P);
     if (plan->ws_bytes < L.total) return PV_EWS;
     if (L.fused && (L.enc_compact || L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
       const double bc1 = 1.0 - pow((double)plan->adam_beta1, (double)plan->adam_step);
@@ -1307,9 +1416,31 @@ extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
                           plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
     }
   }
-  PV_TRY(pv_ivae_loss_and_grads(plan, 1, stream));
+  PV_TRY(loss_and_grads_impl(plan, P, 1, stream));
   return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
                       plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
+}
+extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
+  PV_RANGE("pv_ivae_step");
+  return step_impl(plan, 1, stream);
+}
+
+// ---- the multi-particle ELBO (v17, added without a layout change; include/pyroved_amd.h) ----
+extern "C" int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
+  if (num_particles < 1) return PV_EINVAL;
+  if (num_particles == 1) return pv_ivae_workspace_bytes_for(plan, PV_WS_STEP);
+  if (!valid_plan(plan) || !particles_supported(plan)) return PV_EINVAL;
+  Layout L;
+  carve(plan, nullptr, L, false, false, num_particles);
+  return L.total;
+}
+extern "C" int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_particles_loss_and_grads");
+  return loss_and_grads_impl(plan, num_particles, want_grads, stream);
+}
+extern "C" int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream) {
+  PV_RANGE("pv_ivae_particles_step");
+  return step_impl(plan, num_particles, stream);
 }
 
 extern "C" int pv_ivae_encode(const pv_ivae_plan* plan, float* z_loc, float* z_scale, void* stream) {

@@ -35,6 +35,12 @@ def _kl_name(kl) -> str:
     return kl
 
 
+def _particle_count(p) -> int:
+    if isinstance(p, bool) or not isinstance(p, int) or p < 1:
+        raise ValueError("particles must be an int >= 1 (got %r)" % (p,))
+    return p
+
+
 def _linears(seq: nn.Sequential) -> List[nn.Linear]:
     return [m for m in seq if isinstance(m, nn.Linear)]
 
@@ -58,9 +64,11 @@ class IVAEEngine:
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
 
-    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled"):
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
+                 particles: int = 1):
         self.model = model
         self.kl = _kl_name(kl)
+        self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
         self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.fused = int(fused)         # 0 layered kernels, 1 fused f32-MFMA decoder, 2 fused bf16x3 decoder, 3 fused plain-bf16 decoder
         self.adam_t = 0                 # number of optimizer steps taken (incl. evaluate()'s, see SVItrainer)
@@ -75,6 +83,7 @@ class IVAEEngine:
         self._layout: Dict[str, int] = {}
         self._views: Dict[str, torch.Tensor] = {}
         self._check_model()
+        self._check_particles()
         self.bind()
 
     # ------------------------------------------------------------------ structure
@@ -232,7 +241,23 @@ class IVAEEngine:
             raise ValueError("kl='analytic' (TraceMeanField_ELBO) is not defined for models with a discrete latent (jiVAE): "
                              "their objective enumerates or samples the class (TraceEnum_ELBO / Trace_ELBO)")
 
-    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None):
+    def _check_particles(self):
+        """particles > 1 (pv_ivae_particles_*): the fc-encoder iVAE on the layered or the bf16-class fused decoder path."""
+        self.supports_dp_step = type(self).supports_dp_step and self.particles == 1    # (the native one-call DP step is one-particle)
+        if self.particles == 1:
+            return
+        if type(self) is not IVAEEngine:
+            raise ValueError("particles > 1 is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
+        if self.K > 0:
+            raise ValueError("particles > 1 is not defined here for models with a discrete latent (jiVAE): their objective "
+                             "enumerates or samples the class")
+        if self.conv_enc or self.ext_enc or self.ext_dec:
+            raise ValueError("particles > 1 needs the model's own fully connected encoder and decoder (no convolutional or "
+                             "user-defined networks)")
+        if self.fused == 1:
+            raise ValueError("particles > 1 runs on fused = 0, 2 or 3 (not on the f32-MFMA fused kernel, fused = 1)")
+
+    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them)."""
         if lr is not None:
@@ -241,9 +266,18 @@ class IVAEEngine:
             self.betas = (float(betas[0]), float(betas[1]))
         if eps is not None:
             self.adam_eps = float(eps)
+        old_fused, old_particles = self.fused, self.particles
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
             self.ws = None
+        if particles is not None:
+            self.particles = _particle_count(particles)
+        try:
+            self._check_particles()
+        except ValueError:
+            self.fused, self.particles = old_fused, old_particles
+            self._check_particles()
+            raise
         if kl is not None:
             old, self.kl = self.kl, _kl_name(kl)
             try:
@@ -487,7 +521,10 @@ class IVAEEngine:
         p.ev_start, p.ev_stop = self.events
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
-        need = _abi.lib().pv_ivae_workspace_bytes_for(C.byref(p), what)
+        if what == 1 and self.particles > 1:             # the training step's layout for P decoder samples per image
+            need = _abi.lib().pv_ivae_particles_workspace_bytes(C.byref(p), self.particles)
+        else:
+            need = _abi.lib().pv_ivae_workspace_bytes_for(C.byref(p), what)
         if need < 0:
             raise _abi.PvError("pyroved_amd: unsupported plan (pv_ivae_workspace_bytes_for -> %d)" % need)
         if self.ws is None or self.ws.numel() < need:
@@ -522,8 +559,14 @@ class IVAEEngine:
         (pv_ivae_plan.class_onehot; the trainer's default enumerate_parallel=False).
         step=True with comm (a dist.NativeComm): the DATA-PARALLEL step as one library call on this stream (pv_ivae_dp_step):
         this rank's shard's loss and gradients -> ncclAllReduce(SUM) of [gradients | loss scalars] -> Adam, with the reduced
-        scalars written to hist_out (4 floats) in the optimizer's launch."""
+        scalars written to hist_out (4 floats) in the optimizer's launch.
+        particles = P > 1 (model.engine(particles=P)): eps is (P*B, z_dim) with rows ordered [p][b], loc_out (P*B, n_pix) in the
+        same order, z_out stays (B, z_dim); the encoder runs once, the scalars hold means over particles
+        (pv_ivae_particles_loss_and_grads / pv_ivae_particles_step).  Not with comm=, row_w / row_elbo / dy."""
         self.ensure_bound()
+        P = self.particles
+        if P > 1 and (comm is not None or row_w is not None or row_elbo is not None or dy is not None or class_onehot is not None):
+            raise ValueError("particles > 1 cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
         if self.conv_enc:
             self._check_conv_weight_range()
         if step and (self.ext_enc or self.ext_dec or getattr(self, "ext_y", False) or not want_grads):
@@ -545,10 +588,15 @@ class IVAEEngine:
             dhead = torch.empty_like(head)
             p.ext_head, p.ext_dhead = head.data_ptr(), dhead.data_ptr()
         x = self._prep(x, "x", (b, p.n_pix))
-        eps = self._prep(eps, "eps", (b, p.z_dim))
+        if P > 1 and eps.numel() != P * b * p.z_dim:
+            raise ValueError("particles=%d: eps must be (%d, %d) = (particles * batch, z_dim), rows ordered [p][b] (got %s)"
+                             % (P, P * b, p.z_dim, tuple(eps.shape)))
+        eps = self._prep(eps, "eps", (P * b, p.z_dim))
         y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
         if p.c_dim > 0 and y is None:
             raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        if P > 1 and loc_out is not None and loc_out.numel() != P * b * p.n_pix:
+            raise ValueError("particles=%d: loc_out must hold (%d, %d) values" % (P, P * b, p.n_pix))
         p.x, p.eps = x.data_ptr(), eps.data_ptr()
         p.y = y.data_ptr() if y is not None else None
         if z_out is not None:
@@ -579,9 +627,14 @@ class IVAEEngine:
                         _abi.require_device(hist_out, "hist_out")
                     _abi.check(_abi.lib().pv_ivae_dp_step(C.byref(p), comm.handle, _abi.ptr(hist_out), _abi.current_stream()),
                                "pv_ivae_dp_step")
+                elif P > 1:
+                    _abi.check(_abi.lib().pv_ivae_particles_step(C.byref(p), P, _abi.current_stream()), "pv_ivae_particles_step")
                 else:
                     _abi.check(_abi.lib().pv_ivae_step(C.byref(p), _abi.current_stream()), "pv_ivae_step")
                 self.adam_t += 1
+            elif P > 1:
+                _abi.check(_abi.lib().pv_ivae_particles_loss_and_grads(C.byref(p), P, int(want_grads), _abi.current_stream()),
+                           "pv_ivae_particles_loss_and_grads")
             else:
                 _abi.check(_abi.lib().pv_ivae_loss_and_grads(C.byref(p), int(want_grads), _abi.current_stream()),
                            "pv_ivae_loss_and_grads")

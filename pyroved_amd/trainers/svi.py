@@ -13,6 +13,8 @@ the caller's DataLoader (whose shuffling consumes the global CPU generator exact
 reference), and draws `eps = torch.empty(B, z_dim).normal_()` on the global CPU generator once
 per step — the stream a CPU run of the reference consumes — so that the same seed yields the
 same numbers as the reference's CPU path.  `rng="device"` draws eps on the GPU instead.
+With `num_particles=P` the step draws P such tensors in particle order — Pyro's (non-vectorised)
+particles run the guide P times per step — and stacks them as one (P*B, z_dim) tensor, rows [p][b].
 """
 from typing import Type, Optional, Union
 
@@ -41,6 +43,11 @@ class SVItrainer:
         seed: enforces reproducibility
 
     Keyword Args:
+        num_particles: particles of the ELBO estimate (int >= 1, default 1), what Trace_ELBO(num_particles=P) /
+            TraceMeanField_ELBO(num_particles=P) mean in the reference: P draws of z per image, the loss and its gradients
+            averaged over them.  The encoder runs once per image, the decoder on the P*B samples.  Composes with both loss
+            strings and every keyword below; models.iVAE only (not jiVAE / enumerate_parallel).  With Pyro optimizer / loss
+            objects set num_particles on the Pyro ELBO object instead
         lr: learning rate (Default: 1e-3)
         device: device of the model (defaults to the model's)
         rng: "cpu" (default; bit-compatible with the reference's CPU stream) or "device"
@@ -81,6 +88,13 @@ class SVItrainer:
                                "pass enumerate_parallel=True")
         if enumerate_parallel and not is_joint:
             raise ValueError("enumerate_parallel=True needs a model with a discrete latent (models.jiVAE)")
+        P = kwargs.get("num_particles", 1)
+        if isinstance(P, bool) or not isinstance(P, int) or P < 1:
+            raise ValueError("num_particles must be an int >= 1 (got %r)" % (P,))
+        if P > 1 and (is_joint or enumerate_parallel):
+            raise ValueError("num_particles > 1 is not implemented for models.jiVAE / enumerate_parallel=True: the discrete "
+                             "latent is enumerated or sampled per class, not per particle")
+        self.num_particles = P
         self.model = model
         self.svi = None
         # (attributes every route leaves behind, so that code probing a trainer never meets a missing one)
@@ -95,6 +109,10 @@ class SVItrainer:
             raise ValueError("loss='TraceMeanField_ELBO' is not defined for models.jiVAE: the discrete latent is enumerated "
                              "(TraceEnum_ELBO) or sampled (Trace_ELBO), and neither has a mean-field form")
         pyro_objects = (optimizer is not None and not isinstance(optimizer, dict)) or kl is None
+        if pyro_objects and "num_particles" in kwargs:
+            raise ValueError("num_particles belongs to the HIP training path (optimizer None or a dict, loss None or a string); "
+                             "with Pyro optimizer / loss objects set num_particles on the Pyro ELBO object, e.g. "
+                             "pyro.infer.Trace_ELBO(num_particles=%d)" % P)
         if pyro_objects:
             # Pyro optimizer / ELBO OBJECTS (the reference's signature, svi.py:66-67): the generic Pyro route —
             # pyro.infer.SVI over model.model / model.guide (models/_pyro_programs.py), the networks as differentiable
@@ -140,12 +158,13 @@ class SVItrainer:
             # test hook: a stand-in engine (tests drive the data-parallel host logic on CPU/gloo with it)
             self.engine = kwargs["engine"]
             self.engine.kl = kl
+            self.engine.particles = P
         else:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
-                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl)
+                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P)
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
@@ -168,17 +187,28 @@ class SVItrainer:
 
     # ------------------------------------------------------------------ one minibatch
     def _draw_eps(self, b: int) -> torch.Tensor:
-        z_dim = self.model.z_dim
+        """One step's noise: (num_particles * b, z_dim), rows ordered [p][b] — P sequential draws, as P runs of the guide make them."""
+        z_dim, P = self.model.z_dim, self.num_particles
         if self.rng == "cpu":
-            return torch.empty(b, z_dim).normal_()
-        return torch.empty(b, z_dim, device=self.engine.device).normal_()
+            if P == 1:
+                return torch.empty(b, z_dim).normal_()
+            return torch.cat([torch.empty(b, z_dim).normal_() for _ in range(P)])
+        return torch.empty(P * b, z_dim, device=self.engine.device).normal_()
+
+    def _eps_rows(self, eps: torch.Tensor, x0: int, n: int) -> torch.Tensor:
+        """Rows [x0, x0 + n) of every particle of a step's eps ((P * rows, z_dim), [p][b]), stacked [p][b] again."""
+        P = self.num_particles
+        if P == 1:
+            return eps[x0:x0 + n]
+        return eps.view(P, -1, eps.shape[-1])[:, x0:x0 + n].reshape(P * n, eps.shape[-1])
 
     def _svi_step(self, i: int, x: torch.Tensor, y: Optional[torch.Tensor], train: bool, eps=None, shard=None,
                   **kwargs) -> None:
         """SVI.step on one (global) minibatch; the loss lands in slot i of the device history.
         x / y / eps may already live on the device (device feed, _epoch_device_feed).
         shard = (lo, hi, b): x / y / eps are already THIS rank's rows [lo, hi) of a global minibatch of b samples
-        (the data-parallel device feed gathers nothing else)."""
+        (the data-parallel device feed gathers nothing else).
+        num_particles = P > 1: eps holds P rows per image, [p][b]; a shard takes rows [lo, hi) of every particle."""
         eng = self.engine
         beta = kwargs.get("scale_factor", 1.)          # jiVAE: scalar or [continuous, discrete] (jivae.py:161-165)
         if torch.is_tensor(beta):
@@ -218,7 +248,7 @@ class SVItrainer:
             extra["class_onehot"] = y1h[x0:x0 + hi - lo].contiguous()
         if hi > lo:
             xs = x[x0:x0 + hi - lo].to(dev, torch.float32)
-            es = eps[x0:x0 + hi - lo].to(dev, torch.float32)
+            es = self._eps_rows(eps, x0, hi - lo).to(dev, torch.float32)
             ys = None if y is None else y[x0:x0 + hi - lo].to(dev, torch.float32)
             one_call = (direct and train and getattr(eng, "supports_step", False)
                         and not (getattr(eng, "ext_enc", False) or getattr(eng, "ext_dec", False)))
@@ -316,7 +346,9 @@ class SVItrainer:
     def _draw_eps_epoch(self, sizes) -> torch.Tensor:
         """Every step's eps, drawn on the global CPU generator in step order, as ONE (sum(sizes), z_dim) tensor.  CPU
         normal_ fills 16 values at a time and re-draws the last 16 of a tensor whose size is not a multiple of 16, so a
-        run of batches with numel % 16 == 0 is one draw of their total; the others are drawn one by one."""
+        run of batches with numel % 16 == 0 is one draw of their total; the others are drawn one by one.
+        (num_particles = P: the caller lists every step's size P times — the P draws of a step are consecutive, so step i's
+        rows, [p][b], are one contiguous block of the result)"""
         z = self.model.z_dim
         if self.rng != "cpu":
             return torch.empty(sum(sizes), z, device=self.engine.device).normal_()
@@ -358,7 +390,8 @@ class SVItrainer:
         batches = self._epoch_batches(loader, len(ds))         # LongTensors of sample indices, the loader's order
         if not batches:
             return 0
-        eps = self._draw_eps_epoch([len(b) for b in batches])
+        P = self.num_particles
+        eps = self._draw_eps_epoch([len(b) for b in batches for _ in range(P)])
         if getattr(self, "_rand_n", None) and self.rng == "cpu":
             self._prefetch_perm(self._rand_n)                  # the next shuffled epoch's order, off the critical path
         dev = self.engine.device
@@ -391,8 +424,9 @@ class SVItrainer:
                 c0 = 0
                 for k, (lo, hi, bsz, r0) in enumerate(bounds):
                     w_ = hi - lo
+                    e0 = P * (off + r0)                 # the step's block of P * bsz rows; the shard's rows of every particle
                     self._svi_step(n + k, xs[c0:c0 + w_], None if ys is None else ys[c0:c0 + w_], train,
-                                   eps=eps_dev[off + r0 + lo:off + r0 + hi], shard=(lo, hi, bsz), **kwargs)
+                                   eps=self._eps_rows(eps_dev[e0:e0 + P * bsz], lo, hi - lo), shard=(lo, hi, bsz), **kwargs)
                     c0 += w_
             else:
                 idx = idx_dev[off:off + rows]
@@ -401,8 +435,9 @@ class SVItrainer:
                 r0 = 0
                 for k in range(m):
                     bsz = sizes[n + k]
+                    e0 = P * (off + r0)
                     self._svi_step(n + k, xs[r0:r0 + bsz], None if ys is None else ys[r0:r0 + bsz], train,
-                                   eps=eps_dev[off + r0:off + r0 + bsz], **kwargs)
+                                   eps=eps_dev[e0:e0 + P * bsz], **kwargs)
                     r0 += bsz
             off += rows
             n += m
