@@ -367,6 +367,32 @@ int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_
 int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream);
 int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream);    /* + Adam, as pv_ivae_step */
 
+/* ---- (v17, added without a layout change) the importance-weighted (Renyi / IWAE) bound -------------------------------------
+ * pyro.infer.RenyiELBO(alpha, num_particles=P) on these models (the `data` plate encloses every site, so the log-weights stay
+ * per image).  With z_pb and the plan as in the multi-particle ELBO above (eps (P*B, z_dim) ordered [p][b], ...):
+ *   lw_pb = log p(x_b | z_pb) + beta (log p(z_pb) - log q(z_pb | x_b))
+ *   a_pb  = (1 - alpha) lw_pb,   w_pb = softmax over p of a_pb            (sum_p w_pb = 1; computed with the max subtracted)
+ *   L_b   = (logsumexp_p a_pb - log P) / (1 - alpha)
+ *   loss  = -sum_b L_b,   gradients = -sum_b sum_p w_pb grad lw_pb        (w held constant: exactly the gradient of loss)
+ * alpha is any finite float other than 1; 0 is the IWAE bound, alpha -> 1 approaches the multi-particle ELBO.
+ *   scalars[0] = loss
+ *   scalars[2] = sum_b sum_p w_pb beta log p(z_pb),   scalars[3] = sum_b sum_p w_pb beta log q(z_pb | x_b)
+ *   scalars[1] = sum_b (sum_p w_pb log p(x_b | z_pb) + c_b),   c_b = L_b - sum_p w_pb lw_pb = (H(w_b) - log P) / (1 - alpha):
+ *          scalars[1] carries the weights' entropy term, so that scalars[0] = -(scalars[1] + scalars[2] - scalars[3]) holds as
+ *          it does for every other objective.
+ *   weights_out   optional DEVICE pointer to P*B floats, [p][b]: the normalised weights w (effective sample size 1 / sum_p w^2).
+ *   ws     sized by pv_ivae_renyi_workspace_bytes.
+ * On the fused decoder (fused = 2, 3) a gradient step runs the decoder forward twice — once without gradients for the weights,
+ * once with them — because that kernel fuses forward and backward; the loss is the first forward's.  Every sum over particles
+ * runs in ascending p without atomics: a step is bit-reproducible.
+ * num_particles == 1 forwards to the one-particle entry points, bit for bit (weights_out <- 1).
+ * PV_EINVAL, at every num_particles and from the workspace query too: alpha == 1 or not finite, num_particles < 1 or > 1024,
+ * kl_mode != PV_KL_SAMPLED (the analytic KL has no per-sample weight), and every plan the multi-particle entry points refuse. */
+int64_t pv_ivae_renyi_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles);
+int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, float alpha, int want_grads, float* weights_out,
+                                 void* stream);
+int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream);   /* + Adam */
+
 /* ---- (v16) the data-parallel step with its collective INSIDE the library --------------------------------------------------
  * The reference has no distributed code.  What is sharded is trainers/svi.py:104-113 (`self.svi.step(x)` per
  * minibatch): the loss is a SUM over the data plate (models/ivae.py:177,215), so every replica computes its contiguous slice of

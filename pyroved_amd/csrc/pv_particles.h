@@ -2,6 +2,7 @@
 // One encoder pass over the B images, P decoder samples per image ordered [p][b] (sample s = p * B + b — the order jiVAE's
 // enumerated decoder samples already have), each weighted sw[s] = 1 / P; their dL/dz is reduced over p, in ascending p, into the
 // image's head gradient.
+// The importance-weighted (Renyi) bound is the same step with another fill of sw: pv_renyi_weights, below.
 #pragma once
 #include "pv_common.h"
 #include "pv_kernels.h"
@@ -29,7 +30,7 @@ struct PvParticleExpand {
 int pv_particle_expand(const PvParticleExpand& e, hipStream_t s);
 
 // the particle-reducing latent backward: one workgroup per image b, its P samples in ascending p
-//   llb[b]   = sum_p sw[s] ll_s
+//   llb[b]   = sum_p sw[s] ll_s (+ llb_add[b])
 //   dhead[b] = sum_p pv_head_bwd_math_kl(dz_s, ..., beta * sw[s])        (the decoder's dz_s arrives weighted by sw[s])
 // fused form (llkb == null): gathers ll_s, d(phi, scale, tx, ty) and dL/d(hz_s) from the fused decoder launch's outputs as
 // pv_latent_bwd does per sample (dhz[s] is written for fc_latent's weight gradient), dL/dz_s = dhz_s Wz;
@@ -41,6 +42,9 @@ struct PvParticleBwd {
   const float* llkb; const float* dzc; int64_t ldzc; const float* dtp;     // (P*B), (P*B, ldzc), (P*B, 4)
   const float* sw;                  // (P*B)
   float* llb;                       // (B)
+  const float* llb_add;             // (B) or null: added to llb[b] (the Renyi bound's c_b, pv_renyi_weights)
+  const float* ll_s;                // (P*B) or null, fused form: ll_s is read here, not gathered from the decoder launch's outputs (the
+                                    //   Renyi step's loss is that of the forward launch its weights came from)
   int P, fwd_only;
   PvHeadBwd hb;                     // z, eps: (P*B, z_dim); z_scale, head, dhead: per image; dzc / dtp fields unused
   int enc_n;
@@ -54,3 +58,24 @@ int pv_particle_bwd(const PvParticleBwd& p, hipStream_t s);
 // ... in one launch with the sums of the fused decoder's gradient records (as pv_latent_bwd_reduce)
 int pv_particle_bwd_reduce(const PvParticleBwd& p, const float* part, int grid, float* G, const PvFusedOffsets& o, int cd,
                            hipStream_t s, int rec_fmt);
+
+// the importance-weighted (Renyi, alpha != 1; alpha = 0: IWAE) bound's per-sample weights: one workgroup per image b,
+//   lw_pb = ll_pb + beta (log p(z_pb) - log q(z_pb | x_b)),   a_pb = (1 - alpha) lw_pb,   w_pb = softmax_p a_pb   (max subtracted)
+//   sw[p B + b] = w_pb (and weights_out)
+//   kl_part[b]  = {sum_p w_pb beta log p(z_pb), sum_p w_pb beta log q(z_pb | x_b)}   (replaces the mean the expansion wrote)
+//   c[b]        = L_b - sum_p w_pb lw_pb = (H(w_b) - log P) / (1 - alpha),   L_b = (logsumexp_p a_pb - log P) / (1 - alpha)
+// so that llb[b] = sum_p w_pb ll_pb + c[b] (PvParticleBwd::llb_add) and the two kl_part columns finish to the bound's four scalars.
+// The sums over p run in ascending order in one thread (P is small: 2 .. 16 in practice, at most PV_RENYI_MAX_P): no atomics.
+#define PV_RENYI_MAX_P 1024
+struct PvRenyiWeights {
+  const float* llkb;                // (P*B) log p(x_b | z_pb)
+  const float* z; const float* eps; // (P*B, z_dim)
+  const float* z_scale;             // (B, z_dim)
+  float* sw;                        // (P*B)
+  float* weights_out;               // (P*B) or null
+  float* kl_part;                   // (B, 2)
+  float* c;                         // (B)
+  int B, P, z_dim;
+  float beta, alpha;
+};
+int pv_renyi_weights(const PvRenyiWeights& r, hipStream_t s);

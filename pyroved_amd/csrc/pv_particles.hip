@@ -1,7 +1,8 @@
 // pv_particles.hip — the kernels of the multi-particle ELBO step (pv_particles.h): the guide's expansion into P decoder samples per
-// image and the latent backward that reduces them.  Every sum runs in a fixed order (particles ascending, no float atomics): a step
+// image, the latent backward that reduces them, and the importance-weighted bound's weights.  Every sum runs in a fixed order (particles ascending, no float atomics): a step
 // is bit-reproducible run to run.
 #include "pv_particles.h"
+#include <cmath>
 
 #define PX_THREADS 128
 #define PX_MAX_Z 256
@@ -157,7 +158,7 @@ __device__ __forceinline__ void pv_particle_bwd_block(const PvParticleBwd& p, in
     }
     __syncthreads();
     const float w = p.sw[s];
-    if (t == 0) ll_acc += w * sh_a[0];
+    if (t == 0) ll_acc += w * (p.ll_s ? p.ll_s[s] : sh_a[0]);
     if (!p.fwd_only && t < zd) {
       const float dz = pv_head_dz(p.hb, t, [&](int c) { return sh_a[1 + c]; }, [&](int k) { return sh_dzc[k]; });
       const int64_t e = s * zd + t;
@@ -169,7 +170,7 @@ __device__ __forceinline__ void pv_particle_bwd_block(const PvParticleBwd& p, in
     }
     __syncthreads();                                   // (sh_a / sh_dhz / sh_dzc are rewritten by the next particle)
   }
-  if (t == 0) p.llb[b] = ll_acc;
+  if (t == 0) p.llb[b] = p.llb_add ? ll_acc + p.llb_add[b] : ll_acc;
   if (p.fwd_only) return;
   if (t < zd) {
     p.hb.dhead[(int64_t)b * ldh + t] = acc_g;
@@ -249,6 +250,56 @@ int pv_particle_bwd_reduce(const PvParticleBwd& p, const float* part, int grid, 
   PV_TRY(particle_bwd_check(p));
   hipLaunchKernelGGL(pv_particle_bwd_reduce_kernel, dim3(pv_fused_reduce_blocks(rec_fmt) + p.hb.B), dim3(256), 0, s, p, part, grid, G, o,
                      cd, rec_fmt);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- importance-weighted (Renyi) bound: the P samples' weights, one wave per image ----
+__global__ __launch_bounds__(64) void pv_renyi_weights_kernel(PvRenyiWeights r) {
+  __shared__ float sh_a[PV_RENYI_MAX_P], sh_lp[PV_RENYI_MAX_P], sh_lq[PV_RENYI_MAX_P];
+  const int b = blockIdx.x, t = threadIdx.x, zd = r.z_dim;
+  const float oma = 1.0f - r.alpha;
+  for (int p = 0; p < r.P; ++p) {
+    const int64_t s = (int64_t)p * r.B + b;
+    float lp = 0.0f, lq = 0.0f;
+    for (int i = t; i < zd; i += 64) {
+      const float z = r.z[s * zd + i], e = r.eps[s * zd + i], sig = r.z_scale[(int64_t)b * zd + i];
+      lq += -(e * e) / 2.0f - logf(sig) - LOG_SQRT_2PI;      // Normal(mu, sig).log_prob(mu + sig eps)
+      lp += -(z * z) / 2.0f - LOG_SQRT_2PI;
+    }
+    lp = r.beta * pv_wave_sum(lp);
+    lq = r.beta * pv_wave_sum(lq);
+    if (t == 0) {
+      sh_lp[p] = lp;
+      sh_lq[p] = lq;
+      sh_a[p] = oma * (r.llkb[s] + (lp - lq));
+    }
+  }
+  if (t != 0) return;                                  // (thread 0 reads back what it wrote: no barrier)
+  float m = sh_a[0];
+  for (int p = 1; p < r.P; ++p) m = fmaxf(m, sh_a[p]);
+  float sum = 0.0f;
+  for (int p = 0; p < r.P; ++p) sum += expf(sh_a[p] - m);
+  const float inv = 1.0f / sum, lsum = logf(sum);
+  float klp = 0.0f, klq = 0.0f, ent = 0.0f;
+  for (int p = 0; p < r.P; ++p) {
+    const int64_t s = (int64_t)p * r.B + b;
+    const float d = sh_a[p] - m, w = expf(d) * inv;
+    r.sw[s] = w;
+    if (r.weights_out) r.weights_out[s] = w;
+    klp += w * sh_lp[p];
+    klq += w * sh_lq[p];
+    ent -= w * (d - lsum);                             // H(w_b) = - sum_p w log w, log w = d - log(sum)
+  }
+  r.kl_part[2 * b] = klp;
+  r.kl_part[2 * b + 1] = klq;
+  r.c[b] = (ent - logf((float)r.P)) / oma;
+}
+
+int pv_renyi_weights(const PvRenyiWeights& r, hipStream_t s) {
+  if (r.B < 1 || r.P < 1 || r.P > PV_RENYI_MAX_P || r.z_dim < 1 || !std::isfinite(r.alpha) || r.alpha == 1.0f) return PV_EINVAL;
+  if (!r.llkb || !r.z || !r.eps || !r.z_scale || !r.sw || !r.kl_part || !r.c) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_renyi_weights_kernel, dim3(r.B), dim3(64), 0, s, r);
   PV_LAUNCH_CHECK();
   return 0;
 }

@@ -6,6 +6,7 @@
 // No allocation, no synchronisation, no retained state: everything lives in the caller's plan.
 #include "pv_common.h"
 #include <algorithm>
+#include <cmath>
 #include <stdlib.h>
 #include "pv_kernels.h"
 #include "pv_sdec_fused.h"
@@ -61,6 +62,9 @@ struct Layout {
   // multi-particle ELBO (pv_ivae_particles_*): P decoder samples per image ordered [p][b]; z, tp, zy, hz, sw, llkb hold P*B rows.
   // The count travels here, not in the ABI struct; 1 everywhere else
   int P;
+  // importance-weighted (Renyi) bound (pv_ivae_renyi_*; pv_particles.h: pv_renyi_weights): sw is filled with the softmax weights.
+  // Like P, these travel here
+  bool renyi; float r_alpha; float* r_c; float* r_wout;     // c_b (B); the caller's optional (P*B) copy of the weights
   int64_t total;
 };
 
@@ -109,9 +113,12 @@ bool valid_plan(const pv_ivae_plan* p) {
 // inference_only: encode / decode process B samples (jiVAE's K-fold enumeration exists only in the training step)
 // encode_only (with inference_only): none of the decoder's per-row buffers is touched, so they get no room
 // P > 1 (training step only): the multi-particle ELBO's layout; P == 1 is byte for byte the one-particle layout
-void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1) {
+// renyi (with P > 1): room for c_b at the very end, behind the multi-particle layout, which is unchanged
+void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1,
+           bool renyi = false) {
   Carver c{base, 0};
   L.P = inference_only ? 1 : P;
+  L.renyi = renyi && L.P > 1; L.r_alpha = 0.0f; L.r_wout = nullptr;
   const int64_t B = p->batch, N = encode_only ? 0 : p->n_pix, z = p->z_dim;
   const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
   const bool multi = K > 0 || L.P > 1;              // several decoder samples per input
@@ -268,6 +275,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     L.cfin_ws = base ? base + c.off : nullptr;
     c.off += L.cfin_bytes;
   }
+  L.r_c = L.renyi ? c.take(B) : nullptr;           // (behind everything else: the multi-particle layout's offsets stay)
   L.total = c.off;
 }
 
@@ -719,7 +727,16 @@ PvParticleBwd particle_bwd_desc(const pv_ivae_plan* p, const Layout& L) {
   PvParticleBwd pb{};
   pb.hb = head_bwd_desc(p, L);
   pb.sw = L.sw; pb.llb = L.llb; pb.P = L.P;
+  pb.llb_add = L.renyi ? L.r_c : nullptr;
   return pb;
+}
+// the Renyi bound's weights from the P samples' log-likelihoods in L.llkb: sw, the image's KL row, c_b
+int renyi_weights(const pv_ivae_plan* p, const Layout& L, hipStream_t s) {
+  PvRenyiWeights r{};
+  r.llkb = L.llkb; r.z = L.z; r.eps = p->eps; r.z_scale = L.z_scale;
+  r.sw = L.sw; r.weights_out = L.r_wout; r.kl_part = L.kl_part; r.c = L.r_c;
+  r.B = (int)p->batch; r.P = L.P; r.z_dim = p->z_dim; r.beta = p->beta; r.alpha = L.r_alpha;
+  return pv_renyi_weights(r, s);
 }
 // the scopes of pv_ivae_particles_*: the fc-encoder iVAE (spatial or vanilla decoder, with or without c_dim), layered or on the
 // bf16-class fused decoder kernels
@@ -927,6 +944,7 @@ void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) 
     pb = particle_bwd_desc(p, L);
     pb.llrow = L.llrow; pb.rowtp = L.f_rowtp; pb.part_hz = L.f_part_hz; pb.part_rs = f.part_rs; pb.Wz = Wz; pb.dhz = L.dhz;
     pb.M = R; pb.N = (int)N; pb.kmax = L.f_kmax; pb.H = H; pb.lat_in = (int)lat_in;
+    if (L.renyi) pb.ll_s = L.llkb;                   // (the loss of the forward launch the weights came from)
     if (st.chain) {
       pb.enc_n = p->n_enc; pb.enc_params = p->params; pb.enc_head = p->head;
       for (int i = 0; i < p->n_enc; ++i) { pb.enc_l[i] = p->enc[i]; pb.enc_act[i] = L.eact[i]; pb.enc_dp[i] = L.edp[i]; }
@@ -988,6 +1006,11 @@ int fused_close_forward(const FusedStep& st) {
   if (L.P > 1) {                                     // llb[b] = sum_p sw ll_pb
     PvParticleBwd pf = particle_bwd_desc(p, L);
     pf.llrow = L.llrow; pf.M = L.rows; pf.N = (int)N; pf.kmax = 1; pf.fwd_only = 1;
+    if (L.renyi) {                                   // ... with the bound's weights: llb[b] = sum_p w_pb ll_pb + c_b
+      PV_TRY(pv_segsum(L.llrow, step_S(p, L), N, L.llkb, s));
+      PV_TRY(renyi_weights(p, L, s));
+      pf.llkb = L.llkb;
+    }
     PV_TRY(pv_particle_bwd(pf, s));
     return pv_finish_scalars(L.llb, (int)B, p->scalars, L.kl_part, st.kl_n, 1.0f, s);
   }
@@ -995,6 +1018,26 @@ int fused_close_forward(const FusedStep& st) {
   PV_TRY(weigh_llb(p, L, s));
   PV_TRY(pv_finish_scalars(L.llb, (int)B, p->scalars, st.kl_part ? L.kl_part : nullptr, st.kl_n, 1.0f /* partials come scaled */, s));
   return extra_outputs(p, L, nullptr, plan_lat_in(p), s);
+}
+
+// Renyi bound, gradient step: the weights need every sample's log-likelihood before the decoder launch that applies them to
+// dL/dlogit, and that launch fuses forward and backward — so a forward-only decoder launch runs first (the one a call without
+// gradients makes), then the per-sample sums and the weights.  The forward-only launch may be another kernel with other weight
+// images than the training launch (pv_sdec_fused_bf16_prep_args): it then gets its own preparation, and the training launch's —
+// the guide hosted it — is repeated.  hz keeps the training launch's scale either way (a kernel that wants it scaled scales an
+// unscaled one itself).
+int fused_renyi_forward(const FusedStep& st) {
+  const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
+  const bool x3 = p->fused == 2;
+  PvFused ff = st.f;
+  ff.part_rs = nullptr; ff.dhz_out = ff.dzc_out = nullptr;            // rows of ll, as every forward-only launch writes them
+  const PvFbPrep pf = pv_sdec_fused_bf16_prep_args(ff, false, x3), pg = pv_sdec_fused_bf16_prep_args(st.f, true, x3);
+  const bool same_images = pf.mode == pg.mode && pf.scale == pg.scale && pf.qswap == pg.qswap;
+  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(ff, false, x3, s));
+  PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, x3, s));
+  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, x3, s));
+  PV_TRY(pv_segsum(L.llrow, step_S(p, L), p->n_pix, L.llkb, s));
+  return renyi_weights(p, L, s);
 }
 
 int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
@@ -1033,6 +1076,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
                p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, p->dec_kernel) : PV_REC_ROWMAJOR};
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
+  if (L.renyi && want_grads) PV_TRY(fused_renyi_forward(st));
   if (want_grads) fused_closing_form(st, adam, adam_done);
   PV_TRY(fused_decoder_launch(st));
   return want_grads ? fused_close(st, adam, adam_done) : fused_close_forward(st);
@@ -1068,11 +1112,14 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   float* oth = L.dbuf[1];
   const float* hlast = L.dact[nd - 1];
   const int Hl = p->dec[nd - 1].out_dim;
+  // Renyi bound: sw is known only once every sample's ll is — the likelihood pass that forms ll and the one that applies sw to
+  // dL/dlogit run apart, with the weights kernel between them (below)
+  const bool renyi = L.renyi;
+  PvOutLik o{};
   if (p->coord_dim > 0) {
-    PvOutLik o{};
     o.h = hlast; o.hpre = L.dpre_[nd - 1]; o.ldh = Hl; o.wo = p->params + p->out.w_off;
     o.bo = bias_of(p->params, p->out); o.x = p->x; o.loc = p->loc; o.llrow = L.llrow;
-    o.dpre = want_grads ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
+    o.dpre = (want_grads && !renyi) ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
     PV_TRY(pv_out_lik(o, s));
@@ -1083,7 +1130,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
                          p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s));
-    if (reps > 1 && want_grads) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
+    if (reps > 1 && want_grads && !renyi) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
   if (K > 0) {
@@ -1095,6 +1142,15 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
                                            p->beta_disc, 0, s));
   } else if (P > 1) {                                // llb[b] = sum_p sw ll_pb
     PV_TRY(pv_segsum(L.llrow, S, N, L.llkb, s));
+    if (renyi) {
+      PV_TRY(renyi_weights(p, L, s));
+      if (want_grads && p->coord_dim > 0) {            // the second likelihood pass: dL/dpre and the output layer's partials
+        o.dpre = cur; o.llrow = nullptr; o.loc = nullptr;
+        PV_TRY(pv_out_lik(o, s));
+      } else if (want_grads) {
+        PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
+      }
+    }
     PvParticleBwd pf = particle_bwd_desc(p, L);
     pf.llkb = L.llkb; pf.fwd_only = 1;
     PV_TRY(pv_particle_bwd(pf, s));
@@ -1322,8 +1378,14 @@ extern "C" int pv_debug_ivae_conv_trace(const pv_ivae_plan* plan, int64_t* out) 
   return 0;
 }
 
+// the Renyi bound's arguments next to the plan (null: the ELBO)
+struct RenyiArgs { float alpha; float* weights_out; };
+static void set_renyi(Layout& L, const RenyiArgs* rn) {
+  if (L.renyi) { L.r_alpha = rn->alpha; L.r_wout = rn->weights_out; }
+}
+
 // P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
-static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream) {
+static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr) {
   if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
   if (!valid_plan(plan) || !plan->params || !plan->x || !plan->eps || !plan->scalars || !plan->ws) return PV_EINVAL;
   if (want_grads && !plan->grads) return PV_EINVAL;
@@ -1331,7 +1393,8 @@ static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, 
   if (plan->coord_dim > 0 && !plan->grid) return PV_EINVAL;
   if (P < 1 || (P > 1 && !particles_supported(plan))) return PV_EINVAL;
   Layout L;
-  carve(plan, (char*)plan->ws, L, false, false, P);
+  carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
+  set_renyi(L, rn);
   if (plan->ws_bytes < L.total) return PV_EWS;
   hipStream_t s = (hipStream_t)stream;
   // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
@@ -1393,7 +1456,7 @@ extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, 
 // SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
 // gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
 // pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
-static int step_impl(const pv_ivae_plan* plan, int P, void* stream) {
+static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr) {
   if (P < 1 || (P > 1 && !(valid_plan(plan) && particles_supported(plan)))) return PV_EINVAL;
   if (plan && !plan->ext_decoder && valid_plan(plan) && plan->params && plan->x && plan->eps && plan->scalars && plan->ws &&
       plan->grads && plan->adam_m && plan->adam_v && plan->adam_step >= 1 && plan->n_params > 0 &&
@@ -1402,7 +1465,8 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream) {
       // riding in that launch they would see the updated weights — such plans take the two-call sequence below
       !plan->dy && !plan->row_elbo) {
     Layout L;
-    carve(plan, (char*)plan->ws, L, false, false, P);
+    carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
+    set_renyi(L, rn);
     if (plan->ws_bytes < L.total) return PV_EWS;
     if (L.fused && (L.enc_compact || L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
       const double bc1 = 1.0 - pow((double)plan->adam_beta1, (double)plan->adam_step);
@@ -1416,7 +1480,7 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream) {
                           plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
     }
   }
-  PV_TRY(loss_and_grads_impl(plan, P, 1, stream));
+  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn));
   return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
                       plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
 }
@@ -1441,6 +1505,41 @@ extern "C" int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_
 extern "C" int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream) {
   PV_RANGE("pv_ivae_particles_step");
   return step_impl(plan, num_particles, stream);
+}
+
+// ---- the importance-weighted (Renyi / IWAE) bound (v17, added without a layout change; include/pyroved_amd.h) ----
+// everything the multi-particle entry points refuse, at every P; the sampled KL form only (the analytic one has no per-sample weight)
+static bool renyi_ok(const pv_ivae_plan* plan, int32_t P, float alpha) {
+  return P >= 1 && P <= PV_RENYI_MAX_P && std::isfinite(alpha) && alpha != 1.0f && valid_plan(plan) && particles_supported(plan) &&
+         plan->kl_mode == PV_KL_SAMPLED;
+}
+extern "C" int64_t pv_ivae_renyi_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
+  if (!renyi_ok(plan, num_particles, 0.0f)) return PV_EINVAL;
+  if (num_particles == 1) return pv_ivae_workspace_bytes_for(plan, PV_WS_STEP);
+  Layout L;
+  carve(plan, nullptr, L, false, false, num_particles, true);
+  return L.total;
+}
+// P = 1: the bound is the ELBO and the one weight per image is 1
+static int renyi_one_particle_weights(const pv_ivae_plan* plan, float* weights_out, void* stream) {
+  if (!weights_out) return 0;
+  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)weights_out, 0x3f800000 /* 1.0f */, (size_t)plan->batch, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : (int)e;
+}
+extern "C" int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, float alpha, int want_grads,
+                                            float* weights_out, void* stream) {
+  PV_RANGE("pv_ivae_renyi_loss_and_grads");
+  if (!renyi_ok(plan, num_particles, alpha)) return PV_EINVAL;
+  const RenyiArgs rn{alpha, weights_out};
+  PV_TRY(loss_and_grads_impl(plan, num_particles, want_grads, stream, num_particles > 1 ? &rn : nullptr));
+  return num_particles == 1 ? renyi_one_particle_weights(plan, weights_out, stream) : 0;
+}
+extern "C" int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream) {
+  PV_RANGE("pv_ivae_renyi_step");
+  if (!renyi_ok(plan, num_particles, alpha)) return PV_EINVAL;
+  const RenyiArgs rn{alpha, weights_out};
+  PV_TRY(step_impl(plan, num_particles, stream, num_particles > 1 ? &rn : nullptr));
+  return num_particles == 1 ? renyi_one_particle_weights(plan, weights_out, stream) : 0;
 }
 
 extern "C" int pv_ivae_encode(const pv_ivae_plan* plan, float* z_loc, float* z_scale, void* stream) {

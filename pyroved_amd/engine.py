@@ -15,6 +15,7 @@ Replaces, for the product, what Pyro's SVI/Trace_ELBO/PyroOptim objects hold in
 the reference (pyroved/trainers/svi.py:79-91).
 """
 import ctypes as C
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -41,6 +42,19 @@ def _particle_count(p) -> int:
     return p
 
 
+def _renyi_alpha(a) -> Optional[float]:
+    """None / False: the ELBO.  A float: the order alpha of the importance-weighted (Renyi) bound — finite and not 1."""
+    if a is None or a is False:
+        return None
+    if isinstance(a, bool) or not isinstance(a, (int, float)):
+        raise ValueError("renyi must be None or the bound's order alpha, a float (got %r)" % (a,))
+    a = float(a)
+    if not math.isfinite(a) or a == 1.0:
+        raise ValueError("renyi: alpha must be a finite float other than 1 (got %r); alpha -> 1 is the multi-particle ELBO, "
+                         "which particles=P without renyi computes" % (a,))
+    return a
+
+
 def _linears(seq: nn.Sequential) -> List[nn.Linear]:
     return [m for m in seq if isinstance(m, nn.Linear)]
 
@@ -63,12 +77,15 @@ class IVAEEngine:
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
+    renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
+                                     # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
-                 particles: int = 1):
+                 particles: int = 1, renyi=None):
         self.model = model
         self.kl = _kl_name(kl)
         self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
+        self.renyi = _renyi_alpha(renyi)
         self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.fused = int(fused)         # 0 layered kernels, 1 fused f32-MFMA decoder, 2 fused bf16x3 decoder, 3 fused plain-bf16 decoder
         self.adam_t = 0                 # number of optimizer steps taken (incl. evaluate()'s, see SVItrainer)
@@ -242,49 +259,53 @@ class IVAEEngine:
                              "their objective enumerates or samples the class (TraceEnum_ELBO / Trace_ELBO)")
 
     def _check_particles(self):
-        """particles > 1 (pv_ivae_particles_*): the fc-encoder iVAE on the layered or the bf16-class fused decoder path."""
-        self.supports_dp_step = type(self).supports_dp_step and self.particles == 1    # (the native one-call DP step is one-particle)
-        if self.particles == 1:
+        """particles > 1 (pv_ivae_particles_*) and renyi (pv_ivae_renyi_*, at every particle count): the fc-encoder iVAE on the
+        layered or the bf16-class fused decoder path; renyi with the sampled KL form only."""
+        # (the native one-call DP step is the one-particle ELBO's)
+        self.supports_dp_step = type(self).supports_dp_step and self.particles == 1 and self.renyi is None
+        if self.particles == 1 and self.renyi is None:
             return
+        what = "particles > 1" if self.renyi is None else "renyi"
         if type(self) is not IVAEEngine:
-            raise ValueError("particles > 1 is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
+            raise ValueError("%s is implemented for models.iVAE only (not for %s)" % (what, type(self.model).__name__))
         if self.K > 0:
-            raise ValueError("particles > 1 is not defined here for models with a discrete latent (jiVAE): their objective "
-                             "enumerates or samples the class")
+            raise ValueError("%s is not defined here for models with a discrete latent (jiVAE): their objective "
+                             "enumerates or samples the class" % what)
         if self.conv_enc or self.ext_enc or self.ext_dec:
-            raise ValueError("particles > 1 needs the model's own fully connected encoder and decoder (no convolutional or "
-                             "user-defined networks)")
+            raise ValueError("%s needs the model's own fully connected encoder and decoder (no convolutional or "
+                             "user-defined networks)" % what)
         if self.fused == 1:
-            raise ValueError("particles > 1 runs on fused = 0, 2 or 3 (not on the f32-MFMA fused kernel, fused = 1)")
+            raise ValueError("%s runs on fused = 0, 2 or 3 (not on the f32-MFMA fused kernel, fused = 1)" % what)
+        if self.renyi is not None and self.kl == "analytic":
+            raise ValueError("renyi needs kl='sampled': the closed-form KL has no per-sample term for the bound to weigh")
 
-    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None):
+    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
-        was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them)."""
+        was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
+        renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting."""
         if lr is not None:
             self.lr = float(lr)
         if betas is not None:
             self.betas = (float(betas[0]), float(betas[1]))
         if eps is not None:
             self.adam_eps = float(eps)
-        old_fused, old_particles = self.fused, self.particles
+        old = (self.fused, self.particles, self.renyi, self.kl)
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
             self.ws = None
         if particles is not None:
             self.particles = _particle_count(particles)
+        if renyi is not None:
+            self.renyi = _renyi_alpha(renyi)
+        if kl is not None:
+            self.kl = _kl_name(kl)
         try:
             self._check_particles()
+            self._check_kl()
         except ValueError:
-            self.fused, self.particles = old_fused, old_particles
+            self.fused, self.particles, self.renyi, self.kl = old
             self._check_particles()
             raise
-        if kl is not None:
-            old, self.kl = self.kl, _kl_name(kl)
-            try:
-                self._check_kl()
-            except ValueError:
-                self.kl = old
-                raise
         if self.flat is not None:
             self._static = self._static_plan()
         return self
@@ -521,7 +542,9 @@ class IVAEEngine:
         p.ev_start, p.ev_stop = self.events
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
-        if what == 1 and self.particles > 1:             # the training step's layout for P decoder samples per image
+        if what == 1 and self.renyi is not None:         # ... plus the bound's per-image term
+            need = _abi.lib().pv_ivae_renyi_workspace_bytes(C.byref(p), self.particles)
+        elif what == 1 and self.particles > 1:           # the training step's layout for P decoder samples per image
             need = _abi.lib().pv_ivae_particles_workspace_bytes(C.byref(p), self.particles)
         else:
             need = _abi.lib().pv_ivae_workspace_bytes_for(C.byref(p), what)
@@ -548,7 +571,8 @@ class IVAEEngine:
                        scalars_out: Optional[torch.Tensor] = None, z_out=None, loc_out=None,
                        row_w: Optional[torch.Tensor] = None, row_elbo: Optional[torch.Tensor] = None,
                        dy: Optional[torch.Tensor] = None, step: bool = False,
-                       class_onehot: Optional[torch.Tensor] = None, comm=None, hist_out: Optional[torch.Tensor] = None):
+                       class_onehot: Optional[torch.Tensor] = None, comm=None, hist_out: Optional[torch.Tensor] = None,
+                       weights_out: Optional[torch.Tensor] = None):
         """Enqueues Trace_ELBO.loss_and_grads (self.kl == "analytic": TraceMeanField_ELBO's) on the current stream.  Results land in
         self.scalars (device, 4 floats) and self.grad[:n_flat]; nothing is synchronised.
         row_w (B): per-sample weights of the ELBO terms; row_elbo (B) / dy (B, c_dim): extra outputs
@@ -562,11 +586,19 @@ class IVAEEngine:
         scalars written to hist_out (4 floats) in the optimizer's launch.
         particles = P > 1 (model.engine(particles=P)): eps is (P*B, z_dim) with rows ordered [p][b], loc_out (P*B, n_pix) in the
         same order, z_out stays (B, z_dim); the encoder runs once, the scalars hold means over particles
-        (pv_ivae_particles_loss_and_grads / pv_ivae_particles_step).  Not with comm=, row_w / row_elbo / dy."""
+        (pv_ivae_particles_loss_and_grads / pv_ivae_particles_step).  Not with comm=, row_w / row_elbo / dy.
+        renyi = alpha (model.engine(particles=P, renyi=alpha)): the importance-weighted bound over the same P samples
+        (pv_ivae_renyi_loss_and_grads / pv_ivae_renyi_step): scalars[0] = -sum_b L_b, scalars[2] / [3] the weighted KL terms,
+        scalars[1] the weighted log-likelihood plus the weights' entropy term; weights_out (P*B,), a device tensor, receives
+        the normalised weights, rows [p][b].  Same restrictions as particles > 1."""
         self.ensure_bound()
         P = self.particles
-        if P > 1 and (comm is not None or row_w is not None or row_elbo is not None or dy is not None or class_onehot is not None):
-            raise ValueError("particles > 1 cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
+        alpha = self.renyi
+        if (P > 1 or alpha is not None) and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
+                                             or class_onehot is not None):
+            raise ValueError("particles > 1 / renyi cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
+        if weights_out is not None and alpha is None:
+            raise ValueError("weights_out belongs to the importance-weighted bound: model.engine(particles=P, renyi=alpha)")
         if self.conv_enc:
             self._check_conv_weight_range()
         if step and (self.ext_enc or self.ext_dec or getattr(self, "ext_y", False) or not want_grads):
@@ -597,6 +629,10 @@ class IVAEEngine:
             raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
         if P > 1 and loc_out is not None and loc_out.numel() != P * b * p.n_pix:
             raise ValueError("particles=%d: loc_out must hold (%d, %d) values" % (P, P * b, p.n_pix))
+        if weights_out is not None:
+            _abi.require_device(weights_out, "weights_out")
+            if not weights_out.is_contiguous() or weights_out.dtype != torch.float32 or weights_out.numel() != P * b:
+                raise ValueError("weights_out must be a contiguous float32 tensor of %d = particles * batch values" % (P * b))
         p.x, p.eps = x.data_ptr(), eps.data_ptr()
         p.y = y.data_ptr() if y is not None else None
         if z_out is not None:
@@ -627,11 +663,17 @@ class IVAEEngine:
                         _abi.require_device(hist_out, "hist_out")
                     _abi.check(_abi.lib().pv_ivae_dp_step(C.byref(p), comm.handle, _abi.ptr(hist_out), _abi.current_stream()),
                                "pv_ivae_dp_step")
+                elif alpha is not None:
+                    _abi.check(_abi.lib().pv_ivae_renyi_step(C.byref(p), P, alpha, _abi.ptr(weights_out), _abi.current_stream()),
+                               "pv_ivae_renyi_step")
                 elif P > 1:
                     _abi.check(_abi.lib().pv_ivae_particles_step(C.byref(p), P, _abi.current_stream()), "pv_ivae_particles_step")
                 else:
                     _abi.check(_abi.lib().pv_ivae_step(C.byref(p), _abi.current_stream()), "pv_ivae_step")
                 self.adam_t += 1
+            elif alpha is not None:
+                _abi.check(_abi.lib().pv_ivae_renyi_loss_and_grads(C.byref(p), P, alpha, int(want_grads), _abi.ptr(weights_out),
+                                                                   _abi.current_stream()), "pv_ivae_renyi_loss_and_grads")
             elif P > 1:
                 _abi.check(_abi.lib().pv_ivae_particles_loss_and_grads(C.byref(p), P, int(want_grads), _abi.current_stream()),
                            "pv_ivae_particles_loss_and_grads")

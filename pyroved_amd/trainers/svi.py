@@ -15,7 +15,9 @@ per step — the stream a CPU run of the reference consumes — so that the same
 same numbers as the reference's CPU path.  `rng="device"` draws eps on the GPU instead.
 With `num_particles=P` the step draws P such tensors in particle order — Pyro's (non-vectorised)
 particles run the guide P times per step — and stacks them as one (P*B, z_dim) tensor, rows [p][b].
+`loss="RenyiELBO"` draws exactly so.
 """
+import math
 from typing import Type, Optional, Union
 
 import torch
@@ -37,7 +39,12 @@ class SVItrainer:
             or "TraceMeanField_ELBO" (the same ELBO with the KL between the encoder's Normal and the N(0, 1) prior in
             closed form — lower gradient variance; what pyro.infer.TraceMeanField_ELBO computes for these models) — both
             run in the HIP library and compose with every keyword below; not for models.jiVAE, whose objective
-            enumerates or samples the class.  A pyro.infer ELBO object (needs pyro-ppl) selects the generic Pyro route
+            enumerates or samples the class.  "RenyiELBO": the importance-weighted bound of order `alpha` over
+            `num_particles` samples, what pyro.infer.RenyiELBO(alpha, num_particles) computes for these models — per image
+            L_b = (logsumexp_p (1 - alpha) lw_pb - log P) / (1 - alpha) with lw_pb the one-sample ELBO term of particle p, the
+            loss -sum_b L_b; alpha = 0 is the IWAE bound, alpha -> 1 the multi-particle ELBO.  Also in the HIP library
+            (models.iVAE only, like num_particles > 1; data parallel by the generic route: the bound is a sum over images).
+            A pyro.infer ELBO object (needs pyro-ppl) selects the generic Pyro route
         enumerate_parallel: exact enumeration of the discrete latent of models.jiVAE (False, the reference's default:
             the class is drawn by the guide — vanilla jiVAE only, as in the reference)
         seed: enforces reproducibility
@@ -47,7 +54,9 @@ class SVItrainer:
             TraceMeanField_ELBO(num_particles=P) mean in the reference: P draws of z per image, the loss and its gradients
             averaged over them.  The encoder runs once per image, the decoder on the P*B samples.  Composes with both loss
             strings and every keyword below; models.iVAE only (not jiVAE / enumerate_parallel).  With Pyro optimizer / loss
-            objects set num_particles on the Pyro ELBO object instead
+            objects set num_particles on the Pyro ELBO object instead.  Defaults to 2 for loss="RenyiELBO" (Pyro's default)
+        alpha: order of loss="RenyiELBO" (any finite float other than 1; default 0.0, the IWAE bound); a ValueError with
+            any other loss
         lr: learning rate (Default: 1e-3)
         device: device of the model (defaults to the model's)
         rng: "cpu" (default; bit-compatible with the reference's CPU stream) or "device"
@@ -64,7 +73,7 @@ class SVItrainer:
             evaluate() (svi.py:126-135 calls svi.step under no_grad) — default True
     """
     # the objectives the HIP library evaluates -> the engines' `kl` setting (pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode)
-    _LOSSES = {None: "sampled", "Trace_ELBO": "sampled", "TraceMeanField_ELBO": "analytic"}
+    _LOSSES = {None: "sampled", "Trace_ELBO": "sampled", "TraceMeanField_ELBO": "analytic", "RenyiELBO": "sampled"}
 
     def __init__(self,
                  model: Type[torch.nn.Module],
@@ -88,13 +97,21 @@ class SVItrainer:
                                "pass enumerate_parallel=True")
         if enumerate_parallel and not is_joint:
             raise ValueError("enumerate_parallel=True needs a model with a discrete latent (models.jiVAE)")
-        P = kwargs.get("num_particles", 1)
+        renyi = isinstance(loss, str) and loss == "RenyiELBO"
+        P = kwargs.get("num_particles", 2 if renyi else 1)
         if isinstance(P, bool) or not isinstance(P, int) or P < 1:
             raise ValueError("num_particles must be an int >= 1 (got %r)" % (P,))
-        if P > 1 and (is_joint or enumerate_parallel):
-            raise ValueError("num_particles > 1 is not implemented for models.jiVAE / enumerate_parallel=True: the discrete "
-                             "latent is enumerated or sampled per class, not per particle")
+        if (P > 1 or renyi) and (is_joint or enumerate_parallel):
+            raise ValueError("num_particles > 1 / loss='RenyiELBO' is not implemented for models.jiVAE / enumerate_parallel=True: "
+                             "the discrete latent is enumerated or sampled per class, not per particle")
+        if "alpha" in kwargs and not renyi:
+            raise ValueError("alpha is the order of loss='RenyiELBO'; it has no meaning for loss=%r" % (loss,))
+        alpha = kwargs.get("alpha", 0.0) if renyi else None
+        if renyi and (isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha == 1):
+            raise ValueError("alpha must be a finite float other than 1 (got %r): alpha -> 1 is the multi-particle ELBO, "
+                             "loss='Trace_ELBO' with num_particles" % (alpha,))
         self.num_particles = P
+        self.alpha = None if alpha is None else float(alpha)
         self.model = model
         self.svi = None
         # (attributes every route leaves behind, so that code probing a trainer never meets a missing one)
@@ -109,7 +126,7 @@ class SVItrainer:
             raise ValueError("loss='TraceMeanField_ELBO' is not defined for models.jiVAE: the discrete latent is enumerated "
                              "(TraceEnum_ELBO) or sampled (Trace_ELBO), and neither has a mean-field form")
         pyro_objects = (optimizer is not None and not isinstance(optimizer, dict)) or kl is None
-        if pyro_objects and "num_particles" in kwargs:
+        if pyro_objects and "num_particles" in kwargs and not renyi:
             raise ValueError("num_particles belongs to the HIP training path (optimizer None or a dict, loss None or a string); "
                              "with Pyro optimizer / loss objects set num_particles on the Pyro ELBO object, e.g. "
                              "pyro.infer.Trace_ELBO(num_particles=%d)" % P)
@@ -140,6 +157,8 @@ class SVItrainer:
                         if enumerate_parallel else infer.Trace_ELBO())
             elif loss == "TraceMeanField_ELBO":      # (named by its string next to a Pyro optimizer object)
                 loss = infer.TraceMeanField_ELBO()
+            elif loss == "RenyiELBO":
+                loss = infer.RenyiELBO(alpha=self.alpha, num_particles=P)
             guide = infer.config_enumerate(model.guide, "parallel", expand=True) if enumerate_parallel else model.guide
             self.svi = infer.SVI(model.model, guide, opt, loss=loss)
             self.loss_history = {"training_loss": [], "test_loss": []}
@@ -159,12 +178,14 @@ class SVItrainer:
             self.engine = kwargs["engine"]
             self.engine.kl = kl
             self.engine.particles = P
+            self.engine.renyi = self.alpha
         else:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
-                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P)
+                                       fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
+                                       renyi=False if self.alpha is None else self.alpha)
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
