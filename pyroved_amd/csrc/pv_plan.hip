@@ -958,6 +958,8 @@ void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) 
   // Needs what that epilogue is written for — the plain iVAE step: no per-sample weights / extra outputs, a head of <= 16 outputs,
   // two hidden layers of width 128, the sampled KL form (the analytic form takes the latent-backward launch) — and, with the
   // optimizer riding, records + tiles covering every parameter.
+  // The hosting launch then writes NO per-row outputs (L.llrow / L.f_rowtp, the dL/d(hz) slots): their only readers after a training
+  // step are the latent-backward launches (not run here), row_elbo, dy, per-sample weights and the K > 0 forms — all excluded below.
   if (st.chain && f.part_rs && f.dhz_out && f.dzc_out && K == 0 && !p->row_w && p->kl_mode == PV_KL_SAMPLED && !p->row_elbo &&
       !p->dy && p->head.out_dim <= 16 && p->n_enc == 2 && p->enc[0].out_dim == FD_H && p->enc[1].in_dim == FD_H &&
       p->enc[1].out_dim == FD_H && p->head.in_dim == FD_H) {

@@ -80,7 +80,9 @@ struct PvEncFold {
   // (round 6, third cut) chain != 0: the workgroup also runs its image's latent backward (models/ivae.py's guide differentiated:
   // head backward from dL/dz and the sampled-KL terms) and the encoder's input-gradient chain in the launch's EPILOGUE — it holds
   // the image's row sums, dL/d(hz) and dL/dz there already (PvFused::part_rs / dhz_out / dzc_out) — so that the step's closing launch
-  // has no per-sample work left (pv_elementwise.hip: pv_rec_wgrad_kernel).  Needs head.out_dim <= 16.
+  // has no per-sample work left (pv_elementwise.hip: pv_rec_wgrad_kernel).  Needs head.out_dim <= 16.  A training launch with chain
+  // set writes NO per-row outputs (PvFused::llrow / rowtp stay untouched, part_hz and all but the image's first part_rs slot too):
+  // the row sums are formed on chip and consumed here.  The plan asks for it only where nothing else reads rows (pv_plan.hip).
   int chain;
   float* dhead; int ldh;           // (B, ldh) dL/d[mu | softplus input]
   float* edp0; float* edp1;        // (B, 128) dL/dpre of the two hidden layers

@@ -20,6 +20,11 @@
 //     pre-scaled by c = 2 log2(e), so the MFMAs deliver c * pre-activation and tanh = 1 - 2 rcp(exp2(.) + 1) is four
 //     instructions; the backward pass then carries c * dpre1 and c^2 * dpre0 and un-scales where a gradient leaves the
 //     kernel (dW1, db1, dWc, dL/d(hz), the per-row transform gradients).
+// The image-owning build (<true, lik, 2>: the launch that hosts the guide and the image's latent backward, one image per workgroup)
+// has no per-row outputs at all: nothing outside the workgroup reads a row's log-likelihood or transform gradients, so it keeps the
+// log-likelihood in one running register per lane, skips the row-local dgrad (no table, no 4 MFMAs, no five stores per row) and forms
+// the image's four transform-gradient sums in its epilogue from the column sums dL/d(hz), dWc_0, dWc_1 it holds there anyway
+// (fp32 Wc, four wave sums: the kernel's OWN switch; -DW8_OWN_SUMS=0 builds the per-row form for A/B).  hz[b] / tp[b] are fetched once.
 // Layout, row -> lane mapping, weight images, staging swizzles and the per-workgroup gradient record are those of
 // pv_sdec_fused_bf16.hip (pv_fb_layout.h), so the rest of the step is unchanged.
 //
@@ -93,6 +98,9 @@ __device__ __forceinline__ float w8_sum_q(float v) {
 #endif
 #ifndef W8_TAIL
 #define W8_TAIL 1                    // 0: the seventh tile row-parallel as in rounds 2-4 (A/B builds)
+#endif
+#ifndef W8_OWN_SUMS
+#define W8_OWN_SUMS 1                // 0: the image-owning build writes per-row ll / transform gradients and reads them back (A/B builds)
 #endif
 #define W8_ABL_LOADS(bit, g) (!(W8_ABL & (bit)) || (((g) & 1) == 0))
 #define W8_ABL_BUF(bit, g) ((W8_ABL & (bit)) ? (((g) >> 1) & 1) : ((g) & 1))
@@ -411,6 +419,11 @@ extern "C" int pv_debug_coop_late_count(unsigned* out) {
 template <bool GRADS, int LIK, int FOLDK>
 __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEncFold e) {
   constexpr bool FOLD = FOLDK != 0, CHAIN = FOLDK >= 2, COOP = FOLDK == 3;
+  // OWN: the workgroup owns its image's five row sums {ll, d(phi), d(scale), d(tx), d(ty)} — the chain build of a training launch
+  // (the launcher selects it only with part_rs, dhz_out and dzc_out set: ONE image per workgroup, its latent backward in the epilogue).
+  // Nothing outside the workgroup reads a per-row value then: no llrow / rowtp stores, no row-local coordinate backward; the four
+  // transform-gradient sums come from the column sums the epilogue holds anyway, the log-likelihood from a running register.
+  constexpr bool OWN = W8_OWN_SUMS && CHAIN && GRADS;
   extern __shared__ __attribute__((aligned(16))) char smb[];
   const int tid = threadIdx.x, lane0 = tid & 63, lane = lane0, r = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -465,7 +478,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       else if (kq == 1) pt_a = f.cd == 2 ? f.Wc[j * 2 + 1] : 0.0f;
       else if (kq == 2) pt_a = f.bc[j];
     }
-    if (tid < 256) {
+    if (!OWN && tid < 256) {
       const int mm = tid >> 6, m = lane & 15, kq = lane >> 4;
 #pragma unroll
       for (int e_ = 0; e_ < 8; ++e_) {
@@ -489,7 +502,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   } else {
     // FOLD: the images straight from the fp32 weights (pv_fb_layout.h pv_fb_prep, mode 0: bf16(C w), permuted columns,
     // swizzled chunks) — 8 float4 of each matrix per thread; and this workgroup's dL/d(hz) slots cleared
-    if (GRADS) {
+    // (OWN: nobody adds slots up — dL/d(hz) and the row sums are consumed inside this workgroup — so none is cleared)
+    if (GRADS && !OWN) {
       const int64_t b0 = (int64_t)g * e.img_per_wg;
       f32x4* zp = reinterpret_cast<f32x4*>(f.part_hz + b0 * f.kmax * FD_H);
       const int n4 = e.img_per_wg * f.kmax * (FD_H / 4);
@@ -734,7 +748,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     else if (kq == 2) { a[0] = hi; a[1] = lo; }
     reinterpret_cast<bf16x4*>(smb + WO_ATAB)[tid] = a;
   }
-  if (tid < 256) {
+  if (!OWN && tid < 256) {
     // row-local dgrad A operands (16x16x32: lane (m, kq) holds A[m][k], k = the 8 logical columns a lane feeds as B:
     // 32mm + 4kq + e (e < 4), 32mm + 16 + 4kq + (e - 4)); rows m: 0 Wc0 hi, 1 Wc0 lo, 2 Wc1 hi, 3 Wc1 lo, others 0
     const int mm = tid >> 6, m = lane & 15, kq = lane >> 4;
@@ -779,13 +793,17 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   // its own (made opaque here), so that a register-pressure spill saves and restores two lanes, not the argument tuple's
   // sixteen — 36 + 21 v_readlane per tile came from fetching llrow / loc / rowtp back that way.
   typedef __attribute__((address_space(1))) float gfloat;         // (explicitly global: an opaque pointer would be stored through flat_*)
-  unsigned long long u_llrow, u_loc, u_rowtp, u_part_hz;
-  int64_t a_M;
+  unsigned long long u_llrow = 0, u_loc, u_rowtp = 0, u_part_hz = 0;
+  int64_t a_M = 0;
   // (real copies: an in-place "+s" keeps the value inside the tuple's registers, and the tuple is still spilled as a whole)
-  asm volatile("s_mov_b64 %0, %5\n\ts_mov_b64 %1, %6\n\ts_mov_b64 %2, %7\n\ts_mov_b64 %3, %8\n\ts_mov_b64 %4, %9"
-               : "=&s"(u_llrow), "=&s"(u_loc), "=&s"(u_rowtp), "=&s"(u_part_hz), "=&s"(a_M)
-               : "s"((unsigned long long)f.llrow), "s"((unsigned long long)f.loc), "s"((unsigned long long)f.rowtp),
-                 "s"((unsigned long long)f.part_hz), "s"(f.M));
+  if constexpr (OWN) {                                            // (no rows of ll / transform gradients, no dL/d(hz) slots: loc alone)
+    asm volatile("s_mov_b64 %0, %1" : "=&s"(u_loc) : "s"((unsigned long long)f.loc));
+  } else {
+    asm volatile("s_mov_b64 %0, %5\n\ts_mov_b64 %1, %6\n\ts_mov_b64 %2, %7\n\ts_mov_b64 %3, %8\n\ts_mov_b64 %4, %9"
+                 : "=&s"(u_llrow), "=&s"(u_loc), "=&s"(u_rowtp), "=&s"(u_part_hz), "=&s"(a_M)
+                 : "s"((unsigned long long)f.llrow), "s"((unsigned long long)f.loc), "s"((unsigned long long)f.rowtp),
+                   "s"((unsigned long long)f.part_hz), "s"(f.M));
+  }
   gfloat* a_llrow = (gfloat*)u_llrow; gfloat* a_loc = (gfloat*)u_loc; gfloat* a_rowtp = (gfloat*)u_rowtp;
   gfloat* a_part_hz = (gfloat*)u_part_hz;
 
@@ -797,6 +815,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     accW1[kb >> 2][kb & 3] = f32x4{0, 0, 0, 0}; accW2[kb >> 2][kb & 3] = f32x4{0, 0, 0, 0}; accS[kb] = f32x4{0, 0, 0, 0};
   }
   float dbo = 0.0f;
+  float llacc = 0.0f;                                // OWN: the log-likelihood of this lane's rows so far (lanes q == 0)
   int cur_b = -1;                                    // the sample whose dL/d(hz) this WAVE is accumulating
   const int upb = f.N / FD_UNIT;
   float* rec = f.part + (int64_t)g * FD_REC;
@@ -847,14 +866,17 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   float* chz = reinterpret_cast<float*>(smb + WO_CHZ) + wave * FD_H;
   float* ctp = reinterpret_cast<float*>(smb + WO_CTP) + wave * 64;
   float* cgr = reinterpret_cast<float*>(smb + WO_CGR) + wave * 64;
-  auto fetch_unit_inputs = [&](const Pos& p_) {
+  // (OWN: every unit of the workgroup belongs to ONE image — hz[b] and tp[b] are fetched once, a tile moves its grid slice only)
+  auto fetch_unit_inputs = [&](const Pos& p_, bool first) {
     const int n0 = p_.loc * FD_UNIT;
-    sd_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + WO_CHZ + wave * (FD_H * 4));
-    sd_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + WO_CHZ + wave * (FD_H * 4) + 256);
-    sd_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + WO_CTP + wave * 256);
+    if (!OWN || first) {
+      sd_glds4(f.hz + (int64_t)p_.b * FD_H + lane, lds0 + WO_CHZ + wave * (FD_H * 4));
+      sd_glds4(f.hz + (int64_t)p_.b * FD_H + 64 + lane, lds0 + WO_CHZ + wave * (FD_H * 4) + 256);
+      sd_glds4(f.tp + (int64_t)p_.b * 8 + (lane & 7), lds0 + WO_CTP + wave * 256);
+    }
     sd_glds4(f.grid + (int64_t)n0 * f.cd + (lane & (16 * f.cd - 1)), lds0 + WO_CGR + wave * 256);
   };
-  fetch_unit_inputs(pos_cur);
+  fetch_unit_inputs(pos_cur, true);
   const W8Addr wad = w8_addr(r, q);
   int tile_no = -1;
   for (int ut = u_lo; ut < u_end; ut += W8_WAVES) {
@@ -943,7 +965,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     }
     asm volatile("; W8_P1_coord_done");
     W8_STAMP(1);
-    fetch_unit_inputs(pos_nx);                 // the slots were consumed by the coordinate layer above
+    fetch_unit_inputs(pos_nx, false);          // the slots were consumed by the coordinate layer above
     {
       w8_layer_fwd(W1h, b1s, h0b, tC, wad, q);
       sd_tanh8<W8_FENCE_MASK>(tC);
@@ -971,7 +993,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       dlda *= act ? swv : 0.0f;
       if (q == 0) {
         if (act) {
-          if (a_llrow) a_llrow[row] = ll;
+          if constexpr (OWN) llacc += ll;
+          else if (a_llrow) a_llrow[row] = ll;
           if (a_loc) a_loc[row] = locv;
         }
         if (GRADS) { dbo += dlda; inf_dl[r] = dlda; }
@@ -1031,20 +1054,24 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       // (the staging area is free between barrier 2 and the round-2 stores: the wave's own rows serve the dpre0 sums now,
       //  which ends p0's life before the round-2 consume)
       // ---- coordinate layer backward, row-local part on the matrix cores: D[m][row] = sum_j T[m][j] dpre0[row][j] ----
-      f32x4 dd = {0.0f, 0.0f, 0.0f, 0.0f};
-      const bf16x8* ttab = reinterpret_cast<const bf16x8*>(smb + WO_TTAB) + lane;
+      // (OWN: not computed — the image's sums of these four follow from the column sums below, in the epilogue; and the wave's
+      //  dL/d(hz) partial is never flushed: it has one sample)
+      if constexpr (!OWN) {
+        f32x4 dd = {0.0f, 0.0f, 0.0f, 0.0f};
+        const bf16x8* ttab = reinterpret_cast<const bf16x8*>(smb + WO_TTAB) + lane;
 #pragma unroll
-      for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], sd_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
-      if (q == 0 && act) {
-        const float d0 = (dd[0] + dd[1]) * SD_RC2, d1 = (dd[2] + dd[3]) * SD_RC2;
-        a_rowtp[row] = sc * (d1 * u0c - d0 * u1c);
-        a_rowtp[a_M + row] = d0 * u0c + d1 * u1c;
-        a_rowtp[2 * a_M + row] = d0;
-        a_rowtp[3 * a_M + row] = d1;
-      }
-      if (act && bu != cur_b) {
-        if (cur_b >= 0) flush_hz(cur_b);
-        cur_b = bu;
+        for (int mm = 0; mm < 4; ++mm) dd = MFMA32(ttab[64 * mm], sd_cat(p0[2 * mm], p0[2 * mm + 1]), dd);
+        if (q == 0 && act) {
+          const float d0 = (dd[0] + dd[1]) * SD_RC2, d1 = (dd[2] + dd[3]) * SD_RC2;
+          a_rowtp[row] = sc * (d1 * u0c - d0 * u1c);
+          a_rowtp[a_M + row] = d0 * u0c + d1 * u1c;
+          a_rowtp[2 * a_M + row] = d0;
+          a_rowtp[3 * a_M + row] = d1;
+        }
+        if (act && bu != cur_b) {
+          if (cur_b >= 0) flush_hz(cur_b);
+          cur_b = bu;
+        }
       }
       // ---- dL/d(hz[b]) = sum_rows dpre0, dWc_k = sum_rows dpre0 x'_k : wave-local MFMA, own rows of staging A;
       // B columns: 0 ones | 1, 5 x0 (hi, lo) | 2, 6 x1 (hi, lo)
@@ -1182,7 +1209,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       dlda *= swv;
       if (q == 0) {
         if (wave == 0) {
-          if (a_llrow) a_llrow[row] = ll;
+          if constexpr (OWN) llacc += ll;
+          else if (a_llrow) a_llrow[row] = ll;
           if (a_loc) a_loc[row] = locv;
           if (GRADS) dbo += dlda;
         }
@@ -1238,8 +1266,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         for (int jb = 0; jb < 8; ++jb) z8[jb] = sd_zero4();
         sd_stage_store(sA, z8, 16 + r, q);
         sd_stage_store(sB, h0b, 16 + r, q);
-      } else if (wave == 2) {
-        // coordinate layer backward, row-local part
+      } else if (!OWN && wave == 2) {
+        // coordinate layer backward, row-local part (OWN: not computed, see the tile loop)
         bf16x4 p0[8];
         w8_xchg_get(smb, 5, p0, lane);
         f32x4 dd = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1257,7 +1285,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         // dL/d(hz[b]) = sum_rows dpre0, dWc_k = sum_rows dpre0 x'_k in this wave's own rows of staging A
         bf16x4 p0[8];
         w8_xchg_get(smb, 5, p0, lane);
-        if (bu != cur_b) {
+        if (!OWN && bu != cur_b) {
           if (cur_b >= 0) flush_hz(cur_b);
           cur_b = bu;
         }
@@ -1289,20 +1317,23 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   //  fetched at kernel entry and carried — spilled — through the tile loop)
   const PvEncFoldArg ep_ = pv_kernarg_fold();
   const bool own_dhz = FOLD && f.dhz_out != nullptr;
-  if (cur_b >= 0 && !own_dhz) flush_hz(cur_b);
+  if (!OWN && cur_b >= 0 && !own_dhz) flush_hz(cur_b);
   // Order of the epilogue (round 6, third cut): barrier -> every LOAD the rest of it needs -> the record stores -> LDS work.  The
   // records are 71 KB per workgroup, 18 MB chip-wide within a microsecond: the memory pipeline takes ~3.5 us to drain them, and a
   // load issued BEHIND them waits for that (scripts/gpu_trace_w8.py: 7.3 k cycles on ten row-sum loads); requested ahead of them,
   // the loads' data arrives while the stores drain under the column sums and the latent backward below.
   W8_STAMP_E(0);
-  __syncthreads();                                     // (every wave is past the last tile: its rows' outputs are in L2, the staging area is free)
+  // (every wave is past the last tile: its rows' outputs are in L2, the staging area is free.  OWN: there are no row outputs to
+  //  drain — the barrier waits for LDS traffic only)
+  if constexpr (OWN) pv_lds_barrier();
+  else __syncthreads();
   W8_STAMP_E(1);
   // (round 6, FOLD: the image's per-row outputs are complete in L2 — the barrier above drains every wave's stores — and are requested
   //  HERE, so that their round trip runs under the column-sum phase below; they are added up behind its barrier)
   // (thread n takes rows 2n, 2n + 1 — one 8-byte load per quantity: a load instruction costs this CU ~10 cycles of issue whatever its
   //  width, and the epilogue is made of little else)
   float rsv[2][5] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
-  const bool fold_rs = FOLD && f.part_rs && f.N <= 2 * W8_THREADS && f.N % 2 == 0;
+  const bool fold_rs = !OWN && FOLD && f.part_rs && f.N <= 2 * W8_THREADS && f.N % 2 == 0;
   if (fold_rs) {
     const int64_t r0 = (int64_t)g * f.N;
     if (2 * tid < f.N) {
@@ -1327,8 +1358,14 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   const bool own_chain = CHAIN && ep_->chain && f.part_rs && f.dhz_out && f.dzc_out;
   float ch_whd[16], ch_a1 = 0.0f, ch_a0 = 0.0f, ch_z = 0.0f, ch_sig = 1.0f, ch_ep = 0.0f, ch_sp = 0.0f;
   f32x4 ch_w1[8];
+  // OWN: the coordinate layer's fp32 weight columns of this thread's hidden unit (threads 0 .. 127), for the transform-gradient sums
+  float wc0 = 0.0f, wc1 = 0.0f;
+  if (OWN && tid < FD_H) {
+    wc0 = f.Wc[tid * f.cd];
+    if (f.cd == 2) wc1 = f.Wc[tid * 2 + 1];
+  }
   if (own_chain) {
-    auto ldc = [](const float* p_) { return __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto ldc =[](const float* p_) { return __hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     const int ho = ep_->head.out_dim;
     if (tid < FD_H) {
       const float* Wh = ep_->params + ep_->head.w_off + tid;
@@ -1413,6 +1450,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   // ---- the column sums over the waves (threads 0 .. 127), then — where the workgroup owns a whole image (FOLD) — the image's row
   // sums, dL/d(hz) and dL/dz for the latent backward (round 6: PvFused::part_rs / dhz_out / dzc_out), one more barrier for all three ----
   float dhz_j = 0.0f;                                                // this thread's dL/d(hz[g][tid]) (tid < 128)
+  float dwc0_j = 0.0f, dwc1_j = 0.0f;                                // ... and its dWc[tid][0 / 1] = sum_rows dpre0[row][tid] x'_k[row]
   if (tid < FD_H) {
     const float* scr = reinterpret_cast<const float*>(smb + WO_SA);
     float vo = 0.0f, v0 = 0.0f, v1 = 0.0f, vh = 0.0f;
@@ -1425,9 +1463,11 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       vo += s_[3 * FD_H] + s_[4 * FD_H];
     }
     dhz_j = vh * SD_RC2;
+    dwc0_j = v0 * SD_RC2;
+    dwc1_j = v1 * SD_RC2;
     if (own_dhz) f.dhz_out[(int64_t)g * FD_H + tid] = dhz_j;
-    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = v0 * SD_RC2;
-    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = v1 * SD_RC2;
+    rec[2 * FD_H * FD_H + 2 * FD_H + tid] = dwc0_j;
+    rec[2 * FD_H * FD_H + 3 * FD_H + tid] = dwc1_j;
     rec[2 * FD_H * FD_H + 4 * FD_H + tid] = vo;
   }
   const bool own_dzc = own_dhz && f.dzc_out != nullptr;
@@ -1438,7 +1478,30 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     // kernels keep in registers do not fit this kernel: profiles/r06h_row_sums_ab.txt).  Fixed order: thread n takes rows n,
     // n + 512; wave sums; waves 0..7.  dL/dz[i] = sum_j dL/d(hz[j]) Wz[j][i] (coord_latent.fc_latent, nets/fc.py:217,230): threads
     // 0 .. 127 hold dL/d(hz[j]); wave sums of waves 0, 1.
-    if (f.part_rs) {
+    // OWN: no rows were written.  The log-likelihood is the sum of the lanes' running registers (wave sums; waves 0..7).  The four
+    // transform-gradient sums follow from the column sums this phase holds — per hidden unit j, H_j = dL/d(hz[j]) = sum_rows dpre0,
+    // A_j = dWc[j][0] = sum_rows dpre0 x'_0, B_j = dWc[j][1]: with d_k[row] = sum_j Wc[j][k] dpre0[row][j] and x'_k = sc u_k + t_k,
+    //   sum_rows sc (d1 u0 - d0 u1) = sum_j Wc[j][1] (A_j - tx H_j) - Wc[j][0] (B_j - ty H_j)              d(phi)
+    //   sum_rows (d0 u0 + d1 u1)    = [sum_j Wc[j][0] (A_j - tx H_j) + Wc[j][1] (B_j - ty H_j)] / sc       d(scale)
+    //   sum_rows d0 = sum_j Wc[j][0] H_j,   sum_rows d1 = sum_j Wc[j][1] H_j                                d(tx), d(ty)
+    // (the translation is taken out per hidden unit, before the dot product: where |t| exceeds sc |u| the difference is formed
+    //  between two numbers of one unit's scale, not between two 128-term sums).  Threads 0 .. 127 hold unit j: four wave sums of
+    //  waves 0 and 1, combined in wave order behind the barrier.  fp32 Wc throughout (the row-local form split it into two bf16).
+    if (OWN && f.part_rs) {
+      const float lw = pv_wave_sum(llacc);
+      if (lane == 0) red[8 + wave] = lw;
+      if (wave < 2) {
+        const float tx = ctp[3], ty = f.cd == 2 ? ctp[4] : 0.0f;
+        const float a_ = dwc0_j - tx * dhz_j, b_ = dwc1_j - ty * dhz_j;
+        const float s4[4] = {wc1 * a_ - wc0 * b_, wc0 * a_ + wc1 * b_, wc0 * dhz_j, wc1 * dhz_j};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float s_ = pv_wave_sum(s4[c]);
+          if (lane == 0) red[16 + 8 * wave + c] = s_;
+        }
+      }
+    }
+    if (!OWN && f.part_rs) {
       const int64_t r0 = (int64_t)g * f.N;
       float a5[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
       if (fold_rs) {
@@ -1468,11 +1531,24 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     pv_lds_barrier();
     W8_STAMP_E(5);
     float* cs = reinterpret_cast<float*>(smb + WO_SA);             // (the column-sum scratch is free behind the barrier above)
-    if (f.part_rs && tid < 5) {
+    // the image's row sum c of {ll, d(phi), d(scale), d(tx), d(ty)} from the waves' partials in LDS, fixed order
+    auto row_sum = [&](int c) {
       float v = 0.0f;
-      for (int w = 0; w < W8_WAVES; ++w) v += red[8 + 8 * tid + w];
-      f.part_rs[((int64_t)g * f.kmax) * PV_RS_W + tid] = v;
-    }
+      if constexpr (OWN) {
+        if (c == 0) {
+#pragma unroll
+          for (int w = 0; w < W8_WAVES; ++w) v += red[8 + w];
+        } else {
+          v = red[16 + c - 1] + red[24 + c - 1];
+          if (c == 2 && f.cd == 2) v /= ctp[2];
+        }
+      } else {
+#pragma unroll
+        for (int w = 0; w < W8_WAVES; ++w) v += red[8 + 8 * c + w];
+      }
+      return v;
+    };
+    if (f.part_rs && tid < 5) f.part_rs[((int64_t)g * f.kmax) * PV_RS_W + tid] = row_sum(tid);
     if (own_dzc && tid < ep_->lat_in) f.dzc_out[(int64_t)g * ep_->lat_in + tid] = info[tid] + info[16 + tid];
     if (own_chain) {
       // ---- the image's latent backward (pv_elementwise.hip: pv_latent_bwd_block, for the one sample this workgroup owns): head
@@ -1487,9 +1563,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         //  other through them with a wait, no barrier.  [0..4] the five row sums, [8..] dL/dz content, [16..31] dhead, zero past its end)
         float* csw = cs + 64 * wave;
         if (lane < 5) {
-          float v = 0.0f;
-#pragma unroll
-          for (int w = 0; w < W8_WAVES; ++w) v += red[8 + 8 * lane + w];
+          const float v = row_sum(lane);
           csw[lane] = v;
           if (tid == 0) ep_->llb[g] = v;
         }
@@ -1580,9 +1654,13 @@ int pv_sdec_fused_w8_launch(const PvFused& f_in, int grid, bool grads, hipStream
 #else
 #define W8_COOP_BUILD 2
 #endif
+  // (the chain builds keep no per-row outputs: the image's sums are consumed in their epilogue, which needs all three of these —
+  //  pv_plan.hip sets them together wherever it asks for the chain)
+  const bool chain = fold && e.chain;
+  if (chain && grads && !(f.part_rs && f.dhz_out && f.dzc_out)) return PV_EINVAL;
 #define W8_PICK(G, L) fn = !fold ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, 0>)                     \
-                               : (G && e.chain && e.coop) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? W8_COOP_BUILD : 1>) \
-                               : (G && e.chain) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? 2 : 1>) \
+                               : (G && chain && e.coop) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? W8_COOP_BUILD : 1>) \
+                               : (G && chain) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? 2 : 1>) \
                                                 : reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, 1>)
   if (grads) {
     if (f.lik == PV_LIK_BERNOULLI) W8_PICK(true, PV_LIK_BERNOULLI);
