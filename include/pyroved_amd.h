@@ -42,7 +42,23 @@ enum pv_act {
 };
 
 /* decoder likelihoods: utils/prob.py:25-29 (get_sampler) */
-enum pv_lik { PV_LIK_BERNOULLI = 0, PV_LIK_GAUSSIAN = 1, PV_LIK_CBERNOULLI = 2 /* ContinuousBernoulli(probs) */ };
+enum pv_lik { PV_LIK_BERNOULLI = 0, PV_LIK_GAUSSIAN = 1, PV_LIK_CBERNOULLI = 2 /* ContinuousBernoulli(probs) */,
+  /* (v17: a new enum value, no struct layout changes) Poisson with a log link, for count data: the decoder's output a is the log-rate.
+   * With a_c = min(a, 30) and rate = exp(a_c):
+   *   log p(x | a) = x a_c - rate - lgamma(x + 1)        (= torch.distributions.Poisson(rate).log_prob(x); x any float >= 0)
+   *   d(-log p)/da = (rate - x) [a <= 30]                (autograd through the clamp)
+   *   loc (decode, loc_out)     = rate                   (the mean image)
+   * Needs sigmoid_out == 0; decoder_sig is ignored.  The data-only normaliser C = sum lgamma(x + 1) over the call's images
+   * (VED: targets) is computed once per call by two small launches of its own (partial sums, then their fixed-order sum)
+   * and enters the reported scalars as scalars[1] -= C, scalars[0] += C (scalars[0] = -(s1 + s2 - s3) still holds) at the
+   * end of every entry point that produces scalars, before anything reads them; the partial sums take 8 KiB at the very
+   * end of a training call's workspace (the workspace queries include them).  Per-image outputs that would need the
+   * per-image normaliser (row_w, row_elbo, dy: the semi-supervised models) are refused with PV_EINVAL.
+   * Range: |rate - x| may be anything fp32 holds.  With fused == 2 a Poisson plan runs the bf16 three-product decoder
+   * kernel at every size (what dec_kernel == 1 names): the fp16 builds that path otherwise takes from 16 384 decoder rows
+   * up stage a per-row power of two of dL/dlogit as fp16, which holds |rate - x| < 32768 only; dec_kernel 21 / 28 with
+   * this likelihood is PV_EINVAL. */
+  PV_LIK_POISSON_LOG = 3 };
 
 /* (v17) the form of the KL term between the guide q(z|x) = N(mu, sigma) and the N(0, 1) prior (pv_ivae_plan.kl_mode,
  * pv_ved_plan.kl_mode).  z = mu + sigma * eps is drawn once per sample for the likelihood either way.

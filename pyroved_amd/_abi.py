@@ -22,7 +22,7 @@ PV_MAX_LAYERS = 8
 
 # enum pv_act / pv_lik (include/pyroved_amd.h)
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2, "lrelu": 3, "softplus": 4, "gelu": 5, "sigmoid": 6}
-LIK = {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2}
+LIK = {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2, "poisson_log": 3}
 # enum pv_kl_mode: the sampled log q - log p of Trace_ELBO / the closed-form KL of TraceMeanField_ELBO
 KL = {"sampled": 0, "analytic": 1}
 

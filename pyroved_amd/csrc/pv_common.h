@@ -188,7 +188,21 @@ __device__ __forceinline__ void pv_lik_one(float av, float xv, int lik, int sigm
     lv = pr;
   }
 }
-
+// PV_LIK_POISSON_LOG: Poisson(rate = exp(min(a, 30))).log_prob(x) without its data-only term lgamma(x + 1) (pv_poisson_lognorm adds
+// that to the step's scalars), d(-log p)/da through the clamp, and the rate.  Kept out of pv_lik_one: the run-time switch there is
+// inlined into the plain elementwise kernels, whose register budgets stay what they were; the Poisson has kernels of its own
+// (pv_elementwise.hip) and callers that serve every likelihood from one kernel go through pv_lik_any.
+__device__ __forceinline__ void pv_poisson_one(float av, float xv, float& ll, float& d, float& lv) {
+  const float ac = fminf(av, 30.0f);
+  const float rate = expf(ac);
+  ll = xv * ac - rate;
+  d = av <= 30.0f ? rate - xv : 0.0f;                   // clamp's gradient
+  lv = rate;
+}
+__device__ __forceinline__ void pv_lik_any(float av, float xv, int lik, int sigmoid_out, float sig, float& ll, float& d, float& lv) {
+  if (lik == PV_LIK_POISSON_LOG) pv_poisson_one(av, xv, ll, d, lv);
+  else pv_lik_one(av, xv, lik, sigmoid_out, sig, ll, d, lv);
+}
 
 // v summed over the four 16-lane rows of the wave (lanes r, r + 16, r + 32, r + 48), result in every lane: gfx950's row / half swaps
 // (v_permlane16_swap, v_permlane32_swap: plain VALU) instead of two ds_bpermute round trips through the LDS pipeline.  The pairings

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(D1_THREADS) void pv_dec1d_kernel(D1Args A) {
       for (int e = tid; e < per; e += D1_THREADS) {
         const int l = d1_div(e, o.N), c = e - l * o.N;
         float ll, d, lv;
-        pv_lik_one(src[(l + 1) * Po + c], A.y[(int64_t)b * per + e], A.lik, A.sigmoid_out, A.sig, ll, d, lv);
+        pv_lik_any(src[(l + 1) * Po + c], A.y[(int64_t)b * per + e], A.lik, A.sigmoid_out, A.sig, ll, d, lv);
         if (A.loc) A.loc[(int64_t)b * per + e] = lv;
         if (A.dlda) A.dlda[(int64_t)b * per + e] = d;
         acc += ll;

@@ -376,6 +376,13 @@ __global__ __launch_bounds__(256) void pv_out_lik_kernel(PvOutLik p) {
       locv = pr;
     } else if (p.lik == PV_LIK_CBERNOULLI) {
       pv_cbern(a, x, ll, dlda, locv);
+    } else if (p.lik == PV_LIK_POISSON_LOG) {
+      // Poisson(rate = exp(min(a, 30))).log_prob(x) without lgamma(x + 1) (data only: pv_poisson_lognorm)
+      const float ac = fminf(a, 30.0f);
+      const float rate = expf(ac);
+      ll = x * ac - rate;
+      dlda = a <= 30.0f ? rate - x : 0.0f;
+      locv = rate;
     } else {
       const float pr = p.sigmoid_out ? 1.0f / (1.0f + expf(-a)) : a;
       const float d = x - pr;
@@ -1245,10 +1252,42 @@ __global__ __launch_bounds__(256) void pv_lik_rows_kernel(const float* __restric
   if (threadIdx.x == 0) llb[blockIdx.x] = acc;
 }
 
+// the two kernels above for PV_LIK_POISSON_LOG (pv_common.h: pv_poisson_one): same indexing, same summation order
+__global__ void pv_lik_elem_poisson_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t M,
+                                           float* __restrict__ loc, float* __restrict__ llrow, float* __restrict__ dlda) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
+    float ll, d, lv;
+    pv_poisson_one(a[e], x[e], ll, d, lv);
+    if (loc) loc[e] = lv;
+    if (llrow) llrow[e] = ll;
+    if (dlda) dlda[e] = d;
+  }
+}
+__global__ __launch_bounds__(256) void pv_lik_rows_poisson_kernel(const float* __restrict__ a, const float* __restrict__ x,
+                                                                  int64_t per, float* __restrict__ loc, float* __restrict__ dlda,
+                                                                  float* __restrict__ llb) {
+  __shared__ float sm[4];
+  const int64_t base = (int64_t)blockIdx.x * per;
+  float acc = 0.0f;
+  for (int64_t n = threadIdx.x; n < per; n += 256) {
+    float ll, d, lv;
+    pv_poisson_one(a[base + n], x[base + n], ll, d, lv);
+    if (loc) loc[base + n] = lv;
+    if (dlda) dlda[base + n] = d;
+    acc += ll;
+  }
+  acc = block_sum_256(acc, sm);
+  if (threadIdx.x == 0) llb[blockIdx.x] = acc;
+}
+
 int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik, int sigmoid_out, float sig, float* loc,
                 float* dlda, float* llb, hipStream_t s) {
   if (B < 1) return 0;
-  hipLaunchKernelGGL(pv_lik_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, lik, sigmoid_out, sig, loc, dlda, llb);
+  if (lik == PV_LIK_POISSON_LOG) {
+    hipLaunchKernelGGL(pv_lik_rows_poisson_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, loc, dlda, llb);
+  } else {
+    hipLaunchKernelGGL(pv_lik_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, lik, sigmoid_out, sig, loc, dlda, llb);
+  }
   PV_LAUNCH_CHECK();
   return 0;
 }
@@ -1258,8 +1297,78 @@ int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_
   int blocks = (int)((M + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) return 0;
-  hipLaunchKernelGGL(pv_lik_elem_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, lik, sigmoid_out, sig, loc, llrow,
-                     dlda);
+  if (lik == PV_LIK_POISSON_LOG) {
+    hipLaunchKernelGGL(pv_lik_elem_poisson_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, loc, llrow, dlda);
+  } else {
+    hipLaunchKernelGGL(pv_lik_elem_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, lik, sigmoid_out, sig, loc, llrow, dlda);
+  }
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// PV_LIK_POISSON_LOG: the normaliser sum lgamma(x + 1).  It depends on the data only, so the decoder kernels never see it
+// (their per-pixel ll is x a - exp(a)); these small kernels add it where the ELBO's value is reported.
+// Every thread sums its strided elements in float64, then a fixed tree over the workgroup: C can be as large as the loss
+// itself.  (The scalars arrive rounded to fp32 by the finishing launch; the correction is applied in float64 and the result is
+// rounded to fp32 again.)
+#define PL_CHUNK 4096            // elements per workgroup of the partial-sum launch (until PV_POISSON_PARTS workgroups are in use)
+__device__ __forceinline__ double pl_block_sum(double v, double* sm /* blockDim.x doubles */) {
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = (int)blockDim.x >> 1; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) sm[threadIdx.x] += sm[threadIdx.x + h];
+    __syncthreads();
+  }
+  return sm[0];
+}
+// part[blockIdx.x] = sum of lgamma(x[i] + 1) over the block's contiguous chunk [blockIdx.x * per, min(n, (blockIdx.x + 1) * per))
+__global__ __launch_bounds__(256) void pv_poisson_lognorm_part_kernel(const float* __restrict__ x, int64_t n, int64_t per,
+                                                                      double* __restrict__ part) {
+  __shared__ double sm[256];
+  const int64_t beg = (int64_t)blockIdx.x * per;
+  const int64_t end = beg + per < n ? beg + per : n;
+  double acc = 0.0;
+  for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)lgammaf(x[i] + 1.0f);
+  const double c = pl_block_sum(acc, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = c;
+}
+__global__ __launch_bounds__(PV_POISSON_PARTS) void pv_poisson_lognorm_kernel(const double* __restrict__ part, int nparts,
+                                                                              float* scalars) {
+  __shared__ double sm[PV_POISSON_PARTS];
+  const double c = pl_block_sum((int)threadIdx.x < nparts ? part[threadIdx.x] : 0.0, sm);
+  if (threadIdx.x == 0) {
+    scalars[1] = (float)((double)scalars[1] - c);
+    scalars[0] = (float)((double)scalars[0] + c);
+  }
+}
+int pv_poisson_lognorm(const float* x, int64_t n, double* part, float* scalars, hipStream_t s) {
+  if (!x || !part || !scalars || n < 0) return PV_EINVAL;
+  int64_t nparts = (n + PL_CHUNK - 1) / PL_CHUNK;
+  if (nparts < 1) nparts = 1;
+  if (nparts > PV_POISSON_PARTS) nparts = PV_POISSON_PARTS;
+  const int64_t per = (n + nparts - 1) / nparts;
+  hipLaunchKernelGGL(pv_poisson_lognorm_part_kernel, dim3((unsigned)nparts), dim3(256), 0, s, x, n, per, part);
+  PV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pv_poisson_lognorm_kernel, dim3(1), dim3(PV_POISSON_PARTS), 0, s, part, (int)nparts, scalars);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+__global__ __launch_bounds__(256) void pv_poisson_lognorm_rows_kernel(const float* __restrict__ x, int64_t N, float* __restrict__ llkb,
+                                                                      int64_t B, int K) {
+  __shared__ double sm[256];
+  const float* xb = x + (int64_t)blockIdx.x * N;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += 256) acc += (double)lgammaf(xb[i] + 1.0f);
+  const double c = pl_block_sum(acc, sm);
+  if ((int)threadIdx.x < K) {
+    float* d = llkb + (int64_t)threadIdx.x * B + blockIdx.x;
+    *d = (float)((double)*d - c);
+  }
+}
+int pv_poisson_lognorm_rows(const float* x, int64_t B, int64_t N, float* llkb, int K, hipStream_t s) {
+  if (!x || !llkb || B <= 0 || N <= 0 || K < 1 || K > 256) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_poisson_lognorm_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, x, N, llkb, B, K);
   PV_LAUNCH_CHECK();
   return 0;
 }

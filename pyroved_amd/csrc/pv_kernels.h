@@ -233,6 +233,15 @@ int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik,
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
                 float* llrow, float* dlda, hipStream_t s);
 
+// The Poisson (log link) likelihood's data-only normaliser C = sum_i lgamma(x[i] + 1) over the call's n observations, applied to the
+// finished scalars: scalars[1] -= C, scalars[0] += C.  Two launches: up to PV_POISSON_PARTS workgroups each sum a contiguous chunk
+// in float64 into part[], then one workgroup sums the partials in a fixed order and corrects the scalars.  No atomics; the same
+// bits every call; must run after the launch that finishes the scalars and before anything reads them.
+#define PV_POISSON_PARTS 1024
+int pv_poisson_lognorm(const float* x, int64_t n, double* part /* PV_POISSON_PARTS */, float* scalars, hipStream_t s);
+// per image instead: llkb[k*B + b] -= sum_n lgamma(x[b*N + n] + 1) for k < K (the sampled-class jiVAE objective)
+int pv_poisson_lognorm_rows(const float* x, int64_t B, int64_t N, float* llkb, int K, hipStream_t s);
+
 // ---- compact encoder kernels (pv_encoder.hip) ----
 // deterministic block-wide sum for any blockDim.x that is a multiple of 64 (<= 1024); result valid in every thread
 __device__ __forceinline__ float pv_block_sum(float v, float* sm /* >= 16 floats */) {

@@ -65,6 +65,7 @@ struct Layout {
   // importance-weighted (Renyi) bound (pv_ivae_renyi_*; pv_particles.h: pv_renyi_weights): sw is filled with the softmax weights.
   // Like P, these travel here
   bool renyi; float r_alpha; float* r_c; float* r_wout;     // c_b (B); the caller's optional (P*B) copy of the weights
+  double* pl_part;                                          // Poisson plans: pv_poisson_lognorm's partial sums (PV_POISSON_PARTS doubles)
   int64_t total;
 };
 
@@ -88,6 +89,17 @@ static inline int64_t plan_lat_in(const pv_ivae_plan* p) {
   return (p->coord_dim > 0 ? p->latent_dim : p->z_dim) + p->c_dim + plan_K(p);
 }
 
+// The decoder-kernel selection a plan runs with.  Poisson plans on the split-precision path (fused = 2) take the bf16 three-product
+// kernel at every size: the fp16 builds the size rule picks from 16 384 rows up stage a row's 2^e of dL/dlogit = m 2^e as fp16, which
+// holds |rate - x| < 2^15 only — counts (and rates up to exp(30)) go far beyond that, and an overflow there turns the weight gradients
+// into inf silently.  bf16 pieces have fp32's exponent range.  Asking for the fp16 builds by name is refused (valid_plan).
+// Every launch of a TRAINING layout takes this selection, the forward-only one of a call without gradients included (so evaluate runs
+// the 4-wave kind 0 whatever the size: its layout — waves, records — is the training step's); pv_ivae_decode has a layout of its own
+// and no fp16 build to avoid, so it keeps the plan's dec_kernel and with it the 8-wave forward-only build at large sizes.
+static inline int plan_sel(const pv_ivae_plan* p) {
+  return (p->lik == PV_LIK_POISSON_LOG && p->fused == 2 && p->dec_kernel == 0) ? 1 : p->dec_kernel;
+}
+
 bool valid_plan(const pv_ivae_plan* p) {
   if (!p || p->batch <= 0 || p->n_pix <= 0 || p->z_dim <= 0) return false;
   if (p->coord_dim < 0 || p->coord_dim > 2) return false;
@@ -100,8 +112,13 @@ bool valid_plan(const pv_ivae_plan* p) {
   if (p->discrete_dim > 0 && p->c_dim != 0) return false;                            // jiVAE: no conditioning vector
   if ((p->row_w || p->row_elbo || p->dy) && (p->discrete_dim > 0 || p->n_enc_ops > 0 || p->ext_encoder)) return false;
   if (p->dy && p->c_dim == 0) return false;
-  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI) return false;
-  if (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out) return false;   // probs outside (0,1): unsupported
+  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI && p->lik != PV_LIK_POISSON_LOG)
+    return false;
+  if (p->lik == PV_LIK_POISSON_LOG) {
+    if (p->sigmoid_out) return false;                               // the decoder's output is the log-rate
+    if (p->row_w || p->row_elbo || p->dy) return false;             // (per-image outputs would need the per-image normaliser)
+    if (p->fused == 2 && p->dec_kernel > 1) return false;           // (the fp16 builds: plan_sel)
+  } else if (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out) return false;   // probs outside (0,1): unsupported
   if (p->coord_dim > 0 && p->out.out_dim != 1) return false;
   if (p->coord_dim == 0 && p->out.out_dim != p->n_pix) return false;
   if (p->dec_kernel != 0 && !pv_sdec_fused_sel_valid(p->fused, p->dec_kernel)) return false;
@@ -198,12 +215,12 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
       const int64_t units = R / FD_UNIT;
       L.f_grid = pv_sdec_fused_grid(units);
       L.f_kmax = pv_sdec_fused_kmax((int)N, units, L.f_grid);
-      if (p->fused >= 2) L.f_kmax *= pv_sdec_fused_bf16_waves(p->fused == 2, units, p->dec_kernel);   // the bf16 kernels publish dL/d(hz) per wave
+      if (p->fused >= 2) L.f_kmax *= pv_sdec_fused_bf16_waves(p->fused == 2, units, plan_sel(p));   // the bf16 kernels publish dL/d(hz) per wave
       L.f_part = c.take((int64_t)L.f_grid * FD_REC);
       L.f_part_hz = c.take(S * L.f_kmax * (H0 + PV_RS_W));        // (+ the row-sum slots behind it: PvFused::part_rs, one zero fill)
       L.f_rowtp = c.take(4 * R);
       L.f_wimg = c.take(FB_WIMG_BYTES / (int64_t)sizeof(float));
-      const int64_t park = (p->fused == 2 && !inference_only) ? pv_sdec_fused_bf16_park_bytes(true, units, L.f_grid, p->dec_kernel) : 0;
+      const int64_t park = (p->fused == 2 && !inference_only) ? pv_sdec_fused_bf16_park_bytes(true, units, L.f_grid, plan_sel(p)) : 0;
       L.f_park = park ? c.take(park / (int64_t)sizeof(float)) : nullptr;
       upd(pv_colsum_ws(B, (int)H0));
     }
@@ -276,6 +293,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     c.off += L.cfin_bytes;
   }
   L.r_c = L.renyi ? c.take(B) : nullptr;           // (behind everything else: the multi-particle layout's offsets stay)
+  // (at the very end, training layouts of Poisson plans only: every other offset is what it was)
+  L.pl_part = (p->lik == PV_LIK_POISSON_LOG && !inference_only) ? reinterpret_cast<double*>(c.take(2 * PV_POISSON_PARTS)) : nullptr;
   L.total = c.off;
 }
 
@@ -807,7 +826,7 @@ void fused_decoder_args(FusedStep& st) {
   f.wimg = L.f_wimg; f.park = L.f_park;
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
   f.sw = multi ? L.sw : p->row_w; f.x_units = multi ? B * N / FD_UNIT : 0;
-  f.sigmoid_out = p->sigmoid_out; f.kmax = L.f_kmax; f.sig = p->decoder_sig; f.sel = p->dec_kernel;
+  f.sigmoid_out = p->sigmoid_out; f.kmax = L.f_kmax; f.sig = p->decoder_sig; f.sel = plan_sel(p);
   // fp16 builds of the fp32-class kernel: where the per-row exponent of dL/dlogit is centred (|dL/dlogit| <= 1 for the Bernoulli
   // likelihoods; ~ residual / sig^2 for the Gaussian): exact powers of two either way, only the representable RANGE moves
   f.dl_exp = 4;
@@ -1075,7 +1094,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
   if (K > 0 && !L.enc_compact) return PV_EINVAL;
   const bool cat_in = p->c_dim > 0 || K > 0;         // the decoder's latent input is a materialised concatenation
   FusedStep st{p, L, want_grads != 0, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
-               p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, p->dec_kernel) : PV_REC_ROWMAJOR};
+               p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, plan_sel(p)) : PV_REC_ROWMAJOR};
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
   if (L.renyi && want_grads) PV_TRY(fused_renyi_forward(st));
@@ -1137,6 +1156,8 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   }
   if (K > 0) {
     PV_TRY(pv_segsum(L.llrow, S, N, L.llkb, s));
+    // (the drawn class's score-function term -log_r (onehot - alpha) carries ll_b itself: the per-image normaliser goes in here)
+    if (sampled && p->lik == PV_LIK_POISSON_LOG) PV_TRY(pv_poisson_lognorm_rows(p->x, B, N, L.llkb, (int)K, s));
     if (!want_grads && sampled)
       PV_TRY(pv_jiv_combine_sampled(L.llkb, L.alpha, p->class_onehot, L.llb, nullptr, 0, 0, nullptr, 0, (int)z, (int)B,
                                     (int)K, p->beta, p->beta_disc, 0, nullptr, nullptr, nullptr, s));
@@ -1264,6 +1285,10 @@ static pv_ivae_plan decode_plan(const pv_ivae_plan* plan) {
 
 static pv_ivae_plan guide_plan(const pv_ivae_plan* plan);
 
+// the likelihood branch a forward-only launch borrows to turn logits into `loc`: the Gaussian one (sigmoid(a) or a) for every
+// likelihood whose mean is that; the Poisson's own for its rate exp(min(a, 30))
+static int loc_lik(const pv_ivae_plan* lay) { return lay->lik == PV_LIK_POISSON_LOG ? PV_LIK_POISSON_LOG : PV_LIK_GAUSSIAN; }
+
 // ---- forward-only decode on the fused spatial-decoder kernel (models/base.py:145-171) ----
 // decode(z, angle, shift, scale) of an invariant model whose decoder the fused kernel is specialised for: the per-sample
 // transform is the uniform (angle, scale, shift), hz = fc_latent(z), and the persistent kernel runs its forward half only
@@ -1304,8 +1329,8 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   fused_weights(f, lay);
   f.llrow = nullptr; f.loc = loc; f.wimg = D.wimg;
   f.M = B * N; f.units = f.M / FD_UNIT; f.N = (int)N; f.cd = lay->coord_dim; f.B = (int)B;
-  f.lik = PV_LIK_GAUSSIAN; f.sigmoid_out = lay->sigmoid_out; f.sig = 1.0f;      // loc = sigmoid(a) or a
-  f.sel = lay->dec_kernel;
+  f.lik = loc_lik(lay); f.sigmoid_out = lay->sigmoid_out; f.sig = 1.0f;         // loc = sigmoid(a) or a (Poisson: exp(a))
+  f.sel = lay->dec_kernel;                             // (forward-only: no fp16 build, the parent's selection for every likelihood)
   const int grid = pv_sdec_fused_grid(f.units);
   if (lay->fused == 1) return pv_sdec_fused_launch(f, grid, false, s);
   f.hz_scale = 0.0f;                                   // hz is written unscaled here; the 8-wave kernels scale it themselves
@@ -1363,7 +1388,7 @@ extern "C" int pv_ivae_guide_folds(const pv_ivae_plan* plan) {
   carve(plan, nullptr, L);                             // (offsets only: nothing is dereferenced)
   if (!L.fused || !plan_guide_may_fold(plan, L)) return 0;
   PvFused f{};
-  f.M = L.rows; f.units = L.rows / FD_UNIT; f.N = plan->n_pix; f.B = (int)plan_S(plan); f.sel = plan->dec_kernel;
+  f.M = L.rows; f.units = L.rows / FD_UNIT; f.N = plan->n_pix; f.B = (int)plan_S(plan); f.sel = plan_sel(plan);
   return pv_sdec_fused_fold_ok(f, L.f_grid, false) ? 1 : 0;
 }
 
@@ -1386,6 +1411,16 @@ static void set_renyi(Layout& L, const RenyiArgs* rn) {
   if (L.renyi) { L.r_alpha = rn->alpha; L.r_wout = rn->weights_out; }
 }
 
+// Poisson plans: the data-only normaliser C = sum lgamma(x + 1) into the finished scalars ([1] -= C, [0] += C): two small trailing
+// launches on the caller's stream (partial sums, then their fixed-order sum), after the step's own launches and before anything
+// reads the scalars.  The same
+// correction for every objective (C does not depend on the latent sample).  The sampled-class jiVAE objective is the exception:
+// its score-function term needs the per-image value, which went into llkb in front of pv_jiv_combine_sampled (nothing to do here).
+static int poisson_lognorm(const pv_ivae_plan* plan, const Layout& L, hipStream_t s) {
+  if (plan->lik != PV_LIK_POISSON_LOG || (plan_K(plan) > 0 && plan->class_onehot)) return 0;
+  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s);
+}
+
 // P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
 static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr) {
   if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
@@ -1402,8 +1437,9 @@ static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, 
   // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
   // cannot run it with invariances (models/jivae.py:181-189) — and only the layer-by-layer path implements it
   if (plan->class_onehot && (L.fused || plan->coord_dim > 0)) return PV_EINVAL;
-  if (L.fused) return loss_and_grads_fused(plan, L, want_grads, s);
-  return loss_and_grads_layered(plan, L, want_grads, s);
+  if (L.fused) PV_TRY(loss_and_grads_fused(plan, L, want_grads, s));
+  else PV_TRY(loss_and_grads_layered(plan, L, want_grads, s));
+  return poisson_lognorm(plan, L, s);
 }
 extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, void* stream) {
   PV_RANGE("pv_ivae_loss_and_grads");
@@ -1477,6 +1513,7 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiA
                           plan->adam_beta2, plan->adam_eps, (float)((double)plan->lr / bc1), (float)sqrt(bc2)};
       bool done = false;
       PV_TRY(loss_and_grads_fused(plan, L, 1, (hipStream_t)stream, &ad, &done));
+      PV_TRY(poisson_lognorm(plan, L, (hipStream_t)stream));
       if (done) return 0;
       return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
                           plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
@@ -1591,9 +1628,9 @@ extern "C" int pv_ivae_decode(const pv_ivae_plan* plan, const float* z, float an
     o.h = L.dact[nd - 1]; o.ldh = plan->dec[nd - 1].out_dim; o.wo = plan->params + plan->out.w_off;
     o.bo = bias_of(plan->params, plan->out);
     o.x = L.llrow /* unused for loc */; o.loc = loc; o.llrow = nullptr; o.dpre = nullptr; o.M = R;
-    o.H = plan->dec[nd - 1].out_dim; o.lik = PV_LIK_GAUSSIAN; o.sigmoid_out = plan->sigmoid_out; o.sig = 1.0f;
+    o.H = plan->dec[nd - 1].out_dim; o.lik = loc_lik(plan); o.sigmoid_out = plan->sigmoid_out; o.sig = 1.0f;
     o.act_last = plan->dec[nd - 1].act;
     return pv_out_lik(o, s);
   }
-  return pv_lik_elem(L.logits, L.logits, B * N, PV_LIK_GAUSSIAN, plan->sigmoid_out, 1.0f, loc, nullptr, nullptr, s);
+  return pv_lik_elem(L.logits, L.logits, B * N, loc_lik(plan), plan->sigmoid_out, 1.0f, loc, nullptr, nullptr, s);
 }

@@ -314,6 +314,12 @@ __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_kernel(PvFused f)
         locv = pr;
       } else if (f.lik == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
+      } else if (f.lik == PV_LIK_POISSON_LOG) {
+        const float ac = fminf(a, 30.0f);
+        const float rate = sd_exp(ac);
+        ll = xv * ac - rate;
+        dlda = a <= 30.0f ? rate - xv : 0.0f;
+        locv = rate;
       } else {
         const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;

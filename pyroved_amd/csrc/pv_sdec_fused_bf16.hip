@@ -1038,6 +1038,12 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pv_sdec_fused_bf16_kernel(PvFus
         locv = pr;
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
+      } else if (LIK == PV_LIK_POISSON_LOG) {
+        const float ac = fminf(a, 30.0f);
+        const float rate = sd_exp(ac);
+        ll = xv * ac - rate;
+        dlda = a <= 30.0f ? rate - xv : 0.0f;
+        locv = rate;
       } else {
         const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
@@ -1818,10 +1824,16 @@ int pv_sdec_fused_bf16_launch(const PvFused& f_in, int grid, bool grads, bool x3
 #endif
     }
     else if (f.lik == PV_LIK_GAUSSIAN) FB_PICK_G(PV_LIK_GAUSSIAN);
+    else if (f.lik == PV_LIK_POISSON_LOG) {
+      // (no fp16 build: their staged per-row exponent holds |dL/dlogit| < 2^15 only — pv_plan.hip: plan_sel keeps Poisson plans off them)
+      if (prec >= FB_P_H221) return PV_EINVAL;
+      FB_PICK(true, PV_LIK_POISSON_LOG);
+    }
     else FB_PICK_G(PV_LIK_CBERNOULLI);
   } else {
     if (f.lik == PV_LIK_BERNOULLI) FB_PICK(false, PV_LIK_BERNOULLI);
     else if (f.lik == PV_LIK_GAUSSIAN) FB_PICK(false, PV_LIK_GAUSSIAN);
+    else if (f.lik == PV_LIK_POISSON_LOG) FB_PICK(false, PV_LIK_POISSON_LOG);
     else FB_PICK(false, PV_LIK_CBERNOULLI);
   }
 #undef FB_PICK_G

@@ -1199,6 +1199,12 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         locv = pr;
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
+      } else if (LIK == PV_LIK_POISSON_LOG) {
+        const float ac = fminf(a, 30.0f);
+        const float rate = sd_exp(ac);
+        ll = xv * ac - rate;
+        dlda = a <= 30.0f ? rate - xv : 0.0f;
+        locv = rate;
       } else {
         const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
@@ -1665,10 +1671,12 @@ int pv_sdec_fused_w8_launch(const PvFused& f_in, int grid, bool grads, hipStream
   if (grads) {
     if (f.lik == PV_LIK_BERNOULLI) W8_PICK(true, PV_LIK_BERNOULLI);
     else if (f.lik == PV_LIK_GAUSSIAN) W8_PICK(true, PV_LIK_GAUSSIAN);
+    else if (f.lik == PV_LIK_POISSON_LOG) W8_PICK(true, PV_LIK_POISSON_LOG);
     else W8_PICK(true, PV_LIK_CBERNOULLI);
   } else {
     if (f.lik == PV_LIK_BERNOULLI) W8_PICK(false, PV_LIK_BERNOULLI);
     else if (f.lik == PV_LIK_GAUSSIAN) W8_PICK(false, PV_LIK_GAUSSIAN);
+    else if (f.lik == PV_LIK_POISSON_LOG) W8_PICK(false, PV_LIK_POISSON_LOG);
     else W8_PICK(false, PV_LIK_CBERNOULLI);
   }
 #undef W8_PICK

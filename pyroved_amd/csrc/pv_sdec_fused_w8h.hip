@@ -701,6 +701,7 @@ int pv_sdec_fused_w8h_launch(const PvFused& f_in, int grid, bool ds, hipStream_t
   const void* fn = nullptr;
 #define H8_PICK(L) fn = ds ? reinterpret_cast<const void*>(&pv_sdec_w8h_kernel<L, true>) \
                            : reinterpret_cast<const void*>(&pv_sdec_w8h_kernel<L, false>)
+  if (f.lik == PV_LIK_POISSON_LOG) return PV_EINVAL;             // (no Poisson instance of this dropped variant)
   if (f.lik == PV_LIK_BERNOULLI) H8_PICK(PV_LIK_BERNOULLI);
   else if (f.lik == PV_LIK_GAUSSIAN) H8_PICK(PV_LIK_GAUSSIAN);
   else H8_PICK(PV_LIK_CBERNOULLI);

@@ -680,6 +680,12 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
         locv = pr;
       } else if (LIK == PV_LIK_CBERNOULLI) {
         pv_cbern(a, xv, ll, dlda, locv);
+      } else if (LIK == PV_LIK_POISSON_LOG) {
+        const float ac = fminf(a, 30.0f);
+        const float rate = sd_exp(ac);
+        ll = xv * ac - rate;
+        dlda = a <= 30.0f ? rate - xv : 0.0f;
+        locv = rate;
       } else {
         const float pr = f.sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
         const float d = xv - pr;
@@ -959,6 +965,7 @@ int pv_sdec_fused_w8x3_launch(const PvFused& f_in, int grid, bool grads, hipStre
     // the TRAINING forms of this source measured no faster than pv_sdec_fused_bf16.hip's: they exist in
     // the experiments build only; the shipped library instantiates the forward-only forms (decode, evaluate)
 #ifdef PV_EXPERIMENTS
+    if (f.lik == PV_LIK_POISSON_LOG) return PV_EINVAL;           // (no Poisson instance of the dropped training forms)
     if (f.lik == PV_LIK_BERNOULLI) X3_PICK(true, PV_LIK_BERNOULLI);
     else if (f.lik == PV_LIK_GAUSSIAN) X3_PICK(true, PV_LIK_GAUSSIAN);
     else X3_PICK(true, PV_LIK_CBERNOULLI);
@@ -968,6 +975,7 @@ int pv_sdec_fused_w8x3_launch(const PvFused& f_in, int grid, bool grads, hipStre
   } else {
     if (f.lik == PV_LIK_BERNOULLI) X3_PICK(false, PV_LIK_BERNOULLI);
     else if (f.lik == PV_LIK_GAUSSIAN) X3_PICK(false, PV_LIK_GAUSSIAN);
+    else if (f.lik == PV_LIK_POISSON_LOG) X3_PICK(false, PV_LIK_POISSON_LOG);
     else X3_PICK(false, PV_LIK_CBERNOULLI);
   }
 #undef X3_PICK

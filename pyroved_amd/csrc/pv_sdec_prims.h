@@ -158,6 +158,14 @@ __device__ __forceinline__ void sd_pixel_lik(float a, float xv, float sig, int s
     locv = pr;
   } else if (LIK == PV_LIK_CBERNOULLI) {
     pv_cbern(a, xv, ll, dlda, locv);
+  } else if (LIK == PV_LIK_POISSON_LOG) {
+    // Poisson with a log link, a = the log-rate clamped at 30: one transcendental.  The data-only term lgamma(x + 1) is not
+    // computed here (pv_poisson_lognorm adds its sum to the step's scalars)
+    const float ac = fminf(a, 30.0f);
+    const float rate = sd_exp(ac);
+    ll = xv * ac - rate;
+    dlda = a <= 30.0f ? rate - xv : 0.0f;
+    locv = rate;
   } else {
     const float pr = sigmoid_out ? sd_rcp(1.0f + sd_exp(-a)) : a;
     const float d = xv - pr;

@@ -40,6 +40,7 @@ struct VLayout {
   pvcs::WtPlan wtp; char* wt;                          // the step's tiled conv weights (both stacks, both orientations)
   float* head_wt;                                      // features2latent's weight re-indexed channels-last (null: GEMM path)
   char* fin_ws; int64_t fin_bytes;                     // every weight gradient's partials until the one finish launch
+  double* pl_part;                                     // Poisson plans: pv_poisson_lognorm's partial sums (at the very end)
   float* l2f_wt;                                       // latent2features' weight re-indexed channels-last (null: GEMM path)
   float* d1_wt;                                        // the 1-D decoder's weights tiled for its fused launches (pv_dec1d.hip; null: not that shape)
   int64_t F;                                           // flattened feature size C*S of the encoder output
@@ -52,8 +53,9 @@ bool valid_ved(const pv_ved_plan* p) {
   if (p->in_ch < 1 || p->out_ch < 1 || p->n_enc_ops < 1 || p->n_enc_ops > PV_MAX_OPS || p->n_dec_ops < 1 ||
       p->n_dec_ops > PV_MAX_OPS)
     return false;
-  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI) return false;
-  if (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out) return false;
+  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI && p->lik != PV_LIK_POISSON_LOG)
+    return false;
+  if (p->lik == PV_LIK_POISSON_LOG ? p->sigmoid_out != 0 : (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out)) return false;
   if (p->head.out_dim != 2 * p->z_dim || p->l2f.in_dim != p->z_dim) return false;
   if (p->kl_mode != PV_KL_SAMPLED && p->kl_mode != PV_KL_ANALYTIC) return false;
   return true;
@@ -131,6 +133,7 @@ bool vcarve(const pv_ved_plan* p, char* base, VLayout& L) {
   L.fin_bytes = pv_align_up(nd.wg_sum, 256);
   L.fin_ws = base ? base + c.off : nullptr;
   c.off += L.fin_bytes;
+  L.pl_part = p->lik == PV_LIK_POISSON_LOG ? reinterpret_cast<double*>(c.take(2 * PV_POISSON_PARTS)) : nullptr;
   L.total = c.off;
   L.sc.wt = L.wt; L.sc.wtp = &L.wtp;
   return true;
@@ -254,8 +257,17 @@ extern "C" int pv_debug_ved_conv_trace(const pv_ved_plan* p, int64_t* out) {
   return 0;
 }
 
+static int ved_loss_and_grads_impl(const pv_ved_plan* p, int want_grads, void* stream);
 extern "C" int pv_ved_loss_and_grads(const pv_ved_plan* p, int want_grads, void* stream) {
   PV_RANGE("pv_ved_loss_and_grads");
+  PV_TRY(ved_loss_and_grads_impl(p, want_grads, stream));
+  // Poisson plans: the targets' normaliser into the finished scalars (pv_plan.hip: poisson_lognorm); the side streams have joined
+  if (p->lik != PV_LIK_POISSON_LOG) return 0;
+  VLayout L;
+  if (!vcarve(p, (char*)p->ws, L)) return PV_EINVAL;
+  return pv_poisson_lognorm(p->y, L.ds[p->n_dec_ops].elems(p->batch), L.pl_part, p->scalars, (hipStream_t)stream);
+}
+static int ved_loss_and_grads_impl(const pv_ved_plan* p, int want_grads, void* stream) {
   if (!valid_ved(p) || !p->params || !p->x || !p->y || !p->eps || !p->scalars || !p->ws) return PV_EINVAL;
   if (want_grads && !p->grads) return PV_EINVAL;
   VLayout L;
@@ -398,7 +410,8 @@ extern "C" int pv_ved_decode(const pv_ved_plan* p, const float* z, float* loc, v
   const int64_t OUT = od.elems(B), S = (int64_t)od.H * od.W;
   float* out = p->out_ch > 1 ? L.loc_nsc : loc;
   // the output non-linearity only (no likelihood): reuse lik_elem's `loc` output
-  PV_TRY(pv_lik_elem(L.da[p->n_dec_ops], L.da[p->n_dec_ops], OUT, PV_LIK_GAUSSIAN, p->sigmoid_out, 1.0f, out, nullptr,
+  PV_TRY(pv_lik_elem(L.da[p->n_dec_ops], L.da[p->n_dec_ops], OUT, p->lik == PV_LIK_POISSON_LOG ? PV_LIK_POISSON_LOG : PV_LIK_GAUSSIAN,
+                     p->sigmoid_out, 1.0f, out, nullptr,
                      nullptr, s));
   if (p->out_ch > 1) PV_TRY(pv_nsc_to_ncs(L.loc_nsc, loc, B, p->out_ch, S, s));
   return 0;

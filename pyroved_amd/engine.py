@@ -141,8 +141,10 @@ class IVAEEngine:
             if len(_linears(dec.fc_layers)) > _abi.PV_MAX_LAYERS:
                 raise UnsupportedModel("more than %d hidden layers" % _abi.PV_MAX_LAYERS)
             name = m.sampler_d.name
-            if name not in _abi.LIK or (name != "gaussian" and not dec.sigmoid_out):
+            if name not in _abi.LIK or (name not in ("gaussian", "poisson_log") and not dec.sigmoid_out):
                 raise UnsupportedModel("decoder sampler %r / sigmoid_d combination is not implemented" % name)
+            if name == "poisson_log" and dec.sigmoid_out:
+                raise UnsupportedModel("poisson_log likelihood needs sigmoid_d=False (the decoder's output is the log-rate)")
             if (m.coord > 0) != isinstance(dec, sDecoderNet):
                 raise UnsupportedModel("invariant models need the spatial decoder, vanilla models fcDecoderNet")
             return
@@ -161,6 +163,8 @@ class IVAEEngine:
             raise UnsupportedModel("decoder sampler %r is not implemented in the HIP path yet" % name)
         if name in ("bernoulli", "continuous_bernoulli") and not dec.sigmoid_out:
             raise UnsupportedModel("%s likelihood needs sigmoid_d=True" % name)
+        if name == "poisson_log" and dec.sigmoid_out:
+            raise UnsupportedModel("poisson_log likelihood needs sigmoid_d=False (the decoder's output is the log-rate)")
         if len(_linears(dec.fc_layers)) > _abi.PV_MAX_LAYERS:
             raise UnsupportedModel("more than %d hidden layers" % _abi.PV_MAX_LAYERS)
 
@@ -726,6 +730,10 @@ class IVAEEngine:
             zc = torch.cat([zc, y], -1)
         return m.decoder(xc, zc)
 
+    def _torch_loc(self, out):
+        """The mean image from a user-defined decoder's output: the output itself, except for 'poisson_log' (the rate)."""
+        return torch.exp(out.clamp(max=30)) if self.model.sampler_d.name == "poisson_log" else out
+
     def _torch_likelihood(self, loc):
         import torch.distributions as td
         s = self.model.sampler_d
@@ -733,6 +741,8 @@ class IVAEEngine:
             return td.Bernoulli(loc, validate_args=False)
         if s.name == "continuous_bernoulli":
             return td.ContinuousBernoulli(loc)
+        if s.name == "poisson_log":
+            return td.Poisson(torch.exp(loc.clamp(max=30)), validate_args=False)
         return td.Normal(loc, s.decoder_sig)
 
     def _loss_and_grads_ext_decoder(self, x, eps, beta, y, want_grads, scalars_out, z_out, loc_out):
@@ -765,7 +775,7 @@ class IVAEEngine:
                 loc = self._torch_decode(zt, y)
                 ll = self._torch_likelihood(loc.reshape(b, -1)).log_prob(x).sum()
             if loc_out is not None:
-                loc_out.copy_(loc.detach().reshape(loc_out.shape))
+                loc_out.copy_(self._torch_loc(loc.detach()).reshape(loc_out.shape))
             dz = None
             if want_grads:
                 for q in self._enc_params:
@@ -868,7 +878,7 @@ class IVAEEngine:
         if self.ext_dec:
             with torch.no_grad():
                 loc = self._torch_decode(z.to(self.device, torch.float32), None, angle, shift, scale)
-            return loc.reshape(z.shape[0], *self.model.data_dim)
+            return self._torch_loc(loc).reshape(z.shape[0], *self.model.data_dim)
         b = z.shape[0]
         p = self._plan(b, what=3)
         lat_in = (p.latent_dim if p.coord_dim > 0 else p.z_dim) + p.c_dim + self.K

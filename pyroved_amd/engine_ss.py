@@ -33,6 +33,11 @@ class SSEngine(IVAEEngine):
         # its output enters the HIP steps, dloss/d(output) comes back and torch.autograd carries it into the module
         self.ext_y = not isinstance(net, (fcClassifierNet, fcRegressorNet))
         super()._check_model()
+        if m.sampler_d.name == "poisson_log":
+            # the per-image outputs of these models (row_elbo, row_w, dy) would need the per-image normaliser lgamma(x + 1),
+            # which the HIP path applies to the summed scalars only (include/pyroved_amd.h: PV_LIK_POISSON_LOG)
+            raise UnsupportedModel("the poisson_log likelihood is not implemented for the semi-supervised models: their "
+                                   "per-image ELBO terms need the per-image normaliser sum lgamma(x + 1)")
         if self.ext_enc or self.ext_dec:
             raise UnsupportedModel("user-defined encoder_z / decoder are not combined with the semi-supervised models here")
         self.task = "classification" if hasattr(m, "num_classes") else "regression"

@@ -41,6 +41,8 @@ class VEDEngine(IVAEEngine):
             raise UnsupportedModel("decoder sampler %r is not implemented in the HIP path yet" % name)
         if name in ("bernoulli", "continuous_bernoulli") and not dec.sigmoid_out:
             raise UnsupportedModel("%s likelihood needs sigmoid_d=True" % name)
+        if name == "poisson_log" and dec.sigmoid_out:
+            raise UnsupportedModel("poisson_log likelihood needs sigmoid_d=False (the decoder's output is the log-rate)")
         self._ops(enc.feature_extractor.layers, enc.feature_extractor.activation)      # validates
         self._ops(dec.upsampler.layers, dec.upsampler.activation)
 

@@ -37,6 +37,8 @@ def _likelihood(m, dist, loc):
         return dist.Bernoulli(loc, validate_args=False)
     if name == "continuous_bernoulli":
         return dist.ContinuousBernoulli(loc)
+    if name == "poisson_log":
+        return dist.Poisson(torch.exp(loc.clamp(max=30)), validate_args=False)
     return dist.Normal(loc, m.sampler_d.decoder_sig)
 
 

@@ -43,7 +43,8 @@ class iVAE(baseVAE):
         c_dim: "feature dimension" of the class vector for class-conditioned VAEs
         hidden_dim_e / hidden_dim_d: hidden layer widths of encoder / decoder (default [128, 128])
         activation: 'tanh' (default), 'lrelu', 'softplus', 'relu', 'gelu'
-        sampler_d: 'bernoulli' (default), 'continuous_bernoulli', 'gaussian'
+        sampler_d: 'bernoulli' (default), 'continuous_bernoulli', 'gaussian', or 'poisson_log' for count data: a Poisson
+            whose log-rate is the decoder's output (needs sigmoid_d=False; decode / manifold2d return the rate)
         sigmoid_d: sigmoid at the decoder output (default True)
         seed: seed used in torch.manual_seed(seed)
 

@@ -33,6 +33,7 @@ class jiVAE(baseVAE):
         discrete_dim: number of classes of the discrete latent
         invariances: e.g. ['r'], ['r', 't'], ['r', 't', 's'], ['t'] (1D)
         hidden_dim_e / hidden_dim_d, activation, sampler_d, sigmoid_d, seed: as in models.iVAE
+            (sampler_d='poisson_log' with sigmoid_d=False included)
 
     Keyword Args:
         device, dx_prior, dy_prior, sc_prior, decoder_sig — as in the reference.

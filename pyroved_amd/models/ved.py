@@ -27,7 +27,8 @@ class VED(baseVAE):
         hidden_dim_d: decoder conv filters per block (default [(128, 128), (64, 64), (32,)])
         activation: 'lrelu' (default), 'tanh', 'softplus', 'relu'
         batchnorm: batch normalisation after every conv activation (default False; op PV_OP_BATCHNORM of the HIP conv stack)
-        sampler_d: 'bernoulli' (default) or 'gaussian'
+        sampler_d: 'bernoulli' (default), 'gaussian', or 'poisson_log' for a target of counts (a Poisson whose log-rate
+            is the decoder's output; needs sigmoid_d=False; decode returns the rate)
         sigmoid_d: sigmoid at the decoder output (default True)
         seed: seed used in torch.manual_seed(seed)
     """
