@@ -305,6 +305,12 @@ int pv_experiments_build(void);
  *   from element to element, averages out of the sum over every pixel of every sample and stays in its own tensor (5 ... 8e-5;
  *   DESIGN.md section 4.3). */
 #define PV_PLAN_CONV_X3        64
+/* PV_PLAN_GENERIC_TILE_LOOP (pv_ivae_plan): the training launch that hosts the guide and owns one image per workgroup (fused == 3,
+ *   batch == decoder grid, see PV_PLAN_NO_ENC_FOLD) keeps the generic tile loop of the 8-wave decoder kernel.  By default, an image of
+ *   8 n or 8 n + 1 units of 16 pixels (n >= 1; 28 x 28 is 49) with two coordinates and no per-sample weights runs a loop
+ *   specialised for full tiles: no unit-position bookkeeping, activity masks or run-time k-step count.  Same arithmetic in the same
+ *   order: results are bit-identical either way (the switch is for A/B runs and the parity test).  No reference counterpart. */
+#define PV_PLAN_GENERIC_TILE_LOOP 128
 
 /* Bytes of workspace pv_ivae_* calls need for this plan (depends on batch, n_pix,
  * layer widths).  Returns < 0 on an unsupported plan. */

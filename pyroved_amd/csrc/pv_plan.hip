@@ -998,7 +998,8 @@ void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) 
   }
   if (st.own_chain()) {
     PvEncFold& ef = st.ef;
-    ef.chain = 1; ef.dhead = L.dhead; ef.ldh = (int)plan_head_w(p); ef.edp0 = L.edp[0]; ef.edp1 = L.edp[1]; ef.llb = L.llb;
+    ef.chain = 1 | ((p->flags & PV_PLAN_GENERIC_TILE_LOOP) ? PV_CHAIN_GENERIC_LOOP : 0);
+    ef.dhead = L.dhead; ef.ldh = (int)plan_head_w(p); ef.edp0 = L.edp[0]; ef.edp1 = L.edp[1]; ef.llb = L.llb;
   }
 }
 

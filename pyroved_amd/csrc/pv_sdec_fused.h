@@ -83,8 +83,12 @@ struct PvEncFold {
   // has no per-sample work left (pv_elementwise.hip: pv_rec_wgrad_kernel).  Needs head.out_dim <= 16.  A training launch with chain
   // set writes NO per-row outputs (PvFused::llrow / rowtp stay untouched, part_hz and all but the image's first part_rs slot too):
   // the row sums are formed on chip and consumed here.  The plan asks for it only where nothing else reads rows (pv_plan.hip).
+  // Bit 0 asks for the chain; bit 1 (PV_CHAIN_GENERIC_LOOP, from PV_PLAN_GENERIC_TILE_LOOP) is read by the 8-wave launcher alone: the
+  // image-owning training launch keeps the generic tile loop where it would take the full-tile one (pv_sdec_fused_w8.hip, build 4 —
+  // same results bit for bit; an A/B and test switch).  The kernels test chain != 0.
+#define PV_CHAIN_GENERIC_LOOP 2
   int chain;
-  float* dhead; int ldh;           // (B, ldh) dL/d[mu | softplus input]
+  float* dhead; int ldh;          // (B, ldh) dL/d[mu | softplus input]
   float* edp0; float* edp1;        // (B, 128) dL/dpre of the two hidden layers
   float* llb;                      // (B) the image's log-likelihood
   // (round 6, fourth cut) coop != 0 (with chain, grid == 256): the guide's first layer is shared among the 32 workgroups of a group

@@ -90,6 +90,13 @@ __device__ __forceinline__ float w8_sum_q(float v) {
   return pv_sum_rows(v);                             // (pv_common.h: v_permlane16/32_swap, the bits of the two shfl_xor sums)
 }
 
+// sd_glds4 from a wave-uniform base + a 32-bit lane byte offset (the full-tile loop: the base is a scalar pair, no 64-bit lane address)
+__device__ __forceinline__ void w8_glds4_s(const __attribute__((address_space(1))) void* sbase, unsigned voff, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+
 // timing ablations (profiling builds only, results are WRONG; profiles/r03e_w8_ablations.txt): -DW8_ABL=1 the forward loops
 // read every second weight group from LDS and use it twice, 2 the same in the dgrad loops, 4 the wgrad consume reads every
 // second k-step, 8 no dW1 / dW2 record stores
@@ -282,6 +289,68 @@ __device__ __forceinline__ void w8_wgrad_consume(const __bf16* sa, const __bf16*
     la0 += 2 * ROW16; la1 += 2 * ROW16; lb += 2 * ROW16;
   }
 }
+// The full-tile loop forms the lane's two staging offsets ONCE per half tile (W8Stage: six sd_stage_store and four sd_stage_toff per
+// tile each redo theirs behind an opaque zero of their own — ~60 VALU instructions, ten of them quarter-rate multiplies): `se` the
+// element offset of the lane's staged row 16 wave + r (sd_stage_store), `to` its transposing-read offset (sd_stage_toff).  Two short
+// live ranges (d(wo) sums .. round-1 consume, dpre0 sums .. round-2 consume), none across the dgrad phases.  Same addresses.
+struct W8Stage { int se, to; };
+__device__ __forceinline__ W8Stage w8_stage_offs(int wave, int r, int q) {
+  r |= sd_opaque0();
+  W8Stage s;
+  s.se = (16 * wave + r) * LDS2 + 4 * (q ^ ((r >> 2) & 3));
+  s.to = sd_stage_toff(r, q);
+  return s;
+}
+__device__ __forceinline__ void w8_stage_store_at(__bf16* __restrict__ sh, const bf16x4 (&h)[8], int se) {
+#pragma unroll
+  for (int jb = 0; jb < 8; ++jb) *reinterpret_cast<bf16x4*>(sh + se + 16 * jb) = h[jb];
+}
+// w8_colsum_mfma at those offsets
+__device__ __forceinline__ void w8_colsum_mfma_at(__bf16* __restrict__ sc, const bf16x4 (&t)[8], const bf16x4& bop, f32x4 (&accS)[8],
+                                                  int wave, const W8Stage& st) {
+  w8_stage_store_at(sc, t, st.se);
+  sd_wait_lgkm0();
+  const __bf16* base = sc + (16 * wave) * LDS2 + st.to;
+  bf16x4 a[8];
+#pragma unroll
+  for (int jb = 0; jb < 8; ++jb) a[jb] = sd_tr(base + 16 * jb);
+#pragma unroll
+  for (int jb = 0; jb < 8; ++jb) accS[jb] = sd_mfma16(a[jb], bop, accS[jb]);
+}
+// w8_wgrad_consume with a compile-time k-step count (the full-tile loop: all 128 rows staged, KS = 4) and the lane's
+// transposing-read offset from the caller (W8Stage::to): unrolled, every read of every k-step is one of the same three bases + an
+// immediate (the largest, 3 * 2 ROW16 + ROW16 + 96 = 32,352, fits the ds_read offset field) — no loop branch, no address
+// increments.  Same reads, same MFMAs in the same order as w8_wgrad_consume(.., KS): the same bits.
+template <int KS>
+__device__ __forceinline__ void w8_wgrad_consume_k(const __bf16* sa, const __bf16* sb, f32x4 (&accW)[2][4], f32x4& accB,
+                                                   int wave, int toff) {
+  const int jp = wave >> 1, kh = wave & 1;
+  const short one = 0x3f80;                           // bf16 1.0
+  const short8_ ones_s = {one, one, one, one, one, one, one, one};
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_s);
+  unsigned la0 = (unsigned)(size_t)sa + 2u * (unsigned)(toff + 32 * jp + 16 * kh);
+  unsigned la1 = (unsigned)(size_t)sa + 2u * (unsigned)(toff + 32 * jp + 16 * (1 ^ kh));
+  unsigned lb = (unsigned)(size_t)sb + 2u * (unsigned)(toff + 64 * kh);
+  asm volatile("" : "+v"(la0), "+v"(la1), "+v"(lb));
+  constexpr unsigned ROW16 = 2u * 16 * LDS2;         // bytes of 16 staged rows
+  static_assert((2 * KS - 1) * ROW16 + 96 + 8 <= 65535, "every read of the unrolled consume is base + immediate");
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const unsigned k0 = 2u * ROW16 * ks;
+    bf16x8 a[2], b[4];
+    a[0] = sd_cat(sd_tr_at(la0 + k0), sd_tr_at(la0 + k0 + ROW16));
+    a[1] = sd_cat(sd_tr_at(la1 + k0), sd_tr_at(la1 + k0 + ROW16));
+#pragma unroll
+    for (int o = 0; o < 4; ++o) b[o] = sd_cat(sd_tr_at(lb + k0 + 32u * o), sd_tr_at(lb + k0 + 32u * o + ROW16));
+    W8_FENCE();
+    accB = MFMA32(a[0], ones, accB);
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int s_ = 0; s_ < 2; ++s_) accW[s_][o] = MFMA32(a[s_], b[o], accW[s_][o]);
+    W8_FENCE();
+  }
+}
 
 // wave-local column sums on the matrix cores: accS[jb][.] (D[j][n]) += sum over the unit's 16 rows of t[row][j] * Bn[row][n].
 // The wave stages its bf16 tile `t` in its own rows of `sc` (nobody else reads them at this point of the tile), reads it
@@ -416,9 +485,14 @@ extern "C" int pv_debug_coop_late_count(unsigned* out) {
 // of its own: compiled into the FOLD build, the chain's registers cost the launch 2 us even when it is switched off; 3 = 2 + the
 // guide's first layer shared among the 32 workgroups of a group (PvEncFold::coop, below; experiments build: measured SLOWER —
 // 86.7 vs 85.0 us, the hand-off's 7 k cycles cost what the smaller L2 stream saves: profiles/r06k_coop_first_layer.txt)
+// 4 = 2 with the FULL-TILE loop (training launches only): the image has 8 n or 8 n + 1 units (n >= 1), no per-sample weights, two
+// coordinates, hz pre-scaled — what the launcher checks (w8_full_tile_ok).  Every tile then has eight active waves, wave w's unit of
+// tile t is u_lo + 8 t + w, and the loop carries no unit position, no activity masks, no run-time k-step count and no cd / hz_scale
+// branches; the arithmetic and its order are build 2's (bit-identical results).  A build of its own, not a wave-uniform branch.
 template <bool GRADS, int LIK, int FOLDK>
 __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEncFold e) {
-  constexpr bool FOLD = FOLDK != 0, CHAIN = FOLDK >= 2, COOP = FOLDK == 3;
+  constexpr bool FOLD = FOLDK != 0, CHAIN = FOLDK >= 2, COOP = FOLDK == 3, FULL = FOLDK == 4;
+  static_assert(!FULL || (GRADS && W8_OWN_SUMS && W8_TAIL), "the full-tile loop is the image-owning training build's");
   // OWN: the workgroup owns its image's five row sums {ll, d(phi), d(scale), d(tx), d(ty)} — the chain build of a training launch
   // (the launcher selects it only with part_rs, dhz_out and dzc_out set: ONE image per workgroup, its latent backward in the epilogue).
   // Nothing outside the workgroup reads a per-row value then: no llrow / rowtp stores, no row-local coordinate backward; the four
@@ -796,7 +870,14 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   unsigned long long u_llrow = 0, u_loc, u_rowtp = 0, u_part_hz = 0;
   int64_t a_M = 0;
   // (real copies: an in-place "+s" keeps the value inside the tuple's registers, and the tuple is still spilled as a whole)
-  if constexpr (OWN) {                                            // (no rows of ll / transform gradients, no dL/d(hz) slots: loc alone)
+  unsigned long long u_x = 0, u_grid = 0;                         // FULL: the image's observations and the grid
+  if constexpr (FULL) {
+    // (the full-tile loop counts the image's units from 0: the image's offset is in the two row pointers, once)
+    const int64_t r0 = (int64_t)g * f.N;
+    asm volatile("s_mov_b64 %0, %3\n\ts_mov_b64 %1, %4\n\ts_mov_b64 %2, %5"
+                 : "=&s"(u_loc), "=&s"(u_x), "=&s"(u_grid)
+                 : "s"((unsigned long long)(f.loc ? f.loc + r0 : nullptr)), "s"((unsigned long long)(f.x + r0)), "s"((unsigned long long)f.grid));
+  } else if constexpr (OWN) {                                     // (no rows of ll / transform gradients, no dL/d(hz) slots: loc alone)
     asm volatile("s_mov_b64 %0, %1" : "=&s"(u_loc) : "s"((unsigned long long)f.loc));
   } else {
     asm volatile("s_mov_b64 %0, %5\n\ts_mov_b64 %1, %6\n\ts_mov_b64 %2, %7\n\ts_mov_b64 %3, %8\n\ts_mov_b64 %4, %9"
@@ -837,7 +918,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
 
   // units are 32-bit here (the launcher falls back to the 4-wave kernel beyond 2^31 rows), and a unit's sample b / offset
   // inside the sample / observation unit are carried incrementally from tile to tile: no integer division in the loop
-  const int u_lo = (int)((int64_t)g * f.units / G), u_hi = (int)((int64_t)(g + 1) * f.units / G);
+  // (FULL: one image per workgroup, its units counted from 0 — u_x / u_loc point at the image's rows)
+  const int u_lo = FULL ? 0 : (int)((int64_t)g * f.units / G), u_hi = FULL ? upb : (int)((int64_t)(g + 1) * f.units / G);
   const int xun = (int)f.x_units;
   struct Pos { int unit, b, loc, xu; };                 // unit = b * upb + loc ; xu = unit mod x_units (x_units > 0)
   auto pos_of = [&](int unit_) {
@@ -855,14 +937,17 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   const bool has_tail = W8_TAIL && ((u_hi - u_lo) & (W8_WAVES - 1)) == 1;
   const int u_end = has_tail ? u_hi - 1 : u_hi;
   const Pos pos_lo = pos_of(has_tail ? u_end : u_lo);   // what an out-of-range wave fetches instead (valid; unused without a tail)
-  Pos pos_cur = pos_of(u_lo + wave < u_end ? u_lo + wave : (has_tail ? u_end : u_lo));
+  // (FULL: at least one full tile — wave w starts on unit u_lo + w of image g; nothing below carries a position from tile to tile)
+  Pos pos_cur = FULL ? Pos{wave, g, wave, g * upb + wave} : pos_of(u_lo + wave < u_end ? u_lo + wave : (has_tail ? u_end : u_lo));
   Pos pos_nx = pos_cur;
   float sw_next = 1.0f;
   auto x_of = [&](const Pos& p_) -> float {
     if (f.sw) sw_next = f.sw[p_.b];
     return f.x[(int64_t)p_.xu * FD_UNIT + r];
   };
-  float xv_next = x_of(pos_cur);
+  float xv_next = 0.0f;
+  if constexpr (FULL) xv_next = ((const gfloat*)u_x + wave * FD_UNIT)[r];      // (no per-sample weight: sw_next stays the constant 1)
+  else xv_next = x_of(pos_cur);
   float* chz = reinterpret_cast<float*>(smb + WO_CHZ) + wave * FD_H;
   float* ctp = reinterpret_cast<float*>(smb + WO_CTP) + wave * 64;
   float* cgr = reinterpret_cast<float*>(smb + WO_CGR) + wave * 64;
@@ -884,10 +969,17 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     (void)tile_no;                      // (used by the -DW8_TRACE stamps only)
     asm volatile("; W8_TILE_BEGIN");
     W8_STAMP(0);
-    const int nact = (u_end - ut) < W8_WAVES ? (u_end - ut) : W8_WAVES;
+    const int nact = FULL ? W8_WAVES : ((u_end - ut) < W8_WAVES ? (u_end - ut) : W8_WAVES);
     // the unit this wave fetches for the NEXT tile
-    if (ut + W8_WAVES + wave < u_end) advance(pos_nx, W8_WAVES);
-    else pos_nx = pos_lo;
+    // (FULL: its own unit of the next tile, or — behind the last tile — the tail unit, which every wave takes part in; without a
+    //  tail the image's first unit: valid and unused.  Scalar values: the addresses below are a scalar base + a lane offset)
+    int unit_nx = 0;
+    if constexpr (FULL) {
+      unit_nx = ut + W8_WAVES < u_end ? ut + W8_WAVES + wave : (has_tail ? u_end : 0);
+    } else {
+      if (ut + W8_WAVES + wave < u_end) advance(pos_nx, W8_WAVES);
+      else pos_nx = pos_lo;
+    }
     int opq = 0;
     asm volatile("" : "+v"(opq));       // a zero the compiler cannot see through, OR-ed into the lane id: every lane-dependent
     const int lane = lane0 | opq, r = lane & 15, q = lane >> 4;   // address below is then recomputed per tile (one or two
@@ -896,8 +988,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     const float* wos = vec;
     const float* b1s = vec + FD_H;
     const float* b2s = vec + 2 * FD_H;
-    const bool act = wave < nact;
-    const int unit = act ? pos_cur.unit : ut;
+    const bool act = FULL || wave < nact;
+    const int unit = FULL ? ut + wave : (act ? pos_cur.unit : ut);
     const int bu = pos_cur.b;
     const int64_t row = (int64_t)unit * FD_UNIT + r;
     float x0, x1, u0c, u1c, sc;
@@ -905,7 +997,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     {
       const float* t = ctp;
       const float* gr = cgr;
-      if (f.cd == 2) {
+      if (FULL || f.cd == 2) {
         const float gx = gr[2 * r], gy = gr[2 * r + 1];
         u0c = gx * t[0] - gy * t[1];
         u1c = gx * t[1] + gy * t[0];
@@ -952,7 +1044,7 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       }
       if (GRADS && q == 0) { inf_x0[r] = x0; inf_x1[r] = x1; }
       W8_FENCE();
-      if (f.hz_scale == 0.0f) {                  // hz arrives unscaled only when the generic encoder path produced it
+      if (!FULL && f.hz_scale == 0.0f) {         // hz arrives unscaled only when the generic encoder path produced it
 #pragma unroll
         for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * SD_C;
       }
@@ -965,7 +1057,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     }
     asm volatile("; W8_P1_coord_done");
     W8_STAMP(1);
-    fetch_unit_inputs(pos_nx, false);          // the slots were consumed by the coordinate layer above
+    // the slots were consumed by the coordinate layer above
+    if constexpr (FULL) w8_glds4_s((const gfloat*)u_grid + unit_nx * (2 * FD_UNIT), 4u * (unsigned)(lane & 31), lds0 + WO_CGR + wave * 256);
+    else fetch_unit_inputs(pos_nx, false);
     {
       w8_layer_fwd(W1h, b1s, h0b, tC, wad, q);
       sd_tanh8<W8_FENCE_MASK>(tC);
@@ -990,22 +1084,27 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       const float a = w8_sum_q((part4[0] + part4[1]) + (part4[2] + part4[3])) + bo;
       float ll, locv;
       sd_pixel_lik<LIK>(a, xv, f.sig, f.sigmoid_out, ll, dlda, locv);
-      dlda *= act ? swv : 0.0f;
+      if constexpr (!FULL) dlda *= act ? swv : 0.0f;             // (FULL: every wave active, no per-sample weight)
       if (q == 0) {
-        if (act) {
+        if constexpr (FULL) {
+          llacc += ll;
+          if (a_loc) (a_loc + unit * FD_UNIT)[r] = locv;
+        } else if (act) {
           if constexpr (OWN) llacc += ll;
           else if (a_llrow) a_llrow[row] = ll;
           if (a_loc) a_loc[row] = locv;
         }
         if (GRADS) { dbo += dlda; inf_dl[r] = dlda; }
       }
-      xv_next = x_of(pos_nx);
+      if constexpr (FULL) xv_next = ((const gfloat*)u_x + unit_nx * FD_UNIT)[r];
+      else xv_next = x_of(pos_nx);
     }
-    pos_cur = pos_nx;                          // (unit, bu, row of THIS tile were taken above)
+    if constexpr (!FULL) pos_cur = pos_nx;     // (unit, bu, row of THIS tile were taken above)
     asm volatile("; W8_P3_fwd_done");
     W8_STAMP(3);
     if (!GRADS) continue;
     const int ksteps = (nact + 1) >> 1;
+    W8Stage stg{};                              // (FULL: the lane's staging offsets of this half tile)
     {
       // ---- d(wo) += sum_rows dlda h2 : wave-local MFMA through the wave's own rows of staging A (free: every wave
       // passed barrier 4 of the previous tile); B = dlda of rows 4q..4q+3 in columns 3 (hi) and 4 (lo)
@@ -1018,7 +1117,8 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         fb_split(d4[i], hi, lo);
         bw[i] = r == 3 ? hi : (r == 4 ? lo : (__bf16)0.0f);
       }
-      w8_colsum_mfma(sA, pA, bw, accS, wave, r, q);
+      if constexpr (FULL) { stg = w8_stage_offs(wave, r, q); w8_colsum_mfma_at(sA, pA, bw, accS, wave, stg); }
+      else w8_colsum_mfma(sA, pA, bw, accS, wave, r, q);
       // dpre2 = dlda * wo (1 - h2^2)
 #pragma unroll
       for (int jb = 0; jb < 8; ++jb) tC[jb] = tC[jb] * dlda;
@@ -1027,12 +1127,13 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
     asm volatile("; W8_P4_dwo_done");
     W8_STAMP(4);
     // ---- wgrad of layer 2: stage (dpre2, h1) of all 128 rows, one pass ----
-    sd_stage_store(sA, pA, 16 * wave + r, q);
-    sd_stage_store(sB, h1b, 16 * wave + r, q);
+    if constexpr (FULL) { w8_stage_store_at(sA, pA, stg.se); w8_stage_store_at(sB, h1b, stg.se); }
+    else { sd_stage_store(sA, pA, 16 * wave + r, q); sd_stage_store(sB, h1b, 16 * wave + r, q); }
     __syncthreads();                                                // barrier 1
     asm volatile("; W8_P5_bar1");
     W8_STAMP(5);
-    w8_wgrad_consume(sA, sB, accW2, accB2, wave, r, q, ksteps);
+    if constexpr (FULL) w8_wgrad_consume_k<W8_WAVES / 2>(sA, sB, accW2, accB2, wave, stg.to);
+    else w8_wgrad_consume(sA, sB, accW2, accB2, wave, r, q, ksteps);
     asm volatile("; W8_P6_cons2");
     W8_STAMP(6);
     bf16x4 p0[8];
@@ -1088,18 +1189,20 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
         if (r == 3 || r == 4 || r > 6) v = (__bf16)0.0f;
         bc_[i] = v;
       }
-      w8_colsum_mfma(sA, p0, bc_, accS, wave, r, q);
+      if constexpr (FULL) { stg = w8_stage_offs(wave, r, q); w8_colsum_mfma_at(sA, p0, bc_, accS, wave, stg); }
+      else w8_colsum_mfma(sA, p0, bc_, accS, wave, r, q);
       sd_wait_lgkm0();                                              // (own reads done before the rows are re-staged)
     }
     asm volatile("; W8_P12_rowlocal");
     W8_STAMP(12);
     // ---- wgrad of layer 1: stage (C dpre1, h0) ----
-    sd_stage_store(sA, pA, 16 * wave + r, q);
-    sd_stage_store(sB, h0b, 16 * wave + r, q);
+    if constexpr (FULL) { w8_stage_store_at(sA, pA, stg.se); w8_stage_store_at(sB, h0b, stg.se); }
+    else { sd_stage_store(sA, pA, 16 * wave + r, q); sd_stage_store(sB, h0b, 16 * wave + r, q); }
     __syncthreads();                                                // barrier 3
     asm volatile("; W8_P10_bar3");
     W8_STAMP(10);
-    w8_wgrad_consume(sA, sB, accW1, accB1, wave, r, q, ksteps);
+    if constexpr (FULL) w8_wgrad_consume_k<W8_WAVES / 2>(sA, sB, accW1, accB1, wave, stg.to);
+    else w8_wgrad_consume(sA, sB, accW1, accB1, wave, r, q, ksteps);
     asm volatile("; W8_P11_cons1");
     W8_STAMP(11);
     __syncthreads();                                                // barrier 4: round 2 consumed everywhere
@@ -1112,7 +1215,9 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   if (has_tail) {
     // ================= column-parallel tail: ONE unit, eight waves (helpers above the kernel) =================
     asm volatile("; W8_TAIL_BEGIN");
-    const int lane = lane0, r = lane & 15, q = lane >> 4;
+    // (FULL: the lane id behind an opaque zero, as in the tile loop — the tail's lane addresses are formed here, not ahead of the loop
+    //  and carried through it)
+    const int lane = FULL ? (lane0 | sd_opaque0()) : lane0, r = lane & 15, q = lane >> 4;
     const float* wos = vec;
     const float* b1s = vec + FD_H;
     const float* b2s = vec + 2 * FD_H;
@@ -1638,6 +1743,22 @@ bool pv_sdec_fused_w8_fold_ok(const PvFused& f, int grid) {
   return ipw == 1 && f.units == (int64_t)f.B * (f.N / FD_UNIT);      // ONE image per workgroup: batch == grid
 }
 
+// the image-owning training launch takes the full-tile loop (build 4) when its promise holds (batch == grid, one image per
+// workgroup), the image is n >= 1 full tiles with or without the one-unit tail, and the loop's constants are the launch's: no
+// per-sample weights, two coordinates, hz pre-scaled by the hosted guide.  Everything else keeps the generic loop (build 2).
+// (Not the Gaussian likelihood: its full-tile build spills one register to scratch — vgpr_spill_count 1, 16 bytes — where its
+//  generic build has none, and a form that spills is not shipped.  Bernoulli and Poisson: no scratch in either build; continuous
+//  Bernoulli: 10 spilled registers where its generic build has 29.)
+#define W8_FULL_BUILD (W8_OWN_SUMS && W8_TAIL && !(W8_ABL & 4))
+static bool w8_full_tile_ok(const PvFused& f, int grid) {
+  const int upb = f.N / FD_UNIT;
+  return W8_FULL_BUILD && pv_sdec_fused_w8_fold_ok(f, grid) && upb >= W8_WAVES && (upb & (W8_WAVES - 1)) <= 1 && !f.sw && f.cd == 2 &&
+         f.hz_scale != 0.0f && f.lik != PV_LIK_GAUSSIAN;
+}
+// test / measurement hook (not in include/): the build (FOLDK) the last launch of this process that hosted a guide dispatched, -1: none yet
+static int w8_last_fold_build = -1;
+extern "C" int pv_debug_w8_last_fold_build(void) { return __atomic_load_n(&w8_last_fold_build, __ATOMIC_RELAXED); }
+
 int pv_sdec_fused_w8_launch(const PvFused& f_in, int grid, bool grads, hipStream_t s, const PvEncFold* fold) {
   PvFused f = f_in;
   static const int ablate = pv_exp_int("PV_FD_ABLATE", 0) & 1024;    // (experiments build: fp32 records, see the record stores)
@@ -1664,8 +1785,18 @@ int pv_sdec_fused_w8_launch(const PvFused& f_in, int grid, bool grads, hipStream
   //  pv_plan.hip sets them together wherever it asks for the chain)
   const bool chain = fold && e.chain;
   if (chain && grads && !(f.part_rs && f.dhz_out && f.dzc_out)) return PV_EINVAL;
+  // (PV_CHAIN_GENERIC_LOOP in PvEncFold::chain — PV_PLAN_GENERIC_TILE_LOOP — keeps build 2)
+  const bool full = chain && grads && !e.coop && !(e.chain & PV_CHAIN_GENERIC_LOOP) && w8_full_tile_ok(f, grid);
+#if W8_FULL_BUILD
+#define W8_FULL_ID 4
+#else
+#define W8_FULL_ID 2
+#endif
+  const int build = !fold ? 0 : (grads && chain) ? (e.coop ? W8_COOP_BUILD : (full ? W8_FULL_ID : 2)) : 1;
+  if (fold) __atomic_store_n(&w8_last_fold_build, build, __ATOMIC_RELAXED);
 #define W8_PICK(G, L) fn = !fold ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, 0>)                     \
                                : (G && chain && e.coop) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? W8_COOP_BUILD : 1>) \
+                               : (G && full) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? ((L) == PV_LIK_GAUSSIAN ? 2 : W8_FULL_ID) : 1>) \
                                : (G && chain) ? reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, G ? 2 : 1>) \
                                                 : reinterpret_cast<const void*>(&pv_sdec_w8_kernel<G, L, 1>)
   if (grads) {

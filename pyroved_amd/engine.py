@@ -75,6 +75,7 @@ class IVAEEngine:
     enc_per_image = True             # the guide of a training step as one workgroup per image (False: PV_PLAN_ENC_TILED, the tiled one-launch encoder)
     conv_x3 = False                  # PV_PLAN_CONV_X3 / conv_bf16 = 0: fp32-class kernel-3 convolutions with both operands as two fp16 pieces
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
+    full_tile_loop = True            # PV_PLAN_GENERIC_TILE_LOOP when False (the image-owning decoder launch keeps its generic tile loop; bit-identical)
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
     renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
@@ -434,6 +435,7 @@ class IVAEEngine:
                 (0 if getattr(self, "dec1d", True) else _abi.PV_PLAN_NO_DEC1D) |
                 (0 if getattr(self, "enc_fold", True) else _abi.PV_PLAN_NO_ENC_FOLD) |
                 (0 if getattr(self, "enc_per_image", True) else _abi.PV_PLAN_ENC_TILED) |
+                (0 if getattr(self, "full_tile_loop", True) else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
                 (_abi.PV_PLAN_CONV_X3 if getattr(self, "conv_x3", False) else 0))
 
     def ensure_bound(self):
