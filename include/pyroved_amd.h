@@ -70,6 +70,9 @@ enum pv_lik { PV_LIK_BERNOULLI = 0, PV_LIK_GAUSSIAN = 1, PV_LIK_CBERNOULLI = 2 /
 enum pv_kl_mode { PV_KL_SAMPLED = 0, PV_KL_ANALYTIC = 1 };
 
 #define PV_MAX_LAYERS 8
+/* Most channels per grid position a spatial decoder may emit (iVAE(..., channels=C)): `out.out_dim` of a plan with coord_dim > 0.
+ * Added in v17; no struct layout changes with it. */
+#define PV_MAX_CHANNELS 8
 
 /* One nn.Linear(+activation) of make_fc_layers (nets/fc.py:307-324).  Offsets are
  * in floats into the flat parameter buffer (and, identically, the flat gradient
@@ -115,7 +118,8 @@ typedef struct pv_op {
 typedef struct pv_ivae_plan {
   /* ---- problem ---- */
   int32_t batch;          /* B: samples in this (local) minibatch                         */
-  int32_t n_pix;          /* N = prod(data_dim)                                           */
+  int32_t n_pix;          /* N: observations per sample = positions * C, positions = prod(data_dim) and C the channels per
+                             position (spatial decoders: C = out.out_dim, n_pix % C == 0; C = 1: N = prod(data_dim) as ever) */
   int32_t coord_dim;      /* 0: vanilla VAE (fcDecoderNet); 1: 1-D grid; 2: 2-D grid      */
   int32_t z_dim;          /* latent_dim + coord (ivae.py:159)                             */
   int32_t latent_dim;     /* content latents (last entries of z)                          */
@@ -148,7 +152,10 @@ typedef struct pv_ivae_plan {
                                       out adjacently in the flat buffer                      */
   pv_layer fc_coord, fc_latent;    /* coord_latent (fc.py:216-217); unused if coord_dim=0 */
   pv_layer dec[PV_MAX_LAYERS];
-  pv_layer out;                    /* decoder.out (fc.py:186 / fc.py:140)                 */
+  pv_layer out;                    /* decoder.out (fc.py:186 / fc.py:140).  coord_dim > 0: out_dim = C, the channels per grid
+                                      position, 1 .. PV_MAX_CHANNELS, weight (C, in_dim); C > 1 runs the layer-by-layer kernels
+                                      whatever `fused` asks for and is refused with discrete_dim, row_w / row_elbo / dy, a conv or
+                                      external encoder and an external decoder.  coord_dim == 0: out_dim = n_pix */
   /* ---- optional convolutional encoder: iVAE.set_encoder(convEncoderNet(data_dim, latent_dim=z_dim))
    * (models/base.py:173-177, nets/conv.py:24-64).  n_enc_ops > 0: `enc` / n_enc are ignored, the encoder is this
    * op sequence over x viewed as (B, 1, *enc_in_dim), and `head` is features2latent.fc_latent (in_dim = C *
@@ -163,10 +170,10 @@ typedef struct pv_ivae_plan {
   float*       adam_m;    /* flat first moments                                           */
   float*       adam_v;    /* flat second moments                                          */
   int64_t      n_params;
-  const float* x;         /* (B, N) observations                                          */
+  const float* x;         /* (B, N) observations; C > 1: channel-last, x[b][pos * C + c]  */
   const float* y;         /* (B, c_dim) or NULL                                           */
   const float* eps;       /* (B, z_dim) standard-normal draws of Normal.rsample           */
-  const float* grid;      /* (N, coord_dim) generate_grid(data_dim) (coord.py:21-44)      */
+  const float* grid;      /* (positions, coord_dim) generate_grid(data_dim) (coord.py:21-44) */
   void*        ws;        /* workspace, >= pv_ivae_workspace_bytes(plan) bytes            */
   int64_t      ws_bytes;
   float*       scalars;   /* out, 4 floats: loss, sum log p(x|z), beta*sum log p(z), beta*sum log q(z|x); loss = -([1] + [2] - [3]).
@@ -175,7 +182,7 @@ typedef struct pv_ivae_plan {
                              so that [3] - [2] = beta * KL and the relation above holds unchanged */
   float*       z_loc;     /* out (B, z_dim), may be NULL                                  */
   float*       z_scale;   /* out (B, z_dim), may be NULL                                  */
-  float*       loc;       /* out (B, N) decoder output, may be NULL ((K*B, N) for jiVAE)  */
+  float*       loc;       /* out (B, N) decoder output, may be NULL ((K*B, N) for jiVAE); channel-last like x */
   float*       alpha;     /* out (B, discrete_dim) class probabilities q(k|x), may be NULL */
   /* ---- external encoder: a user-supplied encoder_z (iVAE.set_encoder(any nn.Module), models/base.py:173-177) runs
    * in the caller's framework.  ext_encoder != 0: the library does not run an encoder; ext_head (B, 2*z_dim) holds

@@ -20,6 +20,7 @@ PV_PLAN_CONV_X3 = 64
 PV_PLAN_ENC_TILED = 32
 PV_PLAN_GENERIC_TILE_LOOP = 128
 PV_MAX_LAYERS = 8
+PV_MAX_CHANNELS = 8         # channels per grid position of a spatial decoder (pv_ivae_plan.out.out_dim)
 
 # enum pv_act / pv_lik (include/pyroved_amd.h)
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2, "lrelu": 3, "softplus": 4, "gelu": 5, "sigmoid": 6}

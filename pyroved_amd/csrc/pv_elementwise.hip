@@ -428,6 +428,127 @@ int pv_out_lik(const PvOutLik& p, hipStream_t s) {
   return 0;
 }
 
+// out_lik_mc: the C-output sibling of out_lik (iVAE(..., channels = C), C = 2 .. PV_MAX_CHANNELS): a_c = h . Wo[c] + bo[c] per row,
+// the likelihood per value, ll of the row and dpre summed over c in ascending order.  Same geometry (one wave per row, lanes stride
+// the hidden width); C is a template parameter so that wo[C][..] / acc[C][..] stay in registers.  Lane c < C owns channel c of the
+// row: it reads x[row * C + c] (one coalesced read), evaluates the likelihood once and writes loc[row * C + c]; dL/da_c reaches the
+// other lanes through a read of lane c.  The waves' partials leave through the one red[] buffer, a channel at a time.
+//   part_dwo (blocks, C * H)   part_dbo (blocks, C)   x null: observations of 0 (forward-only decode)
+template <int C>
+__global__ __launch_bounds__(256) void pv_out_lik_mc_kernel(PvOutLik p) {
+  static_assert(C >= 2 && C <= PV_MAX_CHANNELS, "channels per row");
+  __shared__ float red[4][64 * OL_MAXJ];
+  __shared__ float redb[4][PV_MAX_CHANNELS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int H = p.H;
+  float wo[C][OL_MAXJ], acc[C][OL_MAXJ];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+#pragma unroll
+    for (int jj = 0; jj < OL_MAXJ; ++jj) {
+      const int j = lane + 64 * jj;
+      wo[c][jj] = j < H ? p.wo[c * H + j] : 0.0f;
+      acc[c][jj] = 0.0f;
+    }
+  }
+  const float bo = (p.bo && lane < C) ? p.bo[lane] : 0.0f;
+  float accb = 0.0f;                                  // lane c: sum over the wave's rows of dL/da_c
+  const int64_t rbeg = (int64_t)blockIdx.x * OL_ROWS + wave * (OL_ROWS / 4);
+  for (int i = 0; i < OL_ROWS / 4; ++i) {
+    const int64_t row = rbeg + i;
+    if (row >= p.M) break;
+    const float* hr = p.h + row * p.ldh;
+    float hv[OL_MAXJ];
+#pragma unroll
+    for (int jj = 0; jj < OL_MAXJ; ++jj) {
+      const int j = lane + 64 * jj;
+      hv[jj] = j < H ? hr[j] : 0.0f;
+    }
+    // (the lane index made opaque per row: hoisted out of the row loop, the C masks of `lane == c` would be scalar spills)
+    int lv = lane;
+    asm volatile("" : "+v"(lv));
+    float a = 0.0f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float dot = 0.0f;
+#pragma unroll
+      for (int jj = 0; jj < OL_MAXJ; ++jj) dot += hv[jj] * wo[c][jj];
+      dot = pv_wave_sum(dot);
+      if (lv == c) a = dot;
+    }
+    a += bo;
+    float ll = 0.0f, dlda = 0.0f, locv = 0.0f;
+    if (lane < C) {
+      const float x = p.x ? p.x[(p.xmod > 0 ? row % p.xmod : row) * C + lane] : 0.0f;
+      pv_lik_any(a, x, p.lik, p.sigmoid_out, p.sig, ll, dlda, locv);
+      if (p.loc) p.loc[row * C + lane] = locv;
+      if (p.sw) dlda *= p.sw[row / p.N];
+    }
+    if (p.llrow) {
+      float s = 0.0f;
+#pragma unroll
+      for (int c = 0; c < C; ++c) s += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ll), c));
+      if (lane == 0) p.llrow[row] = s;
+    }
+    if (p.dpre) {
+      float d[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) d[c] = __shfl(dlda, c);      // (vector registers: eight more scalars would spill)
+      float* dr = p.dpre + row * p.ldh;
+      const float* pr_ = p.hpre ? p.hpre + row * p.ldh : nullptr;
+#pragma unroll
+      for (int jj = 0; jj < OL_MAXJ; ++jj) {
+        const int j = lane + 64 * jj;
+        if (j < H) {
+          float g = 0.0f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            g += d[c] * wo[c][jj];
+            acc[c][jj] += d[c] * hv[jj];
+          }
+          dr[j] = g * pv_act_grad2(hv[jj], pr_ ? pr_[j] : 0.0f, p.act_last);
+        }
+      }
+      accb += dlda;
+    }
+  }
+  if (!p.dpre) return;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+#pragma unroll
+    for (int jj = 0; jj < OL_MAXJ; ++jj) red[wave][lane + 64 * jj] = acc[c][jj];
+    __syncthreads();
+    for (int j = threadIdx.x; j < H; j += 256)
+      p.part_dwo[((int64_t)blockIdx.x * C + c) * H + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+    __syncthreads();
+  }
+  if (lane < C) redb[wave][lane] = accb;
+  __syncthreads();
+  if (threadIdx.x < C)
+    p.part_dbo[(int64_t)blockIdx.x * C + threadIdx.x] =
+        (redb[0][threadIdx.x] + redb[1][threadIdx.x]) + (redb[2][threadIdx.x] + redb[3][threadIdx.x]);
+}
+
+template <int C> static void out_lik_mc_launch(const PvOutLik& p, hipStream_t s) {
+  hipLaunchKernelGGL(pv_out_lik_mc_kernel<C>, dim3((unsigned)pv_out_lik_blocks(p.M)), dim3(256), 0, s, p);
+}
+
+int pv_out_lik_mc(const PvOutLik& p, int C, hipStream_t s) {
+  if (p.H > 64 * OL_MAXJ || p.M <= 0) return PV_EINVAL;
+  switch (C) {
+    case 2: out_lik_mc_launch<2>(p, s); break;
+    case 3: out_lik_mc_launch<3>(p, s); break;
+    case 4: out_lik_mc_launch<4>(p, s); break;
+    case 5: out_lik_mc_launch<5>(p, s); break;
+    case 6: out_lik_mc_launch<6>(p, s); break;
+    case 7: out_lik_mc_launch<7>(p, s); break;
+    case 8: out_lik_mc_launch<8>(p, s); break;
+    default: return PV_EINVAL;                        // (C = 1 is pv_out_lik; a missing instance is an error)
+  }
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
 // per-sample sums: out[b] = sum_n v[b*N + n]; then scalars (one workgroup per sample, tree-ordered)
 __global__ __launch_bounds__(256) void pv_segsum_kernel(const float* __restrict__ v, int64_t N, float* __restrict__ out) {
   __shared__ float sm[4];

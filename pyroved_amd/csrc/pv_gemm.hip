@@ -279,6 +279,7 @@ int pv_gemm_pick_splits(int M, int N, int K) {
   // aim for >= ~512 workgroups (2 per CU) when the contraction is long enough to split; a split costs a
   // second (finish) launch, ~6 us on the stream, so short contractions are never split
   const int64_t tiles = (int64_t)((M + GT - 1) / GT) * ((N + GT - 1) / GT);
+  if (tiles <= 0) return 1;                              // (an empty problem — the decoder's zero rows in an encode-only layout — has nothing to split)
   static const int few_env = pv_exp_int("PV_GEMM_NO_FEWSPLIT", 0) ? 0 : 1;
   if (few_env && tiles < 64 && K >= 256 && K <= 1024) {
     // a handful of tiles over a medium contraction (a 256 x 787 -> 128 encoder layer: 8 workgroups walking 25 stages, 24 us):

@@ -66,6 +66,9 @@ struct PvOutLik {
   int64_t xmod;          // > 0: observations are x[row % xmod] (jiVAE: the K decoder passes score the same B*N pixels)
 };
 int pv_out_lik(const PvOutLik& p, hipStream_t s);
+// the same with C = 2 .. PV_MAX_CHANNELS outputs per row (a spatial decoder's channels): wo (C, H), bo (C), x and loc (M, C)
+// channel-last (x null: zeros), llrow (M) the row's sum over channels, part_dwo (blocks, C * H), part_dbo (blocks, C); xmod in rows
+int pv_out_lik_mc(const PvOutLik& p, int C, hipStream_t s);
 int64_t pv_out_lik_blocks(int64_t M);
 int pv_segsum(const float* v, int64_t nseg, int64_t N, float* out, hipStream_t s);
 // scalars[1] = sum_b llb; if kl_part: scalars[2] = beta*sum kl_part[2i], scalars[3] = beta*sum kl_part[2i+1];

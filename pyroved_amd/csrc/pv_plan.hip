@@ -81,6 +81,11 @@ static inline int plan_conv_mode(const pv_ivae_plan* p) {
   // round 5: the cheaper backward (pv_convstack.h mode 4) where the stack's gradient sums are long enough
   return pvcs::conv_mode_for(4, p->enc_ops, p->n_enc_ops, p->enc_ndim, p->batch, 1, p->enc_in_dim);
 }
+// Channels per grid position of a spatial decoder (iVAE(..., channels = C)): its output layer's width.  n_pix counts OBSERVATIONS
+// per sample, positions * C: the encoder's input, x / loc and the Poisson normaliser run over n_pix; the decoder's rows per sample,
+// the grid, the row chunks and the per-sample segment sums run over the positions.  Vanilla decoders: C = 1, positions = n_pix
+static inline int64_t plan_C(const pv_ivae_plan* p) { return p->coord_dim > 0 ? p->out.out_dim : 1; }
+static inline int64_t plan_pos(const pv_ivae_plan* p) { return p->n_pix / plan_C(p); }
 static inline int64_t plan_S(const pv_ivae_plan* p) { return (plan_K(p) > 0 ? plan_K(p) : 1) * (int64_t)p->batch; }
 // decoder samples of a training step: jiVAE's K per input or the multi-particle ELBO's P (never both)
 static inline int64_t step_S(const pv_ivae_plan* p, const Layout& L) { return plan_S(p) * L.P; }
@@ -119,7 +124,11 @@ bool valid_plan(const pv_ivae_plan* p) {
     if (p->row_w || p->row_elbo || p->dy) return false;             // (per-image outputs would need the per-image normaliser)
     if (p->fused == 2 && p->dec_kernel > 1) return false;           // (the fp16 builds: plan_sel)
   } else if (p->lik != PV_LIK_GAUSSIAN && !p->sigmoid_out) return false;   // probs outside (0,1): unsupported
-  if (p->coord_dim > 0 && p->out.out_dim != 1) return false;
+  if (p->coord_dim > 0 && (p->out.out_dim < 1 || p->out.out_dim > PV_MAX_CHANNELS || p->n_pix % p->out.out_dim != 0)) return false;
+  // several channels per position: the fc-encoder iVAE on the layer-by-layer kernels
+  if (p->coord_dim > 0 && p->out.out_dim > 1 &&
+      (p->discrete_dim > 0 || p->row_w || p->row_elbo || p->dy || p->n_enc_ops > 0 || p->ext_encoder || p->ext_decoder))
+    return false;
   if (p->coord_dim == 0 && p->out.out_dim != p->n_pix) return false;
   if (p->dec_kernel != 0 && !pv_sdec_fused_sel_valid(p->fused, p->dec_kernel)) return false;
   if (p->kl_mode != PV_KL_SAMPLED && p->kl_mode != PV_KL_ANALYTIC) return false;
@@ -136,7 +145,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   Carver c{base, 0};
   L.P = inference_only ? 1 : P;
   L.renyi = renyi && L.P > 1; L.r_alpha = 0.0f; L.r_wout = nullptr;
-  const int64_t B = p->batch, N = encode_only ? 0 : p->n_pix, z = p->z_dim;
+  // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
+  const int64_t B = p->batch, N = encode_only ? 0 : plan_pos(p), z = p->z_dim, Cn = plan_C(p);
   const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
   const bool multi = K > 0 || L.P > 1;              // several decoder samples per input
   L.rows = p->coord_dim > 0 ? S * N : S;
@@ -227,8 +237,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     L.logits = nullptr;
     L.llrow = c.take(R);
     const int64_t ob = pv_out_lik_blocks(R);
-    L.part_dwo = c.take(ob * p->out.in_dim);
-    L.part_dbo = c.take(ob);
+    L.part_dwo = c.take(ob * p->out.in_dim * Cn);
+    L.part_dbo = c.take(ob * Cn);
     // row chunks per sample for the coord_latent backward: >= ~1024 workgroups overall
     int nchunk = (int)((1024 + B - 1) / B);
     if (nchunk > (N + 31) / 32) nchunk = (int)((N + 31) / 32);
@@ -365,7 +375,7 @@ int encoder_fwd(const pv_ivae_plan* p, const Layout& L, hipStream_t s, const PvF
 int decoder_hidden_fwd(const pv_ivae_plan* p, const Layout& L, const float* zin, int64_t ldz, int64_t lat_in,
                        hipStream_t s) {
   const int64_t R = L.rows;
-  const int64_t B = p->coord_dim > 0 ? R / p->n_pix : R;       // decoder samples (jiVAE: K per input)
+  const int64_t B = p->coord_dim > 0 ? R / plan_pos(p) : R;    // decoder samples (jiVAE: K per input)
   const float* in;
   int64_t ldin;
   if (p->coord_dim > 0) {
@@ -376,7 +386,7 @@ int decoder_hidden_fwd(const pv_ivae_plan* p, const Layout& L, const float* zin,
                       PV_ACT_NONE, L.scratch, L.scratch_bytes, s));
     PvCoordLat c{};
     c.grid = p->grid; c.tp = L.tp; c.Wc = p->params + p->fc_coord.w_off; c.bc = p->params + p->fc_coord.b_off;
-    c.hz = L.hz; c.h0 = L.h0; c.M = R; c.N = p->n_pix; c.cd = p->coord_dim; c.H0 = (int)H0;
+    c.hz = L.hz; c.h0 = L.h0; c.M = R; c.N = (int)plan_pos(p); c.cd = p->coord_dim; c.H0 = (int)H0;
     PV_TRY(pv_coordlat_fwd(c, s));
     in = L.h0; ldin = H0;
   } else {
@@ -1106,7 +1116,8 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
 
 int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s) {
   const int64_t K = plan_K(p);
-  const int64_t B = p->batch, N = p->n_pix, R = L.rows, z = p->z_dim;
+  // N: rows per sample of the spatial decoder (positions; Cn channels each) or the vanilla decoder's output width
+  const int64_t B = p->batch, N = plan_pos(p), Cn = plan_C(p), R = L.rows, z = p->z_dim;
   const int64_t S = step_S(p, L);                    // decoder samples (jiVAE: K per input, ordered [k][b]; multi-particle: [p][b])
   const int P = L.P;
   const int64_t reps = K > 0 ? K : P;                // decoder passes against the same B observations
@@ -1144,7 +1155,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     o.dpre = (want_grads && !renyi) ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
-    PV_TRY(pv_out_lik(o, s));
+    PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
   } else {
     // oth <- dL/dlogits (R, N); jiVAE: one pass per enumerated class against the same observations, rows then
     // weighted by alpha (the decoder's gradients become the enumerated expectation)
@@ -1170,7 +1181,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
       PV_TRY(renyi_weights(p, L, s));
       if (want_grads && p->coord_dim > 0) {            // the second likelihood pass: dL/dpre and the output layer's partials
         o.dpre = cur; o.llrow = nullptr; o.loc = nullptr;
-        PV_TRY(pv_out_lik(o, s));
+        PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
       } else if (want_grads) {
         PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
       }
@@ -1193,8 +1204,8 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   // ---------------- backward: decoder ----------------
   if (p->coord_dim > 0) {
     const int64_t ob = pv_out_lik_blocks(R);
-    PV_TRY(pv_reduce_partials(L.part_dwo, (int)ob, Hl, G + p->out.w_off, Hl, s));
-    if (p->out.b_off >= 0) PV_TRY(pv_reduce_partials(L.part_dbo, (int)ob, 1, G + p->out.b_off, 1, s));
+    PV_TRY(pv_reduce_partials(L.part_dwo, (int)ob, Cn * Hl, G + p->out.w_off, Cn * Hl, s));
+    if (p->out.b_off >= 0) PV_TRY(pv_reduce_partials(L.part_dbo, (int)ob, Cn, G + p->out.b_off, Cn, s));
   } else {
     // out layer of the vanilla decoder: logits = hlast Wout^T + bout
     PV_TRY(linear_wgrad(oth, N, hlast, Hl, G + p->out.w_off, bias_of(G, p->out), R, Hl, N,
@@ -1285,6 +1296,8 @@ static pv_ivae_plan decode_plan(const pv_ivae_plan* plan) {
 }
 
 static pv_ivae_plan guide_plan(const pv_ivae_plan* plan);
+// several channels per position with an external decoder: refused (the guide plan below no longer knows the decoder)
+static bool ext_decoder_channels(const pv_ivae_plan* plan) { return plan->ext_decoder && plan->coord_dim > 0 && plan->out.out_dim > 1; }
 
 // the likelihood branch a forward-only launch borrows to turn logits into `loc`: the Gaussian one (sigmoid(a) or a) for every
 // likelihood whose mean is that; the Poisson's own for its rate exp(min(a, 30))
@@ -1345,7 +1358,7 @@ extern "C" int64_t pv_ivae_workspace_bytes_for(const pv_ivae_plan* plan, int wha
   if (what < PV_WS_ALL || what > PV_WS_DECODE) return PV_EINVAL;
   if (plan && plan->ext_decoder) {                       // only the guide half runs in the library
     const pv_ivae_plan q = guide_plan(plan);
-    if (!valid_plan(&q)) return PV_EINVAL;
+    if (!valid_plan(&q) || ext_decoder_channels(plan)) return PV_EINVAL;
     Layout L;
     carve(&q, nullptr, L, what == PV_WS_ENCODE, what == PV_WS_ENCODE);
     return L.total;
@@ -1463,6 +1476,7 @@ static pv_ivae_plan guide_plan(const pv_ivae_plan* plan) {
 extern "C" int pv_ivae_guide(const pv_ivae_plan* plan, void* stream) {
   PV_RANGE("pv_ivae_guide");
   if (!plan || !plan->ext_decoder || plan->discrete_dim > 0 || plan->row_w || plan->row_elbo || plan->dy) return PV_EINVAL;
+  if (ext_decoder_channels(plan)) return PV_EINVAL;
   const pv_ivae_plan q = guide_plan(plan);
   if (!valid_plan(&q) || !q.params || !q.x || !q.eps || !q.scalars || !q.ws || !q.ext_z) return PV_EINVAL;
   if (q.ext_encoder && !q.ext_head) return PV_EINVAL;
@@ -1477,7 +1491,7 @@ extern "C" int pv_ivae_guide(const pv_ivae_plan* plan, void* stream) {
 
 extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, void* stream) {
   PV_RANGE("pv_ivae_guide_backward");
-  if (!plan || !plan->ext_decoder || plan->discrete_dim > 0) return PV_EINVAL;
+  if (!plan || !plan->ext_decoder || plan->discrete_dim > 0 || ext_decoder_channels(plan)) return PV_EINVAL;
   const pv_ivae_plan q = guide_plan(plan);
   if (!valid_plan(&q) || !q.params || !q.eps || !q.scalars || !q.ws || !q.ext_ll) return PV_EINVAL;
   if (want_grads && (!q.ext_dz || (!q.ext_encoder && !q.grads) || (q.ext_encoder && !q.ext_dhead))) return PV_EINVAL;
@@ -1584,7 +1598,7 @@ extern "C" int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particle
 
 extern "C" int pv_ivae_encode(const pv_ivae_plan* plan, float* z_loc, float* z_scale, void* stream) {
   PV_RANGE("pv_ivae_encode");
-  if (!plan) return PV_EINVAL;
+  if (!plan || ext_decoder_channels(plan)) return PV_EINVAL;
   pv_ivae_plan lay = plan->ext_decoder ? guide_plan(plan) : *plan;
   if (!valid_plan(&lay) || plan->ext_encoder || !plan->params || !plan->x || !plan->ws || !z_loc || !z_scale) return PV_EINVAL;
   lay.fused = 0;
@@ -1631,6 +1645,7 @@ extern "C" int pv_ivae_decode(const pv_ivae_plan* plan, const float* z, float an
     o.x = L.llrow /* unused for loc */; o.loc = loc; o.llrow = nullptr; o.dpre = nullptr; o.M = R;
     o.H = plan->dec[nd - 1].out_dim; o.lik = loc_lik(plan); o.sigmoid_out = plan->sigmoid_out; o.sig = 1.0f;
     o.act_last = plan->dec[nd - 1].act;
+    if (plan_C(plan) > 1) { o.x = nullptr; return pv_out_lik_mc(o, (int)plan_C(plan), s); }
     return pv_out_lik(o, s);
   }
   return pv_lik_elem(L.logits, L.logits, B * N, loc_lik(plan), plan->sigmoid_out, 1.0f, loc, nullptr, nullptr, s);

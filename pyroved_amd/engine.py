@@ -61,7 +61,9 @@ def _linears(seq: nn.Sequential) -> List[nn.Linear]:
 
 class IVAEEngine:
     """Binds an iVAE-like model (encoder_z: fcEncoderNet, decoder: sDecoderNet | fcDecoderNet)
-    to the HIP library."""
+    to the HIP library.  A multi-channel model (models.iVAE(..., channels=C), self.C > 1) takes x as (B, *data_dim, C), channel-last,
+    returns loc / decode in that shape, and runs the layer-by-layer kernels whatever `fused` asks for (plan.out.out_dim = C,
+    plan.n_pix = prod(data_dim) * C)."""
     supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
@@ -76,6 +78,7 @@ class IVAEEngine:
     conv_x3 = False                  # PV_PLAN_CONV_X3 / conv_bf16 = 0: fp32-class kernel-3 convolutions with both operands as two fp16 pieces
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
     full_tile_loop = True            # PV_PLAN_GENERIC_TILE_LOOP when False (the image-owning decoder launch keeps its generic tile loop; bit-identical)
+    C = 1                            # channels per grid position (models.iVAE(..., channels=C)); set by _check_model
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
     renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
@@ -117,6 +120,19 @@ class IVAEEngine:
         # (pv_ivae_guide / pv_ivae_guide_backward), the decoder, the coordinate transform and the likelihood run in PyTorch
         self.ext_dec = not isinstance(dec, (sDecoderNet, fcDecoderNet))
         self.K = 0
+        # channels per grid position (models.iVAE(..., channels=C)): observations are channel-last, n_pix = positions * C
+        self.C = int(getattr(m, "channels", 1))
+        if self.C != 1:
+            if type(self) is not IVAEEngine or isinstance(enc, jfcEncoderNet):
+                raise UnsupportedModel("channels=%d: multi-channel data is implemented for models.iVAE only (not for %s)"
+                                       % (self.C, type(m).__name__))
+            if isinstance(self.C, bool) or not 1 <= self.C <= _abi.PV_MAX_CHANNELS:
+                raise UnsupportedModel("channels must be an int in 1 .. %d (got %r)" % (_abi.PV_MAX_CHANNELS, self.C))
+            if self.ext_enc or self.conv_enc or self.ext_dec:
+                raise UnsupportedModel("channels=%d: a multi-channel model needs its own fully connected encoder and decoder "
+                                       "(no convolutional or user-defined networks)" % self.C)
+            if isinstance(dec, sDecoderNet) and dec.out.out_features != self.C:
+                raise UnsupportedModel("channels=%d, but decoder.out has %d outputs" % (self.C, dec.out.out_features))
         if self.ext_dec:
             if getattr(m, "discrete_dim", 0):
                 raise UnsupportedModel("a user-defined decoder cannot be combined with discrete latents here")
@@ -266,8 +282,9 @@ class IVAEEngine:
     def _check_particles(self):
         """particles > 1 (pv_ivae_particles_*) and renyi (pv_ivae_renyi_*, at every particle count): the fc-encoder iVAE on the
         layered or the bf16-class fused decoder path; renyi with the sampled KL form only."""
-        # (the native one-call DP step is the one-particle ELBO's)
-        self.supports_dp_step = type(self).supports_dp_step and self.particles == 1 and self.renyi is None
+        # (the native one-call DP step is the one-particle, single-channel ELBO's)
+        self.supports_dp_step = (type(self).supports_dp_step and self.particles == 1 and self.renyi is None
+                                 and getattr(self, "C", 1) == 1)
         if self.particles == 1 and self.renyi is None:
             return
         what = "particles > 1" if self.renyi is None else "renyi"
@@ -473,6 +490,7 @@ class IVAEEngine:
         p.n_pix = 1
         for d in m.data_dim:
             p.n_pix *= int(d)
+        p.n_pix *= self.C                              # observations per sample: positions * channels
         p.coord_dim = 0 if m.coord == 0 else (1 if m.ndim == 1 else 2)
         p.z_dim, p.c_dim = m.z_dim, m.c_dim
         p.latent_dim = m.z_dim - m.coord
@@ -562,6 +580,18 @@ class IVAEEngine:
         p.ws_bytes = self.ws.numel()
         return p
 
+    def _sample_shape(self):
+        """One observation as the model's interface has it: data_dim, channel-last (*data_dim, C) when C > 1."""
+        dd = tuple(int(d) for d in self.model.data_dim)
+        return dd if self.C == 1 else dd + (self.C,)
+
+    def _check_x(self, x, p):
+        """Multi-channel input: (B, *data_dim, C) or already flat (B, n_pix) — anything else (channel-first, say) has the
+        right number of values in the wrong order, so it is refused, not reshaped."""
+        if self.C > 1 and tuple(x.shape[1:]) not in (self._sample_shape(), (p.n_pix,)):
+            raise ValueError("channels=%d: x must be channel-last, (batch, %s) (got %s)"
+                             % (self.C, ", ".join(str(d) for d in self._sample_shape()), tuple(x.shape)))
+
     def _prep(self, t: Optional[torch.Tensor], what: str, shape=None) -> Optional[torch.Tensor]:
         if t is None:
             return None
@@ -615,6 +645,7 @@ class IVAEEngine:
             return self._loss_and_grads_ext_decoder(x, eps, beta, y, want_grads, scalars_out, z_out, loc_out)
         b = x.shape[0]
         p = self._plan(b, beta)
+        self._check_x(x, p)
         head = dhead = None
         if self.ext_enc:
             # the user's encoder in PyTorch on the same stream; its outputs are the step's (z_loc, z_scale)
@@ -854,6 +885,7 @@ class IVAEEngine:
             self._check_conv_weight_range()
         b = x.shape[0]
         p = self._plan(b, what=2)
+        self._check_x(x, p)
         x = self._prep(x, "x", (b, p.n_pix))
         y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
         if p.c_dim > 0 and y is None:
@@ -889,7 +921,7 @@ class IVAEEngine:
         _abi.check(_abi.lib().pv_ivae_decode(C.byref(p), _abi.ptr(z), float(angle), float(shift[0]), float(shift[1]),
                                              float(scale), _abi.ptr(loc), _abi.current_stream()), "pv_ivae_decode")
         self._keep = (z,)
-        return loc.view(b, *self.model.data_dim)
+        return loc.view(b, *self._sample_shape())
 
     @_abi.on_device
     def uses_fused(self, batch: int) -> bool:

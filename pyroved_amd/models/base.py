@@ -17,6 +17,13 @@ from ..utils import iter_batches, generate_grid
 tt = torch.tensor
 
 
+def _channel_count(c) -> int:
+    from .._abi import PV_MAX_CHANNELS
+    if isinstance(c, bool) or not isinstance(c, int) or not 1 <= c <= PV_MAX_CHANNELS:
+        raise ValueError("channels must be an int in 1 .. %d (got %r)" % (PV_MAX_CHANNELS, c))
+    return c
+
+
 def _to_host(t: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """Device -> host copy of a result tensor into `out` (an ordinary pageable CPU tensor of t's shape; allocated when None).
     Large results go through a page-locked STAGING buffer (torch's caching host allocator keeps the block for the next chunk
@@ -88,10 +95,18 @@ class baseVAE(nn.Module):
         device: defaults to 'cuda' if a GPU is available, else 'cpu' (on which the
             model can be built and inspected, but not run: the compute path is HIP only).
         dx_prior, dy_prior: translational priors; sc_prior: scale prior.
+        channels: values per grid position (default 1).  More than one is models.iVAE's alone; every other model
+            refuses it here (their constructors pass unknown keywords on, so the check is explicit).
     """
+    _multichannel = False      # models.iVAE: channels > 1 is implemented
+
     def __init__(self, *args, **kwargs: str):
         super(baseVAE, self).__init__()
         data_dim, invariances = args
+        self.channels = _channel_count(kwargs.get("channels", 1))
+        if self.channels != 1 and not self._multichannel:
+            raise ValueError("channels=%d: multi-channel data is implemented for models.iVAE only (not for %s)"
+                             % (self.channels, type(self).__name__))
         self.device = kwargs.get(
             "device", 'cuda' if torch.cuda.is_available() else 'cpu')
         self.data_dim = tuple(int(d) for d in data_dim)
@@ -217,11 +232,17 @@ class baseVAE(nn.Module):
 
     def set_encoder(self, encoder_net: Type[torch.nn.Module]) -> None:
         """Sets a user-defined encoder neural network."""
+        from ..nets import fcEncoderNet
+        if self.channels != 1 and not isinstance(encoder_net, fcEncoderNet):
+            raise ValueError("channels=%d: a multi-channel model keeps a fully connected encoder (set_encoder with a "
+                             "convolutional or user-defined module is not implemented)" % self.channels)
         self.encoder_z = encoder_net.to(self.device)
         self._engine = None
 
     def set_decoder(self, decoder_net: Type[torch.nn.Module]) -> None:
         """Sets a user-defined decoder neural network."""
+        if self.channels != 1:
+            raise ValueError("channels=%d: set_decoder is not implemented for multi-channel models" % self.channels)
         self.decoder = decoder_net.to(self.device)
         self._engine = None
 

@@ -47,10 +47,20 @@ class iVAE(baseVAE):
             whose log-rate is the decoder's output (needs sigmoid_d=False; decode / manifold2d return the rate)
         sigmoid_d: sigmoid at the decoder output (default True)
         seed: seed used in torch.manual_seed(seed)
+        channels: values per grid position, 1 .. 8 (default 1).  With C > 1 the data is channel-last, x of shape
+            (B, *data_dim, C): data_dim stays the grid's shape, so 1-D spectra take channels too, (B, l, C).  The spatial
+            decoder's output layer becomes Linear(hidden, C) (decoder.out.weight (C, hidden), decoder.out.bias (C,)), the
+            likelihood and sigmoid_d apply per value, log p(x | z) sums over positions and channels, and rotation, shift and
+            scale are shared by the channels; decode / manifold2d return (n, *data_dim, C).  The encoder sees the flattened
+            (B, prod(data_dim) * C [+ c_dim]).  Trains on the layer-by-layer HIP kernels at fp32 (SVItrainer(precision="bf16")
+            is refused); set_encoder with a convolutional or user-defined module, set_decoder and the Pyro-program hooks
+            model() / guide() are refused.  channels=1 is the single-channel model in every respect.
 
     Keyword Args:
         device, dx_prior, dy_prior, sc_prior, decoder_sig — as in the reference.
     """
+
+    _multichannel = True
 
     def __init__(
         self,
@@ -64,24 +74,34 @@ class iVAE(baseVAE):
         sampler_d: str = "bernoulli",
         sigmoid_d: bool = True,
         seed: int = 1,
+        channels: int = 1,
         **kwargs: Union[str, float]
          ) -> None:
         args = (data_dim, invariances)
-        super(iVAE, self).__init__(*args, **kwargs)
+        super(iVAE, self).__init__(*args, channels=channels, **kwargs)
 
         # same RNG consumption as the reference (models/ivae.py:140-154): seed, then the
         # encoder's Linear layers, then the decoder's, all on the CPU generator
         set_deterministic_mode(seed)
 
+        # channels > 1: the fully connected nets see (*data_dim, C), channel-last; the spatial decoder keeps the grid's shape
+        # and emits C values per position.  channels == 1 builds exactly what it always did
+        C = self.channels
+        full_dim = data_dim if C == 1 else (*data_dim, C)
         self.encoder_z = fcEncoderNet(
-            data_dim, latent_dim + self.coord, c_dim, hidden_dim_e,
+            full_dim, latent_dim + self.coord, c_dim, hidden_dim_e,
             activation, softplus_out=True
         )
-        dnet = sDecoderNet if 0 < self.coord < 5 else fcDecoderNet
-        self.decoder = dnet(
-            data_dim, latent_dim, c_dim, hidden_dim_d,
-            activation, sigmoid_out=sigmoid_d
-        )
+        if 0 < self.coord < 5:
+            self.decoder = sDecoderNet(
+                data_dim, latent_dim, c_dim, hidden_dim_d,
+                activation, sigmoid_out=sigmoid_d, **({} if C == 1 else {"channels": C})
+            )
+        else:
+            self.decoder = fcDecoderNet(
+                full_dim, latent_dim, c_dim, hidden_dim_d,
+                activation, sigmoid_out=sigmoid_d
+            )
         self.sampler_d = get_sampler(sampler_d, **kwargs)
 
         self.z_dim = latent_dim + self.coord
@@ -110,12 +130,19 @@ class iVAE(baseVAE):
         pyro.infer.SVI); raises NotImplementedError without it.  SVItrainer evaluates the same objective in HIP kernels
         and does not go through here (iVAE.elbo_terms does neither)."""
         from ._pyro_programs import ivae_model
+        self._no_pyro_channels("model")
         return ivae_model(self, x, y, **kwargs)
 
     def guide(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, **kwargs: float) -> None:
         """q(z|x) as a Pyro program (models/ivae.py:204-221); see `model`."""
         from ._pyro_programs import ivae_guide
+        self._no_pyro_channels("guide")
         return ivae_guide(self, x, y, **kwargs)
+
+    def _no_pyro_channels(self, what: str) -> None:
+        if self.channels != 1:
+            raise ValueError("channels=%d: the Pyro-program hook %s() is written for single-channel data; train with "
+                             "SVItrainer (the HIP path)" % (self.channels, what))
 
     def split_latent(self, z: torch.Tensor) -> Tuple[torch.Tensor]:
         """Split latent variable into parts associated with coordinate transformations
@@ -144,7 +171,8 @@ class iVAE(baseVAE):
                    **kwargs: Union[str, int, float]) -> torch.Tensor:
         """Decodes a d x d grid of the 2-D latent space (models/ivae.py:277-310).  The grid is the
         reference's generate_latent_grid: inverse normal CDF of linspace(0.05, 0.95, d) unless
-        z_coord=[z1, z2, z3, z4] is given; plot=True draws the mosaic (utils.plot_img_grid / plot_spect_grid)."""
+        z_coord=[z1, z2, z3, z4] is given; plot=True draws the mosaic (utils.plot_img_grid / plot_spect_grid; of a
+        multi-channel model: channel `channel`, default 0)."""
         import torch.distributions as td
         if isinstance(d, int):
             d = [d, d]
@@ -169,7 +197,9 @@ class iVAE(baseVAE):
         else:
             loc = self.decode(z, **kwargs)
         if plot:
-            _plot_manifold(self.ndim, loc, d, grid_x, grid_y, kwargs)
+            # (multi-channel: the mosaic shows one channel, channel=0 unless given)
+            shown = loc if self.channels == 1 else loc[..., int(kwargs.get("channel", 0))]
+            _plot_manifold(self.ndim, shown, d, grid_x, grid_y, {k: v for k, v in kwargs.items() if k != "channel"})
         return loc
 
     def predict_on_latent(self, train_data, gp_labels, gp_iterations: int = 1, d: int = 12, plot: bool = False):

@@ -157,16 +157,18 @@ class coord_latent(nn.Module):
 
 class sDecoderNet(nn.Module):
     """Spatial generator (decoder): a per-pixel MLP over transformed coordinates and the
-    latent code (pyroved/nets/fc.py:155-199)."""
+    latent code (pyroved/nets/fc.py:155-199).  channels = C > 1: C values per grid position (the output layer is
+    Linear(hidden, C)), returned channel-last as (B, *out_dim, C); out_dim stays the grid's shape."""
     def __init__(self, out_dim: Tuple[int], latent_dim: int, c_dim: int = 0,
                  hidden_dim: List[int] = None, activation: str = 'tanh',
-                 sigmoid_out: bool = True, unflat: bool = True) -> None:
+                 sigmoid_out: bool = True, unflat: bool = True, channels: int = 1) -> None:
         super(sDecoderNet, self).__init__()
         if len(out_dim) not in [1, 2, 3]:
             raise ValueError("in_dim must be (h, w), (h, w, c), or (l,)")
         self.unflat = unflat
+        self.channels = int(channels)
         if self.unflat:
-            self.reshape = out_dim
+            self.reshape = out_dim if self.channels == 1 else (*out_dim, self.channels)
         if hidden_dim is None:
             hidden_dim = [128, 128]
         coord_dim = 1 if len(out_dim) < 2 else 2
@@ -175,7 +177,7 @@ class sDecoderNet(nn.Module):
         self.concat = Concat()
         self.coord_latent = coord_latent(latent_dim + c_dim, hidden_dim[0], coord_dim)
         self.fc_layers = make_fc_layers(hidden_dim[0], hidden_dim, activation)
-        self.out = nn.Linear(hidden_dim[-1], 1)
+        self.out = nn.Linear(hidden_dim[-1], self.channels)
 
     def forward(self, x_coord: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
         """x_coord: (B, N, coord_dim) transformed coordinates, z: (B, latent_dim [+ c_dim]) or the list the

@@ -183,6 +183,10 @@ class SVItrainer:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
+            if precision == "bf16" and getattr(model, "channels", 1) != 1:
+                raise ValueError("precision='bf16' is not implemented for channels=%d: no bf16 multi-channel decoder kernel "
+                                 "exists, and training at another precision than the one asked for is worse than refusing"
+                                 % model.channels)
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
                                        renyi=False if self.alpha is None else self.alpha)

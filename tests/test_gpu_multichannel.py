@@ -1,0 +1,269 @@
+"""
+GPU tests (-m gpu) of multi-channel models: iVAE(..., channels=C), x of shape (B, *data_dim, C), the spatial decoder's output
+layer Linear(H, C) on the C-output likelihood kernel (pv_out_lik_mc) of the layer-by-layer path.
+
+The reference is the project's own float64 oracles, unchanged, with the C-output decoder attached
+(tests/_multichannel_ref.attach; Poisson inside tests/_poisson_ref.poisson_reference()).  Cases, data and eps come from
+tests/_multichannel_ref.CASES / case_data (torch.Generator().manual_seed(0): data first, then the eps draws).  Every step
+case runs two steps with Adam between, each from identical float32 parameters, at the bars of tests/test_gpu_parity.py:
+loss and ll 2e-5 (+ the atol test_model_variants_vs_oracle gives the sampler), the KL scalars 1e-4, every gradient tensor
+1e-4 relative L2, parameters after Adam by check_params_after_adam's rule with the 5e-5 bar (its 1 % cap is confirmed with
+the reference alone in tests/test_multichannel_cpu.py), z_loc / z_scale rtol 1e-4 atol 5e-6, loc_out and decode rtol 1e-4
+atol 2e-6.
+"""
+import numpy as np
+import pytest
+import torch
+
+import pyroved_amd as pv
+from oracle import svi_oracle as orc
+import _meanfield_ref as mf
+import _particles_ref as pref
+import _renyi_ref as rr
+import _poisson_ref as pr
+import _multichannel_ref as mc
+from test_gpu_meanfield import check_params_after_adam, rel_l2, state, RTOL_ELBO, RTOL_GRAD, LR
+from test_gpu_renyi import weight_check
+
+pytestmark = pytest.mark.gpu
+
+RTOL_KL = 1e-4
+CASE1 = "c01_8x8_rts_c2_b6"
+
+
+@pytest.fixture(autouse=True)
+def _reference_setup():
+    n = torch.get_num_threads()
+    torch.set_num_threads(16)                      # (the float64 references)
+    try:
+        with pr.poisson_reference():
+            yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def make(name, **engine_kw):
+    c = mc.CASES[name]
+    model = pv.models.iVAE(c["dims"], 2, c["inv"], seed=1, device="cuda", **mc.model_kwargs(c))
+    return c, model, model.engine(**engine_kw)
+
+
+def loss_atol(c):
+    """test_model_variants_vs_oracle: 1e-6 per value of the batch for the continuous Bernoulli, none otherwise."""
+    return 1e-6 * c["b"] * int(np.prod(c["dims"])) if c.get("sampler") == "continuous_bernoulli" else 0.0
+
+
+def ref_loc(o, last):
+    """What loc_out holds: the decoder's mean, (rows, P*C) channel-last; the rate for the Poisson."""
+    loc = last["loc"].detach()
+    return torch.exp(loc.clamp(max=30.0)) if o.cfg.sampler == "poisson_log" else loc
+
+
+def check_step(eng, o, last, tag, atol=0.0, zl=None, zs=None, loc=None, grads=None):
+    s = eng.scalars.cpu().numpy()
+    print("%s: loss %.6f (ref %.6f) ll %.6f (ref %.6f) s2 %.6f (ref %.6f) s3 %.6f (ref %.6f)"
+          % (tag, s[0], last["loss"].item(), s[1], last["ll"].item(), s[2], last["logpz"].item(), s[3], last["logqz"].item()))
+    # (Poisson: the reference's log_prob carries lgamma(x + 1), as the reported loss does)
+    ref = {k: last[k].item() for k in ("loss", "ll", "logpz", "logqz")}
+    np.testing.assert_allclose(s[0], ref["loss"], rtol=RTOL_ELBO, atol=atol, err_msg="%s loss" % tag)
+    np.testing.assert_allclose(s[1], ref["ll"], rtol=RTOL_ELBO, atol=atol, err_msg="%s ll" % tag)
+    np.testing.assert_allclose(s[2], ref["logpz"], rtol=RTOL_KL, err_msg="%s s2" % tag)
+    np.testing.assert_allclose(s[3], ref["logqz"], rtol=RTOL_KL, err_msg="%s s3" % tag)
+    if zl is not None:
+        np.testing.assert_allclose(zl.cpu().numpy(), last["z_loc"].detach().numpy(), rtol=1e-4, atol=5e-6, err_msg="%s z_loc" % tag)
+        np.testing.assert_allclose(zs.cpu().numpy(), last["z_scale"].detach().numpy(), rtol=1e-4, atol=5e-6, err_msg="%s z_scale" % tag)
+    if loc is not None:
+        want = ref_loc(o, last).reshape(loc.shape[0], -1).numpy()
+        err = np.abs(loc.cpu().numpy() - want).max()
+        print("%s: loc_out max abs error %.2e" % (tag, err))
+        np.testing.assert_allclose(loc.cpu().numpy(), want, rtol=1e-4, atol=2e-6, err_msg="%s loc_out" % tag)
+    grads = o.last_grads if grads is None else grads
+    worst, which = 0.0, None
+    for key in o.p:
+        err = rel_l2(eng.grad_of(key), grads[key])
+        if err > worst:
+            worst, which = err, key
+    print("%s: worst gradient rel l2 %.2e (%s)" % (tag, worst, which))
+    for key in o.p:
+        err = rel_l2(eng.grad_of(key), grads[key])
+        assert err < RTOL_GRAD, "%s grad %s: rel l2 error %.3e vs the float64 reference" % (tag, key, err)
+
+
+def reload(model, o):
+    mc.round_to_float32(o)                         # both sides continue from the SAME float32 parameters
+    model.load_state_dict({k: v.detach().float() for k, v in o.p.items()})
+
+
+def run_steps(name, fused, make_oracle, engine_kw=None, particles=1):
+    c, model, eng = make(name, fused=fused, **(engine_kw or {}))
+    b, n_obs = c["b"], int(np.prod(c["dims"])) * c["C"]
+    assert eng.uses_fused(b) is False and eng.supports_dp_step is False
+    x, y, eps = mc.case_data(c, particles)
+    o = mc.attach(make_oracle(state(model), mc.case_config(c)), c["C"])
+    z_dim = o.cfg.z_dim
+    zl, zs = torch.empty(b, z_dim, device="cuda"), torch.empty(b, z_dim, device="cuda")
+    loc = torch.full((particles * b, n_obs), float("nan"), device="cuda")
+    yg = None if y is None else y.cuda()
+    for k in range(2):
+        tag = "%s fused=%d step %d" % (name, fused, k)
+        eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, yg, z_out=(zl, zs), loc_out=loc)
+        o.step(x, eps[k], 1.0, y)
+        check_step(eng, o, o.last, tag, loss_atol(c), zl, zs, loc)
+        eng.adam_step()
+        check_params_after_adam(model, o, 0, tag)                  # (0: the 5e-5 bar)
+        reload(model, o)
+    return c, model, eng, o, x, y
+
+
+# ------------------------------------------------------------------------------- 1. steps
+STEP_PARAMS = [(n, 2) for n in sorted(mc.CASES)] + [(CASE1, 0)]
+
+
+@pytest.mark.parametrize("name,fused", STEP_PARAMS)
+def test_steps_vs_reference(gpu_device, name, fused):
+    """Two steps per case with the default request fused = 2 (it falls back to the layered kernels), and fused = 0 on case 1;
+    then encode and decode from the trained state."""
+    c, model, eng, o, x, y = run_steps(name, fused, lambda p, cfg: orc.SVIOracle(p, cfg, lr=LR, dtype=torch.float64))
+    shape = (c["b"],) + tuple(c["dims"]) + (c["C"],)
+    enc_args = (x,) if y is None else (x, y)
+    z_loc, z_scale = model.encode(*enc_args)
+    zl, zs = o.encode(x, y)
+    np.testing.assert_allclose(z_loc.numpy(), zl.numpy(), rtol=1e-4, atol=5e-6)
+    np.testing.assert_allclose(z_scale.numpy(), zs.numpy(), rtol=1e-4, atol=5e-6)
+    zc = z_loc[:, -2:] if c["inv"] else z_loc
+    dec = model.decode(zc, y)
+    assert tuple(dec.shape) == shape
+    want = mc.decode(o, zc, y)
+    print("%s: decode max abs error %.2e" % (name, (dec.double() - want).abs().max().item()))
+    np.testing.assert_allclose(dec.numpy(), want.numpy(), rtol=1e-4, atol=2e-6)
+
+
+def test_both_requests_run_the_same_launches(gpu_device):
+    """fused = 0 and the default fused = 2 on case 1: the same path, so the same bits."""
+    out = []
+    for fused in (0, 2):
+        c, model, eng = make(CASE1, fused=fused)
+        x, y, eps = mc.case_data(c)
+        eng.loss_and_grads(x.cuda(), eps[0].cuda(), 1.0)
+        torch.cuda.synchronize()
+        out.append(eng.grad.clone())
+    assert torch.equal(out[0], out[1])
+
+
+def test_elbo_terms_and_manifold(gpu_device):
+    c, model, eng = make(CASE1)
+    x, y, eps = mc.case_data(c)
+    o = mc.attach(orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64), c["C"])
+    with torch.no_grad():
+        ref = orc.elbo(o.p, o.cfg, x.double(), eps[0].double(), 1.0, None, o.grid)
+    t = model.elbo_terms(x, eps=eps[0])
+    np.testing.assert_allclose(t["loss"], ref["loss"].item(), rtol=RTOL_ELBO)
+    np.testing.assert_allclose(t["ll"], ref["ll"].item(), rtol=RTOL_ELBO)
+    man = model.manifold2d(3, plot=False)
+    assert tuple(man.shape) == (9, 8, 8, 2)
+    with pytest.raises(ValueError, match="channels"):
+        eng.loss_and_grads(x.permute(0, 3, 1, 2).contiguous().cuda(), eps[0].cuda())      # channel-first: refused, not reshaped
+
+
+# ------------------------------------------------------------------------------- 2. the other objectives, on case 1's shape
+def test_analytic_kl_steps(gpu_device):
+    run_steps(CASE1, 2, lambda p, cfg: mf.MeanFieldOracle(p, cfg, lr=LR, dtype=torch.float64), dict(kl="analytic"))
+
+
+def test_three_particles_steps(gpu_device):
+    run_steps(CASE1, 2, lambda p, cfg: pref.ParticlesOracle(p, cfg, 3, lr=LR, dtype=torch.float64), dict(particles=3), particles=3)
+
+
+def test_renyi_steps_with_the_weights_held(gpu_device):
+    """RenyiELBO(alpha = 0, num_particles = 3), as tests/test_gpu_renyi.py tests the bound: scalars and weights against the free
+    float64 bound, gradients and the Adam step against the reference with the engine's weights held."""
+    P, alpha = 3, 0.0
+    c, model, eng = make(CASE1, fused=2, particles=P, renyi=alpha)
+    b = c["b"]
+    x, y, eps = mc.case_data(c, P)
+    zl, zs = torch.empty(b, model.z_dim, device="cuda"), torch.empty(b, model.z_dim, device="cuda")
+    w = torch.full((P * b,), float("nan"), device="cuda")
+    held = None
+    for k in range(2):
+        tag = "renyi step %d" % k
+        eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, z_out=(zl, zs), weights_out=w)
+        torch.cuda.synchronize()
+        free = mc.attach(rr.RenyiOracle(state(model), mc.case_config(c), P, alpha, lr=LR, dtype=torch.float64), c["C"])
+        of = free.loss_and_grads(x, eps[k], 1.0)
+        if held is None:
+            held = mc.attach(rr.RenyiOracle(state(model), mc.case_config(c), P, alpha, lr=LR, dtype=torch.float64), c["C"])
+        held.weights = w.detach().cpu().double()
+        held.step(x, eps[k], 1.0)
+        weight_check(tag, w, of, alpha, RTOL_ELBO)
+        check_step(eng, held, of, tag, 0.0, zl, zs, grads=held.last_grads)
+        eng.adam_step()
+        check_params_after_adam(model, held, 0, tag)
+        reload(model, held)
+
+
+# ------------------------------------------------------------------------------- 3. determinism
+@pytest.mark.parametrize("name", [CASE1, "c05_4x4_r_c8_b2_512_512", "c10_28x28_rt_c3_b16"])
+def test_repeated_call_is_bit_identical(gpu_device, name):
+    c, model, eng = make(name)
+    x, y, eps = mc.case_data(c)
+    xg, eg = x.cuda(), eps[0].cuda()
+    eng.loss_and_grads(xg, eg, 1.0)
+    torch.cuda.synchronize()
+    first = eng.grad.clone()
+    eng.grad.fill_(float("nan"))                                # (every tensor and the four scalars are written again)
+    eng.loss_and_grads(xg, eg, 1.0)
+    torch.cuda.synchronize()
+    for k, v in model.state_dict().items():                     # (per tensor: the flat buffer's alignment padding is never written)
+        lo, n = eng._layout[k], v.numel()
+        assert torch.equal(first[lo:lo + n], eng.grad[lo:lo + n]), k
+    assert torch.equal(first[-4:], eng.grad[-4:]) and torch.isfinite(first[-4:]).all()      # the four scalars
+
+
+# ------------------------------------------------------------------------------- 4. decode with a transform
+@pytest.mark.parametrize("name", [CASE1, "c03_1d16_t_c4_b5_gelu"])
+def test_decode_with_angle_shift_scale(gpu_device, name):
+    c, model, eng = make(name)
+    o = mc.attach(orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64), c["C"])
+    z = torch.randn(5, 2, generator=torch.Generator().manual_seed(2))
+    dec = model.decode(z, angle=0.3, shift=[0.1, -0.2], scale=1.2)
+    assert tuple(dec.shape) == (5,) + tuple(c["dims"]) + (c["C"],)
+    want = mc.decode(o, z, None, 0.3, [0.1, -0.2], 1.2)
+    np.testing.assert_allclose(dec.numpy(), want.numpy(), rtol=1e-4, atol=2e-6)
+    plain = mc.decode(o, z)
+    assert (plain - want).abs().max().item() > 1e-3             # (the transform does something)
+
+
+# ------------------------------------------------------------------------------- 5. trainer
+def test_trainer_history_and_weights_round_trip(gpu_device, tmp_path):
+    """SVItrainer(model).step(loader), two epochs of three minibatches of case 1's kind, against SVIOracle.train_epoch driven by
+    the same generator: loss_history to 1e-4; evaluate runs; save_weights / load_weights round-trips."""
+    c = mc.CASES[CASE1]
+    x = mc.images(torch.Generator().manual_seed(0), 18, c["dims"], c["C"])
+    loader = pv.utils.init_dataloader(x, batch_size=6)
+    model = pv.models.iVAE(c["dims"], 2, c["inv"], seed=1, device="cuda", **mc.model_kwargs(c))
+    params0 = state(model)
+    tr = pv.trainers.SVItrainer(model, seed=1)
+    st = torch.get_rng_state()
+    for _ in range(2):
+        tr.step(loader)
+    torch.cuda.synchronize()
+    torch.set_rng_state(st)
+    o = mc.attach(orc.SVIOracle(params0, mc.case_config(c), lr=LR), c["C"])
+    want = [o.train_epoch(loader) for _ in range(2)]
+    print("trainer: history %s, reference %s" % (tr.loss_history["training_loss"], want))
+    np.testing.assert_allclose(tr.loss_history["training_loss"], want, rtol=1e-4)
+    assert np.isfinite(tr.evaluate(loader))
+    path = str(tmp_path / "mc")
+    model.save_weights(path)
+    other = pv.models.iVAE(c["dims"], 2, c["inv"], seed=5, device="cuda", **mc.model_kwargs(c))
+    other.load_weights(path + ".pt")
+    for k, v in model.state_dict().items():
+        assert torch.equal(other.state_dict()[k], v), k
+    z = torch.randn(4, 2, generator=torch.Generator().manual_seed(2))
+    assert torch.equal(other.decode(z), model.decode(z))
+
+
+def test_bf16_precision_is_refused(gpu_device):
+    c, model, eng = make(CASE1)
+    with pytest.raises(ValueError, match="channels"):
+        pv.trainers.SVItrainer(model, precision="bf16")
