@@ -42,6 +42,59 @@ restatement (tests/golden/_minipyro.py) because pyro-ppl cannot be installed
 here.  So: PINNED for every function under /root/reference; PARITY UNPINNED at
 the Pyro boundary (Trace_ELBO / SVI / optim.Adam glue), where neither the
 reference's tests nor a runnable Pyro hold a number.
+
+Five extensions beyond the reference, with the same switches as the product's engine (engine(kl=, particles=, renyi=),
+sampler_d="poisson_log", channels=C).  The default path — sampled KL, one particle, no Renyi order, one channel, the
+reference's three samplers — runs exactly the torch operations it ran before them, which is what the fixtures pin.
+Pyro is not a dependency and is not run here: each extension is pinned to the torch function Pyro's objective calls, or
+to Pyro's published semantics.
+
+1. Analytic KL, kl="analytic" — pyro.infer.TraceMeanField_ELBO on iVAE.guide / iVAE.model (and VED's).  The `latent`
+   sites of guide and model are both Normal, so that objective takes kl_divergence(guide site, model site) instead of the
+   sampled log q(z|x) - log p(z), under the same poutine.scale(beta); z = mu + sigma * eps is still drawn once per sample
+   for the likelihood:
+       loss = -sum_b log p(x_b | z_b) + beta * sum_b sum_i KL(N(mu_bi, sigma_bi) || N(0, 1))
+   Pinned to torch.distributions.kl_divergence.  The four scalars keep the sampled objective's slots and relation
+   loss = -(ll + logpz - logqz), with logpz / logqz the analytic expectations of the terms they hold there
+   (logqz - logpz = beta * KL).
+
+2. Particles, particles=P — Trace_ELBO(num_particles=P) / TraceMeanField_ELBO(num_particles=P).  Pyro's (non-vectorised)
+   particles run the guide P times on the same minibatch and average the P one-particle estimates; the encoder's output
+   does not depend on the draw, so it is evaluated once:
+       z_pb = mu_b + sigma_b * eps_pb
+       e_pb = log p(x_b | z_pb) + beta * (log p(z_pb) - log q(z_pb | x_b))          sampled form
+       e_pb = log p(x_b | z_pb) - beta * KL(N(mu_b, sigma_b) || N(0, 1))            analytic form
+       loss = -(1/P) * sum_p sum_b e_pb
+   `eps` is ONE (P*B, z_dim) tensor with rows ordered [p][b]; `loc`, `z` and `ll_per_sample` come back (P*B, ...) in the
+   same order, z_loc and z_scale stay (B, z_dim).  Each of the four scalars is the mean over particles of the term it
+   holds for one particle.  P = 1 is the one-particle path itself; P = 3 is the mean of three one-particle evaluations.
+
+3. Renyi / IWAE bound, renyi=alpha — pyro.infer.RenyiELBO(alpha, num_particles=P), sampled KL only.  The `data` plate
+   encloses every site of these models, so Pyro's log-weights stay per image:
+       lw_pb = log p(x_b | z_pb) + beta * (log p(z_pb) - log q(z_pb | x_b))
+       a_pb  = (1 - alpha) * lw_pb,   w_pb = softmax over p of a_pb
+       L_b   = (logsumexp_p a_pb - log P) / (1 - alpha)
+       loss  = -sum_b L_b
+   The gradient of `loss` is autograd's — it equals -sum_b sum_p w_pb grad lw_pb with w held constant, which is what the
+   library computes; `weights=` (a (P*B) tensor, rows [p][b]) evaluates exactly that surrogate, -sum w lw + const, with
+   the GIVEN weights held fixed (const places the value on the bound of those weights: their entropy term).  The slots:
+       logpz = sum_b sum_p w_pb beta log p(z_pb),   logqz = sum_b sum_p w_pb beta log q(z_pb | x_b)
+       ll    = sum_b (sum_p w_pb ll_pb + c_b),      c_b = L_b - sum_p w_pb lw_pb = (H(w_b) - log P) / (1 - alpha)
+   With one sample L_b = lw_b whatever alpha is: P = 1 is the one-particle path; alpha -> 1 meets the particle ELBO.
+
+4. Poisson (log link), cfg.sampler == "poisson_log".  The decoder's output a is the log-rate (sigmoid_d=False); with
+   a_c = min(a, 30):
+       log p(x | a) = x a_c - exp(a_c) - lgamma(x + 1)
+   Pinned to torch.distributions.Poisson(exp(a_c)).log_prob(x) (validate_args=False: non-integer x is legal).
+
+5. Channels, cfg.channels == C > 1.  The data has prod(data_dim) grid positions and C values per position, channel-last:
+   x is (B, *data_dim, C).  The spatial decoder is the single-channel one up to its last hidden layer (one row per sample
+   and position); its output layer is Linear(H, C).  A vanilla decoder ends in Linear(H, positions * C).  The output
+   sigmoid and the likelihood apply per value, log p(x_b | z_b) sums over positions and channels, the encoder sees the
+   flattened (B, positions * C [+ c_dim]); `loc` is (B, *data_dim, C).
+
+The unified objective covers iVAE-class models; jiVAE (discrete_dim > 0) keeps its own estimators (jelbo, jelbo_sampled)
+and is refused together with any of extensions 1 - 3.
 """
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -81,10 +134,15 @@ class Config:
     dy_prior: Optional[float] = None
     sc_prior: float = 0.1
     decoder_sig: float = 0.5
+    channels: int = 1              # values per grid position, channel-last: x and loc are (B, *data_dim, C) for C > 1
 
     @property
     def ndim(self):
         return len(self.data_dim)
+
+    @property
+    def out_shape(self):
+        return tuple(self.data_dim) if self.channels == 1 else (*self.data_dim, self.channels)
 
     @property
     def coord(self):
@@ -201,7 +259,8 @@ def jencoder_forward(p: Params, cfg: Config, x):
 
 
 def sdecoder_forward(p: Params, cfg: Config, x_coord, z):
-    """sDecoderNet.forward + coord_latent.forward (nets/fc.py:189-199, 220-237)."""
+    """sDecoderNet.forward + coord_latent.forward (nets/fc.py:189-199, 220-237); decoder.out is Linear(H, channels), one row
+    per sample and position, so the output is channel-last."""
     if cfg.bf16_plan is not None:
         return cfg.bf16_plan.sdecoder_forward(p, cfg, x_coord, z)
     act = _ACT[cfg.activation]
@@ -214,17 +273,17 @@ def sdecoder_forward(p: Params, cfg: Config, x_coord, z):
     out = F.linear(h, p["decoder.out.weight"], p["decoder.out.bias"])
     if cfg.sigmoid_d:
         out = torch.sigmoid(out)
-    return out.view(-1, *cfg.data_dim)
+    return out.view(-1, *cfg.out_shape)
 
 
 def fcdecoder_forward(p: Params, cfg: Config, z):
-    """fcDecoderNet.forward (nets/fc.py:143-152)."""
+    """fcDecoderNet.forward (nets/fc.py:143-152); decoder.out is Linear(H, positions * channels), channel-last."""
     act = _ACT[cfg.activation]
     h = _fc_stack(p, "decoder.fc_layers", cfg.n_hidden_d, act, z)
     out = F.linear(h, p["decoder.out.weight"], p["decoder.out.bias"])
     if cfg.sigmoid_d:
         out = torch.sigmoid(out)
-    return out.view(-1, *cfg.data_dim)
+    return out.view(-1, *cfg.out_shape)
 
 
 def decode_from_latent(p: Params, cfg: Config, z, y=None, grid=None):
@@ -249,35 +308,97 @@ def decode_from_latent(p: Params, cfg: Config, z, y=None, grid=None):
     return fcdecoder_forward(p, cfg, z), None
 
 
+POISSON_CLAMP = 30.0
+
+
 def likelihood(cfg: Config, loc):
-    """utils/prob.py:25-29."""
+    """utils/prob.py:25-29; "poisson_log": loc is the log-rate, clamped from above (extension 4 of the module docstring)."""
     if cfg.sampler == "bernoulli":
         return td.Bernoulli(loc, validate_args=False)
     if cfg.sampler == "continuous_bernoulli":
         return td.ContinuousBernoulli(loc)
     if cfg.sampler == "gaussian":
         return td.Normal(loc, cfg.decoder_sig)
+    if cfg.sampler == "poisson_log":
+        return td.Poisson(torch.exp(loc.clamp(max=POISSON_CLAMP)), validate_args=False)
     raise KeyError(cfg.sampler)
 
 
 # ---------------------------------------------------------------------- ELBO
-def elbo(p: Params, cfg: Config, x, eps, beta=1.0, y=None, grid=None):
-    """One-particle Trace_ELBO of iVAE.guide/model (models/ivae.py:165-221).
+LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def _kl_and_slots(z_loc, z_scale, beta):
+    """Analytic KL per image, and the logpz / logqz slots' analytic expectations beta E_q log p(z), beta E_q log q(z|x)."""
+    kl = td.kl_divergence(td.Normal(z_loc, z_scale), td.Normal(torch.zeros_like(z_loc), torch.ones_like(z_scale))).sum(-1)
+    e_logp = (-(z_loc ** 2 + z_scale ** 2) / 2 - LOG_SQRT_2PI).sum(-1)
+    e_logq = (-0.5 - torch.log(z_scale) - LOG_SQRT_2PI).sum(-1)
+    return kl, (beta * e_logp).sum(), (beta * e_logq).sum()
+
+
+def _per_particle(t, P):
+    """(B, n) -> (P*B, n) with row p*B + b = image b; one particle: t itself."""
+    return t if P == 1 or t is None else t.repeat(P, 1)
+
+
+def _renyi_slots(ll, logp, logq, P, b, alpha, weights):
+    """The Renyi bound over P > 1 particles from per-row ll and beta-scaled logp / logq, rows [p][b] (extension 3)."""
+    lw = (ll + logp - logq).view(P, b)
+    a = (1.0 - alpha) * lw
+    if weights is None:
+        logw = torch.log_softmax(a, 0).detach()
+        w = logw.exp()
+        bound = (torch.logsumexp(a, 0) - math.log(P)) / (1.0 - alpha)           # L_b
+    else:
+        w = weights.detach().to(lw.dtype).view(P, b)
+        logw = torch.log(w.clamp_min(torch.finfo(lw.dtype).tiny))
+        # the surrogate: value sum_p w lw + (H(w) - log P) / (1 - alpha) per image, gradient that of sum_p w lw
+        ent = -(w * logw).sum(0)
+        bound = (w * lw).sum(0) + (ent - math.log(P)) / (1.0 - alpha)
+    loss = -bound.sum()
+    wf = w.reshape(-1)
+    t_lp, t_lq = (wf * logp).sum(), (wf * logq).sum()
+    t_ll = -loss - t_lp + t_lq                                                  # sum_b (sum_p w ll + c_b)
+    return dict(loss=loss, ll=t_ll, logpz=t_lp, logqz=t_lq, weights=wf, log_weights=logw.reshape(-1), bound_per_image=bound)
+
+
+def elbo(p: Params, cfg: Config, x, eps, beta=1.0, y=None, grid=None, kl="sampled", particles=1, renyi=None, weights=None):
+    """The bound of iVAE.guide/model (models/ivae.py:165-221).  By default the one-particle Trace_ELBO:
 
     loss = -( sum_b log p(x_b|z_b) + beta*sum_b log N(z_b;0,1) - beta*sum_b log N(z_b;mu_b,sigma_b) ),
     z = mu + sigma*eps (Normal.rsample), summed — not averaged — over the batch.
+
+    kl="analytic", particles=P (eps (P*B, z_dim), rows [p][b]), renyi=alpha and its one-shot `weights`: extensions 1 - 3
+    of the module docstring.  The encoder runs once per image whatever P is.
     """
-    b = x.shape[0]
+    b, P = x.shape[0], int(particles)
+    assert kl in ("sampled", "analytic") and P >= 1
+    assert renyi is None or (kl == "sampled" and renyi != 1.0 and math.isfinite(renyi))
+    assert P == 1 or eps.shape[0] == P * b, "eps must be (particles * batch, z_dim), rows [p][b]"
     z_loc, z_scale = _encode_any(p, cfg, x, y)
-    z = z_loc + z_scale * eps
-    logq = td.Normal(z_loc, z_scale).log_prob(z).sum(-1)                      # guide site "latent"
-    logp = td.Normal(torch.zeros_like(z), torch.ones_like(z)).log_prob(z).sum(-1)   # model site "latent"
+    zl, zs, y = _per_particle(z_loc, P), _per_particle(z_scale, P), _per_particle(y, P)
+    z = zl + zs * eps
+    if kl == "analytic":
+        kl_b, t_lp, t_lq = _kl_and_slots(z_loc, z_scale, beta)                # does not depend on p
+    else:
+        logq = td.Normal(zl, zs).log_prob(z).sum(-1)                          # guide site "latent"
+        logp = td.Normal(torch.zeros_like(z), torch.ones_like(z)).log_prob(z).sum(-1)   # model site "latent"
     loc, xc = decode_from_latent(p, cfg, z, y, grid)
-    ll = likelihood(cfg, loc.reshape(b, -1)).log_prob(x.reshape(b, -1)).sum(-1)     # model site "obs"
-    t_ll, t_lp, t_lq = ll.sum(), (beta * logp).sum(), (beta * logq).sum()
-    loss = -(t_ll + t_lp - t_lq)
-    return dict(loss=loss, ll=t_ll, logpz=t_lp, logqz=t_lq, z_loc=z_loc, z_scale=z_scale, z=z,
-                loc=loc, x_coord_prime=xc, ll_per_sample=ll)
+    ll = likelihood(cfg, loc.reshape(P * b, -1)).log_prob(_per_particle(x.reshape(b, -1), P)).sum(-1)   # model site "obs"
+    out = dict(z_loc=z_loc, z_scale=z_scale, z=z, loc=loc, x_coord_prime=xc, ll_per_sample=ll)
+    if renyi is not None and P > 1:
+        return dict(out, **_renyi_slots(ll, beta * logp, beta * logq, P, b, renyi, weights))
+    t_ll = ll.sum() if P == 1 else ll.sum() / P
+    if kl == "analytic":
+        out.update(loss=-t_ll + (beta * kl_b).sum(), kl=kl_b)
+    else:
+        t_lp, t_lq = (beta * logp).sum(), (beta * logq).sum()
+        if P > 1:
+            t_lp, t_lq = t_lp / P, t_lq / P
+        out.update(loss=-(t_ll + t_lp - t_lq))
+    if renyi is not None:           # one sample: L_b = lw_b whatever alpha is
+        out.update(weights=torch.ones_like(ll), log_weights=torch.zeros_like(ll))
+    return dict(out, ll=t_ll, logpz=t_lp, logqz=t_lq)
 
 
 def jelbo(p: Params, cfg: Config, x, eps, beta=1.0, grid=None):
@@ -532,25 +653,34 @@ def conv_decoder_forward(p: Params, cfg: VedConfig, z, bufs=None, training=True)
     return torch.sigmoid(h) if cfg.sigmoid_d else h
 
 
-def ved_elbo(p: Params, cfg: VedConfig, x, y, eps, beta=1.0, bufs=None, training=True, decisions=None):
+def ved_elbo(p: Params, cfg: VedConfig, x, y, eps, beta=1.0, bufs=None, training=True, decisions=None, kl="sampled"):
     """Trace_ELBO of VED.guide/model (models/ved.py:122-163): z = mu + sigma*eps,
-    loss = -( sum_b log p(y_b | z_b) + beta*sum_b log N(z_b;0,1) - beta*sum_b log N(z_b;mu_b,sigma_b) )."""
+    loss = -( sum_b log p(y_b | z_b) + beta*sum_b log N(z_b;0,1) - beta*sum_b log N(z_b;mu_b,sigma_b) );
+    kl="analytic": extension 1 of the module docstring."""
+    assert kl in ("sampled", "analytic")
     b = x.shape[0]
     z_loc, z_scale = conv_encoder_forward(p, cfg, x, bufs, training, decisions)
     z = z_loc + z_scale * eps
-    logq = td.Normal(z_loc, z_scale).log_prob(z).sum(-1)
-    logp = td.Normal(torch.zeros_like(z), torch.ones_like(z)).log_prob(z).sum(-1)
+    if kl == "analytic":
+        kl_b, t_lp, t_lq = _kl_and_slots(z_loc, z_scale, beta)
+    else:
+        logq = td.Normal(z_loc, z_scale).log_prob(z).sum(-1)
+        logp = td.Normal(torch.zeros_like(z), torch.ones_like(z)).log_prob(z).sum(-1)
     loc = conv_decoder_forward(p, cfg, z, bufs, training)
     ll = likelihood(cfg, loc.flatten(1)).log_prob(y.reshape(b, -1)).sum(-1)
+    out = dict(z_loc=z_loc, z_scale=z_scale, z=z, loc=loc)
+    if kl == "analytic":
+        t_ll = ll.sum()
+        return dict(out, loss=-t_ll + (beta * kl_b).sum(), ll=t_ll, logpz=t_lp, logqz=t_lq, kl=kl_b)
     t_ll, t_lp, t_lq = ll.sum(), (beta * logp).sum(), (beta * logq).sum()
-    return dict(loss=-(t_ll + t_lp - t_lq), ll=t_ll, logpz=t_lp, logqz=t_lq, z_loc=z_loc, z_scale=z_scale, z=z, loc=loc)
+    return dict(out, loss=-(t_ll + t_lp - t_lq), ll=t_ll, logpz=t_lp, logqz=t_lq)
 
 
 class VedOracle:
     """SVI.step for VED restated (same conventions as SVIOracle)."""
 
-    def __init__(self, params: Params, cfg: VedConfig, lr: float = 1e-3, dtype=torch.float32):
-        self.cfg = cfg
+    def __init__(self, params: Params, cfg: VedConfig, lr: float = 1e-3, dtype=torch.float32, kl="sampled"):
+        self.cfg, self.kl = cfg, kl
         # `params`: a state_dict; batch-norm buffers (running_mean / running_var / num_batches_tracked) are split off
         is_buf = lambda k: k.rsplit(".", 1)[-1] in ("running_mean", "running_var", "num_batches_tracked")
         self.p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in params.items() if not is_buf(k)}
@@ -563,7 +693,7 @@ class VedOracle:
 
     def step(self, x, y, eps, beta=1.0) -> float:
         out = ved_elbo(self.p, self.cfg, x.to(self.dtype), y.to(self.dtype), eps.to(self.dtype), beta, self.bufs,
-                       self.training)
+                       self.training, kl=self.kl)
         if out["loss"].requires_grad:
             out["loss"].backward()
         self.last = out
@@ -606,10 +736,15 @@ def param_order(p: Params, cfg: Config) -> List[str]:
 class SVIOracle:
     """SVI.step restated: Trace_ELBO loss -> backward -> Adam(lr, betas=(0.9,0.999), eps=1e-8)
     -> grads set to zero tensors.  `params` is updated in place; tensors are leaf
-    tensors owned by this object (cloned from the dict passed in)."""
+    tensors owned by this object (cloned from the dict passed in).
 
-    def __init__(self, params: Params, cfg: Config, lr: float = 1e-3, dtype=torch.float32):
+    kl / particles / renyi: the objective's switches (elbo's keyword arguments), plain attributes that may be set between
+    calls.  `weights` (set by a test, consumed by the next evaluation): the Renyi surrogate with those weights held fixed."""
+
+    def __init__(self, params: Params, cfg: Config, lr: float = 1e-3, dtype=torch.float32, kl="sampled", particles=1,
+                 renyi=None):
         self.cfg = cfg
+        self.kl, self.particles, self.renyi, self.weights = kl, particles, renyi, None
         is_buf = lambda k: k.rsplit(".", 1)[-1] in ("running_mean", "running_var", "num_batches_tracked")
         self.p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in params.items() if not is_buf(k)}
         self.bufs = {k: v.detach().clone() for k, v in params.items() if is_buf(k)}     # (batch-norm conv encoder)
@@ -625,6 +760,9 @@ class SVIOracle:
         self.last_grads = None
 
     def loss_and_grads(self, x, eps, beta=1.0, y=None):
+        w, self.weights = self.weights, None
+        assert self.cfg.discrete_dim == 0 or (self.kl == "sampled" and self.particles == 1 and self.renyi is None), \
+            "analytic KL, particles and the Renyi bound cover iVAE-class models only"
         if self.cfg.discrete_dim > 0 and getattr(self, "sampled_class", False):
             # SVItrainer(jiVAE, enumerate_parallel=False): y = the drawn class (one-hot) or None (drawn inside)
             out = jelbo_sampled(self.p, self.cfg, x.to(self.dtype), eps.to(self.dtype),
@@ -633,7 +771,7 @@ class SVIOracle:
             out = jelbo(self.p, self.cfg, x.to(self.dtype), eps.to(self.dtype), beta, self.grid)
         else:
             out = elbo(self.p, self.cfg, x.to(self.dtype), eps.to(self.dtype), beta,
-                       None if y is None else y.to(self.dtype), self.grid)
+                       None if y is None else y.to(self.dtype), self.grid, self.kl, self.particles, self.renyi, w)
         if out["loss"].requires_grad:
             out["loss"].backward()
         self.last = out
@@ -652,8 +790,11 @@ class SVIOracle:
         return out["loss"].item()
 
     def draw_eps(self, b):
-        """Normal.rsample's draw: torch.empty(shape).normal_() on the global CPU generator."""
-        return torch.empty(b, self.cfg.z_dim).normal_()
+        """Normal.rsample's draw: torch.empty(shape).normal_() on the global CPU generator; P particles are P sequential
+        draws (P runs of the guide), stacked [p][b]."""
+        if self.particles == 1:
+            return torch.empty(b, self.cfg.z_dim).normal_()
+        return torch.cat([torch.empty(b, self.cfg.z_dim).normal_() for _ in range(self.particles)])
 
     def train_epoch(self, loader, beta=1.0) -> float:
         """SVItrainer.train (trainers/svi.py:95-115)."""
@@ -681,7 +822,8 @@ class SVIOracle:
                 return jencoder_forward(self.p, self.cfg, x.to(self.dtype))      # (mu, sigma, alpha)
             return _encode_any(self.p, self.cfg, x.to(self.dtype), y)
 
-    def decode(self, z, y=None, angle=0.0, shift=0.0, scale=1.0):
+    def decode(self, z, y=None, angle=0.0, shift=0.0, scale=1.0, rate=False):
+        """The decoder's output, (n, *data_dim[, C]); rate=True: a Poisson model's rate instead of its log-rate."""
         cfg = self.cfg
         with torch.no_grad():
             z = z.to(self.dtype)
@@ -690,11 +832,16 @@ class SVIOracle:
             if cfg.coord > 0:
                 g = self.grid.unsqueeze(0)
                 a = torch.as_tensor(angle, dtype=self.dtype).reshape(1)
-                t = torch.as_tensor(shift, dtype=self.dtype).unsqueeze(0)
+                t = torch.as_tensor(shift, dtype=self.dtype).reshape(-1)        # (a 1-D grid takes the first entry, as the model does)
+                t = (t.expand(cfg.ndim) if t.numel() == 1 else t[:cfg.ndim]).unsqueeze(0)
                 s = torch.as_tensor(scale, dtype=self.dtype).reshape(1)
                 g = transform_coordinates(g, a, t, s).squeeze(0)
-                return sdecoder_forward(self.p, cfg, g.expand(z.shape[0], *g.shape), z)
-            return fcdecoder_forward(self.p, cfg, z)
+                out = sdecoder_forward(self.p, cfg, g.expand(z.shape[0], *g.shape), z)
+            else:
+                out = fcdecoder_forward(self.p, cfg, z)
+            if rate and cfg.sampler == "poisson_log":
+                out = torch.exp(out.clamp(max=POISSON_CLAMP))
+            return out
 
 
 # ======================================================================================

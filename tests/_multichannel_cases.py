@@ -1,81 +1,10 @@
 """
-_multichannel_ref.py — the reference of multi-channel models, iVAE(..., channels=C), and the data their tests run on.
-
-Semantics: the data has P = prod(data_dim) grid positions and C values per position, channel-last: x is (B, *data_dim, C).
-The spatial decoder is the single-channel one up to its last hidden layer (one row per sample and position); its output
-layer is Linear(H, C).  The likelihood and the output sigmoid apply per value, log p(x_b | z_b) sums over positions and
-channels, the encoder sees the flattened (B, P*C [+ c_dim]).  A vanilla model's decoder ends in Linear(H, P*C).
-
-oracle/svi_oracle.py decodes one value per position and is not edited: `attach(o, C)` gives an oracle of that module (or of
-tests/_meanfield_ref, _particles_ref, _renyi_ref, which subclass it) a `Config.custom_decoder` — a closure over the oracle's
-OWN parameter dict o.p, so autograd reaches the leaves its Adam steps — that restates the C-output decoder and returns
-(B, P*C) channel-last.  Everything else (encoder, priors, KL forms, likelihoods incl. tests/_poisson_ref.poisson_reference(),
-Adam, the epoch loops) is the oracle's, unchanged.  With C = 1 the closure is oracle.svi_oracle.sdecoder_forward /
-fcdecoder_forward up to the final reshape (tests/test_multichannel_cpu.py pins that to 1e-12 in float64).
+_multichannel_cases.py — the data and the case table the tests of multi-channel models, iVAE(..., channels=C), run on.  The
+reference itself is oracle.svi_oracle with Config(channels=C): x is (B, *data_dim, C), channel-last.
 """
 import torch
-import torch.nn.functional as F
 
 from oracle import svi_oracle as orc
-
-
-def config(dims, inv, **kw):
-    return orc.Config(data_dim=tuple(dims), latent_dim=2, invariances=inv, **kw)
-
-
-def attach(o, C):
-    """Make oracle `o` a C-channel model: its cfg gets the custom decoder described above.  Returns o."""
-    cfg, p = o.cfg, o.p
-    act = orc._ACT[cfg.activation]
-
-    def head(h, b):
-        out = F.linear(h, p["decoder.out.weight"], p["decoder.out.bias"])
-        if cfg.sigmoid_d:
-            out = torch.sigmoid(out)
-        return out.reshape(b, -1)
-
-    if cfg.coord > 0:
-        assert p["decoder.out.weight"].shape[0] == C
-
-        def decoder(x_coord, z):
-            b, n = x_coord.shape[:2]
-            h_x = F.linear(x_coord.reshape(b * n, -1), p["decoder.coord_latent.fc_coord.weight"],
-                           p["decoder.coord_latent.fc_coord.bias"]).reshape(b, n, -1)
-            h_z = F.linear(z, p["decoder.coord_latent.fc_latent.weight"])
-            h = torch.tanh((h_x + h_z.unsqueeze(1)).reshape(b * n, -1))
-            h = orc._fc_stack(p, "decoder.fc_layers", cfg.n_hidden_d, act, h)
-            return head(h, b)                       # rows (b, n) x C values -> (b, n*C): channel-last
-    else:
-        assert p["decoder.out.weight"].shape[0] == cfg.n_pix * C
-
-        def decoder(z):
-            return head(orc._fc_stack(p, "decoder.fc_layers", cfg.n_hidden_d, act, z), z.shape[0])
-
-    cfg.custom_decoder = decoder
-    o.channels = C
-    return o
-
-
-def decode(o, z, y=None, angle=0.0, shift=0.0, scale=1.0):
-    """SVIOracle.decode for an attached oracle: (n, *data_dim, C); Poisson models: the rate."""
-    cfg = o.cfg
-    with torch.no_grad():
-        z = z.to(o.dtype)
-        if y is not None:
-            z = torch.cat([z, y.to(o.dtype)], -1)
-        if cfg.coord > 0:
-            g = o.grid.unsqueeze(0)
-            a = torch.as_tensor(angle, dtype=o.dtype).reshape(1)
-            t = torch.as_tensor(shift, dtype=o.dtype).reshape(-1)          # (a 1-D grid takes the first entry, as the model does)
-            t = (t.expand(cfg.ndim) if t.numel() == 1 else t[:cfg.ndim]).unsqueeze(0)
-            s = torch.as_tensor(scale, dtype=o.dtype).reshape(1)
-            g = orc.transform_coordinates(g, a, t, s).squeeze(0)
-            out = cfg.custom_decoder(g.expand(z.shape[0], *g.shape), z)
-        else:
-            out = cfg.custom_decoder(z)
-        if cfg.sampler == "poisson_log":
-            out = torch.exp(out.clamp(max=30.0))
-        return out.reshape(z.shape[0], *cfg.data_dim, o.channels)
 
 
 # ------------------------------------------------------------------------------- data
@@ -138,8 +67,9 @@ def model_kwargs(c):
 
 
 def case_config(c):
-    return config(c["dims"], c["inv"], c_dim=c.get("c_dim", 0), activation=c.get("activation", "tanh"),
-                  sampler=c.get("sampler", "bernoulli"), sigmoid_d=c.get("sigmoid_d", True))
+    return orc.Config(data_dim=tuple(c["dims"]), latent_dim=2, invariances=c["inv"], channels=c["C"], c_dim=c.get("c_dim", 0),
+                      activation=c.get("activation", "tanh"), sampler=c.get("sampler", "bernoulli"),
+                      sigmoid_d=c.get("sigmoid_d", True))
 
 
 def case_data(c, particles=1):

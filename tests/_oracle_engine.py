@@ -4,6 +4,9 @@ trainer's host logic (data order, eps stream, evaluate semantics, data-parallel 
 with gloo).  Compute is the oracle (test infrastructure); the product never selects it.
 It mimics the engine's device-memory contract: a flat gradient buffer with the 4 ELBO
 scalars in its last slots, `flat` parameters, `adam_step()` that also zeroes the grads.
+The objective's switches are the engine's attributes `kl` / `particles` / `renyi`, which the trainer sets; they are handed
+to the oracle before each call, and every `eps` the engine is handed is recorded in `seen_eps` (what the generator-order
+and data-parallel tests look at).  expect_renyi=True: the trainer must have handed over the bound's order.
 """
 import torch
 
@@ -11,9 +14,15 @@ from oracle import svi_oracle as orc
 
 
 class OracleEngine:
-    def __init__(self, model, cfg, lr=1e-3):
+    kl = "sampled"
+    particles = 1
+    renyi = None
+
+    def __init__(self, model, cfg, lr=1e-3, expect_renyi=False):
         self.model = model
         self.cfg = cfg
+        self.expect_renyi = expect_renyi
+        self.seen_eps = []
         self.o = orc.SVIOracle(model.state_dict(), cfg, lr=lr)
         self.keys = list(self.o.p.keys())
         self.sizes = [self.o.p[k].numel() for k in self.keys]
@@ -34,6 +43,9 @@ class OracleEngine:
                 off += n
 
     def loss_and_grads(self, x, eps, beta=1.0, y=None, want_grads=True, **kw):
+        assert self.renyi is not None or not self.expect_renyi, "the trainer did not hand the engine the bound's order"
+        self.o.kl, self.o.particles, self.o.renyi = self.kl, self.particles, self.renyi
+        self.seen_eps.append(eps.detach().clone())
         self._sync_params_from_flat()
         for p in self.o.p.values():
             p.grad = None

@@ -1,29 +1,14 @@
 """
-_poisson_ref.py — the reference of the Poisson (log link) likelihood, sampler_d="poisson_log", and the count data its
-tests run on.
+_poisson_data.py — the count data the tests of the Poisson (log link) likelihood, sampler_d="poisson_log", run on, and the
+likelihood's formulas restated term by term.  The reference distribution itself is oracle.svi_oracle.likelihood's.
 
 The decoder's output a is the log-rate (sigmoid_d=False).  With a_c = min(a, 30):
 
     log p(x | a) = x a_c - exp(a_c) - lgamma(x + 1)        = torch.distributions.Poisson(exp(a_c)).log_prob(x)
-
-oracle/svi_oracle.py knows the reference's three samplers only and is not edited: `poisson_reference()` wraps
-oracle.svi_oracle.likelihood for the duration of a `with` block so that cfg.sampler == "poisson_log" yields that
-distribution; every other sampler falls through to the original function, which is put back on exit.  Every oracle of the
-suite (SVIOracle, VedOracle, tests/_meanfield_ref, _particles_ref, _renyi_ref, oracle.bf16_plan through SVIOracle) looks the
-function up in that module at call time, so all of them serve as the Poisson reference unchanged inside the block.
 """
-import contextlib
-
 import torch
-import torch.distributions as td
-
-from oracle import svi_oracle as orc
 
 CLAMP = 30.0
-
-
-def poisson_of_logits(a):
-    return td.Poisson(torch.exp(a.clamp(max=CLAMP)), validate_args=False)
 
 
 def log_prob_formula(a, x):
@@ -40,22 +25,6 @@ def dnll_da_formula(a, x):
 def lognorm(x):
     """C = sum lgamma(x + 1) over every image and pixel, float64."""
     return torch.lgamma(x.double() + 1).sum().item()
-
-
-@contextlib.contextmanager
-def poisson_reference():
-    orig = orc.likelihood
-
-    def likelihood(cfg, loc):
-        if cfg.sampler == "poisson_log":
-            return poisson_of_logits(loc)
-        return orig(cfg, loc)
-
-    orc.likelihood = likelihood
-    try:
-        yield
-    finally:
-        orc.likelihood = orig
 
 
 def rates(centres, dims):

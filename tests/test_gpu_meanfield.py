@@ -2,7 +2,7 @@
 GPU tests (-m gpu) of the analytic-KL (mean-field) objective: SVItrainer(loss="TraceMeanField_ELBO"),
 model.engine(kl="analytic"), pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode = PV_KL_ANALYTIC.
 
-The reference is tests/_meanfield_ref.py (oracle.svi_oracle's networks and Adam, torch.distributions.kl_divergence for the
+The reference is oracle.svi_oracle with kl="analytic" (its networks and Adam, torch.distributions.kl_divergence for the
 KL term).  Every case runs from identical parameters at each step, as tests/test_gpu_parity.py's step tests do, and holds
 the kernels to that file's bars for the same path (restated next to each use).
 """
@@ -22,7 +22,6 @@ from conftest import GOLDEN, load_golden, make_x, meta_of
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
-import _meanfield_ref as mf
 
 pytestmark = pytest.mark.gpu
 
@@ -98,7 +97,7 @@ def test_meanfield_steps_vs_reference(gpu_device, name, fused):
     model = pv.models.iVAE(meta["data_dim"], meta["latent_dim"], meta["invariances"], seed=1, device="cuda")
     cfg = orc.Config(data_dim=meta["data_dim"], latent_dim=meta["latent_dim"], invariances=meta["invariances"])
     eng = model.engine(fused=fused, kl="analytic")
-    o = mf.MeanFieldOracle(state(model), cfg)
+    o = orc.SVIOracle(state(model), cfg, kl="analytic")
     x = make_x(meta["xkind"], meta["batch"], meta["data_dim"])
     b = meta["batch"]
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
@@ -151,7 +150,7 @@ def test_meanfield_model_variants_vs_reference(gpu_device, vname, fused):
     eng = model.engine(fused=fused, kl="analytic")
     # ContinuousBernoulli: the float64 reference, as test_model_variants_vs_oracle (torch's fp32 log C(p) cancels near p = 1/2)
     odt = torch.float64 if kw.get("sampler_d") == "continuous_bernoulli" else torch.float32
-    o = mf.MeanFieldOracle(state(model), cfg, dtype=odt)
+    o = orc.SVIOracle(state(model), cfg, dtype=odt, kl="analytic")
     b = 7
     g = torch.Generator().manual_seed(11)
     x = torch.rand(b, *data_dim, generator=g)
@@ -200,7 +199,7 @@ def test_meanfield_on_every_guide_route(gpu_device, route, fused):
     eng.loss_and_grads(x.cuda(), eps.cuda(), 1.3, z_out=(zl, zs))
     assert torch.equal(rec[0], eng.scalars) and torch.equal(rec[1], eng.grad)   # bit-reproducible
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv)
-    o = mf.MeanFieldOracle(state(model), cfg)
+    o = orc.SVIOracle(state(model), cfg, kl="analytic")
     o.step(x, eps, 1.3)
     if fused == 3:      # the throughput precision's bars (test_bf16_mode_steps_vs_golden_and_oracle, batch >= 128)
         check_scalars_and_grads(eng, o, "%s fused=3" % route, loss_rtol=1e-4, grad_bar=3e-2, zl=zl, zs=zs)
@@ -223,7 +222,7 @@ def test_meanfield_bf16_mode_steps_vs_reference(gpu_device, name):
     cfg = orc.Config(data_dim=meta["data_dim"], latent_dim=meta["latent_dim"], invariances=meta["invariances"])
     eng = model.engine(fused=3, kl="analytic")
     assert eng.uses_fused(meta["batch"])
-    o = mf.MeanFieldOracle(state(model), cfg)
+    o = orc.SVIOracle(state(model), cfg, kl="analytic")
     x = make_x(meta["xkind"], meta["batch"], meta["data_dim"])
     b = meta["batch"]
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
@@ -254,7 +253,7 @@ def test_meanfield_convenc_steps_vs_reference(gpu_device, name, fused):
     gold = load_golden(name)
     meta, model, cfg = convenc_model(gold, "cuda")
     eng = model.engine(fused=fused, kl="analytic")
-    o = mf.MeanFieldOracle(state(model), cfg, dtype=torch.float64)
+    o = orc.SVIOracle(state(model), cfg, dtype=torch.float64, kl="analytic")
     x = make_x(meta["xkind"], meta["batch"], meta["data_dim"])
     for k in range(meta["steps"]):
         eps = torch.from_numpy(gold["s%d.eps" % k])
@@ -281,7 +280,7 @@ def test_meanfield_ved_steps_vs_reference(gpu_device, name):
                         hidden_dim_e=c["kw"].get("hidden_dim_e"), hidden_dim_d=c["kw"].get("hidden_dim_d"),
                         activation=c["kw"].get("activation", "lrelu"))
     eng = model.engine(kl="analytic")
-    o = mf.MeanFieldVedOracle(state(model), cfg)
+    o = orc.VedOracle(state(model), cfg, kl="analytic")
     x, y = torch.from_numpy(gold["x"]), torch.from_numpy(gold["y"])
     b = x.shape[0]
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
@@ -309,7 +308,7 @@ def test_meanfield_ved_bf16_mode_vs_reference(gpu_device):
     model = pv.models.VED(c["input_dim"], c["output_dim"], latent_dim=c["latent_dim"], seed=1, device="cuda", **c["kw"])
     cfg = orc.VedConfig(input_dim=c["input_dim"], output_dim=c["output_dim"], latent_dim=c["latent_dim"])
     eng = model.engine(fused=3, kl="analytic")
-    o = mf.MeanFieldVedOracle(state(model), cfg)
+    o = orc.VedOracle(state(model), cfg, kl="analytic")
     x, y = torch.from_numpy(gold["x"]), torch.from_numpy(gold["y"])
     for k in range(c["steps"]):
         eps = torch.from_numpy(gold["s%d.eps" % k])
@@ -388,7 +387,7 @@ def test_meanfield_user_defined_modules(gpu_device, inv, which):
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv, custom_encoder=re_, custom_decoder=rd)
     lib_params = {k: v.cpu() for k, v in model.state_dict().items()
                   if not (ue is not None and k.startswith("encoder_z.")) and not (ud is not None and k.startswith("decoder."))}
-    o = mf.MeanFieldOracle(lib_params, cfg)
+    o = orc.SVIOracle(lib_params, cfg, kl="analytic")
     user = [m_ for m_ in (ue, ud) if m_ is not None]
     refs = [m_ for m_ in (re_, rd) if m_ is not None]
     ref_params = [q for m_ in refs for q in m_.parameters()]
@@ -441,7 +440,7 @@ def test_meanfield_trainer_epochs_vs_reference(gpu_device):
         trainer.step(tl, sl, scale_factor=1.5)
     from pyroved_amd.utils import set_deterministic_mode
     set_deterministic_mode(1)
-    o = mf.MeanFieldOracle(init, orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv))
+    o = orc.SVIOracle(init, orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv), kl="analytic")
     tl, sl = loaders()
     want_train, want_test = [], []
     for _ in range(3):
@@ -565,7 +564,7 @@ def test_meanfield_elbo_terms_and_row_elbo_agree_with_the_scalars(gpu_device, fu
     x, eps = torch.rand(b, *data_dim, generator=g), torch.randn(b, 5, generator=g)
     model = pv.models.iVAE(data_dim, 2, inv, seed=1, device="cuda")
     eng = model.engine(fused=fused, kl="analytic")
-    o = mf.MeanFieldOracle(state(model), orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv))
+    o = orc.SVIOracle(state(model), orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv), kl="analytic")
     o.step(x, eps, beta)
     terms = model.elbo_terms(x, eps=eps, scale_factor=beta)
     tol = 5e-4 if fused == 3 else RTOL_ELBO
@@ -617,7 +616,7 @@ def test_meanfield_differs_from_the_sampled_objective(gpu_device, fused):
     np.testing.assert_allclose(av[0] - sv[0], (av[3] - av[2]) - (sv[3] - sv[2]), rtol=0, atol=4e-6 * abs(sv[0]))
     assert gdiff > 10 * (3e-2 if fused == 3 else RTOL_GRAD)
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv)
-    for kl, oracle in (("sampled", orc.SVIOracle), ("analytic", mf.MeanFieldOracle)):
-        o = oracle(state(model), cfg)
+    for kl in ("sampled", "analytic"):
+        o = orc.SVIOracle(state(model), cfg, kl=kl)
         ref = o.step(x, eps, 1.0)
         np.testing.assert_allclose(out[kl][0][0].item(), ref, rtol=5e-4 if fused == 3 else RTOL_ELBO)

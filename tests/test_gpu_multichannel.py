@@ -2,9 +2,8 @@
 GPU tests (-m gpu) of multi-channel models: iVAE(..., channels=C), x of shape (B, *data_dim, C), the spatial decoder's output
 layer Linear(H, C) on the C-output likelihood kernel (pv_out_lik_mc) of the layer-by-layer path.
 
-The reference is the project's own float64 oracles, unchanged, with the C-output decoder attached
-(tests/_multichannel_ref.attach; Poisson inside tests/_poisson_ref.poisson_reference()).  Cases, data and eps come from
-tests/_multichannel_ref.CASES / case_data (torch.Generator().manual_seed(0): data first, then the eps draws).  Every step
+The reference is the project's own float64 oracle (oracle.svi_oracle) with Config(channels=C).  Cases, data and eps come from
+tests/_multichannel_cases.CASES / case_data (torch.Generator().manual_seed(0): data first, then the eps draws).  Every step
 case runs two steps with Adam between, each from identical float32 parameters, at the bars of tests/test_gpu_parity.py:
 loss and ll 2e-5 (+ the atol test_model_variants_vs_oracle gives the sampler), the KL scalars 1e-4, every gradient tensor
 1e-4 relative L2, parameters after Adam by check_params_after_adam's rule with the 5e-5 bar (its 1 % cap is confirmed with
@@ -17,11 +16,7 @@ import torch
 
 import pyroved_amd as pv
 from oracle import svi_oracle as orc
-import _meanfield_ref as mf
-import _particles_ref as pref
-import _renyi_ref as rr
-import _poisson_ref as pr
-import _multichannel_ref as mc
+import _multichannel_cases as mc
 from test_gpu_meanfield import check_params_after_adam, rel_l2, state, RTOL_ELBO, RTOL_GRAD, LR
 from test_gpu_renyi import weight_check
 
@@ -36,8 +31,7 @@ def _reference_setup():
     n = torch.get_num_threads()
     torch.set_num_threads(16)                      # (the float64 references)
     try:
-        with pr.poisson_reference():
-            yield
+        yield
     finally:
         torch.set_num_threads(n)
 
@@ -99,7 +93,7 @@ def run_steps(name, fused, make_oracle, engine_kw=None, particles=1):
     b, n_obs = c["b"], int(np.prod(c["dims"])) * c["C"]
     assert eng.uses_fused(b) is False and eng.supports_dp_step is False
     x, y, eps = mc.case_data(c, particles)
-    o = mc.attach(make_oracle(state(model), mc.case_config(c)), c["C"])
+    o = make_oracle(state(model), mc.case_config(c))
     z_dim = o.cfg.z_dim
     zl, zs = torch.empty(b, z_dim, device="cuda"), torch.empty(b, z_dim, device="cuda")
     loc = torch.full((particles * b, n_obs), float("nan"), device="cuda")
@@ -133,7 +127,7 @@ def test_steps_vs_reference(gpu_device, name, fused):
     zc = z_loc[:, -2:] if c["inv"] else z_loc
     dec = model.decode(zc, y)
     assert tuple(dec.shape) == shape
-    want = mc.decode(o, zc, y)
+    want = o.decode(zc, y, rate=True)
     print("%s: decode max abs error %.2e" % (name, (dec.double() - want).abs().max().item()))
     np.testing.assert_allclose(dec.numpy(), want.numpy(), rtol=1e-4, atol=2e-6)
 
@@ -153,7 +147,7 @@ def test_both_requests_run_the_same_launches(gpu_device):
 def test_elbo_terms_and_manifold(gpu_device):
     c, model, eng = make(CASE1)
     x, y, eps = mc.case_data(c)
-    o = mc.attach(orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64), c["C"])
+    o = orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64)
     with torch.no_grad():
         ref = orc.elbo(o.p, o.cfg, x.double(), eps[0].double(), 1.0, None, o.grid)
     t = model.elbo_terms(x, eps=eps[0])
@@ -167,11 +161,11 @@ def test_elbo_terms_and_manifold(gpu_device):
 
 # ------------------------------------------------------------------------------- 2. the other objectives, on case 1's shape
 def test_analytic_kl_steps(gpu_device):
-    run_steps(CASE1, 2, lambda p, cfg: mf.MeanFieldOracle(p, cfg, lr=LR, dtype=torch.float64), dict(kl="analytic"))
+    run_steps(CASE1, 2, lambda p, cfg: orc.SVIOracle(p, cfg, lr=LR, dtype=torch.float64, kl="analytic"), dict(kl="analytic"))
 
 
 def test_three_particles_steps(gpu_device):
-    run_steps(CASE1, 2, lambda p, cfg: pref.ParticlesOracle(p, cfg, 3, lr=LR, dtype=torch.float64), dict(particles=3), particles=3)
+    run_steps(CASE1, 2, lambda p, cfg: orc.SVIOracle(p, cfg, lr=LR, dtype=torch.float64, particles=3), dict(particles=3), particles=3)
 
 
 def test_renyi_steps_with_the_weights_held(gpu_device):
@@ -188,10 +182,10 @@ def test_renyi_steps_with_the_weights_held(gpu_device):
         tag = "renyi step %d" % k
         eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, z_out=(zl, zs), weights_out=w)
         torch.cuda.synchronize()
-        free = mc.attach(rr.RenyiOracle(state(model), mc.case_config(c), P, alpha, lr=LR, dtype=torch.float64), c["C"])
+        free = orc.SVIOracle(state(model), mc.case_config(c), lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
         of = free.loss_and_grads(x, eps[k], 1.0)
         if held is None:
-            held = mc.attach(rr.RenyiOracle(state(model), mc.case_config(c), P, alpha, lr=LR, dtype=torch.float64), c["C"])
+            held = orc.SVIOracle(state(model), mc.case_config(c), lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
         held.weights = w.detach().cpu().double()
         held.step(x, eps[k], 1.0)
         weight_check(tag, w, of, alpha, RTOL_ELBO)
@@ -223,13 +217,13 @@ def test_repeated_call_is_bit_identical(gpu_device, name):
 @pytest.mark.parametrize("name", [CASE1, "c03_1d16_t_c4_b5_gelu"])
 def test_decode_with_angle_shift_scale(gpu_device, name):
     c, model, eng = make(name)
-    o = mc.attach(orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64), c["C"])
+    o = orc.SVIOracle(state(model), mc.case_config(c), dtype=torch.float64)
     z = torch.randn(5, 2, generator=torch.Generator().manual_seed(2))
     dec = model.decode(z, angle=0.3, shift=[0.1, -0.2], scale=1.2)
     assert tuple(dec.shape) == (5,) + tuple(c["dims"]) + (c["C"],)
-    want = mc.decode(o, z, None, 0.3, [0.1, -0.2], 1.2)
+    want = o.decode(z, None, 0.3, [0.1, -0.2], 1.2, rate=True)
     np.testing.assert_allclose(dec.numpy(), want.numpy(), rtol=1e-4, atol=2e-6)
-    plain = mc.decode(o, z)
+    plain = o.decode(z, rate=True)
     assert (plain - want).abs().max().item() > 1e-3             # (the transform does something)
 
 
@@ -248,7 +242,7 @@ def test_trainer_history_and_weights_round_trip(gpu_device, tmp_path):
         tr.step(loader)
     torch.cuda.synchronize()
     torch.set_rng_state(st)
-    o = mc.attach(orc.SVIOracle(params0, mc.case_config(c), lr=LR), c["C"])
+    o = orc.SVIOracle(params0, mc.case_config(c), lr=LR)
     want = [o.train_epoch(loader) for _ in range(2)]
     print("trainer: history %s, reference %s" % (tr.loss_history["training_loss"], want))
     np.testing.assert_allclose(tr.loss_history["training_loss"], want, rtol=1e-4)

@@ -2,7 +2,7 @@
 GPU tests (-m gpu) of the multi-particle ELBO: SVItrainer(num_particles=P), model.engine(particles=P),
 pv_ivae_particles_loss_and_grads / pv_ivae_particles_step.
 
-The reference is tests/_particles_ref.py (oracle.svi_oracle's networks and Adam; one encoder pass, P decoder samples per
+The reference is oracle.svi_oracle with particles=P (its networks and Adam; one encoder pass, P decoder samples per
 image ordered [p][b], the mean over particles).  Inputs are conftest.make_x and eps from a seeded torch.Generator.  The
 bars are those tests/test_gpu_parity.py and tests/test_gpu_meanfield.py hold the same path to, restated next to each
 use; averaging over particles loosens none of them.  Shapes are the smallest at which each new piece can go wrong.
@@ -19,7 +19,6 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
-import _particles_ref as pr
 # the throughput precision's helpers and ceilings (importable: used as they are)
 from test_gpu_bf16_emulated import _judge, _kernel_name, _cus, GRAD_CEIL, LOSS_CEIL, SELF_CHECK, LIK
 
@@ -41,8 +40,7 @@ def state(model):
 
 
 def oracle_of(kl, params, cfg, P, dtype=torch.float32):
-    cls = pr.ParticlesMeanFieldOracle if kl == "analytic" else pr.ParticlesOracle
-    return cls(params, cfg, P, lr=LR, dtype=dtype)
+    return orc.SVIOracle(params, cfg, lr=LR, dtype=dtype, kl=kl, particles=P)
 
 
 def check_scalars_and_grads(eng, o, tag, zl=None, zs=None):

@@ -1,9 +1,8 @@
 """
 GPU tests (-m gpu) of the Poisson (log link) likelihood for count data: sampler_d="poisson_log" / PV_LIK_POISSON_LOG.
 
-The reference is the project's own oracles, unchanged, inside tests/_poisson_ref.poisson_reference() (which makes
-oracle.svi_oracle.likelihood yield torch.distributions.Poisson(exp(min(a, 30))) for that sampler).  Inputs are counts
-(tests/_poisson_ref.counts: rates 1 .. 3 around a blob per image), drawn from torch.Generator().manual_seed(0): centres, counts,
+The reference is the project's own oracle (oracle.svi_oracle.likelihood yields torch.distributions.Poisson(exp(min(a, 30)))
+for that sampler).  Inputs are counts (tests/_poisson_data.counts: rates 1 .. 3 around a blob per image), drawn from torch.Generator().manual_seed(0): centres, counts,
 then the eps draws.  Every step case runs from identical parameters at each step, two steps, Adam between, and is held to the
 bars of the existing step tests for the same path (restated next to each use).  The reported loss includes the data-only
 normaliser C = sum lgamma(x + 1), which the kernels leave to pv_poisson_lognorm.
@@ -20,10 +19,7 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
-import _meanfield_ref as mf
-import _particles_ref as pref
-import _renyi_ref as rr
-import _poisson_ref as pr
+import _poisson_data as pr
 from test_gpu_meanfield import check_scalars_and_grads, check_params_after_adam, rel_l2, state, RTOL_ELBO, RTOL_GRAD, LR
 from test_gpu_bf16_emulated import _judge, _kernel_name, _cus, GRAD_CEIL, LOSS_CEIL, LOC_CEIL, SELF_CHECK
 
@@ -38,8 +34,7 @@ def _poisson_oracle():
     n = torch.get_num_threads()
     torch.set_num_threads(16)                      # (the float64 references)
     try:
-        with pr.poisson_reference():
-            yield
+        yield
     finally:
         torch.set_num_threads(n)
 
@@ -221,7 +216,7 @@ def _bf16_setup(name):
 @pytest.mark.parametrize("name", sorted(BF16_CASES))
 def test_poisson_bf16_step_vs_emulated_reference(gpu_device, name):
     """fused = 3 (which build the size rule selects: see _bf16_setup) against the reference that rounds where the kernel rounds (oracle/bf16_plan.py emulates the decoder up to the
-    logit; the likelihood is the wrapped function), with tests/test_gpu_bf16_emulated.py's judge; then the forward-only launch:
+    logit; the likelihood is the oracle's), with tests/test_gpu_bf16_emulated.py's judge; then the forward-only launch:
     loss and loc (the rate) against the same emulation."""
     model, eng, x, eps, dims, inv, b, kernel = _bf16_setup(name)
     zl, zs = torch.empty(b, model.z_dim, device="cuda"), torch.empty(b, model.z_dim, device="cuda")
@@ -275,7 +270,7 @@ def test_poisson_analytic_kl_steps_vs_reference(gpu_device, fused):
     model, cfg, x, eps = _obj_inputs(1)
     b = OBJ["b"]
     eng = model.engine(fused=fused, kl="analytic")
-    o = mf.MeanFieldOracle(state(model), cfg, lr=LR, dtype=torch.float64)
+    o = orc.SVIOracle(state(model), cfg, lr=LR, dtype=torch.float64, kl="analytic")
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
     for k in range(2):
         tag = "poisson analytic fused=%d step %d" % (fused, k)
@@ -294,7 +289,7 @@ def test_poisson_three_particle_steps_vs_reference(gpu_device, fused):
     model, cfg, x, eps = _obj_inputs(OBJ["P"])
     b, P = OBJ["b"], OBJ["P"]
     eng = model.engine(fused=fused, particles=P)
-    o = pref.ParticlesOracle(state(model), cfg, P, lr=LR, dtype=torch.float64)
+    o = orc.SVIOracle(state(model), cfg, lr=LR, dtype=torch.float64, particles=P)
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
     for k in range(2):
         tag = "poisson P=3 fused=%d step %d" % (fused, k)

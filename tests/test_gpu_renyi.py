@@ -2,7 +2,7 @@
 GPU tests (-m gpu) of the importance-weighted (Renyi / IWAE) bound: SVItrainer(loss="RenyiELBO"),
 model.engine(particles=P, renyi=alpha), pv_ivae_renyi_loss_and_grads / pv_ivae_renyi_step.
 
-The reference is tests/_renyi_ref.py (oracle.svi_oracle's networks and Adam; one encoder pass, P decoder samples per image
+The reference is oracle.svi_oracle with renyi=alpha (its networks and Adam; one encoder pass, P decoder samples per image
 ordered [p][b], the softmax-weighted bound) in float64.  Shapes, seeds and beta are tests/test_gpu_particles.py's STEP_CASES;
 tests/test_renyi_cpu.py confirms with the reference alone that their weights are spread (ESS >= 1.9 on some image) and
 that the bound sits more than 0.25 nats above the ELBO.
@@ -26,7 +26,6 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
-import _renyi_ref as rr
 from test_gpu_particles import (STEP_CASES, STEP_SEEDS, step_case, state, rel_l2, check_params_after_adam,
                                 RTOL_ELBO, RTOL_KL, RTOL_GRAD, LR)
 # the throughput precision's helpers and ceilings (importable: used as they are)
@@ -87,11 +86,11 @@ def _free_and_held(params, cfg, P, alpha, x, eps, beta, y, w_gpu, held=None):
     """The float64 reference twice: the bound itself (free weights) from `params`, and the oracle `held` (made from `params`
     when not given: it carries Adam's state from step to step) that takes the Adam step on the gradient with the engine's
     weights held."""
-    free = rr.RenyiOracle(params, cfg, P, alpha, lr=LR, dtype=torch.float64)
+    free = orc.SVIOracle(params, cfg, lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
     of = free.loss_and_grads(x, eps, beta, y)
     g_free = {k: v.grad.detach().clone() for k, v in free.p.items()}
     if held is None:
-        held = rr.RenyiOracle(params, cfg, P, alpha, lr=LR, dtype=torch.float64)
+        held = orc.SVIOracle(params, cfg, lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
     held.weights = w_gpu.detach().cpu().double()
     held.step(x, eps, beta, y)
     return of, g_free, held
@@ -164,11 +163,11 @@ def _bf16_body(which):
 
     def reference(plan):
         c = orc.Config(data_dim=cfg.data_dim, latent_dim=2, invariances=cfg.invariances, bf16_plan=plan)
-        free = rr.RenyiOracle(params, c, P, alpha, dtype=torch.float64)
+        free = orc.SVIOracle(params, c, dtype=torch.float64, particles=P, renyi=alpha)
         with torch.set_grad_enabled(plan is None):           # (float64: also the free-weight gradient, for the end-to-end figure)
             out = free.loss_and_grads(x, eps[0], beta)
         g_free = {k: v.grad.detach().clone() for k, v in free.p.items()} if plan is None else None
-        o = rr.RenyiOracle(params, c, P, alpha, dtype=torch.float64)
+        o = orc.SVIOracle(params, c, dtype=torch.float64, particles=P, renyi=alpha)
         o.weights = wc
         o.loss_and_grads(x, eps[0], beta)
         return out, {k: v.grad.detach().clone() for k, v in o.p.items()}, g_free
@@ -338,7 +337,7 @@ def test_trainer_with_three_particles_vs_reference_loop(gpu_device):
     torch.cuda.synchronize()
     torch.set_rng_state(st)
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv)
-    o = rr.RenyiOracle(params0, cfg, P, alpha, lr=LR, dtype=torch.float64)
+    o = orc.SVIOracle(params0, cfg, lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
     want = [o.train_epoch(loader) for _ in range(2)]
     print("trainer RenyiELBO P=3 alpha=0.5: history %s, reference %s" % (tr.loss_history["training_loss"], want))
     np.testing.assert_allclose(tr.loss_history["training_loss"], want, rtol=RTOL_ELBO)

@@ -1,6 +1,6 @@
 """
 The analytic-KL (mean-field) objective — SVItrainer(loss="TraceMeanField_ELBO"), engine(kl="analytic"), plan.kl_mode —
-where no GPU is needed: the reference helper itself (tests/_meanfield_ref.py), the trainer's argument handling, the ABI
+where no GPU is needed: the reference itself (oracle.svi_oracle with kl="analytic"), the trainer's argument handling, the ABI
 struct and the library's plan validation (host arithmetic).
 """
 import ctypes as C
@@ -16,7 +16,6 @@ from conftest import ROOT
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
-import _meanfield_ref as mf
 
 
 def _params(cfg, seed=0):
@@ -40,7 +39,7 @@ def test_helper_loss_and_gradients_equal_the_formulas_in_float64(data_dim, inv):
     b, beta = 5, 1.7
     x = torch.rand(b, *data_dim, generator=g, dtype=torch.float64)
     eps = torch.randn(b, cfg.z_dim, generator=g, dtype=torch.float64)
-    out = mf.meanfield_elbo(p, cfg, x, eps, beta)
+    out = orc.elbo(p, cfg, x, eps, beta, kl="analytic")
     mu, sig = out["z_loc"], out["z_scale"]
     kl = (0.5 * (sig ** 2 + mu ** 2 - 1.0) - torch.log(sig)).sum()
     want = -out["ll"] + beta * kl
@@ -67,7 +66,7 @@ def test_sampled_kl_converges_to_the_analytic_one():
     b, beta, n = 6, 1.3, 4096
     x = torch.rand(b, 8, 8, generator=g, dtype=torch.float64)
     with torch.no_grad():
-        ref = mf.meanfield_elbo(p, cfg, x, torch.zeros(b, cfg.z_dim, dtype=torch.float64), beta)
+        ref = orc.elbo(p, cfg, x, torch.zeros(b, cfg.z_dim, dtype=torch.float64), beta, kl="analytic")
         want = (ref["logqz"] - ref["logpz"]).item()
         assert abs(want - beta * ref["kl"].sum().item()) < 1e-12 * abs(want)
         draws = torch.empty(n, dtype=torch.float64)
@@ -81,7 +80,7 @@ def test_sampled_kl_converges_to_the_analytic_one():
 def test_meanfield_oracle_inherits_adam_and_epochs():
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"])
     p = {k: v.float() for k, v in _params(cfg).items()}
-    o, s = mf.MeanFieldOracle(p, cfg), orc.SVIOracle(p, cfg)
+    o, s = orc.SVIOracle(p, cfg, kl="analytic"), orc.SVIOracle(p, cfg)
     g = torch.Generator().manual_seed(1)
     x, eps = torch.rand(4, 8, 8, generator=g), torch.randn(4, cfg.z_dim, generator=g)
     l0, l1 = o.step(x, eps), s.step(x, eps)

@@ -1,6 +1,6 @@
 """
 The multi-particle ELBO — SVItrainer(num_particles=P), engine(particles=P), pv_ivae_particles_* — where no GPU is needed:
-the reference itself (tests/_particles_ref.py) against the oracles it extends, the trainer's argument handling and
+the reference itself (oracle.svi_oracle with particles=P) against its one-particle path, the trainer's argument handling and
 generator order, a two-rank gloo run, and the library's entry points as far as they are host arithmetic.
 """
 import ctypes as C
@@ -17,9 +17,7 @@ from conftest import ROOT
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
-import _meanfield_ref as mf
-import _particles_ref as pr
-from _particles_engine import ParticlesOracleEngine
+from _oracle_engine import OracleEngine
 
 
 def _params(cfg, seed=0, c_dim=0):
@@ -42,18 +40,20 @@ def _inputs(cfg, b, P, seed=3, c_dim=0):
 
 # (data_dim, invariances, c_dim)
 CASES = [((8, 8), ["r", "t", "s"], 0), ((16,), ["t"], 0), ((8, 8), None, 0), ((8, 8), ["r", "t"], 3)]
-PAIRS = [(pr.ParticlesOracle, orc.SVIOracle), (pr.ParticlesMeanFieldOracle, mf.MeanFieldOracle)]
+# the KL form of the particle oracle and of its one-particle parent (the ids are the ones these cases have always had)
+PAIRS = [pytest.param("sampled", id="ParticlesOracle-SVIOracle"),
+         pytest.param("analytic", id="ParticlesMeanFieldOracle-MeanFieldOracle")]
 SLOTS = ("loss", "ll", "logpz", "logqz")
 
 
 # ------------------------------------------------------------------------------- the reference against its parents
 @pytest.mark.parametrize("data_dim,inv,c_dim", CASES)
-@pytest.mark.parametrize("new,parent", PAIRS)
-def test_reference_with_one_particle_is_the_parent_oracle(new, parent, data_dim, inv, c_dim):
+@pytest.mark.parametrize("kl", PAIRS)
+def test_reference_with_one_particle_is_the_parent_oracle(kl, data_dim, inv, c_dim):
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv, c_dim=c_dim)
     p = _params(cfg, c_dim=c_dim)
     x, eps, y = _inputs(cfg, 5, 1, c_dim=c_dim)
-    a, b = new(p, cfg, 1, dtype=torch.float64), parent(p, cfg, dtype=torch.float64)
+    a, b = orc.SVIOracle(p, cfg, dtype=torch.float64, kl=kl, particles=1), orc.SVIOracle(p, cfg, dtype=torch.float64, kl=kl)
     oa, ob = a.loss_and_grads(x, eps, 1.7, y), b.loss_and_grads(x, eps, 1.7, y)
     for k in SLOTS + ("z_loc", "z_scale", "loc"):
         assert torch.equal(oa[k], ob[k]), k
@@ -62,19 +62,19 @@ def test_reference_with_one_particle_is_the_parent_oracle(new, parent, data_dim,
 
 
 @pytest.mark.parametrize("data_dim,inv,c_dim", CASES)
-@pytest.mark.parametrize("new,parent", PAIRS)
-def test_reference_with_three_particles_is_the_mean_of_three_parent_evaluations(new, parent, data_dim, inv, c_dim):
+@pytest.mark.parametrize("kl", PAIRS)
+def test_reference_with_three_particles_is_the_mean_of_three_parent_evaluations(kl, data_dim, inv, c_dim):
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv, c_dim=c_dim)
     p = _params(cfg, c_dim=c_dim)
     b, P, beta = 5, 3, 1.7
     x, eps, y = _inputs(cfg, b, P, c_dim=c_dim)
-    a = new(p, cfg, P, dtype=torch.float64)
+    a = orc.SVIOracle(p, cfg, dtype=torch.float64, kl=kl, particles=P)
     oa = a.loss_and_grads(x, eps, beta, y)
     assert abs((oa["loss"] + (oa["ll"] + oa["logpz"] - oa["logqz"])).item()) <= 1e-12 * abs(oa["loss"].item())
     assert oa["z_loc"].shape == (b, cfg.z_dim) and oa["loc"].shape[0] == P * b
     outs, grads = [], []
     for q in range(P):
-        o = parent(p, cfg, dtype=torch.float64)
+        o = orc.SVIOracle(p, cfg, dtype=torch.float64, kl=kl)
         outs.append(o.loss_and_grads(x, eps[q * b:(q + 1) * b], beta, y))
         grads.append({k: v.grad for k, v in o.p.items()})
     for k in SLOTS:
@@ -91,7 +91,7 @@ def test_reference_with_three_particles_is_the_mean_of_three_parent_evaluations(
 def test_reference_oracles_inherit_adam_and_draw_particles_in_order():
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"])
     p = {k: v.float() for k, v in _params(cfg).items()}
-    o = pr.ParticlesOracle(p, cfg, 3, dtype=torch.float32)
+    o = orc.SVIOracle(p, cfg, dtype=torch.float32, particles=3)
     torch.manual_seed(4)
     eps = o.draw_eps(5)
     torch.manual_seed(4)
@@ -181,7 +181,7 @@ def test_epoch_consumes_the_generator_as_sequential_particle_draws(inv, n, batch
     assert (batch * cfg.z_dim) % 16 == (2 if inv == ["r"] else 0)
     x = torch.rand(n, 8, 8, generator=torch.Generator().manual_seed(9))
     loader = pv.utils.init_dataloader(x, batch_size=batch)
-    eng = ParticlesOracleEngine(model, cfg)
+    eng = OracleEngine(model, cfg)
     tr = pv.trainers.SVItrainer(model, seed=1, engine=eng, device="cpu", num_particles=P, device_feed=device_feed)
     st0 = torch.get_rng_state()
     tr.step(loader)
@@ -202,7 +202,7 @@ def _dp_run(P, analytic):
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=inv)
     x = torch.rand(10, 8, 8, generator=torch.Generator().manual_seed(5))
     loader = pv.utils.init_dataloader(x, batch_size=5)              # two steps; two ranks take 3 + 2 rows of each
-    eng = ParticlesOracleEngine(model, cfg, analytic=analytic)
+    eng = OracleEngine(model, cfg)                                  # (the trainer hands it kl="analytic" with that loss)
     tr = pv.trainers.SVItrainer(model, loss="TraceMeanField_ELBO" if analytic else None, seed=1, engine=eng, device="cpu",
                                 num_particles=P)
     tr.step(loader)

@@ -1,6 +1,6 @@
 """
 The Poisson (log link) likelihood — sampler_d="poisson_log", PV_LIK_POISSON_LOG — where no GPU is needed: the reference
-(tests/_poisson_ref.py) against torch.distributions.Poisson and autograd, the sampler and the ABI constants, plan validation
+(oracle.svi_oracle.likelihood, the formulas of tests/_poisson_data.py) against torch.distributions.Poisson and autograd, the sampler and the ABI constants, plan validation
 through the library's workspace queries (host arithmetic), what the engines refuse at construction, and the condition the GPU
 step tests' parameter check rests on (near-zero gradient entries below 1 % per tensor, with the reference alone).
 """
@@ -18,7 +18,7 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from pyroved_amd.engine import UnsupportedModel
 from oracle import svi_oracle as orc
-import _poisson_ref as pr
+import _poisson_data as pr
 
 
 # ------------------------------------------------------------------------------- the reference
@@ -34,16 +34,14 @@ def test_formula_and_gradient_equal_torch_poisson_in_float64():
     (-lp.sum()).backward()
     torch.testing.assert_close(pr.dnll_da_formula(a.detach(), x), a.grad, rtol=1e-13, atol=1e-13)
     assert a.grad[0].item() == 0.0 and a.grad[1].item() != 0.0      # the clamp's gradient: nothing above 30, everything at it
-    # the wrapped oracle likelihood is that distribution; every other sampler is the original's
+    # the oracle's likelihood is that distribution; every other sampler is what it was, and an unknown one is no sampler
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"], sampler="poisson_log", sigmoid_d=False)
+    assert orc.POISSON_CLAMP == pr.CLAMP == 30.0
+    torch.testing.assert_close(orc.likelihood(cfg, a.detach()).log_prob(x), lp.detach(), rtol=0, atol=0)
+    bern = orc.likelihood(orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"]), torch.sigmoid(a.detach()))
+    assert isinstance(bern, td.Bernoulli)
     with pytest.raises(KeyError):
-        orc.likelihood(cfg, a.detach())
-    orig = orc.likelihood
-    with pr.poisson_reference():
-        torch.testing.assert_close(orc.likelihood(cfg, a.detach()).log_prob(x), lp.detach(), rtol=0, atol=0)
-        bern = orc.likelihood(orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"]), torch.sigmoid(a.detach()))
-        assert isinstance(bern, td.Bernoulli)
-    assert orc.likelihood is orig
+        orc.likelihood(orc.Config(data_dim=(8, 8), latent_dim=2, invariances=["r"], sampler="poisson"), a.detach())
 
 
 def test_counts_recipe():
@@ -188,13 +186,12 @@ def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent():
     share reaches 2 - 27 % in encoder_z.fc_layers.0.weight)."""
     from test_gpu_poisson import STEP_CASES, step_case
     torch.set_num_threads(min(8, torch.get_num_threads()))
-    with pr.poisson_reference():
-        for name in sorted(STEP_CASES):
-            model, cfg, x, y, eps, b = step_case(name, "cpu")
-            o = orc.SVIOracle({k: v.detach() for k, v in model.state_dict().items()}, cfg, dtype=torch.float64)
-            o.sampled_class = STEP_CASES[name].get("sampled", False)
-            for k in range(2):
-                o.step(x, eps[k], 1.0, y[k] if isinstance(y, list) else y)
-                for key, g in o.last_grads.items():
-                    share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
-                    assert share < 0.01, (name, k, key, share)
+    for name in sorted(STEP_CASES):
+        model, cfg, x, y, eps, b = step_case(name, "cpu")
+        o = orc.SVIOracle({k: v.detach() for k, v in model.state_dict().items()}, cfg, dtype=torch.float64)
+        o.sampled_class = STEP_CASES[name].get("sampled", False)
+        for k in range(2):
+            o.step(x, eps[k], 1.0, y[k] if isinstance(y, list) else y)
+            for key, g in o.last_grads.items():
+                share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
+                assert share < 0.01, (name, k, key, share)

@@ -1,6 +1,6 @@
 """
 The importance-weighted (Renyi / IWAE) bound — SVItrainer(loss="RenyiELBO"), engine(particles=P, renyi=alpha),
-pv_ivae_renyi_* — where no GPU is needed: the reference itself (tests/_renyi_ref.py) against the oracles it extends, the
+pv_ivae_renyi_* — where no GPU is needed: the reference itself (oracle.svi_oracle with renyi=alpha) against its other objectives, the
 trainer's argument handling and generator order, a two-rank gloo run, the library's entry points as far as they are host
 arithmetic, and the condition tests/test_gpu_renyi.py puts on its inputs.
 """
@@ -19,9 +19,7 @@ from conftest import ROOT
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
-import _particles_ref as pr
-import _renyi_ref as rr
-from _renyi_engine import RenyiOracleEngine
+from _oracle_engine import OracleEngine
 from test_particles_cpu import _params, _inputs, _small_plan, _free_port, _plain_loop, _StandInEngine, _ivae, CASES, SLOTS, PLAN_FIELDS
 
 
@@ -37,7 +35,7 @@ def test_reference_with_one_particle_is_the_svi_oracle(data_dim, inv, c_dim, alp
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv, c_dim=c_dim)
     p = _params(cfg, c_dim=c_dim)
     x, eps, y = _inputs(cfg, 5, 1, c_dim=c_dim)
-    a, b = rr.RenyiOracle(p, cfg, 1, alpha, dtype=torch.float64), orc.SVIOracle(p, cfg, dtype=torch.float64)
+    a, b = orc.SVIOracle(p, cfg, dtype=torch.float64, particles=1, renyi=alpha), orc.SVIOracle(p, cfg, dtype=torch.float64)
     oa, ob = a.loss_and_grads(x, eps, 1.7, y), b.loss_and_grads(x, eps, 1.7, y)
     for k in SLOTS + ("z_loc", "z_scale", "loc"):
         assert torch.equal(oa[k], ob[k]), k
@@ -56,10 +54,10 @@ def test_autograd_of_the_bound_is_autograd_of_the_surrogate_with_its_own_weights
     p = _params(cfg, c_dim=c_dim)
     b, P, beta = 5, 3, 1.7
     x, eps, y = _inputs(cfg, b, P, c_dim=c_dim)
-    free = rr.RenyiOracle(p, cfg, P, alpha, dtype=torch.float64)
+    free = orc.SVIOracle(p, cfg, dtype=torch.float64, particles=P, renyi=alpha)
     of = free.loss_and_grads(x, eps, beta, y)
     assert torch.allclose(of["weights"].view(P, b).sum(0), torch.ones(b, dtype=torch.float64), rtol=0, atol=1e-14)
-    held = rr.RenyiOracle(p, cfg, P, alpha, dtype=torch.float64)
+    held = orc.SVIOracle(p, cfg, dtype=torch.float64, particles=P, renyi=alpha)
     held.weights = of["weights"].clone()
     oh = held.loss_and_grads(x, eps, beta, y)
     assert held.weights is None
@@ -78,8 +76,8 @@ def test_bound_dominates_the_elbo_grows_with_alpha_and_meets_the_elbo_at_one(dat
     b, P, beta = 5, 3, 1.7
     x, eps, y = _inputs(cfg, b, P, c_dim=c_dim)
     with torch.no_grad():
-        elbo = pr.ParticlesOracle(p, cfg, P, dtype=torch.float64).loss_and_grads(x, eps, beta, y)["loss"].item()
-        loss = {a: rr.RenyiOracle(p, cfg, P, a, dtype=torch.float64).loss_and_grads(x, eps, beta, y)["loss"].item()
+        elbo = orc.SVIOracle(p, cfg, dtype=torch.float64, particles=P).loss_and_grads(x, eps, beta, y)["loss"].item()
+        loss = {a: orc.SVIOracle(p, cfg, dtype=torch.float64, particles=P, renyi=a).loss_and_grads(x, eps, beta, y)["loss"].item()
                 for a in (-1.0, 0.0, 0.5, 0.9, 1.0 - 1e-6)}
     assert loss[0.0] <= elbo                                  # IWAE bound >= ELBO on the same draws (Jensen)
     seq = [loss[a] for a in (-1.0, 0.0, 0.5, 0.9)]
@@ -97,7 +95,7 @@ def test_slots_relation_and_what_each_slot_holds(data_dim, inv, c_dim, alpha):
     b, P, beta = 5, 3, 1.7
     x, eps, y = _inputs(cfg, b, P, c_dim=c_dim)
     with torch.no_grad():
-        o = rr.RenyiOracle(p, cfg, P, alpha, dtype=torch.float64).loss_and_grads(x, eps, beta, y)
+        o = orc.SVIOracle(p, cfg, dtype=torch.float64, particles=P, renyi=alpha).loss_and_grads(x, eps, beta, y)
     assert abs((o["loss"] + (o["ll"] + o["logpz"] - o["logqz"])).item()) <= 1e-12 * abs(o["loss"].item())
     # s1 = sum_b (sum_p w ll + c_b), c_b = (H(w_b) - log P) / (1 - alpha)
     w, ll = o["weights"].view(P, b), o["ll_per_sample"].view(P, b)
@@ -167,13 +165,12 @@ def test_engine_rejects_what_the_bound_does_not_cover():
 def test_epoch_consumes_the_generator_as_the_particle_trainer_does(inv, n, batch, device_feed):
     """The eps draw order is the particle path's: P sequential draws per step (tests/test_particles_cpu.py's plain loop), and
     the same tensors SVItrainer(num_particles=P) hands its engine."""
-    from _particles_engine import ParticlesOracleEngine
     P = 3
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=inv)
     x = torch.rand(n, 8, 8, generator=torch.Generator().manual_seed(9))
     loader = pv.utils.init_dataloader(x, batch_size=batch)
     model = pv.models.iVAE((8, 8), 2, inv, seed=1, device="cpu")
-    eng = RenyiOracleEngine(model, cfg)
+    eng = OracleEngine(model, cfg, expect_renyi=True)
     tr = pv.trainers.SVItrainer(model, loss="RenyiELBO", alpha=0.5, seed=1, engine=eng, device="cpu", num_particles=P,
                                 device_feed=device_feed)
     st0 = torch.get_rng_state()
@@ -186,7 +183,7 @@ def test_epoch_consumes_the_generator_as_the_particle_trainer_does(inv, n, batch
     for got, w in zip(eng.seen_eps, want):
         assert got.shape == w.shape and torch.equal(got, w)
     model2 = pv.models.iVAE((8, 8), 2, inv, seed=1, device="cpu")
-    eng2 = ParticlesOracleEngine(model2, cfg)
+    eng2 = OracleEngine(model2, cfg)
     tr2 = pv.trainers.SVItrainer(model2, seed=1, engine=eng2, device="cpu", num_particles=P, device_feed=device_feed)
     torch.set_rng_state(st0)
     tr2.step(loader)
@@ -203,7 +200,7 @@ def _dp_run(P, alpha):
     cfg = orc.Config(data_dim=(8, 8), latent_dim=2, invariances=inv)
     x = torch.rand(10, 8, 8, generator=torch.Generator().manual_seed(5))
     loader = pv.utils.init_dataloader(x, batch_size=5)              # two steps; two ranks take 3 + 2 rows of each
-    eng = RenyiOracleEngine(model, cfg)
+    eng = OracleEngine(model, cfg, expect_renyi=True)
     tr = pv.trainers.SVItrainer(model, loss="RenyiELBO", alpha=alpha, seed=1, engine=eng, device="cpu", num_particles=P)
     tr.step(loader)
     return tr.loss_history, {k: v.detach().numpy().copy() for k, v in eng.o.p.items()}, eng.adam_t, [e.shape[0] for e in eng.seen_eps]
@@ -320,8 +317,8 @@ def test_gpu_cases_have_spread_weights_and_a_bound_away_from_the_elbo():
         assert beta == BETA
         for alpha in (ALPHAS if name != "28x28_r_b128_p2" else (0.0,)):
             with torch.no_grad():
-                o = rr.RenyiOracle(params, cfg, P, alpha, dtype=torch.float64).loss_and_grads(x, eps[0], beta, y)
-                e = pr.ParticlesOracle(params, cfg, P, dtype=torch.float64).loss_and_grads(x, eps[0], beta, y)
+                o = orc.SVIOracle(params, cfg, dtype=torch.float64, particles=P, renyi=alpha).loss_and_grads(x, eps[0], beta, y)
+                e = orc.SVIOracle(params, cfg, dtype=torch.float64, particles=P).loss_and_grads(x, eps[0], beta, y)
             ess = (1.0 / (o["weights"].view(P, b) ** 2).sum(0)).max().item()
             gap = e["loss"].item() - o["loss"].item()
             print("%s alpha=%g: max ESS %.3f, bound - ELBO %.3f nats" % (name, alpha, ess, gap))
@@ -329,7 +326,7 @@ def test_gpu_cases_have_spread_weights_and_a_bound_away_from_the_elbo():
             assert gap > 0.25, (name, alpha, gap)
             if name not in STEP_CASES:
                 continue
-            o = rr.RenyiOracle(params, cfg, P, alpha, dtype=torch.float64)
+            o = orc.SVIOracle(params, cfg, dtype=torch.float64, particles=P, renyi=alpha)
             for k in range(2):
                 o.step(x, eps[k], beta, y)
                 for key, g in o.last_grads.items():
