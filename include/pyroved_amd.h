@@ -154,7 +154,7 @@ typedef struct pv_ivae_plan {
   pv_layer dec[PV_MAX_LAYERS];
   pv_layer out;                    /* decoder.out (fc.py:186 / fc.py:140).  coord_dim > 0: out_dim = C, the channels per grid
                                       position, 1 .. PV_MAX_CHANNELS, weight (C, in_dim); C > 1 runs the layer-by-layer kernels
-                                      whatever `fused` asks for and is refused with discrete_dim, row_w / row_elbo / dy, a conv or
+                                      whatever `fused` asks for (but fused == 1 with PV_PLAN_FUSED_CHANNELS) and is refused with discrete_dim, row_w / row_elbo / dy, a conv or
                                       external encoder and an external decoder.  coord_dim == 0: out_dim = n_pix */
   /* ---- optional convolutional encoder: iVAE.set_encoder(convEncoderNet(data_dim, latent_dim=z_dim))
    * (models/base.py:173-177, nets/conv.py:24-64).  n_enc_ops > 0: `enc` / n_enc are ignored, the encoder is this
@@ -318,6 +318,17 @@ int pv_experiments_build(void);
  *   specialised for full tiles: no unit-position bookkeeping, activity masks or run-time k-step count.  Same arithmetic in the same
  *   order: results are bit-identical either way (the switch is for A/B runs and the parity test).  No reference counterpart. */
 #define PV_PLAN_GENERIC_TILE_LOOP 128
+/* PV_PLAN_FUSED_CHANNELS (pv_ivae_plan; a new bit of `flags`, no layout change, no version bump): a spatial decoder with several
+ *   channels per position runs on the fused f32 decoder kernel's multi-channel sibling instead of the layer-by-layer kernels.
+ *   Takes effect only for a plan with ALL of: fused == 1, coord_dim > 0, 2 <= out.out_dim <= PV_MAX_CHANNELS, the architecture the
+ *   fused kernel is specialised for (two hidden layers of 128, fc_coord / fc_latent of width 128, tanh, biases, 16-byte aligned
+ *   weight rows) and positions = n_pix / out.out_dim a multiple of 16.  pv_ivae_uses_fused is then 1, the workspace queries return
+ *   the fused layout (no per-row activations), and pv_ivae_loss_and_grads / pv_ivae_step / pv_ivae_decode run that kernel; both
+ *   kl_mode forms, c_dim > 0 and the Poisson likelihood included.  fp32 matrix instructions throughout: results of fp32 class.
+ *   Everywhere else — fused 0, 2 or 3, one channel, vanilla decoders, other widths or activations, other position counts — the
+ *   bit does nothing: a one-channel plan with it is byte for byte the fused == 1 plan without it.  pv_ivae_particles_* and
+ *   pv_ivae_renyi_* keep refusing fused == 1.  No reference counterpart (the reference has one code path). */
+#define PV_PLAN_FUSED_CHANNELS 256
 
 /* Bytes of workspace pv_ivae_* calls need for this plan (depends on batch, n_pix,
  * layer widths).  Returns < 0 on an unsupported plan. */

@@ -19,6 +19,7 @@ PV_PLAN_ENC_TWO_LAUNCH, PV_PLAN_NO_SIDE_STREAM, PV_PLAN_ENC_NO_WAIT, PV_PLAN_NO_
 PV_PLAN_CONV_X3 = 64
 PV_PLAN_ENC_TILED = 32
 PV_PLAN_GENERIC_TILE_LOOP = 128
+PV_PLAN_FUSED_CHANNELS = 256         # several channels per position on the fused f32 decoder kernel (with fused == 1)
 PV_MAX_LAYERS = 8
 PV_MAX_CHANNELS = 8         # channels per grid position of a spatial decoder (pv_ivae_plan.out.out_dim)
 

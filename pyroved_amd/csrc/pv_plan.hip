@@ -86,6 +86,11 @@ static inline int plan_conv_mode(const pv_ivae_plan* p) {
 // the grid, the row chunks and the per-sample segment sums run over the positions.  Vanilla decoders: C = 1, positions = n_pix
 static inline int64_t plan_C(const pv_ivae_plan* p) { return p->coord_dim > 0 ? p->out.out_dim : 1; }
 static inline int64_t plan_pos(const pv_ivae_plan* p) { return p->n_pix / plan_C(p); }
+// The fused persistent decoder kernel a plan runs on, if any: the one-channel kernels (every `fused` mode) or the f32 kernel's
+// multi-channel sibling (pv_sdec_fused_mc.hip: PV_PLAN_FUSED_CHANNELS with fused == 1 and 2 .. PV_MAX_CHANNELS channels).  The two
+// predicates exclude each other (out.out_dim == 1 / >= 2)
+static inline bool plan_fused_mc(const pv_ivae_plan* p) { return pv_sdec_fused_mc_supported(p); }
+static inline bool plan_fused_ok(const pv_ivae_plan* p) { return pv_sdec_fused_supported(p) || plan_fused_mc(p); }
 static inline int64_t plan_S(const pv_ivae_plan* p) { return (plan_K(p) > 0 ? plan_K(p) : 1) * (int64_t)p->batch; }
 // decoder samples of a training step: jiVAE's K per input or the multi-particle ELBO's P (never both)
 static inline int64_t step_S(const pv_ivae_plan* p, const Layout& L) { return plan_S(p) * L.P; }
@@ -206,7 +211,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.enc_flags = reinterpret_cast<unsigned*>(c.take(8 * L.kl_blocks));     // (the merged encoder launch's tile flags)
   c.take(1024 + 16);                                 // (PvEncFold::coop_flags of the experiments-only shared first layer: the workspace size stays)
   int64_t maxd = 0;
-  L.fused = p->fused && pv_sdec_fused_supported(p) && !(K > 0 && !L.enc_compact);   // (jiVAE + generic encoder: layered)
+  L.fused = p->fused && plan_fused_ok(p) && !(K > 0 && !L.enc_compact);   // (jiVAE + generic encoder: layered)
   L.f_grid = L.f_kmax = 0;
   L.f_part = L.f_part_hz = L.f_rowtp = L.f_wimg = L.f_park = nullptr;
   for (int i = 0; i < p->n_dec; ++i) {
@@ -822,7 +827,7 @@ struct FusedStep {
 
 void fused_decoder_args(FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
-  const int64_t B = p->batch, N = p->n_pix, R = L.rows, K = plan_K(p), S = step_S(p, L);   // jiVAE: S = K*B decoder samples, rows R = S*N
+  const int64_t B = p->batch, N = plan_pos(p), R = L.rows, K = plan_K(p), S = step_S(p, L);   // jiVAE: S = K*B decoder samples, rows R = S*N (N: rows per sample)
   const bool multi = K > 0 || L.P > 1;               // (multi-particle: S = P*B, each weighted 1/P against the same B observations)
   PvFused& f = st.f;
   fused_weights(f, p);
@@ -944,7 +949,7 @@ int fused_guide(FusedStep& st) {
 void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
   PvFused& f = st.f;
-  const int64_t N = p->n_pix, R = L.rows, z = p->z_dim, K = plan_K(p), S = step_S(p, L), lat_in = plan_lat_in(p);
+  const int64_t N = plan_pos(p), R = L.rows, z = p->z_dim, K = plan_K(p), S = step_S(p, L), lat_in = plan_lat_in(p);
   const int H = FD_H;
   const float* Wz = p->params + p->fc_latent.w_off;
   // (round 6) the 4-wave kernels too hand over dL/d(hz) and dL/dz, wherever every workgroup's units are exactly one sample
@@ -1019,6 +1024,14 @@ int fused_decoder_launch(FusedStep& st) {
   if (timed) (void)hipEventRecord((hipEvent_t)p->ev_start, st.s);
   if (p->fused >= 2) PV_TRY(pv_sdec_fused_bf16_launch(st.f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
                                                       (st.own_chain() && !st.fold) ? &st.ef : nullptr));
+  else if (plan_fused_mc(p)) {
+    // several channels per row: the f32 kernel's sibling, then (training) the sums of channels 1 .. C-1 of d(wo), d(bo) into the
+    // flat gradient — in front of every launch that reads it, the one that applies Adam included
+    PvFused f = st.f;
+    f.wimg = nullptr; f.park = nullptr;
+    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s));
+    if (st.grads) PV_TRY(pv_sdec_fused_mc_reduce_out(st.L.f_part, st.L.f_grid, p->grads, p->out.w_off, p->out.b_off, (int)plan_C(p), st.s));
+  }
   else PV_TRY(pv_sdec_fused_launch(st.f, st.L.f_grid, st.grads, st.s));
   if (timed) (void)hipEventRecord((hipEvent_t)p->ev_stop, st.s);
   return 0;
@@ -1027,7 +1040,7 @@ int fused_decoder_launch(FusedStep& st) {
 // no gradients: ll_b from the decoder's rows, the loss scalars, the extra outputs
 int fused_close_forward(const FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
-  const int64_t B = p->batch, N = p->n_pix, K = plan_K(p);
+  const int64_t B = p->batch, N = plan_pos(p), K = plan_K(p);
   if (K > 0) {                                       // llb[b] = sum_k alpha_bk ll_kb
     PvLatentBwd lf{};
     lf.llrow = L.llrow; lf.llb = L.llb; lf.M = L.rows; lf.N = (int)N; lf.H = 0; lf.K = (int)K; lf.alpha = L.alpha;
@@ -1068,7 +1081,7 @@ int fused_renyi_forward(const FusedStep& st) {
   if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(ff, false, x3, s));
   PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, x3, s));
   if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, x3, s));
-  PV_TRY(pv_segsum(L.llrow, step_S(p, L), p->n_pix, L.llkb, s));
+  PV_TRY(pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s));
   return renyi_weights(p, L, s);
 }
 
@@ -1310,7 +1323,7 @@ static int loc_lik(const pv_ivae_plan* lay) { return lay->lik == PV_LIK_POISSON_
 // Always at fp32-class precision (fused = 1: f32 matrix instructions; otherwise bf16 split precision), whatever the
 // training precision: reconstructions are what parity is judged on.
 struct DecodeLayout { float* tp; float* hz; float* wimg; float* xdummy; void* scratch; int64_t scratch_bytes, total; };
-static bool decode_fused(const pv_ivae_plan* lay) { return lay->fused && lay->coord_dim > 0 && pv_sdec_fused_supported(lay); }
+static bool decode_fused(const pv_ivae_plan* lay) { return lay->fused && lay->coord_dim > 0 && plan_fused_ok(lay); }
 static void carve_decode(const pv_ivae_plan* lay, char* base, DecodeLayout& D) {
   Carver c{base, 0};
   const int64_t B = lay->batch, H0 = lay->fc_coord.out_dim, lat_in = plan_lat_in(lay);
@@ -1328,7 +1341,7 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   DecodeLayout D;
   carve_decode(lay, (char*)lay->ws, D);
   if (lay->ws_bytes < D.total) return PV_EWS;
-  const int64_t B = lay->batch, N = lay->n_pix, lat_in = plan_lat_in(lay);
+  const int64_t B = lay->batch, N = plan_pos(lay), lat_in = plan_lat_in(lay);      // N: rows per sample
   const int H = FD_H;
   if (lay->fc_latent.in_dim != lat_in) return PV_EINVAL;
   PV_TRY(pv_fill_tp(D.tp, (int)B, angle, scale, shift_x, shift_y, s));
@@ -1346,6 +1359,10 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   f.lik = loc_lik(lay); f.sigmoid_out = lay->sigmoid_out; f.sig = 1.0f;         // loc = sigmoid(a) or a (Poisson: exp(a))
   f.sel = lay->dec_kernel;                             // (forward-only: no fp16 build, the parent's selection for every likelihood)
   const int grid = pv_sdec_fused_grid(f.units);
+  if (plan_fused_mc(lay)) {                            // loc is (B, N, C); no observations at all (x null: zeros)
+    f.x = nullptr; f.x_units = 0; f.wimg = nullptr;
+    return pv_sdec_fused_mc_launch(f, (int)plan_C(lay), grid, false, s);
+  }
   if (lay->fused == 1) return pv_sdec_fused_launch(f, grid, false, s);
   f.hz_scale = 0.0f;                                   // hz is written unscaled here; the 8-wave kernels scale it themselves
   PV_TRY(pv_sdec_fused_bf16_prep(f, false, true, s));  // weight images (pre-scaled or not: the launch below makes the same choice)
@@ -1393,7 +1410,7 @@ extern "C" int64_t pv_ivae_workspace_bytes_for(const pv_ivae_plan* plan, int wha
 extern "C" int64_t pv_ivae_workspace_bytes(const pv_ivae_plan* plan) { return pv_ivae_workspace_bytes_for(plan, PV_WS_ALL); }
 
 extern "C" int pv_ivae_uses_fused(const pv_ivae_plan* plan) {
-  return valid_plan(plan) && plan->fused && pv_sdec_fused_supported(plan) ? 1 : 0;
+  return valid_plan(plan) && plan->fused && plan_fused_ok(plan) ? 1 : 0;
 }
 
 extern "C" int pv_ivae_guide_folds(const pv_ivae_plan* plan) {

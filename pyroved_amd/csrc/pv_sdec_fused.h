@@ -8,7 +8,8 @@
 #define FD_REC (2 * FD_H * FD_H + 14 * FD_H)  // floats of one per-workgroup partial-gradient record:
 // [dW1 HxH | dW2 HxH | db1 H | db2 H | dWc0 H | dWc1 H | dwo H | dbo (1, padded to H) | 8 spare slots x H]
 // (the spare slots are summed into dwo by the reduction when it is called with dwo_slots = 1; both kernels now
-//  sum their d(wo) in LDS and leave the slots unused)
+//  sum their d(wo) in LDS and leave the slots unused; the multi-channel kernel, pv_sdec_fused_mc.hip, puts channel c >= 1 there:
+//  d(wo)[c] in spare slot c - 1, d(bo)[c] at [c] of the dbo slot — summed by pv_sdec_fused_mc_reduce_out, never with dwo_slots = 1)
 #define PV_RS_W 8               // floats per slot of PvFused::part_rs (5 used)
 #define FB_WIMG_BYTES (4 * FD_H * FD_H * 2 + 256)   // split-precision kernels: global copy of the four LDS weight images (+ the fp16 modes' scales)
 
@@ -132,6 +133,20 @@ int pv_sdec_fused_grid(int64_t units);
 int pv_sdec_fused_kmax(int n_pix, int64_t units, int grid);
 // launches the kernel (grads = false: forward + likelihood only)
 int pv_sdec_fused_launch(const PvFused& f, int grid, bool grads, hipStream_t s);
+// ---- several output channels per row (pv_sdec_fused_mc.hip; the plan asks with PV_PLAN_FUSED_CHANNELS, fused == 1) ----
+// the architecture of pv_sdec_fused_supported without its conditions on the output layer's width and the rows per sample
+bool pv_sdec_fused_trunk_supported(const pv_ivae_plan* p);
+// true when the plan runs the multi-channel kernel: the flag, fused == 1, that architecture, 2 <= out.out_dim <= PV_MAX_CHANNELS
+// with an instance of the kernel, and positions (n_pix / out.out_dim) a multiple of 16
+bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p);
+// f as for pv_sdec_fused_launch with C values per row: x and loc are (M, C) channel-last (x null: zeros — forward-only decode),
+// wo (C, H), bo (C); llrow (M) sums the row's C values, c ascending.  Record (PV_REC_ROWMAJOR): channel 0's d(wo) / d(bo) where
+// the one-channel kernel puts them (slot 4, slot 5 [0]); channel c >= 1: d(wo)[c] in slot 5 + c, d(bo)[c] at slot 5 [c].
+// PV_EINVAL for sw, x_units, part_rs, dhz_out, dzc_out or wimg set, or a C without an instance.  f.ablate is ignored.
+int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s);
+// sums the records' entries of channels 1 .. C-1 — (C - 1) (H + 1) outputs, each over the `grid` records in the shared reduction's
+// fixed order (four slices of ascending workgroups) — into G + wo_off + c H and G + bo_off + c; channel 0 is the shared reduction's
+int pv_sdec_fused_mc_reduce_out(const float* part, int grid, float* G, int64_t wo_off, int64_t bo_off, int C, hipStream_t s);
 // same interface, bf16 split-precision ("bf16x3") matrix math (pv_sdec_fused_bf16.hip); _prep must run first on the
 // same stream, once per parameter state: it writes f.wimg and, with grads, zero-fills f.part_hz
 // x3: split precision (pv_sdec_fused_bf16.hip) or plain bf16 operands (pv_sdec_fused_w8.hip, whose images are

@@ -63,7 +63,9 @@ class IVAEEngine:
     """Binds an iVAE-like model (encoder_z: fcEncoderNet, decoder: sDecoderNet | fcDecoderNet)
     to the HIP library.  A multi-channel model (models.iVAE(..., channels=C), self.C > 1) takes x as (B, *data_dim, C), channel-last,
     returns loc / decode in that shape, and runs the layer-by-layer kernels whatever `fused` asks for (plan.out.out_dim = C,
-    plan.n_pix = prod(data_dim) * C)."""
+    plan.n_pix = prod(data_dim) * C) — unless fused_channels=True: then fused = 1 or 2 runs the step, evaluate and decode on the
+    fused f32 decoder kernel's multi-channel sibling (plan.fused = 1 + PV_PLAN_FUSED_CHANNELS; fp32-class results) wherever the
+    decoder is the one that kernel is written for (hidden [128, 128], tanh, positions a multiple of 16), and layered elsewhere."""
     supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
@@ -79,14 +81,16 @@ class IVAEEngine:
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
     full_tile_loop = True            # PV_PLAN_GENERIC_TILE_LOOP when False (the image-owning decoder launch keeps its generic tile loop; bit-identical)
     C = 1                            # channels per grid position (models.iVAE(..., channels=C)); set by _check_model
+    fused_channels = False           # PV_PLAN_FUSED_CHANNELS (with C > 1 and fused = 1 or 2): the multi-channel fused f32 decoder kernel
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
     renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
                                      # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
-                 particles: int = 1, renyi=None):
+                 particles: int = 1, renyi=None, fused_channels: bool = False):
         self.model = model
+        self.fused_channels = bool(fused_channels)
         self.kl = _kl_name(kl)
         self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
         self.renyi = _renyi_alpha(renyi)
@@ -105,6 +109,7 @@ class IVAEEngine:
         self._views: Dict[str, torch.Tensor] = {}
         self._check_model()
         self._check_particles()
+        self._check_fused_channels()
         self.bind()
 
     # ------------------------------------------------------------------ structure
@@ -301,7 +306,27 @@ class IVAEEngine:
         if self.renyi is not None and self.kl == "analytic":
             raise ValueError("renyi needs kl='sampled': the closed-form KL has no per-sample term for the bound to weigh")
 
-    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None):
+    def _check_fused_channels(self):
+        """fused_channels=True asks for the multi-channel kernel of the f32 fused decoder: the one-particle ELBO (either KL form) at
+        fp32-class precision, so fused = 1 or 2.  With one channel the keyword changes nothing the library sees."""
+        if not self.fused_channels:
+            return
+        if type(self) is not IVAEEngine:
+            raise ValueError("fused_channels is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
+        if self.particles > 1 or self.renyi is not None:
+            raise ValueError("fused_channels=True runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound: "
+                             "the f32 fused kernel it selects has no multi-particle form)")
+        if self.fused == 3:
+            raise ValueError("fused_channels=True selects the f32 fused decoder kernel; fused=3 (precision='bf16') asks for the "
+                             "bf16 throughput kernels, which have no multi-channel form")
+        if self.fused == 0:
+            raise ValueError("fused_channels=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2")
+
+    def _plan_fused(self) -> int:
+        """pv_ivae_plan.fused: the engine's `fused`, or 1 where fused_channels routes a multi-channel model to the f32 kernel."""
+        return 1 if (self.fused_channels and self.C > 1 and self.fused in (1, 2)) else int(self.fused)
+
+    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
         renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting."""
@@ -311,9 +336,12 @@ class IVAEEngine:
             self.betas = (float(betas[0]), float(betas[1]))
         if eps is not None:
             self.adam_eps = float(eps)
-        old = (self.fused, self.particles, self.renyi, self.kl)
+        old = (self.fused, self.particles, self.renyi, self.kl, self.fused_channels)
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
+            self.ws = None
+        if fused_channels is not None and bool(fused_channels) != self.fused_channels:
+            self.fused_channels = bool(fused_channels)
             self.ws = None
         if particles is not None:
             self.particles = _particle_count(particles)
@@ -324,8 +352,9 @@ class IVAEEngine:
         try:
             self._check_particles()
             self._check_kl()
+            self._check_fused_channels()
         except ValueError:
-            self.fused, self.particles, self.renyi, self.kl = old
+            self.fused, self.particles, self.renyi, self.kl, self.fused_channels = old
             self._check_particles()
             raise
         if self.flat is not None:
@@ -453,6 +482,7 @@ class IVAEEngine:
                 (0 if getattr(self, "enc_fold", True) else _abi.PV_PLAN_NO_ENC_FOLD) |
                 (0 if getattr(self, "enc_per_image", True) else _abi.PV_PLAN_ENC_TILED) |
                 (0 if getattr(self, "full_tile_loop", True) else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
+                (_abi.PV_PLAN_FUSED_CHANNELS if (getattr(self, "fused_channels", False) and getattr(self, "C", 1) > 1) else 0) |
                 (_abi.PV_PLAN_CONV_X3 if getattr(self, "conv_x3", False) else 0))
 
     def ensure_bound(self):
@@ -507,7 +537,7 @@ class IVAEEngine:
         p.sigmoid_out = int(getattr(dec, "sigmoid_out", True))
         p.decoder_sig = m.sampler_d.decoder_sig
         p.ext_decoder = int(self.ext_dec)
-        p.fused = int(self.fused)
+        p.fused = self._plan_fused()
         if self.ext_enc:
             p.n_enc = 0
             p.discrete_dim = 0

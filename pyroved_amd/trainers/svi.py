@@ -66,6 +66,11 @@ class SVItrainer:
         fused: spatial-decoder kernel path, overrides `precision`: 2 fused persistent kernel with bf16
             split-precision matrix math (fp32-class results), 3 the same kernel with plain bf16 operands,
             1 fused kernel on the f32-input MFMA, 0 layer-by-layer kernels
+        fused_channels: multi-channel models (models.iVAE(..., channels=C), C > 1) train, evaluate and decode on the fused f32
+            decoder kernel's multi-channel form instead of the layer-by-layer kernels they otherwise take whatever `fused`
+            says (default False; fp32-class results; decoders of hidden size [128, 128] with tanh and a number of grid
+            positions that is a multiple of 16 — others keep the layered kernels).  A ValueError with num_particles > 1,
+            loss="RenyiELBO", fused=0, fused=3 or precision="bf16".  Changes nothing for a single-channel model
         process_group: torch.distributed group for data-parallel training (default: WORLD if initialised)
         device_feed: keep TensorDataset loaders' data on the device and gather minibatches there, in the order the
             loader's own sampler produces (default True; same numbers as iterating the loader)
@@ -146,7 +151,7 @@ class SVItrainer:
             if pvdist.world(self.group)[1] > 1:
                 raise ValueError("Pyro optimizer / loss objects cannot be combined with data-parallel training: replicas "
                                  "would train unsynchronised (pass optimizer=None or a dict of Adam arguments)")
-            bad = [k for k in ("precision", "fused", "rng", "device_feed", "mirror_evaluate_update") if k in kwargs]
+            bad = [k for k in ("precision", "fused", "fused_channels", "rng", "device_feed", "mirror_evaluate_update") if k in kwargs]
             if bad:
                 raise ValueError("%s only apply to the HIP training path, not to Pyro optimizer / loss objects" % bad)
             pyro.clear_param_store()
@@ -183,13 +188,17 @@ class SVItrainer:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
+            fused_channels = bool(kwargs.get("fused_channels", False))
+            if fused_channels and precision == "bf16":
+                raise ValueError("fused_channels=True selects the f32 fused decoder kernel (fp32-class results); it cannot be "
+                                 "combined with precision='bf16'")
             if precision == "bf16" and getattr(model, "channels", 1) != 1:
                 raise ValueError("precision='bf16' is not implemented for channels=%d: no bf16 multi-channel decoder kernel "
                                  "exists, and training at another precision than the one asked for is worse than refusing"
                                  % model.channels)
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
-                                       renyi=False if self.alpha is None else self.alpha)
+                                       renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels)
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
