@@ -433,6 +433,38 @@ int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles
                                  void* stream);
 int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream);   /* + Adam */
 
+/* ---- (v17, new entry points, no layout change) per-observation weights (masks) of the likelihood ----------------------------
+ * A circular aperture for a rotation-invariant model, dead or hot detector pixels, a per-pixel gain or exposure map: one
+ * factor per observed value,
+ *   loss = -( sum_b sum_i w_i log p(x_bi | z_b)  +  beta sum_b [ log p(z_b) - log q(z_b | x_b) ] )        (PV_KL_SAMPLED; the
+ *   analytic KL form likewise), w_i >= 0, shared by all images; w = 1 everywhere is pv_ivae_loss_and_grads' loss.
+ *   pixel_w   DEVICE pointer to n_pix floats: one per observed value, positions x channels, channel-last (the layout of one
+ *             image of x).  The weight multiplies the whole log_prob, normalisers included (the Gaussian's -log sig - log sqrt(2 pi),
+ *             the continuous Bernoulli's log C, the Poisson's -lgamma(x + 1): scalars[1] carries sum_b sum_i w_i of them).  The
+ *             caller guarantees w >= 0 and finite; nothing is checked on the device.
+ *   plan      the one-particle step's; loc (optional) is NOT weighted, the encoder sees x as given; the pointer travels next
+ *             to the plan, the struct is unchanged.
+ *   ws        sized by pv_ivae_weighted_workspace_bytes (a PV_WS_STEP layout of the kernel family that runs, below).
+ * pixel_w == NULL forwards to pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
+ * Which kernels run (pv_ivae_weighted_uses_fused: 1 for the fused f32 kernel, 0 for the layer-by-layer kernels):
+ *   fused == 0, or a decoder the fused f32 kernels are not written for (pv_ivae_uses_fused's architecture: hidden [128, 128],
+ *     tanh, positions a multiple of 16, coord_dim > 0)          the layer-by-layer kernels;
+ *   fused == 1 or 2, one channel, such a decoder                 the weighted fused f32 kernel (fused == 2 promises fp32-class
+ *     results and the f32 kernel delivers them).  NOT the fp16-piece kernel an unweighted fused == 2 step runs: that kernel and
+ *     the bf16 throughput kernels have no weighted form, and a weighted one-channel step costs what the fused == 1 step costs
+ *     (DESIGN.md 4.13 has the measured figures);
+ *   fused == 1 or 2, 2 .. PV_MAX_CHANNELS channels               as unweighted: the fused f32 kernel with PV_PLAN_FUSED_CHANNELS
+ *     and fused == 1, the layer-by-layer kernels otherwise.
+ * Scope: the one-particle ELBO in either kl_mode of the fc-encoder iVAE — spatial or vanilla decoder, 1 .. PV_MAX_CHANNELS
+ * channels, with or without c_dim, every likelihood.  PV_EINVAL (the workspace query too; pv_ivae_weighted_uses_fused: 0) for
+ * discrete_dim > 0, a convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 3.  There
+ * is no weighted form of pv_ivae_particles_*, pv_ivae_renyi_*, pv_ved_*, the semi-supervised calls or pv_ivae_dp_step (a
+ * data-parallel caller reduces [gradients | scalars] itself: the loss stays a sum over images). */
+int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan);                        /* <0 unsupported */
+int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan);
+int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream);
+int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* stream);   /* + Adam, as pv_ivae_step */
+
 /* ---- (v16) the data-parallel step with its collective INSIDE the library --------------------------------------------------
  * The reference has no distributed code.  What is sharded is trainers/svi.py:104-113 (`self.svi.step(x)` per
  * minibatch): the loss is a SUM over the data plate (models/ivae.py:177,215), so every replica computes its contiguous slice of

@@ -390,6 +390,11 @@ __global__ __launch_bounds__(256) void pv_out_lik_kernel(PvOutLik p) {
       dlda = -d / (p.sig * p.sig) * (p.sigmoid_out ? pr * (1.0f - pr) : 1.0f);
       locv = pr;
     }
+    if (p.pw) {                                          // per-observation weight (pv_ivae_weighted_*)
+      const float w = p.pw[row % p.N];
+      ll *= w;
+      dlda *= w;
+    }
     if (lane == 0) {
       if (p.llrow) p.llrow[row] = ll;
       if (p.loc) p.loc[row] = locv;
@@ -422,7 +427,7 @@ __global__ __launch_bounds__(256) void pv_out_lik_kernel(PvOutLik p) {
 int64_t pv_out_lik_blocks(int64_t M) { return (M + OL_ROWS - 1) / OL_ROWS; }
 
 int pv_out_lik(const PvOutLik& p, hipStream_t s) {
-  if (p.H > 64 * OL_MAXJ) return PV_EINVAL;
+  if (p.H > 64 * OL_MAXJ || (p.pw && p.N < 1)) return PV_EINVAL;
   hipLaunchKernelGGL(pv_out_lik_kernel, dim3((unsigned)pv_out_lik_blocks(p.M)), dim3(256), 0, s, p);
   PV_LAUNCH_CHECK();
   return 0;
@@ -482,6 +487,11 @@ __global__ __launch_bounds__(256) void pv_out_lik_mc_kernel(PvOutLik p) {
       const float x = p.x ? p.x[(p.xmod > 0 ? row % p.xmod : row) * C + lane] : 0.0f;
       pv_lik_any(a, x, p.lik, p.sigmoid_out, p.sig, ll, dlda, locv);
       if (p.loc) p.loc[row * C + lane] = locv;
+      if (p.pw) {                                        // per-observation weight (pv_ivae_weighted_*)
+        const float w = p.pw[(row % p.N) * C + lane];
+        ll *= w;
+        dlda *= w;
+      }
       if (p.sw) dlda *= p.sw[row / p.N];
     }
     if (p.llrow) {
@@ -534,7 +544,7 @@ template <int C> static void out_lik_mc_launch(const PvOutLik& p, hipStream_t s)
 }
 
 int pv_out_lik_mc(const PvOutLik& p, int C, hipStream_t s) {
-  if (p.H > 64 * OL_MAXJ || p.M <= 0) return PV_EINVAL;
+  if (p.H > 64 * OL_MAXJ || p.M <= 0 || (p.pw && p.N < 1)) return PV_EINVAL;
   switch (C) {
     case 2: out_lik_mc_launch<2>(p, s); break;
     case 3: out_lik_mc_launch<3>(p, s); break;
@@ -1344,10 +1354,11 @@ extern "C" int pv_adam_step(float* params, float* grads, float* m, float* v, int
 // elementwise likelihood for the vanilla fcDecoderNet path (fc.py:143-152): a[M] logits -> loc, ll, dL/da
 __global__ void pv_lik_elem_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t M, int lik,
                                    int sigmoid_out, float sig, float* __restrict__ loc, float* __restrict__ llrow,
-                                   float* __restrict__ dlda) {
+                                   float* __restrict__ dlda, const float* __restrict__ pw, int64_t per) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
     float ll, d, lv;
     pv_lik_one(a[e], x[e], lik, sigmoid_out, sig, ll, d, lv);
+    if (pw) { const float w = pw[e % per]; ll *= w; d *= w; }
     if (loc) loc[e] = lv;
     if (llrow) llrow[e] = ll;
     if (dlda) dlda[e] = d;
@@ -1358,13 +1369,15 @@ __global__ void pv_lik_elem_kernel(const float* __restrict__ a, const float* __r
 // per sample, ll_b[b] = sum over the sample's `per` elements — pv_lik_elem + pv_segsum in one launch, bit-identical
 __global__ __launch_bounds__(256) void pv_lik_rows_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t per,
                                                           int lik, int sigmoid_out, float sig, float* __restrict__ loc,
-                                                          float* __restrict__ dlda, float* __restrict__ llb) {
+                                                          float* __restrict__ dlda, float* __restrict__ llb,
+                                                          const float* __restrict__ pw) {
   __shared__ float sm[4];
   const int64_t base = (int64_t)blockIdx.x * per;
   float acc = 0.0f;
   for (int64_t n = threadIdx.x; n < per; n += 256) {
     float ll, d, lv;
     pv_lik_one(a[base + n], x[base + n], lik, sigmoid_out, sig, ll, d, lv);
+    if (pw) { const float w = pw[n]; ll *= w; d *= w; }
     if (loc) loc[base + n] = lv;
     if (dlda) dlda[base + n] = d;
     acc += ll;
@@ -1375,10 +1388,12 @@ __global__ __launch_bounds__(256) void pv_lik_rows_kernel(const float* __restric
 
 // the two kernels above for PV_LIK_POISSON_LOG (pv_common.h: pv_poisson_one): same indexing, same summation order
 __global__ void pv_lik_elem_poisson_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t M,
-                                           float* __restrict__ loc, float* __restrict__ llrow, float* __restrict__ dlda) {
+                                           float* __restrict__ loc, float* __restrict__ llrow, float* __restrict__ dlda,
+                                           const float* __restrict__ pw, int64_t per) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
     float ll, d, lv;
     pv_poisson_one(a[e], x[e], ll, d, lv);
+    if (pw) { const float w = pw[e % per]; ll *= w; d *= w; }
     if (loc) loc[e] = lv;
     if (llrow) llrow[e] = ll;
     if (dlda) dlda[e] = d;
@@ -1386,13 +1401,14 @@ __global__ void pv_lik_elem_poisson_kernel(const float* __restrict__ a, const fl
 }
 __global__ __launch_bounds__(256) void pv_lik_rows_poisson_kernel(const float* __restrict__ a, const float* __restrict__ x,
                                                                   int64_t per, float* __restrict__ loc, float* __restrict__ dlda,
-                                                                  float* __restrict__ llb) {
+                                                                  float* __restrict__ llb, const float* __restrict__ pw) {
   __shared__ float sm[4];
   const int64_t base = (int64_t)blockIdx.x * per;
   float acc = 0.0f;
   for (int64_t n = threadIdx.x; n < per; n += 256) {
     float ll, d, lv;
     pv_poisson_one(a[base + n], x[base + n], ll, d, lv);
+    if (pw) { const float w = pw[n]; ll *= w; d *= w; }
     if (loc) loc[base + n] = lv;
     if (dlda) dlda[base + n] = d;
     acc += ll;
@@ -1402,26 +1418,27 @@ __global__ __launch_bounds__(256) void pv_lik_rows_poisson_kernel(const float* _
 }
 
 int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik, int sigmoid_out, float sig, float* loc,
-                float* dlda, float* llb, hipStream_t s) {
+                float* dlda, float* llb, hipStream_t s, const float* pw) {
   if (B < 1) return 0;
   if (lik == PV_LIK_POISSON_LOG) {
-    hipLaunchKernelGGL(pv_lik_rows_poisson_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, loc, dlda, llb);
+    hipLaunchKernelGGL(pv_lik_rows_poisson_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, loc, dlda, llb, pw);
   } else {
-    hipLaunchKernelGGL(pv_lik_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, lik, sigmoid_out, sig, loc, dlda, llb);
+    hipLaunchKernelGGL(pv_lik_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, a, x, per, lik, sigmoid_out, sig, loc, dlda, llb, pw);
   }
   PV_LAUNCH_CHECK();
   return 0;
 }
 
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s) {
+                float* llrow, float* dlda, hipStream_t s, const float* pw, int64_t per) {
   int blocks = (int)((M + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) return 0;
+  if (pw && per < 1) return PV_EINVAL;
   if (lik == PV_LIK_POISSON_LOG) {
-    hipLaunchKernelGGL(pv_lik_elem_poisson_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, loc, llrow, dlda);
+    hipLaunchKernelGGL(pv_lik_elem_poisson_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, loc, llrow, dlda, pw, per);
   } else {
-    hipLaunchKernelGGL(pv_lik_elem_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, lik, sigmoid_out, sig, loc, llrow, dlda);
+    hipLaunchKernelGGL(pv_lik_elem_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, lik, sigmoid_out, sig, loc, llrow, dlda, pw, per);
   }
   PV_LAUNCH_CHECK();
   return 0;
@@ -1444,12 +1461,17 @@ __device__ __forceinline__ double pl_block_sum(double v, double* sm /* blockDim.
   return sm[0];
 }
 // part[blockIdx.x] = sum of lgamma(x[i] + 1) over the block's contiguous chunk [blockIdx.x * per, min(n, (blockIdx.x + 1) * per))
+// (pw != null: every term times the observation's weight pw[i % wper], wper = observations per sample)
 __global__ __launch_bounds__(256) void pv_poisson_lognorm_part_kernel(const float* __restrict__ x, int64_t n, int64_t per,
-                                                                      double* __restrict__ part) {
+                                                                      double* __restrict__ part, const float* __restrict__ pw,
+                                                                      int64_t wper) {
   __shared__ double sm[256];
   const int64_t beg = (int64_t)blockIdx.x * per;
   const int64_t end = beg + per < n ? beg + per : n;
   double acc = 0.0;
+  if (pw) {
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)pw[i % wper] * (double)lgammaf(x[i] + 1.0f);
+  } else
   for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)lgammaf(x[i] + 1.0f);
   const double c = pl_block_sum(acc, sm);
   if (threadIdx.x == 0) part[blockIdx.x] = c;
@@ -1463,13 +1485,13 @@ __global__ __launch_bounds__(PV_POISSON_PARTS) void pv_poisson_lognorm_kernel(co
     scalars[0] = (float)((double)scalars[0] + c);
   }
 }
-int pv_poisson_lognorm(const float* x, int64_t n, double* part, float* scalars, hipStream_t s) {
-  if (!x || !part || !scalars || n < 0) return PV_EINVAL;
+int pv_poisson_lognorm(const float* x, int64_t n, double* part, float* scalars, hipStream_t s, const float* pw, int64_t wper) {
+  if (!x || !part || !scalars || n < 0 || (pw && wper < 1)) return PV_EINVAL;
   int64_t nparts = (n + PL_CHUNK - 1) / PL_CHUNK;
   if (nparts < 1) nparts = 1;
   if (nparts > PV_POISSON_PARTS) nparts = PV_POISSON_PARTS;
   const int64_t per = (n + nparts - 1) / nparts;
-  hipLaunchKernelGGL(pv_poisson_lognorm_part_kernel, dim3((unsigned)nparts), dim3(256), 0, s, x, n, per, part);
+  hipLaunchKernelGGL(pv_poisson_lognorm_part_kernel, dim3((unsigned)nparts), dim3(256), 0, s, x, n, per, part, pw, wper);
   PV_LAUNCH_CHECK();
   hipLaunchKernelGGL(pv_poisson_lognorm_kernel, dim3(1), dim3(PV_POISSON_PARTS), 0, s, part, (int)nparts, scalars);
   PV_LAUNCH_CHECK();

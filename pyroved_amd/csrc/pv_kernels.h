@@ -64,6 +64,8 @@ struct PvOutLik {
   const float* sw;       // per-sample weights of the gradients (row / N indexes it) or null
   int N;                 // rows per sample (used with sw)
   int64_t xmod;          // > 0: observations are x[row % xmod] (jiVAE: the K decoder passes score the same B*N pixels)
+  const float* pw;       // (N * C) per-observation weights shared by all samples (pv_ivae_weighted_*) or null: ll and dL/da of
+                         // channel c of row `row` are multiplied by pw[(row % N) * C + c]; loc is not.  Needs N
 };
 int pv_out_lik(const PvOutLik& p, hipStream_t s);
 // the same with C = 2 .. PV_MAX_CHANNELS outputs per row (a spatial decoder's channels): wo (C, H), bo (C), x and loc (M, C)
@@ -231,17 +233,22 @@ int pv_rec_wgrad(const float* part, int grid, float* G, const PvFusedOffsets& o,
                  const PvAdamFuse* adam, const PvFinishArgs* fin, hipStream_t s, unsigned* tick = nullptr);
 
 // pv_lik_elem + pv_segsum in one launch (one workgroup per sample; same summation order)
+// pw (both; null: no weights, the same bits as before the argument existed): per-observation weights shared by all samples —
+// ll and dL/da of element i of a sample are multiplied by pw[i]; loc is not.  pv_lik_elem: element e is i = e % per of its sample
 int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik, int sigmoid_out, float sig, float* loc,
-                float* dlda, float* llb, hipStream_t s);
+                float* dlda, float* llb, hipStream_t s, const float* pw = nullptr);
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s);
+                float* llrow, float* dlda, hipStream_t s, const float* pw = nullptr, int64_t per = 0);
 
 // The Poisson (log link) likelihood's data-only normaliser C = sum_i lgamma(x[i] + 1) over the call's n observations, applied to the
 // finished scalars: scalars[1] -= C, scalars[0] += C.  Two launches: up to PV_POISSON_PARTS workgroups each sum a contiguous chunk
 // in float64 into part[], then one workgroup sums the partials in a fixed order and corrects the scalars.  No atomics; the same
 // bits every call; must run after the launch that finishes the scalars and before anything reads them.
 #define PV_POISSON_PARTS 1024
-int pv_poisson_lognorm(const float* x, int64_t n, double* part /* PV_POISSON_PARTS */, float* scalars, hipStream_t s);
+// pw != null (pv_ivae_weighted_*): the weighted normaliser C = sum_i pw[i % per] lgamma(x[i] + 1), per = observations per sample —
+// the same two launches, the same fixed order, the same partial sums
+int pv_poisson_lognorm(const float* x, int64_t n, double* part /* PV_POISSON_PARTS */, float* scalars, hipStream_t s,
+                       const float* pw = nullptr, int64_t per = 0);
 // per image instead: llkb[k*B + b] -= sum_n lgamma(x[b*N + n] + 1) for k < K (the sampled-class jiVAE objective)
 int pv_poisson_lognorm_rows(const float* x, int64_t B, int64_t N, float* llkb, int K, hipStream_t s);
 

@@ -66,6 +66,9 @@ struct Layout {
   // Like P, these travel here
   bool renyi; float r_alpha; float* r_c; float* r_wout;     // c_b (B); the caller's optional (P*B) copy of the weights
   double* pl_part;                                          // Poisson plans: pv_poisson_lognorm's partial sums (PV_POISSON_PARTS doubles)
+  // per-observation weights of the likelihood (pv_ivae_weighted_*): (n_pix) floats shared by all images, or null.  Like P, the
+  // pointer travels here, set by the entry point after carve(); the layout itself does not depend on it
+  const float* pw;
   int64_t total;
 };
 
@@ -148,6 +151,7 @@ bool valid_plan(const pv_ivae_plan* p) {
 void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1,
            bool renyi = false) {
   Carver c{base, 0};
+  L.pw = nullptr;
   L.P = inference_only ? 1 : P;
   L.renyi = renyi && L.P > 1; L.r_alpha = 0.0f; L.r_wout = nullptr;
   // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
@@ -838,7 +842,7 @@ void fused_decoder_args(FusedStep& st) {
   // keeping them in LDS cost its in-order waves what the next launch saved (read-modify-write: +-0 on the step; ds_add_f32: +1.4 us
   // on the kernel — profiles/r06h_row_sums_ab.txt)
   f.part_rs = (st.grads && st.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
-  f.wimg = L.f_wimg; f.park = L.f_park;
+  f.wimg = L.f_wimg; f.park = L.f_park;                // (a weighted launch puts the weights in wimg's slot: fused_decoder_launch)
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
   f.sw = multi ? L.sw : p->row_w; f.x_units = multi ? B * N / FD_UNIT : 0;
   f.sigmoid_out = p->sigmoid_out; f.kmax = L.f_kmax; f.sig = p->decoder_sig; f.sel = plan_sel(p);
@@ -1024,13 +1028,16 @@ int fused_decoder_launch(FusedStep& st) {
   if (timed) (void)hipEventRecord((hipEvent_t)p->ev_start, st.s);
   if (p->fused >= 2) PV_TRY(pv_sdec_fused_bf16_launch(st.f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
                                                       (st.own_chain() && !st.fold) ? &st.ef : nullptr));
-  else if (plan_fused_mc(p)) {
+  else if (plan_fused_mc(p) || st.L.pw) {
     // several channels per row: the f32 kernel's sibling, then (training) the sums of channels 1 .. C-1 of d(wo), d(bo) into the
     // flat gradient — in front of every launch that reads it, the one that applies Adam included
+    // (weighted steps, st.L.pw: its weighted instances at every channel count — the entry point routed the plan here,
+    //  weighted_route; with one channel there is nothing for the second launch to sum)
     PvFused f = st.f;
     f.wimg = nullptr; f.park = nullptr;
-    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s));
-    if (st.grads) PV_TRY(pv_sdec_fused_mc_reduce_out(st.L.f_part, st.L.f_grid, p->grads, p->out.w_off, p->out.b_off, (int)plan_C(p), st.s));
+    if (st.L.pw) f.pw = st.L.pw;
+    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s, st.L.pw != nullptr));
+    if (st.grads && plan_C(p) > 1) PV_TRY(pv_sdec_fused_mc_reduce_out(st.L.f_part, st.L.f_grid, p->grads, p->out.w_off, p->out.b_off, (int)plan_C(p), st.s));
   }
   else PV_TRY(pv_sdec_fused_launch(st.f, st.L.f_grid, st.grads, st.s));
   if (timed) (void)hipEventRecord((hipEvent_t)p->ev_stop, st.s);
@@ -1168,6 +1175,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     o.dpre = (want_grads && !renyi) ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
+    o.pw = L.pw;
     PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
   } else {
     // oth <- dL/dlogits (R, N); jiVAE: one pass per enumerated class against the same observations, rows then
@@ -1175,7 +1183,8 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     // (multi-particle: one pass per particle, rows weighted 1/P)
     for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
-                         p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s));
+                         p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s,
+                         L.pw, N));
     if (reps > 1 && want_grads && !renyi) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
@@ -1449,11 +1458,13 @@ static void set_renyi(Layout& L, const RenyiArgs* rn) {
 // its score-function term needs the per-image value, which went into llkb in front of pv_jiv_combine_sampled (nothing to do here).
 static int poisson_lognorm(const pv_ivae_plan* plan, const Layout& L, hipStream_t s) {
   if (plan->lik != PV_LIK_POISSON_LOG || (plan_K(plan) > 0 && plan->class_onehot)) return 0;
-  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s);
+  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s, L.pw, plan->n_pix);
 }
 
 // P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
-static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr) {
+// pw: per-observation weights (pv_ivae_weighted_*: `plan` is then the routed copy, weighted_route) or null
+static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr,
+                               const float* pw = nullptr) {
   if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
   if (!valid_plan(plan) || !plan->params || !plan->x || !plan->eps || !plan->scalars || !plan->ws) return PV_EINVAL;
   if (want_grads && !plan->grads) return PV_EINVAL;
@@ -1463,6 +1474,7 @@ static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, 
   Layout L;
   carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
   set_renyi(L, rn);
+  L.pw = pw;
   if (plan->ws_bytes < L.total) return PV_EWS;
   hipStream_t s = (hipStream_t)stream;
   // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
@@ -1526,7 +1538,7 @@ extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, 
 // SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
 // gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
 // pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
-static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr) {
+static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr, const float* pw = nullptr) {
   if (P < 1 || (P > 1 && !(valid_plan(plan) && particles_supported(plan)))) return PV_EINVAL;
   if (plan && !plan->ext_decoder && valid_plan(plan) && plan->params && plan->x && plan->eps && plan->scalars && plan->ws &&
       plan->grads && plan->adam_m && plan->adam_v && plan->adam_step >= 1 && plan->n_params > 0 &&
@@ -1537,6 +1549,7 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiA
     Layout L;
     carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
     set_renyi(L, rn);
+    L.pw = pw;
     if (plan->ws_bytes < L.total) return PV_EWS;
     if (L.fused && (L.enc_compact || L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
       const double bc1 = 1.0 - pow((double)plan->adam_beta1, (double)plan->adam_step);
@@ -1551,13 +1564,57 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiA
                           plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
     }
   }
-  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn));
+  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn, pw));
   return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
                       plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
 }
 extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
   PV_RANGE("pv_ivae_step");
   return step_impl(plan, 1, stream);
+}
+
+// ---- per-observation weights of the likelihood (v17, added without a layout change; include/pyroved_amd.h) ----
+// loss = -( sum_b sum_i w_i log p(x_bi | z_b) + beta sum_b [log p(z_b) - log q(z_b | x_b)] ), w (n_pix) shared by all images.
+// Scope: the one-particle ELBO (either KL form) of the fc-encoder iVAE, spatial or vanilla decoder, every likelihood
+static bool weighted_scope(const pv_ivae_plan* p) {
+  return valid_plan(p) && p->discrete_dim == 0 && p->n_enc_ops == 0 && !p->ext_encoder && !p->ext_decoder && !p->row_w &&
+         !p->row_elbo && !p->dy && !p->class_onehot && p->fused != 3;
+}
+// The plan a weighted call runs: the caller's with `fused` rewritten to the kernel family that has a weighted form — 1 where the
+// weighted instances of the fused f32 kernel take the decoder (one channel asked with fused 1 or 2: fused = 2 promises fp32-class
+// results and the f32 kernel delivers them; several channels as the unweighted plan decides: PV_PLAN_FUSED_CHANNELS and fused == 1),
+// 0 (the layer-by-layer kernels) everywhere else.  The fp16-piece / bf16 decoder kernels have no weighted form
+static pv_ivae_plan weighted_route(const pv_ivae_plan* p) {
+  pv_ivae_plan q = *p;
+  if (q.fused == 2 && q.coord_dim > 0 && q.out.out_dim == 1) q.fused = 1;
+  if (!(q.fused == 1 && pv_sdec_fused_mc_weighted_supported(&q) && plan_fused_ok(&q))) q.fused = 0;
+  return q;
+}
+extern "C" int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan) {
+  if (!weighted_scope(plan)) return PV_EINVAL;
+  const pv_ivae_plan q = weighted_route(plan);
+  Layout L;
+  carve(&q, nullptr, L);
+  return L.total;
+}
+extern "C" int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan) {
+  if (!weighted_scope(plan)) return 0;
+  const pv_ivae_plan q = weighted_route(plan);
+  return q.fused == 1 ? 1 : 0;
+}
+extern "C" int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream) {
+  if (!pixel_w) return pv_ivae_loss_and_grads(plan, want_grads, stream);
+  PV_RANGE("pv_ivae_weighted_loss_and_grads");
+  if (!weighted_scope(plan)) return PV_EINVAL;
+  const pv_ivae_plan q = weighted_route(plan);
+  return loss_and_grads_impl(&q, 1, want_grads, stream, nullptr, pixel_w);
+}
+extern "C" int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* stream) {
+  if (!pixel_w) return pv_ivae_step(plan, stream);
+  PV_RANGE("pv_ivae_weighted_step");
+  if (!weighted_scope(plan)) return PV_EINVAL;
+  const pv_ivae_plan q = weighted_route(plan);
+  return step_impl(&q, 1, stream, nullptr, pixel_w);
 }
 
 // ---- the multi-particle ELBO (v17, added without a layout change; include/pyroved_amd.h) ----

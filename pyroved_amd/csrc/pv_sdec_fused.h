@@ -42,7 +42,13 @@ struct PvFused {
                          //   ONE sample (grid == B, units == B * N / 16, x_units == 0): the caller's promise, re-checked by the kernel
   const float* sw;       // per-sample weight of dL/dlogit (jiVAE: alpha[b][k] of sample (k, b)); null: 1
   int64_t x_units;       // > 0: the observations repeat every x_units units (jiVAE: B*N/16; x is (B, N)); 0: x is (M)
+  union {
   void* wimg;            // bf16x3 kernel only: FB_WIMG_BYTES of pre-split weight images (pv_sdec_fused_bf16_prep)
+  const float* pw;       // weighted launches of pv_sdec_fused_mc.hip only (pv_sdec_fused_mc_launch(..., weighted = true)): (N * C)
+                         //   per-observation weights of the likelihood, shared by all samples (pv_ivae_weighted_*).  The f32 kernels
+                         //   have no weight images, so the two share the slot: the struct keeps its size and every field its offset —
+                         //   and with them every kernel that takes a PvFused its argument layout, hidden arguments included
+  };
   void* park;            // 8-wave split-precision kernel only: pv_sdec_fused_w8x3_park_bytes(grid) of per-wave parking slots
   int64_t M;             // rows
   int64_t units;         // M / FD_UNIT
@@ -143,7 +149,12 @@ bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p);
 // wo (C, H), bo (C); llrow (M) sums the row's C values, c ascending.  Record (PV_REC_ROWMAJOR): channel 0's d(wo) / d(bo) where
 // the one-channel kernel puts them (slot 4, slot 5 [0]); channel c >= 1: d(wo)[c] in slot 5 + c, d(bo)[c] at slot 5 [c].
 // PV_EINVAL for sw, x_units, part_rs, dhz_out, dzc_out or wimg set, or a C without an instance.  f.ablate is ignored.
-int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s);
+// weighted: the weighted instances (C = 1 .. PV_MAX_CHANNELS; C = 1 exists in this form only): f.pw (the slot of wimg) must be set;
+// ll and dL/da of observation (n, c) of every sample are multiplied by pw[n * C + c]; loc is not.  The record is the unweighted launch's
+int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s, bool weighted = false);
+// true when a WEIGHTED step of the plan (pv_ivae_weighted_*) runs that kernel: fused == 1, the trunk's architecture, positions a
+// multiple of 16, a weighted instance for the channel count — one channel, or 2 .. PV_MAX_CHANNELS with PV_PLAN_FUSED_CHANNELS
+bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p);
 // sums the records' entries of channels 1 .. C-1 — (C - 1) (H + 1) outputs, each over the `grid` records in the shared reduction's
 // fixed order (four slices of ascending workgroups) — into G + wo_off + c H and G + bo_off + c; channel 0 is the shared reduction's
 int pv_sdec_fused_mc_reduce_out(const float* part, int grid, float* G, int64_t wo_off, int64_t bo_off, int C, hipStream_t s);

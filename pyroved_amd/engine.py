@@ -65,7 +65,11 @@ class IVAEEngine:
     returns loc / decode in that shape, and runs the layer-by-layer kernels whatever `fused` asks for (plan.out.out_dim = C,
     plan.n_pix = prod(data_dim) * C) — unless fused_channels=True: then fused = 1 or 2 runs the step, evaluate and decode on the
     fused f32 decoder kernel's multi-channel sibling (plan.fused = 1 + PV_PLAN_FUSED_CHANNELS; fp32-class results) wherever the
-    decoder is the one that kernel is written for (hidden [128, 128], tanh, positions a multiple of 16), and layered elsewhere."""
+    decoder is the one that kernel is written for (hidden [128, 128], tanh, positions a multiple of 16), and layered elsewhere.
+    pixel_weights=w: one weight >= 0 per observed value (a mask, a gain map), shared by all images, multiplies every log p(x_bi | z_b)
+    of the training step, evaluate and elbo_terms (pv_ivae_weighted_*; encode / decode never see it).  models.iVAE with its own
+    fully connected networks, the one-particle ELBO, fused = 0, 1 or 2.  A one-channel model with fused = 1 or 2 then runs the
+    weighted fused f32 decoder kernel (plan.fused = 1), not the fp16-piece kernel of the unweighted fused = 2 step."""
     supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
@@ -86,9 +90,11 @@ class IVAEEngine:
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
     renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
                                      # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
+    pixel_weights = None             # None, or the per-observation weights of the likelihood: one contiguous float32 tensor of n_pix
+                                     # values (positions x channels, channel-last), on the device once the engine is bound — pv_ivae_weighted_*
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
-                 particles: int = 1, renyi=None, fused_channels: bool = False):
+                 particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None):
         self.model = model
         self.fused_channels = bool(fused_channels)
         self.kl = _kl_name(kl)
@@ -108,8 +114,10 @@ class IVAEEngine:
         self._layout: Dict[str, int] = {}
         self._views: Dict[str, torch.Tensor] = {}
         self._check_model()
+        self.pixel_weights = self._pixel_weight_tensor(pixel_weights)
         self._check_particles()
         self._check_fused_channels()
+        self._check_pixel_weights()
         self.bind()
 
     # ------------------------------------------------------------------ structure
@@ -268,6 +276,8 @@ class IVAEEngine:
         self.device = dev
         self.scalars = self.grad[total:total + N_SCALARS]
         self.grid = self.model.grid.to(dev).contiguous() if self.model.coord > 0 else None
+        if getattr(self, "pixel_weights", None) is not None:
+            self.pixel_weights = self.pixel_weights.to(dev).contiguous()
         self.ws = None
         if self.ext_enc or self.ext_dec or getattr(self, "ext_y", False):
             # the user module's parameters: their own torch Adam (zero_grads semantics)
@@ -289,7 +299,7 @@ class IVAEEngine:
         layered or the bf16-class fused decoder path; renyi with the sampled KL form only."""
         # (the native one-call DP step is the one-particle, single-channel ELBO's)
         self.supports_dp_step = (type(self).supports_dp_step and self.particles == 1 and self.renyi is None
-                                 and getattr(self, "C", 1) == 1)
+                                 and getattr(self, "C", 1) == 1 and getattr(self, "pixel_weights", None) is None)
         if self.particles == 1 and self.renyi is None:
             return
         what = "particles > 1" if self.renyi is None else "renyi"
@@ -322,14 +332,69 @@ class IVAEEngine:
         if self.fused == 0:
             raise ValueError("fused_channels=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2")
 
-    def _plan_fused(self) -> int:
-        """pv_ivae_plan.fused: the engine's `fused`, or 1 where fused_channels routes a multi-channel model to the f32 kernel."""
-        return 1 if (self.fused_channels and self.C > 1 and self.fused in (1, 2)) else int(self.fused)
+    def _pixel_weight_tensor(self, w):
+        """pixel_weights as the library takes them: None / False -> None; a tensor, ndarray or bool mask of shape data_dim (the same
+        weight in every channel) or (*data_dim, C) -> a contiguous float32 tensor of n_pix values, channel-last.  ValueError for
+        another shape, negative or non-finite entries, or weights that are all zero."""
+        if w is None or w is False:
+            return None
+        try:
+            t = torch.as_tensor(w).detach()
+        except Exception as e:
+            raise ValueError("pixel_weights must be a tensor, an ndarray or a bool mask (got %s)" % type(w).__name__) from e
+        dd = tuple(int(d) for d in self.model.data_dim)
+        Cn = int(getattr(self, "C", 1))
+        if t.dtype == torch.bool:
+            t = t.to(torch.float32)
+        if not (t.is_floating_point() or t.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+            raise ValueError("pixel_weights must be real-valued or a bool mask (got dtype %s)" % t.dtype)
+        t = t.to(torch.float32)
+        if tuple(t.shape) == dd and Cn > 1:
+            t = t.unsqueeze(-1).expand(*dd, Cn)
+        elif tuple(t.shape) not in (dd + (Cn,), dd if Cn == 1 else None):
+            want = "%s" % (dd,) if Cn == 1 else "%s (one weight per position, every channel) or %s" % (dd, dd + (Cn,))
+            raise ValueError("pixel_weights must have shape %s (got %s)" % (want, tuple(t.shape)))
+        t = t.reshape(-1).contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("pixel_weights must be finite (found nan or inf)")
+        if bool((t < 0).any()):
+            raise ValueError("pixel_weights must be >= 0 (found %g)" % float(t.min()))
+        if not bool((t > 0).any()):
+            raise ValueError("pixel_weights are all zero: no observation would enter the loss")
+        dev = getattr(self, "device", None)
+        return t.to(dev) if dev is not None else t.clone()
 
-    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None):
+    def _check_pixel_weights(self):
+        """pixel_weights (pv_ivae_weighted_*): the one-particle ELBO of models.iVAE with its own fully connected networks, on
+        fused = 0, 1 or 2."""
+        if getattr(self, "pixel_weights", None) is None:
+            return
+        if type(self) is not IVAEEngine or getattr(self, "K", 0) > 0:
+            raise ValueError("pixel_weights is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
+        if self.conv_enc or self.ext_enc or self.ext_dec:
+            raise ValueError("pixel_weights needs the model's own fully connected encoder and decoder (no convolutional or "
+                             "user-defined networks)")
+        if self.particles > 1 or self.renyi is not None:
+            raise ValueError("pixel_weights runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)")
+        if self.fused == 3:
+            raise ValueError("pixel_weights is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
+                             "no weighted form, and training at another precision than the one asked for is worse than refusing")
+
+    def _plan_fused(self) -> int:
+        """pv_ivae_plan.fused: the engine's `fused`, or 1 where fused_channels routes a multi-channel model to the f32 kernel —
+        and where pixel_weights route a one-channel model there (fused = 1 or 2: the weighted fused f32 kernel)."""
+        if self.fused_channels and self.C > 1 and self.fused in (1, 2):
+            return 1
+        if getattr(self, "pixel_weights", None) is not None and self.C == 1 and self.fused in (1, 2):
+            return 1
+        return int(self.fused)
+
+    def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None,
+                  pixel_weights=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
-        renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting."""
+        renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting.
+        pixel_weights: weights set them, False removes them, None leaves the setting."""
         if lr is not None:
             self.lr = float(lr)
         if betas is not None:
@@ -337,6 +402,11 @@ class IVAEEngine:
         if eps is not None:
             self.adam_eps = float(eps)
         old = (self.fused, self.particles, self.renyi, self.kl, self.fused_channels)
+        old_pw = self.pixel_weights
+        if pixel_weights is not None:
+            self.pixel_weights = self._pixel_weight_tensor(pixel_weights)     # (raises before anything is changed)
+            if self.pixel_weights is not None or old_pw is not None:          # (False on an unweighted engine: nothing to reset)
+                self.ws = None
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
             self.ws = None
@@ -353,8 +423,10 @@ class IVAEEngine:
             self._check_particles()
             self._check_kl()
             self._check_fused_channels()
+            self._check_pixel_weights()
         except ValueError:
             self.fused, self.particles, self.renyi, self.kl, self.fused_channels = old
+            self.pixel_weights = old_pw
             self._check_particles()
             raise
         if self.flat is not None:
@@ -596,7 +668,9 @@ class IVAEEngine:
         p.ev_start, p.ev_stop = self.events
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
-        if what == 1 and self.renyi is not None:         # ... plus the bound's per-image term
+        if what == 1 and self.pixel_weights is not None:  # the layout of the kernel family the weighted step runs
+            need = _abi.lib().pv_ivae_weighted_workspace_bytes(C.byref(p))
+        elif what == 1 and self.renyi is not None:       # ... plus the bound's per-image term
             need = _abi.lib().pv_ivae_renyi_workspace_bytes(C.byref(p), self.particles)
         elif what == 1 and self.particles > 1:           # the training step's layout for P decoder samples per image
             need = _abi.lib().pv_ivae_particles_workspace_bytes(C.byref(p), self.particles)
@@ -663,6 +737,10 @@ class IVAEEngine:
         if (P > 1 or alpha is not None) and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
                                              or class_onehot is not None):
             raise ValueError("particles > 1 / renyi cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
+        pw = self.pixel_weights
+        if pw is not None and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
+                               or class_onehot is not None):
+            raise ValueError("pixel_weights cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
         if weights_out is not None and alpha is None:
             raise ValueError("weights_out belongs to the importance-weighted bound: model.engine(particles=P, renyi=alpha)")
         if self.conv_enc:
@@ -735,6 +813,9 @@ class IVAEEngine:
                                "pv_ivae_renyi_step")
                 elif P > 1:
                     _abi.check(_abi.lib().pv_ivae_particles_step(C.byref(p), P, _abi.current_stream()), "pv_ivae_particles_step")
+                elif pw is not None:
+                    _abi.check(_abi.lib().pv_ivae_weighted_step(C.byref(p), _abi.ptr(pw), _abi.current_stream()),
+                               "pv_ivae_weighted_step")
                 else:
                     _abi.check(_abi.lib().pv_ivae_step(C.byref(p), _abi.current_stream()), "pv_ivae_step")
                 self.adam_t += 1
@@ -744,6 +825,9 @@ class IVAEEngine:
             elif P > 1:
                 _abi.check(_abi.lib().pv_ivae_particles_loss_and_grads(C.byref(p), P, int(want_grads), _abi.current_stream()),
                            "pv_ivae_particles_loss_and_grads")
+            elif pw is not None:
+                _abi.check(_abi.lib().pv_ivae_weighted_loss_and_grads(C.byref(p), _abi.ptr(pw), int(want_grads),
+                                                                      _abi.current_stream()), "pv_ivae_weighted_loss_and_grads")
             else:
                 _abi.check(_abi.lib().pv_ivae_loss_and_grads(C.byref(p), int(want_grads), _abi.current_stream()),
                            "pv_ivae_loss_and_grads")
@@ -956,6 +1040,8 @@ class IVAEEngine:
     @_abi.on_device
     def uses_fused(self, batch: int) -> bool:
         """Whether loss_and_grads runs the fused persistent decoder kernel for this batch size."""
+        if self.pixel_weights is not None:
+            return bool(_abi.lib().pv_ivae_weighted_uses_fused(C.byref(self._plan(batch))))
         return bool(_abi.lib().pv_ivae_uses_fused(C.byref(self._plan(batch))))
 
     # views for tests / data-parallel reduction

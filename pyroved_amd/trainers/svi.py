@@ -71,6 +71,12 @@ class SVItrainer:
             says (default False; fp32-class results; decoders of hidden size [128, 128] with tanh and a number of grid
             positions that is a multiple of 16 — others keep the layered kernels).  A ValueError with num_particles > 1,
             loss="RenyiELBO", fused=0, fused=3 or precision="bf16".  Changes nothing for a single-channel model
+        pixel_weights: per-observation weights of the likelihood, shared by all images: a tensor, ndarray or bool mask of shape
+            data_dim (the same weight in every channel of a multi-channel model) or (*data_dim, C); entries >= 0, not all zero.
+            Every log p(x_bi | z_b) of train / evaluate is multiplied by w_i (its normaliser included) — a circular aperture for
+            a rotation-invariant model, dead detector pixels, a gain map.  models.iVAE with its own fully connected networks, the
+            one-particle ELBO (both loss strings), fp32-class precision; a ValueError elsewhere.  A one-channel model then trains
+            on the weighted fused f32 decoder kernel — about the cost of fused=1, well above the default step's
         process_group: torch.distributed group for data-parallel training (default: WORLD if initialised)
         device_feed: keep TensorDataset loaders' data on the device and gather minibatches there, in the order the
             loader's own sampler produces (default True; same numbers as iterating the loader)
@@ -151,7 +157,8 @@ class SVItrainer:
             if pvdist.world(self.group)[1] > 1:
                 raise ValueError("Pyro optimizer / loss objects cannot be combined with data-parallel training: replicas "
                                  "would train unsynchronised (pass optimizer=None or a dict of Adam arguments)")
-            bad = [k for k in ("precision", "fused", "fused_channels", "rng", "device_feed", "mirror_evaluate_update") if k in kwargs]
+            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "rng", "device_feed", "mirror_evaluate_update")
+                   if k in kwargs]
             if bad:
                 raise ValueError("%s only apply to the HIP training path, not to Pyro optimizer / loss objects" % bad)
             pyro.clear_param_store()
@@ -196,9 +203,14 @@ class SVItrainer:
                 raise ValueError("precision='bf16' is not implemented for channels=%d: no bf16 multi-channel decoder kernel "
                                  "exists, and training at another precision than the one asked for is worse than refusing"
                                  % model.channels)
+            pw = kwargs.get("pixel_weights", None)
+            if pw is not None and pw is not False and precision == "bf16":
+                raise ValueError("pixel_weights is not implemented for precision='bf16': the bf16 throughput kernels have no "
+                                 "weighted form")
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
-                                       renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels)
+                                       renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels,
+                                       pixel_weights=False if pw is None else pw)      # (no keyword: a later trainer is unweighted)
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
