@@ -1,0 +1,183 @@
+"""
+CPU tests of tests/_partition_cases.py: the case table of tests/test_gpu_partition_edges.py says what it claims, the slot bound of
+the fused decoder kernels' row partition holds and is tight, and no cell of that GPU test is blind.
+
+Blindness.  The slot arithmetic (`gfirst`, `kmax`) decides where a workgroup's partial of ONE sample lands; an off-by-one there
+puts one workgroup's share of one sample — one or a few 16-row units — into another sample's slots or drops it.  So a cell can
+only notice such an error if taking ONE unit of ONE sample out of the objective moves something the cell checks by well more than
+the bar it is checked at.  The condition asserted here, with the float64 oracle alone: for the first, the middle and the last
+decoder sample, and the first and the last unit of that sample, at least one checked gradient quantity — a gradient tensor
+(relative L2), a row of decoder.out.weight or an entry of decoder.out.bias (C > 1), a row of dy or an entry of row_elbo (where
+the cell carries them) — moves by at least 5x its own bar in that family.  (The loss scalars, z and loc_out are left out of the
+condition on purpose: they would meet it everywhere, and none of them depends on the slots.)
+"""
+import numpy as np
+import pytest
+import torch
+
+import _partition_cases as pc
+
+
+@pytest.fixture(autouse=True)
+def _cpu_threads():
+    n = torch.get_num_threads()
+    torch.set_num_threads(16)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+# ------------------------------------------------------------------------------- 1. the table's claims
+@pytest.mark.parametrize("name", sorted(pc.CASES))
+def test_case_reaches_what_the_table_claims(name):
+    c = pc.CASES[name]
+    p = pc.case_partition(c, 256)
+    print("%s: %s" % (name, pc.describe(p)))
+    assert c["claims"], name
+    for key, want in c["claims"].items():
+        assert p[key] == want, (name, key, p[key], want)
+    assert p["gfirst_ok"] and p["min_slot"] == 0 and p["max_slot"] <= p["kmax"] - 1
+    assert p["units"] * pc.UNIT <= 38400                     # no case exceeds 38 400 decoder rows
+
+
+def test_what_the_cases_reach_together():
+    at = {n: pc.case_partition(c, 256) for n, c in pc.CASES.items()}
+    # a unit count one above a multiple of the grid, and one above the grid itself
+    assert at[pc.E04]["units"] % 256 == 1 and at["e01_1d16_t_b257"]["units"] == 257
+    # three samples in one workgroup at upb = 1
+    assert 3 in at["e02_1d16_t_b600"]["samples_per_wg"]
+    # every tail length of the 4-wave tile (units per workgroup mod 4 = 1, 2, 3, 0) and the 8-wave tile's 1- and 2-unit tails
+    tails = {u % 4 for n in at if n.startswith(("e06", "e07", "e08")) for u in at[n]["units_per_wg"]}
+    assert tails == {0, 1, 2, 3}
+    assert {u % 8 for u in at["e06_8x8_rts_cdim2_b600"]["units_per_wg"]} == {1, 2}
+    # the size rules: H231 from 1024 units, the 8-wave builds from 6 units per workgroup, the guide's own launch up to batch 384
+    assert at["e08_8x8_rts_b256"]["units"] == 1024 and at["e08_8x8_rts_b255"]["units"] < 1024
+    assert at["e06_8x8_rts_cdim2_b600"]["units"] >= 6 * 256 > at["e07_8x8_r_cdim2_b352"]["units"]
+    assert at["e07_8x8_r_cdim2_b416"]["units"] >= 6 * 256
+    # a case whose last slot is the bound itself
+    assert any(p["max_slot"] == p["kmax"] - 1 for p in at.values())
+    # every cell is run or refused with a reason; the instances no other test launches are among the cells
+    cells = pc.cells()
+    for fam in ("mc6", "w4", "w5", "w6", "w7"):
+        assert (pc.E04, fam) in cells
+    for n in pc.CASES:
+        for f in pc.FAMILIES:
+            assert ((n, f) in cells) != bool(pc.refusal(n, f))
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in pc.CASES.items() if c["c_dim"]))
+def test_dy_rows_are_well_conditioned(name):
+    """What the per-row relative bar of dy rests on: no sample's float64 dy row is below DY_FLOOR of the median row norm."""
+    dy = pc.reference(name, "plain")["dy"]
+    norm = dy.norm(dim=1)
+    print("%s: dy row norms min %.3e, median %.3e" % (name, norm.min(), norm.median()))
+    assert dy.shape == (pc.CASES[name]["B"], 2) and norm.min() >= 0.9 * pc.DY_FLOOR * norm.median()
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in pc.CASES.items() if c["kind"] == "ivae"))
+def test_bias_gradients_are_not_cancellations(name):
+    """decoder.out.bias' gradient is the sum of dL/dlogit over every row: the data must not make it cancel (uniform noise around the
+    initial decoder mean 0.5 does), or a relative bar on it measures rounding noise.  |sum| >= 0.1 sum | |, from the reference."""
+    c = pc.CASES[name]                                       # (jiVAE's is judged on an absolute scale; the particle case has e01's data)
+    ref = pc.reference(name, "plain")
+    x = pc.inputs(name, "plain")[0].reshape(c["B"], -1).double()
+    d = ref["loc"] - x                                       # Bernoulli with a sigmoid mean: dL/dlogit = p - x
+    assert abs(d.sum().item() - ref["grads"]["decoder.out.bias"].item()) < 1e-9 * d.abs().sum().item()
+    assert abs(d.sum().item()) >= 0.1 * d.abs().sum().item()
+
+
+# ------------------------------------------------------------------------------- 2. the slot bound, brute force
+def test_slot_bound_holds_and_is_tight():
+    """gfirst(b) is the first workgroup touching sample b, every workgroup touching b uses a slot in [0, kmax), and slot kmax - 1
+    is used in some shape: upb in 1..19, 49, 64, 100, 256 and B in 1..699, 1024, 2048, 4096 at G = 256."""
+    tight = 0
+    for upb in list(range(1, 20)) + [49, 64, 100, 256]:
+        for B in list(range(1, 700)) + [1024, 2048, 4096]:
+            p = pc.partition(upb * pc.UNIT, B, 256)
+            assert p["gfirst_ok"], (upb, B)
+            assert p["min_slot"] == 0 and p["max_slot"] <= p["kmax"] - 1, (upb, B, p["max_slot"], p["kmax"])
+            tight += p["max_slot"] == p["kmax"] - 1
+    print("shapes whose last slot is kmax - 1: %d" % tight)
+    assert tight > 0
+
+
+def test_restatement_against_a_walk_over_the_units():
+    """partition() against the kernels' loop written out: every workgroup walks its units and flushes at a sample's end."""
+    for N, S, cus in ((16, 257, 256), (48, 171, 256), (784, 6, 256), (64, 600, 256), (16, 7, 4), (32, 5, 3)):
+        p = pc.partition(N, S, cus)
+        upb, units, G = p["upb"], p["units"], p["grid"]
+        slots = {}
+        for g in range(G):
+            for u in range(g * units // G, (g + 1) * units // G):
+                b = u // upb
+                gfirst = ((b * upb + 1) * G + units - 1) // units - 1
+                slots.setdefault(b, set()).add(g - gfirst)
+        assert sorted(slots) == list(range(S))
+        assert all(min(v) == 0 and sorted(v) == list(range(len(v))) for v in slots.values())
+        assert max(max(v) for v in slots.values()) == p["max_slot"] <= p["kmax"] - 1
+        assert (min(len(v) for v in slots.values()), max(len(v) for v in slots.values())) == p["wgs_per_sample"]
+
+
+# ------------------------------------------------------------------------------- 3. no cell is blind
+def _norm(t):
+    return t.double().norm().item()
+
+
+def moves(name, variant):
+    """For the first / middle / last sample and its first / last unit: {quantity: relative move} when that unit leaves the
+    objective.  Quantities: "g:<tensor>", "ow:<c>" / "ob:<c>" (rows of decoder.out.weight / entries of .bias, C > 1), "row_elbo",
+    "dy" (relative to that sample's own entry / row)."""
+    c = pc.CASES[name]
+    ref = pc.reference(name, variant)
+    S, upb, B = pc.n_samples(c), pc.n_pos(c) // pc.UNIT, c["B"]
+    out = []
+    for s in sorted({0, S // 2, S - 1}):
+        for u in sorted({0, upb - 1}):
+            g, term, gy = pc.unit_term_grads(name, variant, s, u)
+            m = {}
+            for k, full in ref["grads"].items():
+                m["g:" + k] = _norm(g[k]) / max(_norm(full), 1e-300)
+            if pc.channels_of(variant) > 1:
+                fw, fb = ref["grads"]["decoder.out.weight"], ref["grads"]["decoder.out.bias"]
+                for ch in range(fw.shape[0]):
+                    m["ow:%d" % ch] = _norm(g["decoder.out.weight"][ch]) / max(_norm(fw[ch]), 1e-300)
+                    m["ob:%d" % ch] = abs(g["decoder.out.bias"][ch].item()) / max(abs(fb[ch].item()), 1e-300)
+            if ref["row_elbo"] is not None:
+                m["row_elbo"] = abs(term) / abs(ref["row_elbo"][s % B].item())
+            if gy is not None:
+                m["dy"] = _norm(gy) / max(_norm(ref["dy"][s % B]), 1e-300)
+            out.append(((s, u), m))
+    return out
+
+
+def bar_of(name, family, q):
+    if q.startswith("g:"):
+        return pc.grad_bar(name, family, q[2:])
+    if q.startswith(("ow:", "ob:")):
+        return pc.RTOL_GRAD
+    if not pc.has_rows(name, family):
+        return None                                        # the cell does not carry per-sample quantities
+    return pc.row_bars(name, family)[0 if q == "row_elbo" else 1]
+
+
+_MOVES = {}
+
+
+@pytest.mark.parametrize("name,family", pc.cells(), ids=["%s-%s" % nf for nf in pc.cells()])
+def test_cell_is_not_blind(name, family):
+    variant = pc.FAMILIES[family]["variant"]
+    key = (name, variant)
+    if key not in _MOVES:
+        _MOVES[key] = moves(name, variant)
+    worst_global, worst_any = np.inf, np.inf
+    for (s, u), m in _MOVES[key]:
+        ratios = {q: v / bar_of(name, family, q) for q, v in m.items() if bar_of(name, family, q)}
+        best_global = max((r for q, r in ratios.items() if q not in ("row_elbo", "dy")), default=0.0)
+        best = max(ratios.values())
+        worst_global, worst_any = min(worst_global, best_global), min(worst_any, best)
+    print("%s %s: a unit taken out moves the best global quantity by %.1fx its bar, the best quantity overall by %.1fx"
+          % (name, family, worst_global, worst_any))
+    assert worst_any >= 5.0, (name, family, worst_global, worst_any)
+    if not pc.has_rows(name, family):
+        assert worst_global >= 5.0                         # (global tensors are all such a cell has)
