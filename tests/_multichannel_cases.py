@@ -2,6 +2,7 @@
 _multichannel_cases.py — the data and the case table the tests of multi-channel models, iVAE(..., channels=C), run on.  The
 reference itself is oracle.svi_oracle with Config(channels=C): x is (B, *data_dim, C), channel-last.
 """
+import numpy as np
 import torch
 
 from oracle import svi_oracle as orc
@@ -85,6 +86,11 @@ def case_data(c, particles=1):
         y = torch.zeros(c["b"], c["c_dim"])
         y[torch.arange(c["b"]), torch.arange(c["b"]) % c["c_dim"]] = 1.0
     return x, y, eps
+
+
+def loss_atol(c):
+    """test_model_variants_vs_oracle: 1e-6 per value of the batch for the continuous Bernoulli, none otherwise."""
+    return 1e-6 * c["b"] * int(np.prod(c["dims"])) if c.get("sampler") == "continuous_bernoulli" else 0.0
 
 
 def round_to_float32(o):

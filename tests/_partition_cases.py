@@ -18,7 +18,7 @@ import torch
 import torch.distributions as td
 
 from conftest import jivae_grad_tol
-from test_gpu_parity import h2_grad_tol          # (the module imports without a GPU; its tests are marked gpu)
+from _judge import h2_grad_tol
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
 import _pixel_weight_cases as pw
@@ -328,7 +328,7 @@ RTOL_ELBO, RTOL_KL, RTOL_GRAD, RTOL_ROW = 2e-5, 1e-4, 1e-4, 1e-4       # the pro
 
 # plain bf16 against the emulation (oracle/bf16_plan.py), per (case, family): (gradient bar, loss bar, row_elbo bar, dy bar).  Each is
 # 4x the value measured for that cell on MI355X (256 CUs; in the comment: worst gradient tensor / the worse of loss and ll / worst
-# row_elbo entry / worst dy row), and never above the ceilings of tests/test_gpu_bf16_emulated.py: 1e-3 for gradients and dy rows,
+# row_elbo entry / worst dy row), and never above the ceilings of tests/_bf16_judge.py: 1e-3 for gradients and dy rows,
 # 1e-5 for the loss and the row_elbo entries.  Where 4x would pass the ceiling the ceiling is the bar (two dy bars, 19 row_elbo bars).
 # One deviation from "4x the cell's own value": the loss bar is never below BF16_LOSS_FLOOR = 2 fp32 eps — measured loss residuals go
 # down to 1.4e-8, under fp32's own rounding of the scalar (6e-8), and 4x such a value would be a bar on the scalar's last bit.

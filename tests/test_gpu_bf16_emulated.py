@@ -23,38 +23,11 @@ from pyroved_amd import _abi
 from pyroved_amd.engine import IVAEEngine
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
+from _bf16_judge import judge, SELF_CHECK, DECODE_BAR, LIK
+from _device import cus, kernel_name
+from _judge import rel_l2, near_zero, cpu_threads_16
 
 pytestmark = pytest.mark.gpu
-
-# ceilings (the issue's paper estimate) — the per-case bars below are set from measurement, at most 4x the worst value seen
-GRAD_CEIL, LOSS_CEIL, LOC_CEIL = 1e-3, 1e-5, 1e-4
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _kernel_name(units, lik, fused=3, grads=1):
-    lib = _abi.lib()
-    lib.pv_debug_decoder_kernel_name.restype = C.c_char_p
-    lib.pv_debug_decoder_kernel_name.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
-    return lib.pv_debug_decoder_kernel_name(fused, units, grads, lik).decode()
-
-
-@pytest.fixture(autouse=True)
-def _cpu_threads():
-    """the float64 references run on 16 threads; the setting is restored for whatever runs next"""
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
 
 
 @dataclasses.dataclass
@@ -73,8 +46,6 @@ class Case:
     beta: float = 1.0
     seed: int = 1
 
-
-LIK = {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2}
 
 CASES = {
     # the headline: C2, 8-wave kernel with the guide folded in, 49 units per workgroup = 6 tiles + a column-parallel tail
@@ -109,7 +80,7 @@ CASES = {
 }
 
 # Bars per case, from the measured residuals (MI355X): gradient rel L2 (worst tensor), loss relative.  Each bar is <= 4x the
-# worst value measured (over the three draws for C2) and <= the ceilings above; the comment gives the measurement and the
+# worst value measured (over the three draws for C2) and <= the ceilings of tests/_bf16_judge.py; the comment gives the measurement and the
 # self-check's factor (how much closer the kernel lies to the emulation than to float64, worst tensor more than 1e-3 from it).
 _C2 = (1.8e-4, 2.5e-7)                     # worst of the three draws: 4.66e-5 (seed7) / 6.49e-8 (seed7)
 BARS = {
@@ -136,12 +107,10 @@ BARS = {
     "cbern_16x16_r": (1.0e-3, 6.3e-5),     # 4.28e-4 / 1.6e-5, factor 21.3
     "1d32_t_cdim2": (9.1e-4, 3.0e-7),      # 2.29e-4 / 7.5e-8, factor 11.1
 }
-SELF_CHECK = 10.0
 # trained state: measured 5.42e-4 (fc_layers.0.weight) from the emulation with rounded records, loss 1.16e-7
 TRAINED_BARS = (1.0e-3, 4.6e-7)
 # record rounding alone in the trained state (emulation with rounded vs exact records): measured 1.64e-3 (W1) / 1.70e-3 (W2)
 TRAINED_RECORDS_BAR = 6.5e-3
-DECODE_BAR = 1.2e-6                        # model.decode vs float64: measured 2.42e-7 / 3.05e-7 (fp32-class build)
 
 
 def _setup(case: Case):
@@ -173,9 +142,9 @@ def _setup(case: Case):
             # (the library's name lookup knows the size rule only: that the forced launch IS the 8-wave build is shown by the
             #  result, test_bf16_step_vs_emulated_reference: closer to the 8-wave restatement than to the 4-wave one)
             assert eng._plan(b).dec_kernel == 2
-            assert "pv_sdec_w8_kernel" not in _kernel_name(units, lik)       # unforced, this size takes the other build
+            assert "pv_sdec_w8_kernel" not in kernel_name(fused=3, units=units, lik=lik)       # unforced, this size takes the other build
         else:
-            name = _kernel_name(units, lik)
+            name = kernel_name(fused=3, units=units, lik=lik)
             want = "pv_sdec_w8_kernel<true, %d, 0>" % lik if case.kernel == "w8" else \
                 "pv_sdec_fused_bf16_kernel<true, %d, 0>" % lik
             assert want in name, (name, want)
@@ -196,32 +165,6 @@ def _reference(case, params, x, eps, y, plan):
     return out, {k: v.grad.detach().clone() for k, v in o.p.items()}, o
 
 
-def _report(case_name, rows):
-    print("\n[bf16-emulated] %s" % case_name)
-    for key, e_em, e_64 in rows:
-        print("  %-42s vs emulated %.3e   vs float64 %.3e" % (key, e_em, e_64))
-
-
-def _judge(case_name, eng, ref_out, ref_g, f64_out, f64_g, zl, zs, grad_bar, loss_bar, factor=10.0):
-    loss = eng.scalars[0].item()
-    rows = []
-    le = abs(loss - ref_out["loss"].item()) / abs(ref_out["loss"].item())
-    rows.append(("loss", le, abs(loss - f64_out["loss"].item()) / abs(f64_out["loss"].item())))
-    rows.append(("z_loc", rel_l2(zl, ref_out["z_loc"].detach()), rel_l2(zl, f64_out["z_loc"].detach())))
-    rows.append(("z_scale", rel_l2(zs, ref_out["z_scale"].detach()), rel_l2(zs, f64_out["z_scale"].detach())))
-    for key in ref_g:
-        g = eng.grad_of(key)
-        rows.append((key, rel_l2(g, ref_g[key]), rel_l2(g, f64_g[key])))
-    _report(case_name, rows)
-    assert le < loss_bar, "%s: loss %.3e from the emulation (bar %.1e)" % (case_name, le, loss_bar)
-    for key, e_em, e_64 in rows[1:]:
-        bar = 1e-5 if key.startswith("z_") else grad_bar
-        assert e_em < bar, "%s: %s %.3e from the emulation (bar %.1e)" % (case_name, key, e_em, bar)
-        if e_64 > 1e-3:   # the emulation must explain the error, not just sit under a lucky bar
-            assert e_em * factor <= e_64, "%s: %s %.3e from the emulation, %.3e from float64" % (case_name, key, e_em, e_64)
-    return rows
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_bf16_step_vs_emulated_reference(gpu_device, name):
     case = CASES[name]
@@ -236,15 +179,15 @@ def test_bf16_step_vs_emulated_reference(gpu_device, name):
     finally:
         IVAEEngine.dec_kernel = 0
     params = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-    plan = bp.Bf16Plan(kernel=case.kernel, cus=_cus())
+    plan = bp.Bf16Plan(kernel=case.kernel, cus=cus())
     ref_out, ref_g, o = _reference(case, params, x, eps, y, plan)
     f64_out, f64_g, _ = _reference(case, params, x, eps, y, None)
     grad_bar, loss_bar = BARS[name]
-    _judge(name, eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), grad_bar, loss_bar, SELF_CHECK)
+    judge(name, eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), grad_bar, loss_bar, SELF_CHECK)
     if case.force_w8:
         # which build ran, from its arithmetic: the 8-wave kernel's images of C W and bf16-h derivatives, not the 4-wave
         # build's unscaled images and fp32-h derivatives
-        _, w4_g, _ = _reference(case, params, x, eps, y, bp.Bf16Plan(kernel="w4", cus=_cus()))
+        _, w4_g, _ = _reference(case, params, x, eps, y, bp.Bf16Plan(kernel="w4", cus=cus()))
         for key in ("decoder.fc_layers.0.weight", "decoder.fc_layers.2.weight"):
             e8, e4 = rel_l2(eng.grad_of(key), ref_g[key]), rel_l2(eng.grad_of(key), w4_g[key])
             print("  %s: vs the 8-wave restatement %.3e, vs the 4-wave one %.3e" % (key, e8, e4))
@@ -259,7 +202,7 @@ def test_bf16_step_vs_emulated_reference(gpu_device, name):
         o.opt.step()
         for k, p in model.state_dict().items():
             gr = ref_g[k].reshape(p.shape)
-            ill = gr.abs() < 1e-5 * gr.abs().max()
+            ill = near_zero(gr)
             d = (p.detach().cpu().double() - o.p[k].detach())
             assert ill.double().mean() < 0.01 and (not ill.any() or d[ill].abs().max() <= 2 * eng.lr), k
             step = (o.p[k].detach() - p0[k].cpu().double())[~ill]
@@ -279,7 +222,7 @@ def test_bf16_forward_only_vs_emulated_reference(gpu_device, name):
     eng.loss_and_grads(x.cuda(), eps.cuda(), case.beta, want_grads=False, loc_out=loc)
     torch.cuda.synchronize()
     params = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-    plan = bp.Bf16Plan(kernel=case.kernel, cus=_cus())
+    plan = bp.Bf16Plan(kernel=case.kernel, cus=cus())
     o = orc.SVIOracle(params, _cfg(case, plan), dtype=torch.float64)
     o64 = orc.SVIOracle(params, _cfg(case), dtype=torch.float64)
     with torch.no_grad():
@@ -292,7 +235,7 @@ def test_bf16_forward_only_vs_emulated_reference(gpu_device, name):
     assert le < BARS[name][1] and lo < 4.5e-5       # measured loc 1.03e-5 / 1.10e-5 (ceiling LOC_CEIL)
     # model.decode(): pv_ivae_decode launches the split-precision (fp32-class) build whatever the training precision
     # (pv_plan.hip: decode_fused_run) — not the plain-bf16 kernel — so its reference is the plain float64 oracle
-    dname = _kernel_name(b * n_pix // 16, LIK["gaussian"], fused=2, grads=0)
+    dname = kernel_name(fused=2, units=b * n_pix // 16, grads=0, lik=LIK["gaussian"])
     assert "pv_sdec_w8_kernel" not in dname and "0>(PvFused, PvEncFold)" not in dname, dname
     z = torch.randn(b, 2, generator=torch.Generator().manual_seed(2))
     d = model.decode(z).reshape(b, -1)
@@ -320,12 +263,12 @@ def test_bf16_trained_state_records(gpu_device):
     eng.loss_and_grads(xg, eps.cuda(), z_out=(zl, zs))
     torch.cuda.synchronize()
     params = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-    plan = bp.Bf16Plan(kernel="w8", cus=_cus())
+    plan = bp.Bf16Plan(kernel="w8", cus=cus())
     ref_out, ref_g, _ = _reference(case, params, x, eps, y, plan)
     parts = dict(plan.partials)
-    _, nr_g, _ = _reference(case, params, x, eps, y, bp.Bf16Plan(kernel="w8", cus=_cus(), round_records=False))
+    _, nr_g, _ = _reference(case, params, x, eps, y, bp.Bf16Plan(kernel="w8", cus=cus(), round_records=False))
     f64_out, f64_g, _ = _reference(case, params, x, eps, y, None)
-    rows = _judge("c2_trained", eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), *TRAINED_BARS)
+    rows = judge("c2_trained", eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), *TRAINED_BARS)
     for k, key in (("W1", "decoder.fc_layers.0.weight"), ("W2", "decoder.fc_layers.2.weight")):
         pt = parts[k]
         tot = pt.sum(0)

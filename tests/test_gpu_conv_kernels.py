@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from pyroved_amd import _abi
+from _judge import rel_l2
 
 pytestmark = pytest.mark.gpu
 P = C.c_void_p
@@ -37,11 +38,6 @@ def ptr(t):
 
 def stream():
     return P(torch.cuda.current_stream().cuda_stream)
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 def act_fn(name, v):

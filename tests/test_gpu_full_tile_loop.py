@@ -11,7 +11,7 @@ cd == 1 must stay on the generic loop.
 Which loop ran is read back from the library (pv_debug_w8_last_fold_build: the build the last hosting launch dispatched).
 
 Tolerances: none of its own.  Cases 1-4 are bit-identity; case 4 is also held to the bars tests/test_gpu_own_image_sums.py keeps for
-f_28x28_rt against the float64 oracle (reused, and the oracle result is that module's cached one); case 7 (cd == 1, routed to the
+f_28x28_rt against the float64 oracle (tests/_own_image_cases.py: reused, and the oracle result is that module's cached one); case 7 (cd == 1, routed to the
 generic loop) to the bf16 mode's bars of tests/test_gpu_parity.py (loss 1e-4, gradients 3e-2).
 """
 import ctypes as C
@@ -25,11 +25,11 @@ from conftest import make_x
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
-import test_gpu_own_image_sums as own
+import _own_image_cases as own
+from _device import cus, last_fold_build
+from _judge import rel_l2
 
 pytestmark = pytest.mark.gpu
-
-MODE_LOSS_BAR, MODE_GRAD_BAR = 1e-4, 3e-2          # tests/test_gpu_parity.py: the bf16 mode against the fp32 oracle
 
 # name: (data_dim, invariances, units of 16 pixels per image, build the default engine must dispatch)
 CASES = {
@@ -51,17 +51,6 @@ LIKS = {
 }
 
 
-def _batch():
-    return torch.cuda.get_device_properties(0).multi_processor_count      # the fold needs batch == number of CUs
-
-
-def _last_build():
-    lib = _abi.lib()
-    lib.pv_debug_w8_last_fold_build.restype = C.c_int
-    lib.pv_debug_w8_last_fold_build.argtypes = []
-    return int(lib.pv_debug_w8_last_fold_build())
-
-
 def _make(name, full=True, **kw):
     data_dim, inv, units, _ = CASES[name]
     assert int(np.prod(data_dim)) // 16 == units
@@ -69,16 +58,16 @@ def _make(name, full=True, **kw):
     eng = model.engine(fused=3)
     eng.full_tile_loop = full
     if units < 6:
-        eng.dec_kernel = 2          # below the 8-wave kernel's size threshold: forced, as tests/test_gpu_own_image_sums.py does
-    p = eng._plan(_batch())
+        eng.dec_kernel = 2          # below the 8-wave kernel's size threshold: forced, as tests/_own_image_cases.py does
+    p = eng._plan(cus())
     assert bool(p.flags & _abi.PV_PLAN_GENERIC_TILE_LOOP) == (not full)
-    assert int(_abi.lib().pv_ivae_guide_folds(C.byref(p))) == 1 and eng.uses_fused(_batch()), name
+    assert int(_abi.lib().pv_ivae_guide_folds(C.byref(p))) == 1 and eng.uses_fused(cus()), name
     return model, eng
 
 
 def _inputs(name, model, seed=5):
-    x = make_x("rand", _batch(), CASES[name][0], seed=3)
-    eps = torch.randn(_batch(), model.z_dim, generator=torch.Generator().manual_seed(seed))
+    x = make_x("rand", cus(), CASES[name][0], seed=3)
+    eps = torch.randn(cus(), model.z_dim, generator=torch.Generator().manual_seed(seed))
     return x.cuda(), eps.cuda()
 
 
@@ -88,7 +77,7 @@ def _run(name, full, **kw):
     xg, eg = _inputs(name, model)
     eng.loss_and_grads(xg, eg, step=False)
     torch.cuda.synchronize()
-    return eng.scalars.clone(), eng.grad.clone(), _last_build(), eng, model
+    return eng.scalars.clone(), eng.grad.clone(), last_fold_build(), eng, model
 
 
 def _same_bytes(a, b):
@@ -111,7 +100,7 @@ def test_loss_and_grads_same_bytes_with_either_loop(gpu_device, name):
     xg, eg = _inputs(name, model)
     eng.loss_and_grads(xg, eg, step=False)
     torch.cuda.synchronize()
-    assert _last_build() == want
+    assert last_fold_build() == want
     assert _same_bytes(sc1, eng.scalars) and _same_bytes(g1, eng.grad), name
 
 
@@ -133,14 +122,14 @@ def test_one_call_step_same_bytes_with_either_loop(gpu_device, name):
     xg, _ = _inputs(name, m1)
     gen = torch.Generator().manual_seed(9)
     for k in range(2):
-        eps = torch.randn(_batch(), m1.z_dim, generator=gen).cuda()
+        eps = torch.randn(cus(), m1.z_dim, generator=gen).cuda()
         h1, h0 = torch.zeros(4, device="cuda"), torch.zeros(4, device="cuda")
         e1.loss_and_grads(xg, eps, scalars_out=h1, step=True)
         torch.cuda.synchronize()
-        assert _last_build() == 4, (name, k)
+        assert last_fold_build() == 4, (name, k)
         e0.loss_and_grads(xg, eps, scalars_out=h0, step=True)
         torch.cuda.synchronize()
-        assert _last_build() == 2, (name, k)
+        assert last_fold_build() == 2, (name, k)
         assert _same_bytes(h1, h0), (name, k, h1.tolist(), h0.tolist())
         for what, a, b_ in (("params", e1.flat, e0.flat), ("m", e1.m, e0.m), ("v", e1.v, e0.v)):
             assert _same_bytes(a, b_), (name, k, what, (a - b_).abs().max().item())
@@ -149,22 +138,22 @@ def test_one_call_step_same_bytes_with_either_loop(gpu_device, name):
 
 def test_headline_shape_vs_float64_oracle(gpu_device):
     """case 4 on the full-tile loop against the float64 oracle, at tests/test_gpu_own_image_sums.py's bars for f_28x28_rt (the same
-    model, data and noise: that module's inputs and its cached oracle result)"""
+    model, data and noise: tests/_own_image_cases.py's inputs and its cached oracle result)"""
     name = "f_28x28_rt"
-    model, eng = own._make(name)
+    model, eng = own.make(name)
     assert eng.full_tile_loop
-    x, eps = own._inputs(name, model)
-    ref_loss, ref_g = own._reference(name, model, x, eps)
+    x, eps = own.inputs(name, model)
+    ref_loss, ref_g = own.reference(name, model, x, eps)
     eng.loss_and_grads(x.cuda(), eps.cuda(), step=False)
     torch.cuda.synchronize()
-    assert _last_build() == 4
+    assert last_fold_build() == 4
     loss_bar, enc_bar, dec_bar, _ = own.BARS[name]
     le = abs(eng.scalars[0].item() - ref_loss) / abs(ref_loss)
     print("\n[full-tile-loop] %s: loss vs float64 %.3e (bar %.1e)" % (name, le, loss_bar))
     assert le < loss_bar, (le, loss_bar)
     for key in ref_g:
-        d = own.rel_l2(eng.grad_of(key), ref_g[key])
-        bar = enc_bar if own._is_enc(key) else dec_bar
+        d = rel_l2(eng.grad_of(key), ref_g[key])
+        bar = enc_bar if own.is_enc(key) else dec_bar
         print("  %-42s vs float64 %.3e (bar %.1e)" % (key, d, bar))
         assert d < bar, (key, d, bar)
 
@@ -175,13 +164,13 @@ def test_cd1_with_full_tiles_vs_oracle(gpu_device):
     data_dim, inv, _, _ = CASES[name]
     sc, _, build, eng, model = _run(name, True)
     assert build == 2
-    x = make_x("rand", _batch(), data_dim, seed=3)
-    eps = torch.randn(_batch(), model.z_dim, generator=torch.Generator().manual_seed(5))
+    x = make_x("rand", cus(), data_dim, seed=3)
+    eps = torch.randn(cus(), model.z_dim, generator=torch.Generator().manual_seed(5))
     cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv)
     o = orc.SVIOracle({k: v.detach().cpu() for k, v in model.state_dict().items()}, cfg)
     out = o.loss_and_grads(x, eps)
     ref_loss = out["loss"].item()
     le = abs(sc[0].item() - ref_loss) / abs(ref_loss)
-    worst = max(own.rel_l2(eng.grad_of(k), v.grad) for k, v in o.p.items())
+    worst = max(rel_l2(eng.grad_of(k), v.grad) for k, v in o.p.items())
     print("\n[full-tile-loop] %s: loss vs oracle %.3e, worst gradient %.3e" % (name, le, worst))
-    assert le < MODE_LOSS_BAR and worst < MODE_GRAD_BAR, (le, worst)
+    assert le < own.MODE_LOSS_BAR and worst < own.MODE_GRAD_BAR, (le, worst)

@@ -4,8 +4,8 @@ layer Linear(H, C) on the C-output likelihood kernel (pv_out_lik_mc) of the laye
 
 The reference is the project's own float64 oracle (oracle.svi_oracle) with Config(channels=C).  Cases, data and eps come from
 tests/_multichannel_cases.CASES / case_data (torch.Generator().manual_seed(0): data first, then the eps draws).  Every step
-case runs two steps with Adam between, each from identical float32 parameters, at the bars of tests/test_gpu_parity.py:
-loss and ll 2e-5 (+ the atol test_model_variants_vs_oracle gives the sampler), the KL scalars 1e-4, every gradient tensor
+case runs two steps with Adam between, each from identical float32 parameters (tests/_judge.py: steps_vs_reference), at the
+project's bars for the fp32-class paths: loss and ll 2e-5 (+ the atol test_model_variants_vs_oracle gives the sampler), the KL scalars 1e-4, every gradient tensor
 1e-4 relative L2, parameters after Adam by check_params_after_adam's rule with the 5e-5 bar (its 1 % cap is confirmed with
 the reference alone in tests/test_multichannel_cpu.py), z_loc / z_scale rtol 1e-4 atol 5e-6, loc_out and decode rtol 1e-4
 atol 2e-6.
@@ -17,23 +17,14 @@ import torch
 import pyroved_amd as pv
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
-from test_gpu_meanfield import check_params_after_adam, rel_l2, state, RTOL_ELBO, RTOL_GRAD, LR
-from test_gpu_renyi import weight_check
+from _judge import (RTOL_ELBO, RTOL_KL, LR, state, reload, check_scalars, check_z, check_grads, check_params_after_adam,
+                    steps_vs_reference, cpu_threads_16)
+from _renyi_cases import weight_check
 
 pytestmark = pytest.mark.gpu
 
-RTOL_KL = 1e-4
+Z_ATOL_MC = 5e-6           # z_loc / z_scale's atol in these tests (encode's bar in tests/test_gpu_parity.py)
 CASE1 = "c01_8x8_rts_c2_b6"
-
-
-@pytest.fixture(autouse=True)
-def _reference_setup():
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)                      # (the float64 references)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
 
 
 def make(name, **engine_kw):
@@ -42,70 +33,15 @@ def make(name, **engine_kw):
     return c, model, model.engine(**engine_kw)
 
 
-def loss_atol(c):
-    """test_model_variants_vs_oracle: 1e-6 per value of the batch for the continuous Bernoulli, none otherwise."""
-    return 1e-6 * c["b"] * int(np.prod(c["dims"])) if c.get("sampler") == "continuous_bernoulli" else 0.0
-
-
-def ref_loc(o, last):
-    """What loc_out holds: the decoder's mean, (rows, P*C) channel-last; the rate for the Poisson."""
-    loc = last["loc"].detach()
-    return torch.exp(loc.clamp(max=30.0)) if o.cfg.sampler == "poisson_log" else loc
-
-
-def check_step(eng, o, last, tag, atol=0.0, zl=None, zs=None, loc=None, grads=None):
-    s = eng.scalars.cpu().numpy()
-    print("%s: loss %.6f (ref %.6f) ll %.6f (ref %.6f) s2 %.6f (ref %.6f) s3 %.6f (ref %.6f)"
-          % (tag, s[0], last["loss"].item(), s[1], last["ll"].item(), s[2], last["logpz"].item(), s[3], last["logqz"].item()))
-    # (Poisson: the reference's log_prob carries lgamma(x + 1), as the reported loss does)
-    ref = {k: last[k].item() for k in ("loss", "ll", "logpz", "logqz")}
-    np.testing.assert_allclose(s[0], ref["loss"], rtol=RTOL_ELBO, atol=atol, err_msg="%s loss" % tag)
-    np.testing.assert_allclose(s[1], ref["ll"], rtol=RTOL_ELBO, atol=atol, err_msg="%s ll" % tag)
-    np.testing.assert_allclose(s[2], ref["logpz"], rtol=RTOL_KL, err_msg="%s s2" % tag)
-    np.testing.assert_allclose(s[3], ref["logqz"], rtol=RTOL_KL, err_msg="%s s3" % tag)
-    if zl is not None:
-        np.testing.assert_allclose(zl.cpu().numpy(), last["z_loc"].detach().numpy(), rtol=1e-4, atol=5e-6, err_msg="%s z_loc" % tag)
-        np.testing.assert_allclose(zs.cpu().numpy(), last["z_scale"].detach().numpy(), rtol=1e-4, atol=5e-6, err_msg="%s z_scale" % tag)
-    if loc is not None:
-        want = ref_loc(o, last).reshape(loc.shape[0], -1).numpy()
-        err = np.abs(loc.cpu().numpy() - want).max()
-        print("%s: loc_out max abs error %.2e" % (tag, err))
-        np.testing.assert_allclose(loc.cpu().numpy(), want, rtol=1e-4, atol=2e-6, err_msg="%s loc_out" % tag)
-    grads = o.last_grads if grads is None else grads
-    worst, which = 0.0, None
-    for key in o.p:
-        err = rel_l2(eng.grad_of(key), grads[key])
-        if err > worst:
-            worst, which = err, key
-    print("%s: worst gradient rel l2 %.2e (%s)" % (tag, worst, which))
-    for key in o.p:
-        err = rel_l2(eng.grad_of(key), grads[key])
-        assert err < RTOL_GRAD, "%s grad %s: rel l2 error %.3e vs the float64 reference" % (tag, key, err)
-
-
-def reload(model, o):
-    mc.round_to_float32(o)                         # both sides continue from the SAME float32 parameters
-    model.load_state_dict({k: v.detach().float() for k, v in o.p.items()})
-
-
 def run_steps(name, fused, make_oracle, engine_kw=None, particles=1):
     c, model, eng = make(name, fused=fused, **(engine_kw or {}))
     b, n_obs = c["b"], int(np.prod(c["dims"])) * c["C"]
     assert eng.uses_fused(b) is False and eng.supports_dp_step is False
     x, y, eps = mc.case_data(c, particles)
     o = make_oracle(state(model), mc.case_config(c))
-    z_dim = o.cfg.z_dim
-    zl, zs = torch.empty(b, z_dim, device="cuda"), torch.empty(b, z_dim, device="cuda")
     loc = torch.full((particles * b, n_obs), float("nan"), device="cuda")
-    yg = None if y is None else y.cuda()
-    for k in range(2):
-        tag = "%s fused=%d step %d" % (name, fused, k)
-        eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, yg, z_out=(zl, zs), loc_out=loc)
-        o.step(x, eps[k], 1.0, y)
-        check_step(eng, o, o.last, tag, loss_atol(c), zl, zs, loc)
-        eng.adam_step()
-        check_params_after_adam(model, o, 0, tag)                  # (0: the 5e-5 bar)
-        reload(model, o)
+    steps_vs_reference(eng, model, o, x, y, eps, 1.0, "%s fused=%d" % (name, fused), 0, Z_ATOL_MC, atol=mc.loss_atol(c),
+                       loc_out=loc)                                # (0: the 5e-5 bar after Adam)
     return c, model, eng, o, x, y
 
 
@@ -189,10 +125,12 @@ def test_renyi_steps_with_the_weights_held(gpu_device):
         held.weights = w.detach().cpu().double()
         held.step(x, eps[k], 1.0)
         weight_check(tag, w, of, alpha, RTOL_ELBO)
-        check_step(eng, held, of, tag, 0.0, zl, zs, grads=held.last_grads)
+        check_scalars(eng.scalars.cpu().numpy(), of, tag)
+        check_z(zl, zs, of, RTOL_KL, Z_ATOL_MC, tag)
+        check_grads(eng, held, tag)
         eng.adam_step()
         check_params_after_adam(model, held, 0, tag)
-        reload(model, held)
+        reload(model, held, round32=True)
 
 
 # ------------------------------------------------------------------------------- 3. determinism

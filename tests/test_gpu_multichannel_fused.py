@@ -22,20 +22,9 @@ from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
 import _multichannel_fused_cases as fc
-from test_gpu_meanfield import check_params_after_adam, rel_l2, state, RTOL_GRAD, LR
-from test_gpu_multichannel import check_step, loss_atol, reload
+from _judge import RTOL_GRAD, LR, rel_l2, state, steps_vs_reference, cpu_threads_16
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _reference_setup():
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)                      # (the float64 references)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
 
 
 def make(name, **engine_kw):
@@ -51,8 +40,7 @@ def check_channels(eng, o, tag):
     assert gw.shape == rw.shape and gb.shape == rb.shape and gw.shape[0] == gb.shape[0] == o.cfg.channels
     errs = []
     for ch in range(gw.shape[0]):
-        ew = ((gw[ch] - rw[ch]).norm() / rw[ch].norm().clamp_min(1e-30)).item()
-        eb = (abs(gb[ch] - rb[ch]) / abs(rb[ch]).clamp_min(1e-30)).item()
+        ew, eb = rel_l2(gw[ch], rw[ch]), rel_l2(gb[ch], rb[ch])
         errs.append((ew, eb))
     print("%s: per channel (out.weight row, out.bias) %s" % (tag, " ".join("(%.1e %.1e)" % e for e in errs)))
     for ch, (ew, eb) in enumerate(errs):
@@ -66,19 +54,9 @@ def run_steps(name, oracle_kw=None, engine_kw=None):
     assert eng.uses_fused(b) is True and eng.supports_dp_step is False
     x, y, eps = mc.case_data(c)
     o = orc.SVIOracle(state(model), mc.case_config(c), lr=LR, dtype=torch.float64, **(oracle_kw or {}))
-    z_dim = o.cfg.z_dim
-    zl, zs = torch.empty(b, z_dim, device="cuda"), torch.empty(b, z_dim, device="cuda")
     loc = torch.full((b, n_obs), float("nan"), device="cuda")
-    yg = None if y is None else y.cuda()
-    for k in range(2):
-        tag = "%s fused_channels step %d" % (name, k)
-        eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, yg, z_out=(zl, zs), loc_out=loc)
-        o.step(x, eps[k], 1.0, y)
-        check_step(eng, o, o.last, tag, loss_atol(c), zl, zs, loc)
-        check_channels(eng, o, tag)
-        eng.adam_step()
-        check_params_after_adam(model, o, 0, tag)                  # (0: the 5e-5 bar)
-        reload(model, o)
+    steps_vs_reference(eng, model, o, x, y, eps, 1.0, "%s fused_channels" % name, 0, 5e-6, atol=mc.loss_atol(c),
+                       checks=[check_channels], loc_out=loc)       # (0: the 5e-5 bar after Adam; z atol 5e-6)
     return c, model, eng, o, x, y
 
 

@@ -3,9 +3,9 @@ GPU tests (-m gpu) of the multi-particle ELBO: SVItrainer(num_particles=P), mode
 pv_ivae_particles_loss_and_grads / pv_ivae_particles_step.
 
 The reference is oracle.svi_oracle with particles=P (its networks and Adam; one encoder pass, P decoder samples per
-image ordered [p][b], the mean over particles).  Inputs are conftest.make_x and eps from a seeded torch.Generator.  The
-bars are those tests/test_gpu_parity.py and tests/test_gpu_meanfield.py hold the same path to, restated next to each
-use; averaging over particles loosens none of them.  Shapes are the smallest at which each new piece can go wrong.
+image ordered [p][b], the mean over particles).  Inputs are conftest.make_x and eps from a seeded torch.Generator
+(tests/_particles_cases.py).  The bars are tests/_judge.py's, the ones every fp32-class path is held to; averaging over
+particles loosens none of them.  Shapes are the smallest at which each new piece can go wrong.
 """
 import ctypes as C
 
@@ -19,94 +19,15 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
-# the throughput precision's helpers and ceilings (importable: used as they are)
-from test_gpu_bf16_emulated import _judge, _kernel_name, _cus, GRAD_CEIL, LOSS_CEIL, SELF_CHECK, LIK
+from _bf16_judge import judge, GRAD_CEIL, LOSS_CEIL, SELF_CHECK, LIK
+from _device import cus, kernel_name
+from _judge import RTOL_ELBO, RTOL_KL, Z_ATOL, state, check_params_after_adam, steps_vs_reference
+from _particles_cases import STEP_CASES, step_case, oracle_of
 
 pytestmark = pytest.mark.gpu
 
-RTOL_ELBO = 2e-5      # loss and s1 (tests/test_gpu_parity.py, tests/test_gpu_meanfield.py)
-RTOL_KL = 1e-4        # s2, s3, z_loc, z_scale
-RTOL_GRAD = 1e-4      # every gradient tensor, relative L2, fused 0 and 2
-LR = 1e-3
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def state(model):
-    return {k: v.cpu() for k, v in model.state_dict().items()}
-
-
-def oracle_of(kl, params, cfg, P, dtype=torch.float32):
-    return orc.SVIOracle(params, cfg, lr=LR, dtype=dtype, kl=kl, particles=P)
-
-
-def check_scalars_and_grads(eng, o, tag, zl=None, zs=None):
-    """loss and s1 to 2e-5, s2 / s3 / z_loc / z_scale to 1e-4, the slots' relation, every gradient tensor to 1e-4 relative L2."""
-    s = eng.scalars.cpu().numpy()
-    last = o.last
-    print("%s: loss %.6f (ref %.6f) s1 %.6f (ref %.6f) s2 %.6f (ref %.6f) s3 %.6f (ref %.6f)"
-          % (tag, s[0], last["loss"].item(), s[1], last["ll"].item(), s[2], last["logpz"].item(), s[3], last["logqz"].item()))
-    np.testing.assert_allclose(s[0], last["loss"].item(), rtol=RTOL_ELBO, err_msg="%s loss" % tag)
-    np.testing.assert_allclose(s[1], last["ll"].item(), rtol=RTOL_ELBO, err_msg="%s s1" % tag)
-    np.testing.assert_allclose(s[2], last["logpz"].item(), rtol=RTOL_KL, err_msg="%s s2" % tag)
-    np.testing.assert_allclose(s[3], last["logqz"].item(), rtol=RTOL_KL, err_msg="%s s3" % tag)
-    np.testing.assert_allclose(s[0], -(s[1] + s[2] - s[3]), rtol=2e-6)
-    if zl is not None:
-        np.testing.assert_allclose(zl.cpu().numpy(), last["z_loc"].detach().numpy(), rtol=RTOL_KL, atol=2e-6)
-        np.testing.assert_allclose(zs.cpu().numpy(), last["z_scale"].detach().numpy(), rtol=RTOL_KL, atol=2e-6)
-    worst = 0.0
-    for key in o.p:
-        err = rel_l2(eng.grad_of(key), o.last_grads[key])
-        worst = max(worst, err)
-        assert err < RTOL_GRAD, "%s grad %s: rel l2 error %.3e vs the reference" % (tag, key, err)
-    print("%s: worst gradient rel l2 %.2e" % (tag, worst))
-
-
-def check_params_after_adam(model, o, fused, tag):
-    """tests/test_gpu_meanfield.py check_params_after_adam's rule (test_gpu_parity.py's): entries with |g| < 1e-5 max|g| are
-    held to 2 lr (Adam's first steps are lr * sign(g): summation noise decides their direction) and their share must stay
-    below 1 % (a condition on the case: tests/test_particles_cpu.py confirms it for STEP_CASES and STEP_SEEDS with the
-    reference alone); every other entry to 1e-4 (fused == 2) / 5e-5 relative L2."""
-    for key, p in model.state_dict().items():
-        gref = o.last_grads[key]
-        ill = (gref.abs() < 1e-5 * gref.abs().max()).reshape(p.shape)
-        pc, pr_ = p.detach().cpu(), o.p[key].detach().float()
-        assert ill.float().mean() < 0.01, "%s %s: %d near-zero gradient entries" % (tag, key, int(ill.sum()))
-        assert (pc - pr_)[ill].abs().max().item() <= 2 * LR if ill.any() else True
-        assert rel_l2(pc[~ill], pr_[~ill]) < (1e-4 if fused == 2 else 5e-5), "%s %s" % (tag, key)
-
 
 # ------------------------------------------------------------------------------- 1. fp32-class steps
-# name: (data_dim, invariances, model kwargs, B, P) — what each covers is in the comment
-STEP_CASES = {
-    "8x8_rts_b6_p3": ((8, 8), ["r", "t", "s"], {}, 6, 3),                        # 18 samples: crosses a 16-row block
-    "8x8_none_b6_p3": ((8, 8), None, {}, 6, 3),                                  # vanilla decoder (layered whatever `fused`)
-    "1d16_t_b5_p7": ((16,), ["t"], {}, 5, 7),                                    # 35 samples, odd everything
-    "8x8_rt_cdim3_b6_p2": ((8, 8), ["r", "t"], dict(c_dim=3), 6, 2),             # conditioning
-    "16x16_r_gauss_b4_p2": ((16, 16), ["r"], dict(sampler_d="gaussian", sigmoid_d=False), 4, 2),   # Gaussian sampler
-}
-STEP_SEEDS = dict(model=1, x=0, eps=17)
-
-
-def step_case(name, device):
-    data_dim, inv, kw, b, P = STEP_CASES[name]
-    model = pv.models.iVAE(data_dim, 2, inv, seed=STEP_SEEDS["model"], device=device, **kw)
-    cfg = orc.Config(data_dim=data_dim, latent_dim=2, invariances=inv, c_dim=kw.get("c_dim", 0),
-                     sampler=kw.get("sampler_d", "bernoulli"), sigmoid_d=kw.get("sigmoid_d", True))
-    x = make_x("rand", b, data_dim, seed=STEP_SEEDS["x"])
-    y = None
-    if cfg.c_dim:
-        y = torch.zeros(b, cfg.c_dim)
-        y[torch.arange(b), torch.arange(b) % cfg.c_dim] = 1.0
-        x = x.flatten(1)
-    g = torch.Generator().manual_seed(STEP_SEEDS["eps"])
-    eps = [torch.randn(P * b, cfg.z_dim, generator=g) for _ in range(2)]
-    return model, cfg, x, y, eps, b, P
-
-
 @pytest.mark.parametrize("kl", ["sampled", "analytic"])
 @pytest.mark.parametrize("fused", [0, 2])
 @pytest.mark.parametrize("name", sorted(STEP_CASES))
@@ -116,17 +37,7 @@ def test_particle_steps_vs_reference(gpu_device, name, fused, kl):
     eng = model.engine(fused=fused, kl=kl, particles=P)
     assert eng.supports_dp_step is False
     o = oracle_of(kl, state(model), cfg, P)
-    zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
-    beta = 1.7
-    yg = None if y is None else y.cuda()
-    for k in range(2):
-        eng.loss_and_grads(x.cuda(), eps[k].cuda(), beta, yg, z_out=(zl, zs))
-        o.step(x, eps[k], beta, y)
-        tag = "%s fused=%d %s step %d" % (name, fused, kl, k)
-        check_scalars_and_grads(eng, o, tag, zl=zl, zs=zs)
-        eng.adam_step()
-        check_params_after_adam(model, o, fused, tag)
-        model.load_state_dict({k_: v_.detach() for k_, v_ in o.p.items()})
+    steps_vs_reference(eng, model, o, x, y, eps, 1.7, "%s fused=%d %s" % (name, fused, kl), fused, Z_ATOL)
 
 
 # ------------------------------------------------------------------------------- 2. throughput precision
@@ -142,7 +53,7 @@ def _bf16_case(which):
 @pytest.mark.parametrize("which", ["8x8_rts_b6_p3", "28x28_r_b128_p2"])
 def test_particle_bf16_step_vs_emulated_reference(gpu_device, which, kl):
     """fused=3 against the reference that rounds where the kernel does (oracle/bf16_plan.py through the particle oracle: the
-    decoder's P*B samples take the kernel's unit partition), with tests/test_gpu_bf16_emulated.py's own judge and its
+    decoder's P*B samples take the kernel's unit partition), with the throughput precision's own judge (tests/_bf16_judge.py) and its
     ceilings: loss 1e-5, every gradient tensor 1e-3 relative L2, z_loc / z_scale 1e-5, and a tensor more than 1e-3 from the
     float64 gradient at least 10x closer to the emulation.  28x28 `r`, B = 128, P = 2 has the 256 samples of a batch whose
     guide the decoder launch would host: a fold decided on the sample count computes the wrong guide here."""
@@ -161,7 +72,7 @@ def _bf16_case_body(which, kl, data_dim, inv, b, P, xkind):
     assert eng.uses_fused(b)
     n_pix = int(np.prod(data_dim))
     units = P * b * n_pix // 16
-    name = _kernel_name(units, LIK["bernoulli"])
+    name = kernel_name(fused=3, units=units, lik=LIK["bernoulli"])
     kernel = "w8" if "pv_sdec_w8_kernel" in name else "w4"
     assert kernel == ("w4" if b == 6 else "w8"), name
     x = make_x(xkind, b, data_dim)
@@ -176,9 +87,9 @@ def _bf16_case_body(which, kl, data_dim, inv, b, P, xkind):
         o = oracle_of(kl, params, cfg, P, dtype=torch.float64)
         out = o.loss_and_grads(x, eps, 1.0)
         return out, {k: v.grad.detach().clone() for k, v in o.p.items()}
-    ref_out, ref_g = reference(bp.Bf16Plan(kernel=kernel, cus=_cus()))
+    ref_out, ref_g = reference(bp.Bf16Plan(kernel=kernel, cus=cus()))
     f64_out, f64_g = reference(None)
-    _judge("%s %s" % (which, kl), eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), GRAD_CEIL, LOSS_CEIL, SELF_CHECK)
+    judge("%s %s" % (which, kl), eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), GRAD_CEIL, LOSS_CEIL, SELF_CHECK)
     s = eng.scalars.cpu().numpy()
     np.testing.assert_allclose(s[0], -(s[1] + s[2] - s[3]), rtol=2e-6)
     np.testing.assert_allclose(s[2], ref_out["logpz"].item(), rtol=RTOL_KL)
@@ -231,7 +142,7 @@ def test_one_particle_is_the_old_step_bit_for_bit(gpu_device, shape, fused):
     eng = model.engine(fused=fused)
     assert eng.particles == 1
     folds = _abi.lib().pv_ivae_guide_folds(C.byref(eng._plan(b)))
-    if shape == "28x28_rt_b256" and fused == 3 and _cus() == 256:
+    if shape == "28x28_rt_b256" and fused == 3 and cus() == 256:
         assert folds == 1
     eng.loss_and_grads(x, eps, 1.3)
     torch.cuda.synchronize()

@@ -19,10 +19,10 @@ cells); a repeated call is bit-identical; want_grads=False gives the gradient ca
 
 References and bars.  fp32-class families: the float64 oracle (WeightedOracle with weights) at the project's bars — loss / ll 2e-5,
 the KL scalars 1e-4, z 1e-4 + 5e-6, loc_out 1e-4 + 2e-6, gradients 1e-4 relative L2 per tensor, per-sample rows 1e-4 per row.
-jiVAE: conftest.jivae_grad_tol.  Particles: the same bars (tests/test_gpu_particles.py: z atol 2e-6).  H231 / H221: h2_grad_tol(rows,
+jiVAE: conftest.jivae_grad_tol.  Particles: the same bars (tests/_judge.py: Z_ATOL 2e-6).  H231 / H221: h2_grad_tol(rows,
 kind) per tensor and h2_grad_tol(N, kind) per per-sample row; their loc_out max abs error H2_LOC_ATOL (below, from measurement).  Plain bf16: the emulation
 oracle/bf16_plan.Bf16Plan at bars set from measurement (_partition_cases.BF16_BARS; at most 4x the measured worst, never above the
-ceilings 1e-3 for gradients and dy rows / 1e-5 for the loss and row_elbo entries), plus test_gpu_bf16_emulated's self-check against float64.
+ceilings 1e-3 for gradients and dy rows / 1e-5 for the loss and row_elbo entries), plus tests/_bf16_judge.py's self-check against float64.
 
 What the dispatch assertions cover.  A forced build is asserted through plan.dec_kernel (the launcher's only input besides the size);
 pv_debug_decoder_kernel_name knows the size rule alone and is used to assert that rule on both of its sides.  The multi-channel and
@@ -40,6 +40,9 @@ from pyroved_amd import _abi
 from pyroved_amd.engine import IVAEEngine
 from oracle import bf16_plan as bp
 import _partition_cases as pc
+from _bf16_judge import SELF_CHECK, DECODE_BAR
+from _device import cus, kernel_name, last_fold_build
+from _judge import rel_l2, cpu_threads_16
 
 pytestmark = pytest.mark.gpu
 
@@ -49,44 +52,9 @@ Z_RTOL, Z_ATOL, LOC_RTOL, LOC_ATOL = 1e-4, 5e-6, 1e-4, 2e-6
 # of the 36 H231 / H221 cells, 3.56e-5 (e08).  (A row that reads another sample's hz is off by ~1e-1.)
 H2_LOC_ATOL = 1.4e-4
 BF16_LOC_BAR = 1.1e-5         # plain bf16, loc_out against the emulation, relative L2: measured worst 2.77e-6 over the 36 plain-bf16 cells (ceiling 1e-4,
-                              # tests/test_gpu_bf16_emulated.py: LOC_CEIL)
-BF16_Z_BAR = 1e-5             # ... z_loc / z_scale (that file's _judge)
-SELF_CHECK = 10.0             # ... a tensor more than 1e-3 from float64 lies at least 10x closer to the emulation
+                              # tests/_bf16_judge.py: LOC_CEIL)
+BF16_Z_BAR = 1e-5             # ... z_loc / z_scale (that file's judge)
 EVAL_RTOL = 2e-6
-
-
-@pytest.fixture(autouse=True)
-def _cpu_threads():
-    """the float64 references run on 16 threads; the setting is restored for whatever runs next"""
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _kernel_name(fused, units, grads=1, lik=0):
-    lib = _abi.lib()
-    lib.pv_debug_decoder_kernel_name.restype = C.c_char_p
-    lib.pv_debug_decoder_kernel_name.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
-    return lib.pv_debug_decoder_kernel_name(fused, units, grads, lik).decode()
-
-
-def _last_fold_build():
-    lib = _abi.lib()
-    lib.pv_debug_w8_last_fold_build.restype = C.c_int
-    lib.pv_debug_w8_last_fold_build.argtypes = []
-    return int(lib.pv_debug_w8_last_fold_build())
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
 
 
 def excess(got, want, rtol, atol):
@@ -108,9 +76,9 @@ _EMULATED = {}
 
 def emulated(name, kernel):
     """the bf16 restatement of the case on this device's grid (one evaluation per process)"""
-    key = (name, kernel, _cus())
+    key = (name, kernel, cus())
     if key not in _EMULATED:
-        _EMULATED[key] = pc.run_reference(name, "plain", plan=bp.Bf16Plan(kernel=kernel, cus=_cus()))
+        _EMULATED[key] = pc.run_reference(name, "plain", plan=bp.Bf16Plan(kernel=kernel, cus=cus()))
     return _EMULATED[key]
 
 
@@ -126,18 +94,18 @@ def check_dispatch(name, family, model, eng, part):
     assert bool(p.flags & _abi.PV_PLAN_FUSED_CHANNELS) == (pc.channels_of(variant) > 1)
     # the size rule, restated: what the library names for this many units when nothing is forced
     w8_by_size, h231_by_size = units >= 6 * grid, units >= 1024
-    n3, n2, n1 = _kernel_name(3, units), _kernel_name(2, units), _kernel_name(1, units)
+    n3, n2, n1 = (kernel_name(fused=f, units=units) for f in (3, 2, 1))
     assert ("pv_sdec_w8_kernel<true, 0, 0>" in n3) == w8_by_size, (n3, units, grid)
     assert ("pv_sdec_fused_bf16_kernel<true, 0, 0>" in n3) == (not w8_by_size), n3
     assert ("pv_sdec_fused_bf16_kernel<true, 0, %d>" % (8 if h231_by_size else 1)) in n2, (n2, units)
     assert "pv_sdec_fused_kernel<true>" in n1
     # forward-only launches of the split-precision path: the 8-wave pv_sdec_w8x3 build by size
-    assert ("pv_sdec_w8x3_kernel<false, 0, 8>" in _kernel_name(2, units, grads=0)) == w8_by_size
+    assert ("pv_sdec_w8x3_kernel<false, 0, 8>" in kernel_name(fused=2, units=units, grads=0)) == w8_by_size
     # the guide rides in the decoder launch only on the 8-wave plain-bf16 kernel with one unconditioned image per workgroup
     # (the hook sees the plan, and the particle count travels beside the plan: for e11 it answers for the one-particle step of B
     #  images — asserted as such; the P-particle step itself never folds, pv_plan.hip: plan_guide_may_fold)
     hook = bool(_abi.lib().pv_ivae_guide_folds(C.byref(p)))
-    one = pc.partition(pc.n_pos(c), B, _cus())               # the one-particle / unenumerated plan's partition
+    one = pc.partition(pc.n_pos(c), B, cus())               # the one-particle / unenumerated plan's partition
     want_hook = family == "bf16w8" and c["kind"] != "jivae" and c["c_dim"] == 0 and one["grid"] == B
     assert hook == want_hook, (name, family, hook, want_hook)
     folds = hook and c["kind"] == "ivae"
@@ -152,10 +120,10 @@ def run_cell(name, family):
     variant, sel = fam["variant"], fam["sel"]
     B, S, N, Cn = c["B"], pc.n_samples(c), pc.n_pos(c), pc.channels_of(variant)
     bf16 = family.startswith("bf16")
-    part = pc.case_partition(c, _cus())
-    print("\n[partition-edges] %s %s on %d CUs: %s" % (name, family, _cus(), pc.describe(part)))
+    part = pc.case_partition(c, cus())
+    print("\n[partition-edges] %s %s on %d CUs: %s" % (name, family, cus(), pc.describe(part)))
     assert part["gfirst_ok"] and part["min_slot"] == 0 and part["max_slot"] <= part["kmax"] - 1
-    if _cus() == pc.CUS:
+    if cus() == pc.CUS:
         for key, want in c["claims"].items():
             assert part[key] == want, (name, key, part[key], want)
     x, y, eps = pc.inputs(name, variant)
@@ -183,7 +151,7 @@ def run_cell(name, family):
         eng.loss_and_grads(xg, eg, 1.0, yg, z_out=(zl, zs), loc_out=loc, **extra)
         torch.cuda.synchronize()
         if folds:
-            assert _last_fold_build() == 2, _last_fold_build()           # the image-owning training build, generic tile loop (upb < 8)
+            assert last_fold_build() == 2, last_fold_build()           # the image-owning training build, generic tile loop (upb < 8)
         s = eng.scalars.cpu().double()
         keys = list(model.state_dict().keys())
         g = {k: eng.grad_of(k).detach().cpu().double().clone() for k in keys}
@@ -258,7 +226,7 @@ def run_cell(name, family):
         eng.loss_and_grads(xg, eg, 1.0, yg, want_grads=False)
         torch.cuda.synchronize()
         if folds:
-            assert _last_fold_build() == 1
+            assert last_fold_build() == 1
         se = eng.scalars.cpu().double()
         res.append(("want_grads=False scalars", ((se - s).abs() / s.abs()).max().item(), EVAL_RTOL))
     finally:
@@ -299,14 +267,13 @@ def test_decode_at_the_partition_edges(gpu_device, name, n, mode):
     forward-only builds whatever the training precision — 4 waves at 257 units, the 8-wave pv_sdec_w8x3 build at 2400) against
     SVIOracle.decode in float64, at the bars of the existing decode tests: 1e-4 + 2e-6, and DECODE_BAR (relative L2) in the bf16
     mode."""
-    from test_gpu_bf16_emulated import DECODE_BAR
     c = pc.CASES[name]
     model = pc.make_model(name, "plain", "cuda")
     model.engine(fused=3 if mode == "bf16" else 2)
     units = n * pc.n_pos(c) // pc.UNIT
-    part = pc.partition(pc.n_pos(c), n, _cus())
+    part = pc.partition(pc.n_pos(c), n, cus())
     print("\n[partition-edges] decode %s: %s" % (name, pc.describe(part)))
-    dname = _kernel_name(2, units, grads=0, lik=1)
+    dname = kernel_name(fused=2, units=units, grads=0, lik=1)
     assert ("pv_sdec_w8x3_kernel" in dname) == (units >= 6 * part["grid"]), dname
     g = torch.Generator().manual_seed(2)
     z = torch.randn(n, 2, generator=g)

@@ -6,7 +6,7 @@ pv_lik_elem, the weighted Poisson normaliser).
 
 The reference is tests/_pixel_weight_cases.WeightedOracle in float64: orc.elbo for one particle with
 ll = (log_prob * w).sum(-1).  Cases, weights, data and eps come from _pixel_weight_cases.  Bars are the project's own for these
-kernels (tests/test_gpu_multichannel.py / _fused.py): loss and ll 2e-5 (+ that file's loss_atol), the KL scalars 1e-4, z_loc /
+kernels (tests/test_gpu_multichannel.py / _fused.py): loss and ll 2e-5 (+ _multichannel_cases.loss_atol), the KL scalars 1e-4, z_loc /
 z_scale rtol 1e-4 atol 5e-6, loc_out rtol 1e-4 atol 2e-6, every gradient tensor 1e-4 relative L2 — and each row of
 decoder.out.weight and each decoder.out.bias[c] on its own —, parameters after Adam by check_params_after_adam's rule at the
 5e-5 bar (its 1 % cap is confirmed with the reference alone in tests/test_pixel_weights_cpu.py).
@@ -19,22 +19,11 @@ import pyroved_amd as pv
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
 import _pixel_weight_cases as pw
-from test_gpu_meanfield import check_params_after_adam, rel_l2, state, RTOL_GRAD, LR
-from test_gpu_multichannel import check_step, loss_atol, reload
+from _judge import RTOL_GRAD, LR, rel_l2, state, steps_vs_reference, cpu_threads_16
 
 pytestmark = pytest.mark.gpu
 
 CASE1 = pw.CASE1
-
-
-@pytest.fixture(autouse=True)
-def _reference_setup():
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)                      # (the float64 references)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
 
 
 def build(name, w="case", **engine_kw):
@@ -82,19 +71,9 @@ def run_steps(name, engine_kw, want_fused, kl="sampled"):
     assert eng.supports_dp_step is False
     x, y, eps = pw.case_data(c)
     o = pw.WeightedOracle(state(model), pw.case_config(c), pw.weights(c), lr=LR, dtype=torch.float64, kl=kl)
-    z_dim = o.cfg.z_dim
-    zl, zs = torch.empty(b, z_dim, device="cuda"), torch.empty(b, z_dim, device="cuda")
     loc = torch.full((b, n_obs(c)), float("nan"), device="cuda")
-    yg = None if y is None else y.cuda()
-    for k in range(2):
-        tag = "%s %s %s step %d" % (name, engine_kw, kl, k)
-        eng.loss_and_grads(x.cuda(), eps[k].cuda(), 1.0, yg, z_out=(zl, zs), loc_out=loc)
-        o.step(x, eps[k], 1.0, y)
-        check_step(eng, o, o.last, tag, loss_atol(c), zl, zs, loc)
-        check_output_layer_rows(eng, o, tag)
-        eng.adam_step()
-        check_params_after_adam(model, o, 0, tag)                  # (0: the 5e-5 bar)
-        reload(model, o)
+    steps_vs_reference(eng, model, o, x, y, eps, 1.0, "%s %s %s" % (name, engine_kw, kl), 0, 5e-6, atol=mc.loss_atol(c),
+                       checks=[check_output_layer_rows], loc_out=loc)      # (0: the 5e-5 bar after Adam; z atol 5e-6)
 
 
 # ------------------------------------------------------------------------------- 1. step parity

@@ -16,6 +16,7 @@ import torch
 from conftest import GOLDEN, make_x
 
 import pyroved_amd as pv
+from _judge import rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -39,11 +40,6 @@ def guide_eps(tap, site):
     """the standard-normal draw behind a reparameterised guide site: (z - loc) / scale of its recorded distribution"""
     fn = tap["guide_fns"][site].base_dist
     return ((tap["sites"]["guide." + site] - fn.loc.detach()) / fn.scale.detach()).contiguous()
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 @pytest.mark.parametrize("inv,c_dim,sampler", [(["r", "t", "s"], 0, "bernoulli"), (None, 0, "gaussian"), (["t"], 2, "bernoulli")])

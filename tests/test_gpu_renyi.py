@@ -3,8 +3,8 @@ GPU tests (-m gpu) of the importance-weighted (Renyi / IWAE) bound: SVItrainer(l
 model.engine(particles=P, renyi=alpha), pv_ivae_renyi_loss_and_grads / pv_ivae_renyi_step.
 
 The reference is oracle.svi_oracle with renyi=alpha (its networks and Adam; one encoder pass, P decoder samples per image
-ordered [p][b], the softmax-weighted bound) in float64.  Shapes, seeds and beta are tests/test_gpu_particles.py's STEP_CASES;
-tests/test_renyi_cpu.py confirms with the reference alone that their weights are spread (ESS >= 1.9 on some image) and
+ordered [p][b], the softmax-weighted bound) in float64.  Shapes, seeds and beta are tests/_renyi_cases.py's (the particle tests'
+STEP_CASES); tests/test_renyi_cpu.py confirms with the reference alone that their weights are spread (ESS >= 1.9 on some image) and
 that the bound sits more than 0.25 nats above the ELBO.
 
 How the bars compose.  Loss, s1 (2e-5), s2 / s3 / z_loc / z_scale (1e-4) and the slot relation (2e-6) are the project's bars
@@ -20,81 +20,20 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden, make_x, meta_of
+from conftest import make_x
 
 import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from oracle import bf16_plan as bp
-from test_gpu_particles import (STEP_CASES, STEP_SEEDS, step_case, state, rel_l2, check_params_after_adam,
-                                RTOL_ELBO, RTOL_KL, RTOL_GRAD, LR)
-# the throughput precision's helpers and ceilings (importable: used as they are)
-from test_gpu_bf16_emulated import _judge, _kernel_name, _cus, GRAD_CEIL, LOSS_CEIL, SELF_CHECK, LIK
+from _bf16_judge import judge, GRAD_CEIL, LOSS_CEIL, SELF_CHECK, LIK
+from _device import cus, kernel_name
+from _judge import (RTOL_ELBO, RTOL_KL, Z_ATOL, LR, rel_l2, state, reload, check_scalars, check_z, check_grads,
+                    check_params_after_adam)
+from _particles_cases import STEP_CASES
+from _renyi_cases import BETA, ALPHAS, case_inputs, weight_check, free_and_held
 
 pytestmark = pytest.mark.gpu
-
-BETA = 1.7
-ALPHAS = (0.0, 0.5)
-CASES = dict(STEP_CASES)
-CASES["28x28_r_b128_p2"] = None          # the ivae_28x28_r_b128 fixture's data with P = 2 (throughput precision only)
-
-
-def case_inputs(name, device):
-    """(cfg, parameters on the CPU, x, y, [eps of step 0, eps of step 1], B, P, beta) — what tests/test_renyi_cpu.py checks the
-    condition on and every test here runs; `model` rides along as the ninth item."""
-    if name in STEP_CASES:
-        model, cfg, x, y, eps, b, P = step_case(name, device)
-    else:
-        meta = meta_of(load_golden("ivae_28x28_r_b128"))
-        assert meta["batch"] == 128
-        b, P = meta["batch"], 2
-        model = pv.models.iVAE(meta["data_dim"], 2, meta["invariances"], seed=STEP_SEEDS["model"], device=device)
-        cfg = orc.Config(data_dim=tuple(meta["data_dim"]), latent_dim=2, invariances=meta["invariances"])
-        x, y = make_x(meta["xkind"], b, meta["data_dim"]), None
-        g = torch.Generator().manual_seed(STEP_SEEDS["eps"])
-        eps = [torch.randn(P * b, cfg.z_dim, generator=g) for _ in range(2)]
-    return cfg, state(model), x, y, eps, b, P, BETA, model
-
-
-def weight_check(tag, w_gpu, ref, alpha, ll_bar):
-    """max |log w - log w_ref| over entries with w_ref > 1e-6 against 2 |1 - alpha| ll_bar max_s |ll_s|; printed first."""
-    w_ref, logw_ref = ref["weights"].detach().double(), ref["log_weights"].detach().double()
-    keep = w_ref > 1e-6
-    got = torch.log(w_gpu.double().cpu())[keep]
-    err = (got - logw_ref[keep]).abs().max().item()
-    bar = 2.0 * abs(1.0 - alpha) * ll_bar * ref["ll_per_sample"].detach().abs().max().item()
-    print("%s: max |log w - log w_ref| %.3e (bar %.3e) over %d of %d weights" % (tag, err, bar, int(keep.sum()), keep.numel()))
-    assert err <= bar, "%s: log-weights %.3e from the reference (bar %.3e)" % (tag, err, bar)
-    sums = w_gpu.double().cpu().view(-1, ref["z_loc"].shape[0]).sum(0)
-    np.testing.assert_allclose(sums.numpy(), 1.0, rtol=0, atol=1e-6)
-
-
-def scalar_check(tag, s, ref, zl=None, zs=None):
-    print("%s: loss %.6f (ref %.6f) s1 %.6f (ref %.6f) s2 %.6f (ref %.6f) s3 %.6f (ref %.6f)"
-          % (tag, s[0], ref["loss"].item(), s[1], ref["ll"].item(), s[2], ref["logpz"].item(), s[3], ref["logqz"].item()))
-    np.testing.assert_allclose(s[0], ref["loss"].item(), rtol=RTOL_ELBO, err_msg="%s loss" % tag)
-    np.testing.assert_allclose(s[1], ref["ll"].item(), rtol=RTOL_ELBO, err_msg="%s s1" % tag)
-    np.testing.assert_allclose(s[2], ref["logpz"].item(), rtol=RTOL_KL, err_msg="%s s2" % tag)
-    np.testing.assert_allclose(s[3], ref["logqz"].item(), rtol=RTOL_KL, err_msg="%s s3" % tag)
-    np.testing.assert_allclose(s[0], -(s[1] + s[2] - s[3]), rtol=2e-6)
-    if zl is not None:
-        np.testing.assert_allclose(zl.cpu().numpy(), ref["z_loc"].detach().numpy(), rtol=RTOL_KL, atol=2e-6)
-        np.testing.assert_allclose(zs.cpu().numpy(), ref["z_scale"].detach().numpy(), rtol=RTOL_KL, atol=2e-6)
-
-
-def _free_and_held(params, cfg, P, alpha, x, eps, beta, y, w_gpu, held=None):
-    """The float64 reference twice: the bound itself (free weights) from `params`, and the oracle `held` (made from `params`
-    when not given: it carries Adam's state from step to step) that takes the Adam step on the gradient with the engine's
-    weights held."""
-    free = orc.SVIOracle(params, cfg, lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
-    of = free.loss_and_grads(x, eps, beta, y)
-    g_free = {k: v.grad.detach().clone() for k, v in free.p.items()}
-    if held is None:
-        held = orc.SVIOracle(params, cfg, lr=LR, dtype=torch.float64, particles=P, renyi=alpha)
-    held.weights = w_gpu.detach().cpu().double()
-    held.step(x, eps, beta, y)
-    return of, g_free, held
-
 
 # ------------------------------------------------------------------------------- 1. fp32-class steps
 @pytest.mark.parametrize("alpha", ALPHAS)
@@ -115,26 +54,23 @@ def test_renyi_steps_vs_reference(gpu_device, name, fused, alpha):
         tag = "%s fused=%d alpha=%g step %d" % (name, fused, alpha, k)
         eng.loss_and_grads(x.cuda(), eps[k].cuda(), beta, yg, z_out=(zl, zs), weights_out=w)
         torch.cuda.synchronize()
-        of, g_free, o = _free_and_held(state(model), cfg, P, alpha, x, eps[k], beta, y, w, o)
-        scalar_check(tag, eng.scalars.cpu().numpy(), of, zl, zs)
+        of, g_free, o = free_and_held(state(model), cfg, P, alpha, x, eps[k], beta, y, w, o)
+        check_scalars(eng.scalars.cpu().numpy(), of, tag)
+        check_z(zl, zs, of, RTOL_KL, Z_ATOL, tag)
         weight_check(tag, w, of, alpha, RTOL_ELBO)
-        worst = 0.0
-        for key in o.p:
-            err = rel_l2(eng.grad_of(key), o.last_grads[key])
-            worst = max(worst, err)
-            worst_e2e = max(worst_e2e, rel_l2(eng.grad_of(key), g_free[key]))
-            assert err < RTOL_GRAD, "%s grad %s: rel l2 error %.3e vs the reference with the engine's weights" % (tag, key, err)
-        print("%s: worst gradient rel l2 %.2e with the engine's weights held, %.2e end to end (free weights)" % (tag, worst, worst_e2e))
+        check_grads(eng, o, tag + ", the engine's weights held")
+        worst_e2e = max([worst_e2e] + [rel_l2(eng.grad_of(key), g_free[key]) for key in o.p])
+        print("%s: worst gradient rel l2 %.2e end to end (free weights)" % (tag, worst_e2e))
         eng.adam_step()
         check_params_after_adam(model, o, fused, tag)
-        model.load_state_dict({k_: v_.detach().float() for k_, v_ in o.p.items()})
+        reload(model, o)
 
 
 # ------------------------------------------------------------------------------- 2. throughput precision
 @pytest.mark.parametrize("which", ["8x8_rts_b6_p3", "28x28_r_b128_p2"])
 def test_renyi_bf16_step_vs_emulated_reference(gpu_device, which):
     """fused=3, alpha = 0, against the reference that rounds where the kernel does (oracle/bf16_plan.py through RenyiOracle),
-    with tests/test_gpu_bf16_emulated.py's own judge and ceilings: loss 1e-5, z_loc / z_scale 1e-5, every gradient tensor
+    with the throughput precision's own judge and ceilings (tests/_bf16_judge.py): loss 1e-5, z_loc / z_scale 1e-5, every gradient tensor
     1e-3 relative L2 — gradients with the engine's weights held, in the emulation and in float64 — and the weight bar with
     that file's LOSS_CEIL in place of 2e-5.  28x28 `r`, B = 128, P = 2 has the 256 samples of a batch whose guide the
     decoder launch would host: it must not fold."""
@@ -152,7 +88,7 @@ def _bf16_body(which):
     eng = model.engine(fused=3, particles=P, renyi=alpha)
     assert eng.uses_fused(b)
     units = P * b * cfg.n_pix // 16
-    name = _kernel_name(units, LIK["bernoulli"])
+    name = kernel_name(fused=3, units=units, lik=LIK["bernoulli"])
     kernel = "w8" if "pv_sdec_w8_kernel" in name else "w4"
     assert kernel == ("w4" if b == 6 else "w8"), name
     zl, zs = torch.empty(b, cfg.z_dim, device="cuda"), torch.empty(b, cfg.z_dim, device="cuda")
@@ -171,12 +107,12 @@ def _bf16_body(which):
         o.weights = wc
         o.loss_and_grads(x, eps[0], beta)
         return out, {k: v.grad.detach().clone() for k, v in o.p.items()}, g_free
-    ref_out, ref_g, _ = reference(bp.Bf16Plan(kernel=kernel, cus=_cus()))
+    ref_out, ref_g, _ = reference(bp.Bf16Plan(kernel=kernel, cus=cus()))
     f64_out, f64_g, f64_free = reference(None)
     tag = "%s renyi" % which
     print("%s: worst gradient rel l2 end to end (free-weight float64 reference) %.2e"
           % (tag, max(rel_l2(eng.grad_of(k), f64_free[k]) for k in f64_free)))
-    _judge(tag, eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), GRAD_CEIL, LOSS_CEIL, SELF_CHECK)
+    judge(tag, eng, ref_out, ref_g, f64_out, f64_g, zl.cpu(), zs.cpu(), GRAD_CEIL, LOSS_CEIL, SELF_CHECK)
     weight_check(tag, w, ref_out, alpha, LOSS_CEIL)
     s = eng.scalars.cpu().numpy()
     np.testing.assert_allclose(s[0], -(s[1] + s[2] - s[3]), rtol=2e-6)
@@ -211,7 +147,7 @@ def test_forward_and_training_launches_with_different_weight_images(gpu_device):
     """fused=2 with the fp16 build of the training kernel forced (dec_kernel = 21): its weight images are not the forward-only
     launch's, so the gradient step prepares images twice.  Scalars and weights stay those of the forward-only call bit for
     bit, at the fp32-class bars against the reference; the gradients with the engine's weights held meet that build's bar
-    on toy problems, max(2.5e-4, 0.03 / sqrt(rows)) (tests/test_gpu_parity.py: h2_grad_tol)."""
+    on toy problems, max(2.5e-4, 0.03 / sqrt(rows)) (tests/_judge.py: h2_grad_tol)."""
     from pyroved_amd.engine import IVAEEngine
     name, alpha = "8x8_rts_b6_p3", 0.0
     cfg, _, x, y, eps, b, P, beta, model = case_inputs(name, "cuda")
@@ -225,8 +161,8 @@ def test_forward_and_training_launches_with_different_weight_images(gpu_device):
     finally:
         IVAEEngine.dec_kernel = 0
     assert torch.equal(s0, s1) and torch.equal(w0, w1)
-    of, _, o = _free_and_held(state(model), cfg, P, alpha, x, eps[0], beta, y, w1)
-    scalar_check(name + " h221", s1.cpu().numpy(), of)
+    of, _, o = free_and_held(state(model), cfg, P, alpha, x, eps[0], beta, y, w1)
+    check_scalars(s1.cpu().numpy(), of, name + " h221")
     weight_check(name + " h221", w1, of, alpha, RTOL_ELBO)
     tol = max(2.5e-4, 0.03 / (P * b * cfg.n_pix) ** 0.5)
     for key in o.p:

@@ -21,10 +21,8 @@ from pyroved_amd.nets import fcEncoderNet, sDecoderNet, fcDecoderNet, convEncode
 from pyroved_amd.utils import set_deterministic_mode
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
-
-
-def state(model):
-    return {k: v.detach().cpu() for k, v in model.state_dict().items()}
+from _judge import ILL_SHARE, near_zero_share, state
+from _plan_kit import _plan, _vanilla_plan
 
 
 # ------------------------------------------------------------------------------- the reference
@@ -220,24 +218,6 @@ def test_bf16_precision_is_refused_before_anything_runs():
 
 
 # ------------------------------------------------------------------------------- plan validation (host arithmetic)
-def _plan(fused=2, channels=1, discrete_dim=0):
-    from test_particles_cpu import _small_plan
-    p = _small_plan(discrete_dim=discrete_dim, fused=fused)
-    p.out.out_dim = channels
-    p.n_pix = 784 * channels
-    p.enc[0].in_dim = 784 * channels
-    return p
-
-
-def _vanilla_plan(fused=2):
-    p = _plan(fused)
-    p.coord_dim, p.z_dim, p.latent_dim, p.has_r, p.has_t = 0, 2, 2, 0, 0
-    p.head.out_dim = 4
-    p.dec[0].in_dim = 2
-    p.out.out_dim = 784
-    return p
-
-
 def test_header_constant():
     src = open(os.path.join(ROOT, "include", "pyroved_amd.h")).read()
     m = re.search(r"#define\s+PV_MAX_CHANNELS\s+(\d+)", src)
@@ -321,15 +301,15 @@ PARENT_WS = {
 def _near_zero_share(o, tag, worst):
     for key, g in o.last_grads.items():
         assert g.norm().item() > 0.0, "%s %s: zero gradient" % (tag, key)
-        share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
+        share = near_zero_share(g)
         worst[0] = max(worst[0], share)
-        assert share < 0.01, "%s %s: %.2f %% near-zero gradient entries" % (tag, key, 100 * share)
+        assert share < ILL_SHARE, "%s %s: %.2f %% near-zero gradient entries" % (tag, key, 100 * share)
 
 
 def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent():
-    """tests/test_gpu_multichannel.py's parameter check after Adam holds entries with |g_ref| < 1e-5 max|g_ref| to 2 lr only, on
+    """tests/_judge.py's check_params_after_adam holds entries with |g_ref| < 1e-5 max|g_ref| to 2 lr only, on
     the condition that they are fewer than 1 % of a tensor and that no tensor's gradient vanishes: confirmed here with the
-    float64 reference alone, at every case of that file over its two steps (each from float32-rounded parameters, as there).
+    float64 reference alone, at every case of tests/_multichannel_cases.py over its two steps (each from float32-rounded parameters, as there).
     Measured worst share: 0.78 % (one entry of a 128-entry bias).  (An lrelu decoder breaches the cap with 7 %: no case uses one.)"""
     torch.set_num_threads(min(8, torch.get_num_threads()))
     worst = [0.0]

@@ -2,7 +2,7 @@
 The opt-in fused f32 decoder kernel for multi-channel models — PV_PLAN_FUSED_CHANNELS in the C ABI, fused_channels= in Python —
 where no GPU is needed: the flag's value, which plans it takes effect for (through pv_ivae_uses_fused and the workspace
 queries: host arithmetic), that it does nothing everywhere else, and what the engine and the trainer build and refuse.
-Plans are built as tests/test_multichannel_cpu.py builds them: 784 positions x ch observations, batch 16.
+Plans are tests/_plan_kit.py's: 784 positions x ch observations, batch 16.
 """
 import ctypes as C
 import os
@@ -14,7 +14,7 @@ from conftest import ROOT
 
 import pyroved_amd as pv
 from pyroved_amd import _abi
-from test_multichannel_cpu import _plan, _vanilla_plan
+from _plan_kit import _plan, _vanilla_plan
 
 EINVAL = -1
 FLAG = 256

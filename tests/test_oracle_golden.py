@@ -15,6 +15,7 @@ from conftest import GOLDEN, load_golden, make_x, check_digest, meta_of
 
 import pyroved_amd as pv
 from oracle import svi_oracle as orc
+from _golden_models import convenc_model, ved_case, vedbn_oracle
 
 STEP_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "ivae_*.npz"))
                     if not p.endswith("_fwd.npz"))
@@ -299,19 +300,6 @@ def test_jivae_sampled_class_needs_the_vanilla_decoder():
 VED_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "ved_*.npz")))
 
 
-def ved_case(gold):
-    import ast
-    kw = {}
-    for k in gold:
-        if k.startswith("meta.model_kw."):
-            v = str(gold[k])
-            kw[k[len("meta.model_kw."):]] = ast.literal_eval(v) if (v[0] in "[(" or v in ("True", "False")) else v
-    return dict(input_dim=tuple(int(v) for v in gold["meta.input_dim"]),
-                output_dim=tuple(int(v) for v in gold["meta.output_dim"]),
-                latent_dim=int(gold["meta.latent_dim"]), steps=int(gold["meta.steps"]),
-                beta=float(gold["meta.scale_factor"]), kw=kw)
-
-
 def test_ved_fixture_inventory():
     assert len(VED_CASES) >= 5
 
@@ -350,15 +338,6 @@ def test_ved_oracle_steps_match_reference(name):
 VEDBN_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "vedbn_*.npz")))
 
 
-def vedbn_oracle(gold, device="cpu"):
-    c = ved_case(gold)
-    model = pv.models.VED(c["input_dim"], c["output_dim"], latent_dim=c["latent_dim"], seed=1, device=device, **c["kw"])
-    cfg = orc.VedConfig(input_dim=c["input_dim"], output_dim=c["output_dim"], latent_dim=c["latent_dim"],
-                        hidden_dim_e=c["kw"].get("hidden_dim_e"), hidden_dim_d=c["kw"].get("hidden_dim_d"),
-                        activation=c["kw"].get("activation", "lrelu"), batchnorm=True)
-    return c, model, cfg
-
-
 @pytest.mark.parametrize("name", VEDBN_CASES)
 def test_vedbn_oracle_steps_match_reference(name):
     """VED(batchnorm=True): batch statistics + running estimates while training, and — after encode() / decode() left the
@@ -394,18 +373,6 @@ def test_vedbn_oracle_steps_match_reference(name):
 
 # ---------------------------------------------------------------- iVAE with a convolutional encoder (set_encoder)
 CONVENC_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "ivaeconv_*.npz")))
-
-
-def convenc_model(gold, device):
-    """iVAE + set_encoder(convEncoderNet(data_dim, latent_dim=z_dim, hidden_dim=...)) built like the fixture's model."""
-    import ast
-    meta = meta_of(gold)
-    hid = ast.literal_eval(str(gold["meta.conv_encoder"]))
-    model = pv.models.iVAE(meta["data_dim"], meta["latent_dim"], meta["invariances"], seed=1, device=device)
-    model.set_encoder(pv.nets.convEncoderNet(meta["data_dim"], latent_dim=model.z_dim, hidden_dim=hid))
-    cfg = orc.Config(data_dim=meta["data_dim"], latent_dim=meta["latent_dim"], invariances=meta["invariances"],
-                     conv_encoder=hid)
-    return meta, model, cfg
 
 
 @pytest.mark.parametrize("name", CONVENC_CASES)

@@ -18,32 +18,13 @@ import pyroved_amd as pv
 from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 from _oracle_engine import OracleEngine
+from _judge import ILL_SHARE, near_zero_share
+from _particles_cases import STEP_CASES, step_case, oracle_of
+from _plan_kit import _params, _inputs, _small_plan, _free_port, _plain_loop, _StandInEngine, _ivae, CASES, SLOTS, PLAN_FIELDS
 
-
-def _params(cfg, seed=0, c_dim=0):
-    model = pv.models.iVAE(cfg.data_dim, cfg.latent_dim, cfg.invariances, c_dim=c_dim, seed=1, device="cpu")
-    g = torch.Generator().manual_seed(seed)
-    return {k: (v.detach() + 0.05 * torch.randn(v.shape, generator=g)).double() for k, v in model.state_dict().items()}
-
-
-def _inputs(cfg, b, P, seed=3, c_dim=0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(b, *cfg.data_dim, generator=g, dtype=torch.float64)
-    eps = torch.randn(P * b, cfg.z_dim, generator=g, dtype=torch.float64)
-    y = None
-    if c_dim:
-        y = torch.zeros(b, c_dim, dtype=torch.float64)
-        y[torch.arange(b), torch.arange(b) % c_dim] = 1.0
-        x = x.flatten(1)
-    return x, eps, y
-
-
-# (data_dim, invariances, c_dim)
-CASES = [((8, 8), ["r", "t", "s"], 0), ((16,), ["t"], 0), ((8, 8), None, 0), ((8, 8), ["r", "t"], 3)]
 # the KL form of the particle oracle and of its one-particle parent (the ids are the ones these cases have always had)
 PAIRS = [pytest.param("sampled", id="ParticlesOracle-SVIOracle"),
          pytest.param("analytic", id="ParticlesMeanFieldOracle-MeanFieldOracle")]
-SLOTS = ("loss", "ll", "logpz", "logqz")
 
 
 # ------------------------------------------------------------------------------- the reference against its parents
@@ -104,23 +85,6 @@ def test_reference_oracles_inherit_adam_and_draw_particles_in_order():
 
 
 # ------------------------------------------------------------------------------- trainer arguments
-class _StandInEngine:
-    device = torch.device("cpu")
-    grads_live = False
-    kl = "unset"
-    particles = "unset"
-
-    def __init__(self):
-        self.lr = self.betas = self.adam_eps = None
-
-    def reset_optimizer(self):
-        pass
-
-
-def _ivae():
-    return pv.models.iVAE((8, 8), 2, ["r"], seed=1, device="cpu")
-
-
 @pytest.mark.parametrize("loss", [None, "Trace_ELBO", "TraceMeanField_ELBO"])
 def test_trainer_hands_the_particle_count_to_the_engine(loss):
     eng = _StandInEngine()
@@ -161,15 +125,6 @@ def test_engine_rejects_particle_counts_that_are_not_positive_ints():
 
 
 # ------------------------------------------------------------------------------- generator order
-def _plain_loop(loader, z_dim, P):
-    """What Pyro's P runs of the guide per step draw: P tensors torch.empty(B, z_dim).normal_() in particle order."""
-    out = []
-    for data in loader:
-        b = data[0].shape[0]
-        out.append(torch.cat([torch.empty(b, z_dim).normal_() for _ in range(P)]))
-    return out
-
-
 # z_dim = 3: 6 * 3 = 18 values per draw, no multiple of 16 (CPU normal_ re-draws a short tail: every draw on its own);
 # z_dim = 6: 8 * 6 = 48 values, a multiple of 16 (runs of draws are merged), with a ragged last batch of 4 * 6 = 24
 @pytest.mark.parametrize("inv,n,batch", [(["r"], 18, 6), (["r", "t", "s"], 20, 8)])
@@ -207,15 +162,6 @@ def _dp_run(P, analytic):
                                 num_particles=P)
     tr.step(loader)
     return tr.loss_history, {k: v.detach().numpy().copy() for k, v in eng.o.p.items()}, eng.adam_t, [e.shape[0] for e in eng.seen_eps]
-
-
-def _free_port():
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _dp_worker(rank, world, port, P, analytic, q):
@@ -261,38 +207,6 @@ def test_data_parallel_world2_gloo_with_two_particles_matches_single_process(ana
 
 
 # ------------------------------------------------------------------------------- ABI
-PLAN_FIELDS = [
-    "batch", "n_pix", "coord_dim", "z_dim", "latent_dim", "c_dim", "has_r", "has_t", "has_s", "t_prior", "sc_prior", "beta", "lik",
-    "sigmoid_out", "decoder_sig", "fused", "discrete_dim", "beta_disc", "n_enc", "n_dec", "enc", "head", "fc_coord", "fc_latent",
-    "dec", "out", "n_enc_ops", "enc_ndim", "enc_in_dim", "enc_ops", "params", "grads", "adam_m", "adam_v", "n_params", "x", "y",
-    "eps", "grid", "ws", "ws_bytes", "scalars", "z_loc", "z_scale", "loc", "alpha", "ext_head", "ext_dhead", "ext_encoder",
-    "bn_eval", "row_w", "row_elbo", "dy", "ext_z", "ext_dz", "ext_ll", "ext_decoder", "conv_wide", "lr", "adam_beta1", "adam_beta2",
-    "adam_eps", "adam_step", "flags", "ev_start", "ev_stop", "class_onehot", "conv_ev_start", "conv_ev_stop", "conv_ev_flops",
-    "dec_kernel", "kl_mode",
-]
-
-
-def _small_plan(discrete_dim=0, fused=2):
-    p = _abi.pv_ivae_plan()
-    p.batch, p.n_pix, p.coord_dim, p.z_dim, p.latent_dim = 16, 784, 2, 5, 2
-    p.has_r = p.has_t = 1
-    p.lik, p.sigmoid_out, p.fused = _abi.LIK["bernoulli"], 1, fused
-
-    def layer(i, o, act):
-        l = _abi.pv_layer()
-        l.in_dim, l.out_dim, l.act, l.b_off = i, o, _abi.ACT[act], 0
-        return l
-    p.n_enc = 2
-    p.enc[0], p.enc[1] = layer(784, 128, "tanh"), layer(128, 128, "tanh")
-    p.discrete_dim = discrete_dim
-    p.head = layer(128, 10 + discrete_dim, None)
-    p.fc_coord, p.fc_latent = layer(2, 128, "tanh"), layer(2 + discrete_dim, 128, None)
-    p.n_dec = 2
-    p.dec[0], p.dec[1] = layer(128, 128, "tanh"), layer(128, 128, "tanh")
-    p.out = layer(128, 1, None)
-    return p
-
-
 def test_abi_version_symbols_and_unchanged_plan_struct():
     """The feature arrives as three entry points next to an unchanged v17 plan."""
     lib = _abi.lib()
@@ -335,18 +249,17 @@ def test_particle_workspace_query_validates_and_forwards():
 # ------------------------------------------------------------------------------- the GPU step cases' condition
 @pytest.mark.parametrize("kl", ["sampled", "analytic"])
 def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent(kl):
-    """tests/test_gpu_particles.py's parameter check after Adam holds entries with |g| < 1e-5 max|g| to 2 lr only, on the
-    condition that they are fewer than 1 % of a tensor: confirmed here, with the reference alone, for that file's cases and
-    seeds over its two steps."""
-    from test_gpu_particles import STEP_CASES, step_case, oracle_of
+    """tests/_judge.py's check_params_after_adam holds entries with |g| < 1e-5 max|g| to 2 lr only, on the condition that they
+    are fewer than 1 % of a tensor: confirmed here, with the reference alone, for tests/_particles_cases.py's cases and
+    seeds over their two steps."""
     for name in sorted(STEP_CASES):
         model, cfg, x, y, eps, b, P = step_case(name, "cpu")
         o = oracle_of(kl, {k: v.detach() for k, v in model.state_dict().items()}, cfg, P)
         for k in range(2):
             o.step(x, eps[k], 1.7, y)
             for key, g in o.last_grads.items():
-                share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
-                assert share < 0.01, (name, kl, k, key, share)
+                share = near_zero_share(g)
+                assert share < ILL_SHARE, (name, kl, k, key, share)
 
 
 # ------------------------------------------------------------------------------- out of scope raises at construction

@@ -13,19 +13,9 @@ condition on purpose: they would meet it everywhere, and none of them depends on
 """
 import numpy as np
 import pytest
-import torch
 
 import _partition_cases as pc
-
-
-@pytest.fixture(autouse=True)
-def _cpu_threads():
-    n = torch.get_num_threads()
-    torch.set_num_threads(16)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
+from _judge import cpu_threads_16
 
 
 # ------------------------------------------------------------------------------- 1. the table's claims

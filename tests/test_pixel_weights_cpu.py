@@ -3,7 +3,7 @@ Per-observation weights of the likelihood — pv_ivae_weighted_* in the C ABI, p
 the four symbols and the unchanged ABI, what the workspace query refuses and which kernel family pv_ivae_weighted_uses_fused
 reports (host arithmetic), every ValueError of the engine and the trainer with the configure rollback, the reference
 (tests/_pixel_weight_cases.WeightedOracle) against orc.elbo, and the condition the GPU step tests' parameter check rests on.
-Plans are built as tests/test_multichannel_cpu.py builds them: 784 positions x ch observations, batch 16.
+Plans are tests/_plan_kit.py's: 784 positions x ch observations, batch 16.
 """
 import ctypes as C
 import os
@@ -20,7 +20,8 @@ from pyroved_amd import _abi
 from oracle import svi_oracle as orc
 import _multichannel_cases as mc
 import _pixel_weight_cases as pw
-from test_multichannel_cpu import _plan, _vanilla_plan, state
+from _judge import ILL_SHARE, near_zero_share, state
+from _plan_kit import _plan, _vanilla_plan
 
 EINVAL = -1
 FLAG = _abi.PV_PLAN_FUSED_CHANNELS
@@ -314,7 +315,7 @@ def test_reference_weights_reach_the_right_values():
 
 # ------------------------------------------------------------------------------- the GPU step cases' condition
 def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent():
-    """tests/test_gpu_pixel_weights.py's parameter check after Adam holds entries with |g_ref| < 1e-5 max|g_ref| to 2 lr only, on
+    """tests/_judge.py's check_params_after_adam holds entries with |g_ref| < 1e-5 max|g_ref| to 2 lr only, on
     the condition that they are fewer than 1 % of a tensor and that no tensor's gradient vanishes: confirmed here with the float64
     reference alone, at every case over its two steps (each from float32-rounded parameters, as there), case 1 also with the
     analytic KL.  Measured worst share: 0.78 % (w01, analytic KL, step 1: one entry of 128); every other case <= 0.39 %."""
@@ -328,8 +329,8 @@ def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent():
                 o.step(x, eps[k], 1.0, y)
                 for key, g in o.last_grads.items():
                     assert g.norm().item() > 0.0, "%s %s step %d %s: zero gradient" % (name, kl, k, key)
-                    share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
+                    share = near_zero_share(g)
                     worst = max(worst, share)
-                    assert share < 0.01, "%s %s step %d %s: %.2f %% near-zero gradient entries" % (name, kl, k, key, 100 * share)
+                    assert share < ILL_SHARE, "%s %s step %d %s: %.2f %% near-zero gradient entries" % (name, kl, k, key, 100 * share)
                 mc.round_to_float32(o)
     print("worst near-zero share: %.3f %%" % (100 * worst))

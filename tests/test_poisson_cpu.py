@@ -19,6 +19,8 @@ from pyroved_amd import _abi
 from pyroved_amd.engine import UnsupportedModel
 from oracle import svi_oracle as orc
 import _poisson_data as pr
+from _judge import ILL_SHARE, near_zero_share
+from _plan_kit import PLAN_FIELDS, _small_plan
 
 
 # ------------------------------------------------------------------------------- the reference
@@ -76,15 +78,13 @@ def test_abi_constants_and_unchanged_structs():
     m = re.search(r"PV_LIK_POISSON_LOG\s*=\s*(\d+)", src)
     assert m and int(m.group(1)) == 3 == _abi.LIK["poisson_log"]
     assert _abi.LIK == {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2, "poisson_log": 3}
-    # the plan structs as they were (bytes on x86-64) and the field list tests/test_particles_cpu.py pins
-    from test_particles_cpu import PLAN_FIELDS
+    # the plan structs as they were (bytes on x86-64) and the field list tests/_plan_kit.py pins
     assert [f[0] for f in _abi.pv_ivae_plan._fields_] == PLAN_FIELDS
     assert C.sizeof(_abi.pv_ivae_plan) == 2824 and C.sizeof(_abi.pv_ved_plan) == 3880 and C.sizeof(_abi.pv_layer) == 32
 
 
 # ------------------------------------------------------------------------------- plan validation (host arithmetic)
 def _ivae_plan(fused, lik=3, sigmoid_out=0):
-    from test_particles_cpu import _small_plan
     p = _small_plan(fused=fused)
     p.lik, p.sigmoid_out = lik, sigmoid_out
     return p
@@ -180,18 +180,17 @@ def test_engines_refuse_at_construction():
 
 # ------------------------------------------------------------------------------- the GPU step cases' condition
 def test_gpu_step_cases_keep_near_zero_gradient_entries_below_one_percent():
-    """tests/test_gpu_poisson.py's parameter check after Adam holds entries with |g| < 1e-5 max|g| to 2 lr only, on the
-    condition that they are fewer than 1 % of a tensor: confirmed here with the float64 reference alone, for that file's
-    fp32-class cases over their two steps (the count level matters: at rates of 3 - 12 the tanh encoder saturates and the
+    """tests/_judge.py's check_params_after_adam holds entries with |g| < 1e-5 max|g| to 2 lr only, on the
+    condition that they are fewer than 1 % of a tensor: confirmed here with the float64 reference alone, for the
+    fp32-class cases of tests/_poisson_data.py over their two steps (the count level matters: at rates of 3 - 12 the tanh encoder saturates and the
     share reaches 2 - 27 % in encoder_z.fc_layers.0.weight)."""
-    from test_gpu_poisson import STEP_CASES, step_case
     torch.set_num_threads(min(8, torch.get_num_threads()))
-    for name in sorted(STEP_CASES):
-        model, cfg, x, y, eps, b = step_case(name, "cpu")
+    for name in sorted(pr.STEP_CASES):
+        model, cfg, x, y, eps, b = pr.step_case(name, "cpu")
         o = orc.SVIOracle({k: v.detach() for k, v in model.state_dict().items()}, cfg, dtype=torch.float64)
-        o.sampled_class = STEP_CASES[name].get("sampled", False)
+        o.sampled_class = pr.STEP_CASES[name].get("sampled", False)
         for k in range(2):
             o.step(x, eps[k], 1.0, y[k] if isinstance(y, list) else y)
             for key, g in o.last_grads.items():
-                share = (g.abs() < 1e-5 * g.abs().max()).float().mean().item()
-                assert share < 0.01, (name, k, key, share)
+                share = near_zero_share(g)
+                assert share < ILL_SHARE, (name, k, key, share)

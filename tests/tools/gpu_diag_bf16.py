@@ -4,7 +4,18 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from test_gpu_parity import load_golden, meta_of, build, make_x, rel_l2, orc
+from conftest import load_golden, meta_of, make_x
+from _judge import rel_l2
+import pyroved_amd as pv
+from oracle import svi_oracle as orc
+
+
+def build(meta, fused):
+    model = pv.models.iVAE(meta["data_dim"], meta["latent_dim"], meta["invariances"], seed=1, device="cuda")
+    cfg = orc.Config(data_dim=meta["data_dim"], latent_dim=meta["latent_dim"], invariances=meta["invariances"])
+    return model, cfg, model.engine(fused=fused)
+
+
 name = sys.argv[1]
 gold = load_golden(name); meta = meta_of(gold)
 for fused in (3,):

@@ -4,18 +4,14 @@ paths) against the CPU oracle from identical parameters: loss to 2e-5, every gra
 Prints one line per case and a summary; exit code 1 on any failure.    python tests/tools/gpu_fuzz.py [n_cases] [seed]"""
 import os, sys, random, traceback
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np, torch
 import pyroved_amd as pv
 from oracle import svi_oracle as orc
+from _judge import rel_l2
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 def case():
