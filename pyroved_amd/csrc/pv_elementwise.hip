@@ -1231,7 +1231,7 @@ __global__ __launch_bounds__(256) void pv_latent_bwd_kernel(PvLatentBwd p) { pv_
 __global__ __launch_bounds__(256) void pv_latent_bwd_reduce_kernel(PvLatentBwd p, const float* __restrict__ part,
                                                                    int G_, float* __restrict__ Gr, PvFusedOffsets o,
                                                                    int cd, int fmt) {
-  __shared__ f32x4 smr[4][64];
+  __shared__ PvRedLds smr;
 #ifndef LB_EXP
 #define LB_EXP 0                 // timing experiments (wrong results): 1 no record sums, 2 no latent backward
 #endif
@@ -1262,7 +1262,7 @@ int pv_latent_bwd_reduce(const PvLatentBwd& p, const float* part, int grid, floa
 __global__ __launch_bounds__(256) void pv_rec_wgrad_kernel(const float* __restrict__ part, int G_, float* __restrict__ Gr, PvFusedOffsets o,
                                                            int cd, int fmt, PvWgradSmall w, PvRecAdam ra, int rwx) {
   // (rwx: timing experiments of the experiments build — 1 no record sums, 2 no tiles: wrong results; 0 in the shipped build)
-  __shared__ f32x4 smr[4][64];
+  __shared__ PvRedLds smr;
   __shared__ float wpart[WG_WAVES][16][17];
   __shared__ float wrpart[WG_WAVES][16];
   const int nred = pv_fused_reduce_blocks(fmt), id = (int)blockIdx.x;
@@ -1270,6 +1270,11 @@ __global__ __launch_bounds__(256) void pv_rec_wgrad_kernel(const float* __restri
   if (rwx & 2) return;
   pv_wgrad_small_block(w, id - nred, (int)gridDim.x - nred, wpart, wrpart);
 }
+
+// test / measurement hook (not in include/): launches of pv_rec_wgrad_kernel by this process so far, in the low 32 bits all of them, in
+// the high 32 bits those whose record blocks carried Adam
+static uint64_t rec_wgrad_launches = 0;
+extern "C" uint64_t pv_debug_rec_wgrad_launches(void) { return __atomic_load_n(&rec_wgrad_launches, __ATOMIC_RELAXED); }
 
 // adam: every parameter must be finalised by a record block or a tile (no Adam guests here: the caller checked the coverage)
 int pv_rec_wgrad(const float* part, int grid, float* G, const PvFusedOffsets& o, int cd, int fmt, const PvGemm* gs, int n,
@@ -1284,6 +1289,7 @@ int pv_rec_wgrad(const float* part, int grid, float* G, const PvFusedOffsets& o,
   PvRecAdam ra{};
   if (adam) { ra.a = *adam; ra.on = 1; }
   static const int rwx = pv_exp_int("PV_RW_EXP", 0);
+  __atomic_fetch_add(&rec_wgrad_launches, 1ull + ((uint64_t)ra.on << 32), __ATOMIC_RELAXED);
   hipLaunchKernelGGL(pv_rec_wgrad_kernel, dim3(pv_fused_reduce_blocks(fmt) + tiles + fin_blocks), dim3(256), 0, s, part, grid, G, o, cd,
                      fmt, w, ra, rwx);
   PV_LAUNCH_CHECK();

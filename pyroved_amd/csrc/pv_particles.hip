@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void pv_particle_bwd_kernel(PvParticleBwd p) {
 // workgroups [0, nred) sum the fused decoder's per-workgroup gradient records, the rest run the particle backward
 __global__ __launch_bounds__(256) void pv_particle_bwd_reduce_kernel(PvParticleBwd p, const float* __restrict__ part, int G_,
                                                                      float* __restrict__ Gr, PvFusedOffsets o, int cd, int fmt) {
-  __shared__ f32x4 smr[4][64];
+  __shared__ PvRedLds smr;
   const int nred = pv_fused_reduce_blocks(fmt);
   if ((int)blockIdx.x < nred) pv_sdec_fused_reduce_block(part, G_, Gr, o, cd, 0, blockIdx.x, smr, fmt);
   else pv_particle_bwd_block(p, blockIdx.x - nred);

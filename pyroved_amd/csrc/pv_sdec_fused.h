@@ -227,79 +227,154 @@ __host__ __device__ inline int pv_fused_reduce_blocks(int fmt) {
 #define PV_RED_UNROLL 8          // records in flight per thread of a reducing block
 #endif
 struct PvRecAdam { PvAdamFuse a; int on; };       // (by value: the address of a kernel argument would put it in scratch memory)
-__device__ __forceinline__ void pv_rec_out(float* __restrict__ Gr, int idx, float v, const PvRecAdam& ad) {
-  if (ad.on) pv_adam_update(ad.a.p, ad.a.g, ad.a.m, ad.a.v, (Gr - ad.a.g) + idx, v, ad.a.b1, ad.a.b2, ad.a.eps, ad.a.step_size, ad.a.bc2_sqrt);
+// How a reducing block ends.  Its four waves hand their slice partials over through LDS ONCE (PvRedLds: 8 KB, one pv_lds_barrier —
+// nothing but LDS is handed over) and then EVERY thread finalises its share of the block's elements: (s0 + s1) + (s2 + s3) of the
+// element's four slice partials, then pv_rec_fin.  Which elements a thread finalises depends on the block and the thread alone, so
+// with Adam riding in the launch the thread requests their p / m / v (cold: no earlier launch of the step touched them) right behind
+// the loads of its LAST batch of records — the loop's last PV_RED_UNROLL records are peeled for that: the requests queue behind the
+// record loads, a counted wait on those does not wait for them, and their round trip runs under the last batch's arrival and the LDS
+// exchange; the update then runs on registers.  (Requested at block entry they sit at the head of an in-order queue: measured
+// slower.  Before, wave 0 alone ran eight load -> update -> store chains per lane one after the other, behind the last barrier.)
+typedef f32x4 PvRedLds[2][4][64];
+struct PvRecOps { float p, m, v; };                // one element's Adam operands, requested ahead of its update
+// (ADAM: ad.on as a template argument — the reducing bodies exist once per value, chosen at their entry: behind a run-time `if`
+//  around the requests alone, the counted waits on the record loads would have to assume that nothing was issued after them)
+template <bool ADAM>
+__device__ __forceinline__ PvRecOps pv_rec_request(const float* __restrict__ Gr, int idx, const PvRecAdam& ad) {
+  PvRecOps q = {0.0f, 0.0f, 0.0f};
+  if (ADAM) { const int64_t i = (Gr - ad.a.g) + idx; q.p = ad.a.p[i]; q.m = ad.a.m[i]; q.v = ad.a.v[i]; }
+  return q;
+}
+// pv_adam_update (pv_common.h) on operands already in registers: the same expressions in the same order — and the same ROUNDINGS.
+// Which of the expressions' multiply-adds the compiler contracts depends on the code around them: in pv_adam_kernel (the separate
+// optimizer launch these bytes are held to, tests/test_gpu_record_finalise.py) and in pv_adam_update as the reducing blocks inlined
+// it before, the moments' products and sums stay separate instructions and the parameter's update is one fused multiply-add; with
+// one element per thread it fused the moments' too (parameters one ulp off after three steps).  So the form is written out here.
+__device__ __forceinline__ void pv_adam_update_ops(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t i, float gi, float pi, float mi, float vi,
+                                                   float b1, float b2, float eps, float step_size, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  mi = mi + (gi - mi) * (1.0f - b1);
+  vi = vi * b2 + (1.0f - b2) * gi * gi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p[i] = __builtin_fmaf(-step_size, mi / denom, pi);      // pi - step_size * (mi / denom), one rounding
+  m[i] = mi; v[i] = vi;
+  g[i] = 0.0f;
+}
+template <bool ADAM>
+__device__ __forceinline__ void pv_rec_fin(float* __restrict__ Gr, int idx, float v, const PvRecOps& q, const PvRecAdam& ad) {
+  if (ADAM) pv_adam_update_ops(ad.a.p, ad.a.g, ad.a.m, ad.a.v, (Gr - ad.a.g) + idx, v, q.p, q.m, q.v, ad.a.b1, ad.a.b2, ad.a.eps,
+                                ad.a.step_size, ad.a.bc2_sqrt);
   else Gr[idx] = v;
 }
-template <int FMT>
+// the records [w0, w1) of a slice, in ascending order: all but the last PV_RED_UNROLL in the loop, those as one peeled batch whose
+// loads are followed by `request` (a slice shorter than a batch runs the loop alone).  add(v) sums one record's chunk of type V
+template <typename V, typename Add, typename Req>
+__device__ __forceinline__ void pv_rec_stream(const float* __restrict__ p, int w0, int w1, Add add, Req request) {
+  const bool peel = w1 - w0 >= PV_RED_UNROLL;
+  const int wl = peel ? w1 - PV_RED_UNROLL : w1;
+#pragma unroll PV_RED_UNROLL
+  for (int w = w0; w < wl; ++w) add(*reinterpret_cast<const V*>(p + (int64_t)w * FD_REC));
+  V t[PV_RED_UNROLL];
+  if (peel) {
+#pragma unroll
+    for (int k = 0; k < PV_RED_UNROLL; ++k) t[k] = *reinterpret_cast<const V*>(p + (int64_t)(wl + k) * FD_REC);
+  }
+  request();
+  if (peel) {
+#pragma unroll
+    for (int k = 0; k < PV_RED_UNROLL; ++k) add(t[k]);
+  }
+}
+// Lane-native matrix blocks: thread (chunk c, slice sl) sums its slice of chunk c and then finalises component sl of that chunk —
+// row row0(c >> 4) + sl, column col(c & 15) — of W1 and W2 (packed format) or of the block's one matrix (fp32 format): the 16 lanes
+// that share a row write 16 consecutive columns.  LDS as float [matrix][slice][component][chunk]: a thread stores and loads at
+// consecutive chunks, no bank conflicts either way.
+template <int FMT, bool ADAM>
 __device__ __forceinline__ void pv_sdec_fused_reduce_block_lane(const float* __restrict__ part, int G_, float* __restrict__ Gr,
-                                                                const PvFusedOffsets& o, int block, f32x4 (*sm)[64],
-                                                                const PvRecAdam& ad = PvRecAdam{}) {
+                                                                const PvFusedOffsets& o, int block, f32x4 (*sm)[4][64],
+                                                                const PvRecAdam& ad) {
   const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
   const int per = (G_ + 3) / 4;
   const int w0 = sl * per, w1 = min(G_, w0 + per);
   const float* pbase = part + 4 * (block * 64 + c);
+  float* lds = reinterpret_cast<float*>(sm);
+  const int r = c & 15, q = c >> 4;
+  int ia, ib = 0;                                                      // the thread's elements in the flat gradient
+  if (FMT == PV_REC_LANE_BF16) {
+    const int oo = block & 3, s_ = (block >> 2) & 1, wave = block >> 3, jp = wave >> 1, kh = wave & 1;
+    const int row0 = 32 * jp + 16 * (s_ ^ kh) + 4 * q, col = 64 * kh + 16 * oo + r;
+    ia = o.W1 + (row0 + sl) * FD_H + col;
+    ib = o.W2 + (row0 + sl) * FD_H + col;
+  } else {
+    const int kb = block & 7, s_ = (block >> 3) & 1, wave = (block >> 4) & 3, m = block >> 6;
+    const int row0 = 16 * (2 * wave + s_) + 4 * q, col = 16 * kb + r;
+    ia = (m == 0 ? o.W1 : o.W2) + (row0 + sl) * FD_H + col;
+  }
   f32x4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
+  PvRecOps qa = {0.0f, 0.0f, 0.0f}, qb = {0.0f, 0.0f, 0.0f};
   if (FMT == PV_REC_LANE_BF16) {
     typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-#pragma unroll PV_RED_UNROLL
-    for (int w = w0; w < w1; ++w) {
-      const u32x4_ v = *reinterpret_cast<const u32x4_*>(pbase + (int64_t)w * FD_REC);
+    pv_rec_stream<u32x4_>(pbase, w0, w1, [&](const u32x4_ v) {
       a[0] += __uint_as_float(v[0] << 16); a[1] += __uint_as_float(v[0] & 0xffff0000u);
       a[2] += __uint_as_float(v[1] << 16); a[3] += __uint_as_float(v[1] & 0xffff0000u);
       b[0] += __uint_as_float(v[2] << 16); b[1] += __uint_as_float(v[2] & 0xffff0000u);
       b[2] += __uint_as_float(v[3] << 16); b[3] += __uint_as_float(v[3] & 0xffff0000u);
-    }
+    }, [&]() { qa = pv_rec_request<ADAM>(Gr, ia, ad); qb = pv_rec_request<ADAM>(Gr, ib, ad); });
   } else {
-#pragma unroll PV_RED_UNROLL
-    for (int w = w0; w < w1; ++w) a += *reinterpret_cast<const f32x4*>(pbase + (int64_t)w * FD_REC);
+    pv_rec_stream<f32x4>(pbase, w0, w1, [&](const f32x4 v) { a += v; }, [&]() { qa = pv_rec_request<ADAM>(Gr, ia, ad); });
   }
-  sm[sl][c] = a;
-  __syncthreads();
-  const f32x4 ta = (sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]);
-  f32x4 tb = b;
-  if (FMT == PV_REC_LANE_BF16) {
-    __syncthreads();
-    sm[sl][c] = b;
-    __syncthreads();
-    tb = (sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]);
-  }
-  if (sl != 0) return;
-  const int r = c & 15, q = c >> 4;
-  if (FMT == PV_REC_LANE_BF16) {
-    const int oo = block & 3, s_ = (block >> 2) & 1, wave = block >> 3, jp = wave >> 1, kh = wave & 1;
-    const int row0 = 32 * jp + 16 * (s_ ^ kh) + 4 * q, col = 64 * kh + 16 * oo + r;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      pv_rec_out(Gr, o.W1 + (row0 + i) * FD_H + col, ta[i], ad);
-      pv_rec_out(Gr, o.W2 + (row0 + i) * FD_H + col, tb[i], ad);
-    }
-  } else {
-    const int kb = block & 7, s_ = (block >> 3) & 1, wave = (block >> 4) & 3, m = block >> 6;
-    const int row0 = 16 * (2 * wave + s_) + 4 * q, col = 16 * kb + r;
-    const int dst = m == 0 ? o.W1 : o.W2;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pv_rec_out(Gr, dst + (row0 + i) * FD_H + col, ta[i], ad);
+  for (int i = 0; i < 4; ++i) {
+    lds[(sl * 4 + i) * 64 + c] = a[i];
+    if (FMT == PV_REC_LANE_BF16) lds[((4 + sl) * 4 + i) * 64 + c] = b[i];
   }
+  pv_lds_barrier();
+  const float* la = lds + sl * 64 + c;                                 // [slice s][component sl][chunk c] at la[s * 256]
+  pv_rec_fin<ADAM>(Gr, ia, (la[0] + la[256]) + (la[512] + la[768]), qa, ad);
+  if (FMT == PV_REC_LANE_BF16) pv_rec_fin<ADAM>(Gr, ib, (la[1024] + la[1280]) + (la[1536] + la[1792]), qb, ad);
 }
-__device__ __forceinline__ void pv_sdec_fused_reduce_block(const float* __restrict__ part, int G_,
-                                                           float* __restrict__ Gr, const PvFusedOffsets& o, int cd,
-                                                           int dwo_slots, int block, f32x4 (*sm)[64], int fmt = PV_REC_ROWMAJOR,
-                                                           const PvRecAdam& ad = PvRecAdam{}) {
+// the flat-gradient index of element ei (< total) of a record read as plain floats, or -1 where the slot has no parameter (the
+// second coordinate column with one coordinate)
+__device__ __forceinline__ int pv_rec_elem_index(int ei, const PvFusedOffsets& o, int cd) {
+  const int HH = FD_H * FD_H;
+  if (ei < HH) return o.W1 + ei;
+  if (ei < 2 * HH) return o.W2 + (ei - HH);
+  const int k = ei - 2 * HH, seg = k / FD_H, j = k % FD_H;
+  if (seg == 0) return o.b1 + j;
+  if (seg == 1) return o.b2 + j;
+  if (seg == 2) return o.Wc + j * cd;
+  if (seg == 3) return cd == 2 ? (int)(o.Wc + j * 2 + 1) : -1;
+  if (seg == 4) return o.wo + j;
+  return o.bo;
+}
+template <bool ADAM>
+__device__ __forceinline__ void pv_sdec_fused_reduce_block_on(const float* __restrict__ part, int G_,
+                                                              float* __restrict__ Gr, const PvFusedOffsets& o, int cd,
+                                                              int dwo_slots, int block, f32x4 (*sm)[4][64], int fmt,
+                                                              const PvRecAdam& ad) {
   const int HH = FD_H * FD_H;
   const int total = 2 * HH + 5 * FD_H + 1;          // the record is padded well past this: whole float4s are readable
   const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
   if (fmt != PV_REC_ROWMAJOR && block < pv_fused_reduce_mat_blocks(fmt)) {
-    if (fmt == PV_REC_LANE_BF16) pv_sdec_fused_reduce_block_lane<PV_REC_LANE_BF16>(part, G_, Gr, o, block, sm, ad);
-    else pv_sdec_fused_reduce_block_lane<PV_REC_LANE_F32>(part, G_, Gr, o, block, sm, ad);
+    if (fmt == PV_REC_LANE_BF16) pv_sdec_fused_reduce_block_lane<PV_REC_LANE_BF16, ADAM>(part, G_, Gr, o, block, sm, ad);
+    else pv_sdec_fused_reduce_block_lane<PV_REC_LANE_F32, ADAM>(part, G_, Gr, o, block, sm, ad);
     return;
   }
   // (lane-native formats: the blocks behind the matrices' take the vectors, which sit at float 2*H*H in every format)
-  const int e = fmt != PV_REC_ROWMAJOR ? 2 * HH + ((block - pv_fused_reduce_mat_blocks(fmt)) * 64 + c) * 4 : (block * 64 + c) * 4;
+  // Thread (chunk c, slice sl) sums its slice of the four floats at e; thread t then finalises the ONE float e0 + t of the block's 256
+  // (the chunks sit in LDS as they were summed, [slice][chunk]: thread t loads word t of each slice)
+  const int e0 = fmt != PV_REC_ROWMAJOR ? 2 * HH + (block - pv_fused_reduce_mat_blocks(fmt)) * 256 : block * 256;
+  const int e = e0 + 4 * c, ef = e0 + (int)threadIdx.x;
+  const int idx = ef < total ? pv_rec_elem_index(ef, o, cd) : -1;
   const int per = (G_ + 3) / 4;
   const int w0 = sl * per, w1 = min(G_, w0 + per);
   f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (e < total) {
+  PvRecOps qf = {0.0f, 0.0f, 0.0f};
+  // (a thread without an element requests element 0's: a branch round the requests would cost the counted waits, as above)
+  const auto request = [&]() { qf = pv_rec_request<ADAM>(Gr, max(idx, 0), ad); };
+  if (e >= total) request();
+  else {
     const bool slots = dwo_slots && e >= 2 * HH + 4 * FD_H && e < 2 * HH + 5 * FD_H;   // d(wo): 8 per-wave slots
     if (slots) {
       for (int w = w0; w < w1; ++w) {
@@ -308,32 +383,23 @@ __device__ __forceinline__ void pv_sdec_fused_reduce_block(const float* __restri
         for (int k = 0; k < FD_WAVES; ++k) a += *reinterpret_cast<const f32x4*>(p8 + k * FD_H);
         v += a;
       }
+      request();
     } else {
-      const float* p = part + e;
-#pragma unroll PV_RED_UNROLL
-      for (int w = w0; w < w1; ++w) v += *reinterpret_cast<const f32x4*>(p + (int64_t)w * FD_REC);
+      pv_rec_stream<f32x4>(part + e, w0, w1, [&](const f32x4 x) { v += x; }, request);
     }
   }
-  sm[sl][c] = v;
-  __syncthreads();
-  if (sl != 0 || e >= total) return;
-  v = (sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ei = e + i;
-    if (ei >= total) break;
-    if (ei < HH) pv_rec_out(Gr, o.W1 + ei, v[i], ad);
-    else if (ei < 2 * HH) pv_rec_out(Gr, o.W2 + (ei - HH), v[i], ad);
-    else {
-      const int k = ei - 2 * HH, seg = k / FD_H, j = k % FD_H;
-      if (seg == 0) pv_rec_out(Gr, o.b1 + j, v[i], ad);
-      else if (seg == 1) pv_rec_out(Gr, o.b2 + j, v[i], ad);
-      else if (seg == 2) pv_rec_out(Gr, o.Wc + j * cd, v[i], ad);
-      else if (seg == 3) { if (cd == 2) pv_rec_out(Gr, o.Wc + j * 2 + 1, v[i], ad); }
-      else if (seg == 4) pv_rec_out(Gr, o.wo + j, v[i], ad);
-      else pv_rec_out(Gr, o.bo, v[i], ad);
-    }
-  }
+  sm[0][sl][c] = v;
+  pv_lds_barrier();
+  if (idx < 0) return;
+  const float* lf = reinterpret_cast<const float*>(sm) + threadIdx.x;
+  pv_rec_fin<ADAM>(Gr, idx, (lf[0] + lf[256]) + (lf[512] + lf[768]), qf, ad);
+}
+__device__ __forceinline__ void pv_sdec_fused_reduce_block(const float* __restrict__ part, int G_,
+                                                           float* __restrict__ Gr, const PvFusedOffsets& o, int cd,
+                                                           int dwo_slots, int block, f32x4 (*sm)[4][64], int fmt = PV_REC_ROWMAJOR,
+                                                           const PvRecAdam& ad = PvRecAdam{}) {
+  if (ad.on) pv_sdec_fused_reduce_block_on<true>(part, G_, Gr, o, cd, dwo_slots, block, sm, fmt, ad);
+  else pv_sdec_fused_reduce_block_on<false>(part, G_, Gr, o, cd, dwo_slots, block, sm, fmt, ad);
 }
 
 

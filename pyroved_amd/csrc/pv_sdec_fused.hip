@@ -292,7 +292,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_kernel(PvFused f)
 __global__ __launch_bounds__(256) void pv_sdec_fused_reduce_kernel(const float* __restrict__ part, int G_,
                                                                    float* __restrict__ Gr, PvFusedOffsets o, int cd,
                                                                    int dwo_slots) {
-  __shared__ f32x4 sm[4][64];
+  __shared__ PvRedLds sm;
   pv_sdec_fused_reduce_block(part, G_, Gr, o, cd, dwo_slots, blockIdx.x, sm);
 }
 
