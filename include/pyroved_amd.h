@@ -465,6 +465,26 @@ int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan);
 int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream);
 int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* stream);   /* + Adam, as pv_ivae_step */
 
+/* ---- (v17, new entry points, no layout change) per-IMAGE observation weights (masks) of the likelihood -----------------------
+ * A mask that differs from image to image: sparse or compressed-sensing scans, windows cropped at the edge of a scan, per-frame
+ * saturated or cosmic-ray pixels, stacks merged from detectors with different dead regions, per-frame exposure maps,
+ *   loss = -( sum_b sum_i w_bi log p(x_bi | z_b)  +  beta sum_b [ log p(z_b) - log q(z_b | x_b) ] )       (PV_KL_SAMPLED; the
+ *   analytic KL form likewise), w_bi >= 0; an image whose weights are all zero contributes its KL terms only.
+ *   image_w   DEVICE pointer to batch * n_pix floats in the layout of plan->x (images x positions x channels, channel-last): one
+ *             per observed value of every image.  The weight multiplies the whole log_prob, normalisers included, exactly as
+ *             pixel_w does above.  The caller guarantees w >= 0 and finite; nothing is checked on the device.  The buffer is the
+ *             caller's: no workspace is added for it.
+ *   plan      the one-particle step's; loc (optional) is NOT weighted, and the encoder sees x as given — x must be finite
+ *             everywhere, also where w == 0.
+ *   ws        sized by pv_ivae_weighted_workspace_bytes.
+ * image_w == NULL forwards to pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
+ * Kernels, scope and PV_EINVAL are those of pv_ivae_weighted_*: every channel count has a per-image instance of the fused f32
+ * kernel, so pv_ivae_weighted_workspace_bytes and pv_ivae_weighted_uses_fused answer for these calls too.  The kernels read the
+ * weight at the index they read x at; with the shared weights repeated per image the layer-by-layer kernels give the bits of
+ * pv_ivae_weighted_* (the fused kernel's instances differ: DESIGN.md 4.15). */
+int pv_ivae_weighted_images_loss_and_grads(const pv_ivae_plan* plan, const float* image_w, int want_grads, void* stream);
+int pv_ivae_weighted_images_step(const pv_ivae_plan* plan, const float* image_w, void* stream);   /* + Adam */
+
 /* ---- (v16) the data-parallel step with its collective INSIDE the library --------------------------------------------------
  * The reference has no distributed code.  What is sharded is trainers/svi.py:104-113 (`self.svi.step(x)` per
  * minibatch): the loss is a SUM over the data plate (models/ivae.py:177,215), so every replica computes its contiguous slice of

@@ -165,6 +165,9 @@ SIGNATURES = {
     "pv_ivae_weighted_uses_fused": (C.c_int, [C.POINTER(pv_ivae_plan)]),
     "pv_ivae_weighted_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p, C.c_int, C.c_void_p]),
     "pv_ivae_weighted_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p, C.c_void_p]),
+    # one weight per observation of every image (v17, added without a layout change)
+    "pv_ivae_weighted_images_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p, C.c_int, C.c_void_p]),
+    "pv_ivae_weighted_images_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p, C.c_void_p]),
     "pv_dist_load": (C.c_int, [C.c_char_p]),
     "pv_dist_library": (C.c_char_p, []),
     "pv_dist_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void pv_out_lik_kernel(PvOutLik p) {
       locv = pr;
     }
     if (p.pw) {                                          // per-observation weight (pv_ivae_weighted_*)
-      const float w = p.pw[row % p.N];
+      const float w = p.pw[p.pw_img ? row : row % p.N];   // (pw_img: one weight per observation of every sample)
       ll *= w;
       dlda *= w;
     }
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(256) void pv_out_lik_mc_kernel(PvOutLik p) {
       pv_lik_any(a, x, p.lik, p.sigmoid_out, p.sig, ll, dlda, locv);
       if (p.loc) p.loc[row * C + lane] = locv;
       if (p.pw) {                                        // per-observation weight (pv_ivae_weighted_*)
-        const float w = p.pw[(row % p.N) * C + lane];
+        const float w = p.pw[(p.pw_img ? row : row % p.N) * C + lane];
         ll *= w;
         dlda *= w;
       }
@@ -1364,7 +1364,7 @@ __global__ void pv_lik_elem_kernel(const float* __restrict__ a, const float* __r
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
     float ll, d, lv;
     pv_lik_one(a[e], x[e], lik, sigmoid_out, sig, ll, d, lv);
-    if (pw) { const float w = pw[e % per]; ll *= w; d *= w; }
+    if (pw) { const float w = pw[per > 0 ? e % per : e]; ll *= w; d *= w; }   // (per == 0: one weight per element, pw (M))
     if (loc) loc[e] = lv;
     if (llrow) llrow[e] = ll;
     if (dlda) dlda[e] = d;
@@ -1399,7 +1399,7 @@ __global__ void pv_lik_elem_poisson_kernel(const float* __restrict__ a, const fl
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
     float ll, d, lv;
     pv_poisson_one(a[e], x[e], ll, d, lv);
-    if (pw) { const float w = pw[e % per]; ll *= w; d *= w; }
+    if (pw) { const float w = pw[per > 0 ? e % per : e]; ll *= w; d *= w; }   // (per == 0: one weight per element, pw (M))
     if (loc) loc[e] = lv;
     if (llrow) llrow[e] = ll;
     if (dlda) dlda[e] = d;
@@ -1436,11 +1436,12 @@ int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik,
 }
 
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s, const float* pw, int64_t per) {
+                float* llrow, float* dlda, hipStream_t s, const float* pw, int64_t per, bool pw_img) {
   int blocks = (int)((M + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) return 0;
-  if (pw && per < 1) return PV_EINVAL;
+  if (pw && !pw_img && per < 1) return PV_EINVAL;
+  if (pw_img) per = 0;                                   // (the kernels' sign for "one weight per element")
   if (lik == PV_LIK_POISSON_LOG) {
     hipLaunchKernelGGL(pv_lik_elem_poisson_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, loc, llrow, dlda, pw, per);
   } else {
@@ -1467,7 +1468,8 @@ __device__ __forceinline__ double pl_block_sum(double v, double* sm /* blockDim.
   return sm[0];
 }
 // part[blockIdx.x] = sum of lgamma(x[i] + 1) over the block's contiguous chunk [blockIdx.x * per, min(n, (blockIdx.x + 1) * per))
-// (pw != null: every term times the observation's weight pw[i % wper], wper = observations per sample)
+// (pw != null: every term times the observation's weight pw[i % wper], wper = observations per sample — or, wper == 0, pw[i]:
+// one weight per observation of every sample)
 __global__ __launch_bounds__(256) void pv_poisson_lognorm_part_kernel(const float* __restrict__ x, int64_t n, int64_t per,
                                                                       double* __restrict__ part, const float* __restrict__ pw,
                                                                       int64_t wper) {
@@ -1476,7 +1478,7 @@ __global__ __launch_bounds__(256) void pv_poisson_lognorm_part_kernel(const floa
   const int64_t end = beg + per < n ? beg + per : n;
   double acc = 0.0;
   if (pw) {
-    for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)pw[i % wper] * (double)lgammaf(x[i] + 1.0f);
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)pw[wper > 0 ? i % wper : i] * (double)lgammaf(x[i] + 1.0f);
   } else
   for (int64_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)lgammaf(x[i] + 1.0f);
   const double c = pl_block_sum(acc, sm);
@@ -1491,8 +1493,10 @@ __global__ __launch_bounds__(PV_POISSON_PARTS) void pv_poisson_lognorm_kernel(co
     scalars[0] = (float)((double)scalars[0] + c);
   }
 }
-int pv_poisson_lognorm(const float* x, int64_t n, double* part, float* scalars, hipStream_t s, const float* pw, int64_t wper) {
-  if (!x || !part || !scalars || n < 0 || (pw && wper < 1)) return PV_EINVAL;
+int pv_poisson_lognorm(const float* x, int64_t n, double* part, float* scalars, hipStream_t s, const float* pw, int64_t wper,
+                       bool pw_img) {
+  if (!x || !part || !scalars || n < 0 || (pw && !pw_img && wper < 1)) return PV_EINVAL;
+  if (pw_img) wper = 0;                                  // (the kernel's sign for "one weight per observation of every sample")
   int64_t nparts = (n + PL_CHUNK - 1) / PL_CHUNK;
   if (nparts < 1) nparts = 1;
   if (nparts > PV_POISSON_PARTS) nparts = PV_POISSON_PARTS;

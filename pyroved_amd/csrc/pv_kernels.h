@@ -66,6 +66,7 @@ struct PvOutLik {
   int64_t xmod;          // > 0: observations are x[row % xmod] (jiVAE: the K decoder passes score the same B*N pixels)
   const float* pw;       // (N * C) per-observation weights shared by all samples (pv_ivae_weighted_*) or null: ll and dL/da of
                          // channel c of row `row` are multiplied by pw[(row % N) * C + c]; loc is not.  Needs N
+  int pw_img;            // != 0 (pv_ivae_weighted_images_*): pw is (M * C), one weight per observation of every sample — pw[row * C + c]
 };
 int pv_out_lik(const PvOutLik& p, hipStream_t s);
 // the same with C = 2 .. PV_MAX_CHANNELS outputs per row (a spatial decoder's channels): wo (C, H), bo (C), x and loc (M, C)
@@ -235,10 +236,11 @@ int pv_rec_wgrad(const float* part, int grid, float* G, const PvFusedOffsets& o,
 // pv_lik_elem + pv_segsum in one launch (one workgroup per sample; same summation order)
 // pw (both; null: no weights, the same bits as before the argument existed): per-observation weights shared by all samples —
 // ll and dL/da of element i of a sample are multiplied by pw[i]; loc is not.  pv_lik_elem: element e is i = e % per of its sample
+// (pw_img, pv_ivae_weighted_images_*: pw is (M), one weight per element of every sample — element e is multiplied by pw[e])
 int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik, int sigmoid_out, float sig, float* loc,
                 float* dlda, float* llb, hipStream_t s, const float* pw = nullptr);
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s, const float* pw = nullptr, int64_t per = 0);
+                float* llrow, float* dlda, hipStream_t s, const float* pw = nullptr, int64_t per = 0, bool pw_img = false);
 
 // The Poisson (log link) likelihood's data-only normaliser C = sum_i lgamma(x[i] + 1) over the call's n observations, applied to the
 // finished scalars: scalars[1] -= C, scalars[0] += C.  Two launches: up to PV_POISSON_PARTS workgroups each sum a contiguous chunk
@@ -246,9 +248,9 @@ int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_
 // bits every call; must run after the launch that finishes the scalars and before anything reads them.
 #define PV_POISSON_PARTS 1024
 // pw != null (pv_ivae_weighted_*): the weighted normaliser C = sum_i pw[i % per] lgamma(x[i] + 1), per = observations per sample —
-// the same two launches, the same fixed order, the same partial sums
+// the same two launches, the same fixed order, the same partial sums (pw_img: pw is (n), C = sum_i pw[i] lgamma(x[i] + 1))
 int pv_poisson_lognorm(const float* x, int64_t n, double* part /* PV_POISSON_PARTS */, float* scalars, hipStream_t s,
-                       const float* pw = nullptr, int64_t per = 0);
+                       const float* pw = nullptr, int64_t per = 0, bool pw_img = false);
 // per image instead: llkb[k*B + b] -= sum_n lgamma(x[b*N + n] + 1) for k < K (the sampled-class jiVAE objective)
 int pv_poisson_lognorm_rows(const float* x, int64_t B, int64_t N, float* llkb, int K, hipStream_t s);
 

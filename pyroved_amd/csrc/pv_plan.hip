@@ -69,6 +69,7 @@ struct Layout {
   // per-observation weights of the likelihood (pv_ivae_weighted_*): (n_pix) floats shared by all images, or null.  Like P, the
   // pointer travels here, set by the entry point after carve(); the layout itself does not depend on it
   const float* pw;
+  bool pw_img;              // pv_ivae_weighted_images_*: pw is (batch * n_pix), one weight per observation of every image (the layout of x)
   int64_t total;
 };
 
@@ -151,7 +152,7 @@ bool valid_plan(const pv_ivae_plan* p) {
 void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1,
            bool renyi = false) {
   Carver c{base, 0};
-  L.pw = nullptr;
+  L.pw = nullptr; L.pw_img = false;
   L.P = inference_only ? 1 : P;
   L.renyi = renyi && L.P > 1; L.r_alpha = 0.0f; L.r_wout = nullptr;
   // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
@@ -1036,7 +1037,8 @@ int fused_decoder_launch(FusedStep& st) {
     PvFused f = st.f;
     f.wimg = nullptr; f.park = nullptr;
     if (st.L.pw) f.pw = st.L.pw;
-    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s, st.L.pw != nullptr));
+    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s,
+                                   !st.L.pw ? 0 : st.L.pw_img ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED));
     if (st.grads && plan_C(p) > 1) PV_TRY(pv_sdec_fused_mc_reduce_out(st.L.f_part, st.L.f_grid, p->grads, p->out.w_off, p->out.b_off, (int)plan_C(p), st.s));
   }
   else PV_TRY(pv_sdec_fused_launch(st.f, st.L.f_grid, st.grads, st.s));
@@ -1175,7 +1177,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     o.dpre = (want_grads && !renyi) ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
-    o.pw = L.pw;
+    o.pw = L.pw; o.pw_img = L.pw_img ? 1 : 0;
     PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
   } else {
     // oth <- dL/dlogits (R, N); jiVAE: one pass per enumerated class against the same observations, rows then
@@ -1184,7 +1186,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
                          p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s,
-                         L.pw, N));
+                         L.pw, N, L.pw_img));
     if (reps > 1 && want_grads && !renyi) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
@@ -1458,13 +1460,15 @@ static void set_renyi(Layout& L, const RenyiArgs* rn) {
 // its score-function term needs the per-image value, which went into llkb in front of pv_jiv_combine_sampled (nothing to do here).
 static int poisson_lognorm(const pv_ivae_plan* plan, const Layout& L, hipStream_t s) {
   if (plan->lik != PV_LIK_POISSON_LOG || (plan_K(plan) > 0 && plan->class_onehot)) return 0;
-  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s, L.pw, plan->n_pix);
+  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s, L.pw, plan->n_pix,
+                            L.pw_img);
 }
 
 // P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
-// pw: per-observation weights (pv_ivae_weighted_*: `plan` is then the routed copy, weighted_route) or null
+// pw: per-observation weights (pv_ivae_weighted_*: `plan` is then the routed copy, weighted_route) or null; pw_img: one per
+// observation of every image (pv_ivae_weighted_images_*)
 static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr,
-                               const float* pw = nullptr) {
+                               const float* pw = nullptr, bool pw_img = false) {
   if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
   if (!valid_plan(plan) || !plan->params || !plan->x || !plan->eps || !plan->scalars || !plan->ws) return PV_EINVAL;
   if (want_grads && !plan->grads) return PV_EINVAL;
@@ -1474,7 +1478,7 @@ static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, 
   Layout L;
   carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
   set_renyi(L, rn);
-  L.pw = pw;
+  L.pw = pw; L.pw_img = pw && pw_img;
   if (plan->ws_bytes < L.total) return PV_EWS;
   hipStream_t s = (hipStream_t)stream;
   // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
@@ -1538,7 +1542,8 @@ extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, 
 // SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
 // gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
 // pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
-static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr, const float* pw = nullptr) {
+static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr, const float* pw = nullptr,
+                     bool pw_img = false) {
   if (P < 1 || (P > 1 && !(valid_plan(plan) && particles_supported(plan)))) return PV_EINVAL;
   if (plan && !plan->ext_decoder && valid_plan(plan) && plan->params && plan->x && plan->eps && plan->scalars && plan->ws &&
       plan->grads && plan->adam_m && plan->adam_v && plan->adam_step >= 1 && plan->n_params > 0 &&
@@ -1549,7 +1554,7 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiA
     Layout L;
     carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
     set_renyi(L, rn);
-    L.pw = pw;
+    L.pw = pw; L.pw_img = pw && pw_img;
     if (plan->ws_bytes < L.total) return PV_EWS;
     if (L.fused && (L.enc_compact || L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
       const double bc1 = 1.0 - pow((double)plan->adam_beta1, (double)plan->adam_step);
@@ -1564,7 +1569,7 @@ static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiA
                           plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
     }
   }
-  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn, pw));
+  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn, pw, pw_img));
   return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
                       plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
 }
@@ -1584,10 +1589,11 @@ static bool weighted_scope(const pv_ivae_plan* p) {
 // weighted instances of the fused f32 kernel take the decoder (one channel asked with fused 1 or 2: fused = 2 promises fp32-class
 // results and the f32 kernel delivers them; several channels as the unweighted plan decides: PV_PLAN_FUSED_CHANNELS and fused == 1),
 // 0 (the layer-by-layer kernels) everywhere else.  The fp16-piece / bf16 decoder kernels have no weighted form
-static pv_ivae_plan weighted_route(const pv_ivae_plan* p) {
+// (per_image: pv_ivae_weighted_images_* — the same routing over the per-image instances' list, which today is the same list)
+static pv_ivae_plan weighted_route(const pv_ivae_plan* p, bool per_image = false) {
   pv_ivae_plan q = *p;
   if (q.fused == 2 && q.coord_dim > 0 && q.out.out_dim == 1) q.fused = 1;
-  if (!(q.fused == 1 && pv_sdec_fused_mc_weighted_supported(&q) && plan_fused_ok(&q))) q.fused = 0;
+  if (!(q.fused == 1 && pv_sdec_fused_mc_weighted_supported(&q, per_image) && plan_fused_ok(&q))) q.fused = 0;
   return q;
 }
 extern "C" int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan) {
@@ -1615,6 +1621,26 @@ extern "C" int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixe
   if (!weighted_scope(plan)) return PV_EINVAL;
   const pv_ivae_plan q = weighted_route(plan);
   return step_impl(&q, 1, stream, nullptr, pixel_w);
+}
+
+// ---- one weight per observation of every image (v17, added without a layout change; include/pyroved_amd.h) ----
+// loss = -( sum_b sum_i w_bi log p(x_bi | z_b) + beta sum_b [...] ), image_w (batch * n_pix) in the layout of plan->x.  Scope,
+// routing and workspace are pv_ivae_weighted_*'s (every per-image instance of the fused f32 kernel exists, so
+// pv_ivae_weighted_workspace_bytes / pv_ivae_weighted_uses_fused answer for these calls too); the kernels read the weight at the
+// index they read x at
+extern "C" int pv_ivae_weighted_images_loss_and_grads(const pv_ivae_plan* plan, const float* image_w, int want_grads, void* stream) {
+  if (!image_w) return pv_ivae_loss_and_grads(plan, want_grads, stream);
+  PV_RANGE("pv_ivae_weighted_images_loss_and_grads");
+  if (!weighted_scope(plan)) return PV_EINVAL;
+  const pv_ivae_plan q = weighted_route(plan, true);
+  return loss_and_grads_impl(&q, 1, want_grads, stream, nullptr, image_w, true);
+}
+extern "C" int pv_ivae_weighted_images_step(const pv_ivae_plan* plan, const float* image_w, void* stream) {
+  if (!image_w) return pv_ivae_step(plan, stream);
+  PV_RANGE("pv_ivae_weighted_images_step");
+  if (!weighted_scope(plan)) return PV_EINVAL;
+  const pv_ivae_plan q = weighted_route(plan, true);
+  return step_impl(&q, 1, stream, nullptr, image_w, true);
 }
 
 // ---- the multi-particle ELBO (v17, added without a layout change; include/pyroved_amd.h) ----

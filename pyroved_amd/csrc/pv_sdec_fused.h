@@ -44,8 +44,9 @@ struct PvFused {
   int64_t x_units;       // > 0: the observations repeat every x_units units (jiVAE: B*N/16; x is (B, N)); 0: x is (M)
   union {
   void* wimg;            // bf16x3 kernel only: FB_WIMG_BYTES of pre-split weight images (pv_sdec_fused_bf16_prep)
-  const float* pw;       // weighted launches of pv_sdec_fused_mc.hip only (pv_sdec_fused_mc_launch(..., weighted = true)): (N * C)
-                         //   per-observation weights of the likelihood, shared by all samples (pv_ivae_weighted_*).  The f32 kernels
+  const float* pw;       // weighted launches of pv_sdec_fused_mc.hip only (pv_sdec_fused_mc_launch(..., weighted = 1 or 2)): (N * C)
+                         //   per-observation weights of the likelihood, shared by all samples (pv_ivae_weighted_*), or (M * C), one per
+                         //   observation of every sample (weighted = 2, pv_ivae_weighted_images_*).  The f32 kernels
                          //   have no weight images, so the two share the slot: the struct keeps its size and every field its offset —
                          //   and with them every kernel that takes a PvFused its argument layout, hidden arguments included
   };
@@ -151,10 +152,15 @@ bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p);
 // PV_EINVAL for sw, x_units, part_rs, dhz_out, dzc_out or wimg set, or a C without an instance.  f.ablate is ignored.
 // weighted: the weighted instances (C = 1 .. PV_MAX_CHANNELS; C = 1 exists in this form only): f.pw (the slot of wimg) must be set;
 // ll and dL/da of observation (n, c) of every sample are multiplied by pw[n * C + c]; loc is not.  The record is the unweighted launch's
-int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s, bool weighted = false);
+// weighted == PV_FDM_W_IMAGES (pv_ivae_weighted_images_*): f.pw is (M * C), one weight per observation of every sample in the
+// layout of x — observation (row, c) is multiplied by pw[row * C + c]; the same instances list, everything else as PV_FDM_W_SHARED
+#define PV_FDM_W_SHARED 1
+#define PV_FDM_W_IMAGES 2
+int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s, int weighted = 0);
 // true when a WEIGHTED step of the plan (pv_ivae_weighted_*) runs that kernel: fused == 1, the trunk's architecture, positions a
 // multiple of 16, a weighted instance for the channel count — one channel, or 2 .. PV_MAX_CHANNELS with PV_PLAN_FUSED_CHANNELS
-bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p);
+// (per_image: the instances of pv_ivae_weighted_images_*)
+bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p, bool per_image = false);
 // sums the records' entries of channels 1 .. C-1 — (C - 1) (H + 1) outputs, each over the `grid` records in the shared reduction's
 // fixed order (four slices of ascending workgroups) — into G + wo_off + c H and G + bo_off + c; channel 0 is the shared reduction's
 int pv_sdec_fused_mc_reduce_out(const float* part, int grid, float* G, int64_t wo_off, int64_t bo_off, int C, hipStream_t s);

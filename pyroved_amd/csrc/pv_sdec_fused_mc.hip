@@ -1,7 +1,8 @@
 // pv_sdec_fused_mc.hip — the fused persistent forward+backward kernel of the spatial decoder (pv_sdec_fused.hip) for a decoder
 // with C = 2 .. 8 output channels per grid position (iVAE(..., channels=C); decoder.out = Linear(128, C)): a sibling of
 // pv_sdec_fused_kernel on the same f32 matrix instructions.  The plan asks for it with PV_PLAN_FUSED_CHANNELS and fused == 1.
-// Its WEIGHTED instances (C = 1 .. 8, PvFused::pw: per-observation weights of the likelihood) run the steps of pv_ivae_weighted_*.
+// Its WEIGHTED instances (C = 1 .. 8, PvFused::pw: per-observation weights of the likelihood) run the steps of pv_ivae_weighted_*:
+// WEIGHTED == 1 with weights shared by all images, WEIGHTED == 2 with one weight per observation of every image (pv_ivae_weighted_images_*).
 //
 // Unchanged from the one-channel kernel (pv_sdec_fused_f32.h holds the shared streams): the tile loop, the transposed layers, the
 // three register tiles, the two weight-gradient exchanges, the coordinate layer's backward and flush_hz.  A ROW is still one grid
@@ -58,10 +59,12 @@ __device__ __forceinline__ void fdm_pixel_lik(const PvFused& f, float a, float x
 
 // WEIGHTED (pv_ivae_weighted_*): observation (n, c) of every sample carries the weight f.pw[n * C + c] — ll and dL/da are multiplied
 // by it where they are formed, loc is not; everything downstream is the same code.  C = 1 exists in this form only (the unweighted
-// one-channel kernel is pv_sdec_fused_kernel): channel 0's d(wo) / d(bo) sit where the shared reduction expects them
-template <bool GRADS, int C, bool WEIGHTED>
+// one-channel kernel is pv_sdec_fused_kernel): channel 0's d(wo) / d(bo) sit where the shared reduction expects them.
+// WEIGHTED: 0 none, 1 (PV_FDM_W_SHARED) shared by all samples, 2 (PV_FDM_W_IMAGES, pv_ivae_weighted_images_*) f.pw is (M * C), one
+// weight per observation of every sample, read at the index x is read at: f.pw[row * C + c]
+template <bool GRADS, int C, int WEIGHTED>
 __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_mc_kernel(PvFused f) {
-  static_assert(C >= (WEIGHTED ? 1 : 2) && C <= 8 && C * FD_H <= FD_WAVES * FD_H && FD_UNIT * C <= FD_H && 40 + C <= 64, "LDS regions");
+  static_assert(WEIGHTED >= 0 && WEIGHTED <= 2 && C >= (WEIGHTED ? 1 : 2) && C <= 8 && C * FD_H <= FD_WAVES * FD_H && FD_UNIT * C <= FD_H && 40 + C <= 64, "LDS regions");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // uniform: unit, sample and every 16 * wave offset stay scalar
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_mc_kernel(PvFused
         }
         const float a = fd_sum_q(part) + sm[OFF_BO + c];
         const float xv = f.x ? f.x[row * C + c] : 0.0f;
-        const float pwv = WEIGHTED ? f.pw[n * C + c] : 1.0f;
+        const float pwv = WEIGHTED == 2 ? f.pw[row * C + c] : WEIGHTED == 1 ? f.pw[n * C + c] : 1.0f;
         float ll, locv;
         fdm_pixel_lik(f, a, xv, ll, dlda[c], locv);
         if (WEIGHTED) { ll *= pwv; dlda[c] *= pwv; }
@@ -384,8 +387,9 @@ int pv_sdec_fused_mc_reduce_out(const float* part, int grid, float* G, int64_t w
 // ---- host side -----------------------------------------------------------------------------------------
 // every C of 2 .. PV_MAX_CHANNELS has an instance (no spills under __launch_bounds__(512, 2): profiles/multichannel_fused_resource_usage.txt)
 // weighted: C = 1 .. PV_MAX_CHANNELS (profiles/pixel_weights_resource_usage.txt: none of them spills, so none is refused here —
-// a C whose weighted instance spilled would be taken out of this list and run the layered kernels)
-static bool fdm_has_instance(int C, bool weighted = false) { return C >= (weighted ? 1 : 2) && C <= 8; }
+// a C whose weighted instance spilled would be taken out of this list and run the layered kernels); per image (weighted == 2,
+// PV_FDM_W_IMAGES): the same list, profiles/image_weights_resource_usage.txt
+static bool fdm_has_instance(int C, int weighted = 0) { return weighted >= 0 && weighted <= 2 && C >= (weighted ? 1 : 2) && C <= 8; }
 
 bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p) {
   if (!p || !(p->flags & PV_PLAN_FUSED_CHANNELS) || p->fused != 1) return false;
@@ -395,15 +399,15 @@ bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p) {
   return (p->n_pix / C) % FD_UNIT == 0;
 }
 
-bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p) {
+bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p, bool per_image) {
   if (!p || p->fused != 1 || !pv_sdec_fused_trunk_supported(p)) return false;
   const int C = p->out.out_dim;
-  if (C < 1 || C > PV_MAX_CHANNELS || !fdm_has_instance(C, true) || p->n_pix % C != 0) return false;
+  if (C < 1 || C > PV_MAX_CHANNELS || !fdm_has_instance(C, per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED) || p->n_pix % C != 0) return false;
   if (C > 1 && !(p->flags & PV_PLAN_FUSED_CHANNELS)) return false;
   return (p->n_pix / C) % FD_UNIT == 0;
 }
 
-template <int C, bool W>
+template <int C, int W>
 static int fdm_launch(const PvFused& f, int grid, bool grads, hipStream_t s) {
   const size_t lds = FD_LDS_FLOATS * sizeof(float);
   if (grads) {
@@ -417,33 +421,37 @@ static int fdm_launch(const PvFused& f, int grid, bool grads, hipStream_t s) {
   return 0;
 }
 
-int pv_sdec_fused_mc_launch(const PvFused& f_in, int C, int grid, bool grads, hipStream_t s, bool w) {
+template <int W>
+static int fdm_launch_weighted(const PvFused& f, int C, int grid, bool grads, hipStream_t s) {
+  switch (C) {
+    case 1: return fdm_launch<1, W>(f, grid, grads, s);
+    case 2: return fdm_launch<2, W>(f, grid, grads, s);
+    case 3: return fdm_launch<3, W>(f, grid, grads, s);
+    case 4: return fdm_launch<4, W>(f, grid, grads, s);
+    case 5: return fdm_launch<5, W>(f, grid, grads, s);
+    case 6: return fdm_launch<6, W>(f, grid, grads, s);
+    case 7: return fdm_launch<7, W>(f, grid, grads, s);
+    case 8: return fdm_launch<8, W>(f, grid, grads, s);
+  }
+  return PV_EINVAL;
+}
+
+int pv_sdec_fused_mc_launch(const PvFused& f_in, int C, int grid, bool grads, hipStream_t s, int w) {
   if (f_in.sw || f_in.x_units != 0 || f_in.part_rs || f_in.dhz_out || f_in.dzc_out) return PV_EINVAL;
   if (w ? !f_in.pw : f_in.wimg != nullptr) return PV_EINVAL;         // (one slot: the weights of a weighted launch, else nothing)
   if (!fdm_has_instance(C, w) || grid < 1 || f_in.N % FD_UNIT != 0 || f_in.units * FD_UNIT != f_in.M) return PV_EINVAL;
   PvFused f = f_in;
   f.ablate = 0;
-  if (!w) {
-    switch (C) {
-      case 2: return fdm_launch<2, false>(f, grid, grads, s);
-      case 3: return fdm_launch<3, false>(f, grid, grads, s);
-      case 4: return fdm_launch<4, false>(f, grid, grads, s);
-      case 5: return fdm_launch<5, false>(f, grid, grads, s);
-      case 6: return fdm_launch<6, false>(f, grid, grads, s);
-      case 7: return fdm_launch<7, false>(f, grid, grads, s);
-      case 8: return fdm_launch<8, false>(f, grid, grads, s);
-    }
-    return PV_EINVAL;
-  }
+  if (w == PV_FDM_W_IMAGES) return fdm_launch_weighted<PV_FDM_W_IMAGES>(f, C, grid, grads, s);
+  if (w == PV_FDM_W_SHARED) return fdm_launch_weighted<PV_FDM_W_SHARED>(f, C, grid, grads, s);
   switch (C) {
-    case 1: return fdm_launch<1, true>(f, grid, grads, s);
-    case 2: return fdm_launch<2, true>(f, grid, grads, s);
-    case 3: return fdm_launch<3, true>(f, grid, grads, s);
-    case 4: return fdm_launch<4, true>(f, grid, grads, s);
-    case 5: return fdm_launch<5, true>(f, grid, grads, s);
-    case 6: return fdm_launch<6, true>(f, grid, grads, s);
-    case 7: return fdm_launch<7, true>(f, grid, grads, s);
-    case 8: return fdm_launch<8, true>(f, grid, grads, s);
+    case 2: return fdm_launch<2, 0>(f, grid, grads, s);
+    case 3: return fdm_launch<3, 0>(f, grid, grads, s);
+    case 4: return fdm_launch<4, 0>(f, grid, grads, s);
+    case 5: return fdm_launch<5, 0>(f, grid, grads, s);
+    case 6: return fdm_launch<6, 0>(f, grid, grads, s);
+    case 7: return fdm_launch<7, 0>(f, grid, grads, s);
+    case 8: return fdm_launch<8, 0>(f, grid, grads, s);
   }
   return PV_EINVAL;
 }

@@ -55,6 +55,16 @@ def _renyi_alpha(a) -> Optional[float]:
     return a
 
 
+def _image_weights_flag(v) -> bool:
+    """image_weights of engine() / configure(): a switch — the weights themselves come with every loss_and_grads call."""
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError("image_weights must be True or False here: the weights of a batch go to loss_and_grads(..., "
+                         "image_weights=w) (got %s)" % type(v).__name__)
+    return v
+
+
 def _linears(seq: nn.Sequential) -> List[nn.Linear]:
     return [m for m in seq if isinstance(m, nn.Linear)]
 
@@ -69,7 +79,13 @@ class IVAEEngine:
     pixel_weights=w: one weight >= 0 per observed value (a mask, a gain map), shared by all images, multiplies every log p(x_bi | z_b)
     of the training step, evaluate and elbo_terms (pv_ivae_weighted_*; encode / decode never see it).  models.iVAE with its own
     fully connected networks, the one-particle ELBO, fused = 0, 1 or 2.  A one-channel model with fused = 1 or 2 then runs the
-    weighted fused f32 decoder kernel (plan.fused = 1), not the fp16-piece kernel of the unweighted fused = 2 step."""
+    weighted fused f32 decoder kernel (plan.fused = 1), not the fp16-piece kernel of the unweighted fused = 2 step.
+    image_weights=True: every call of loss_and_grads (and model.elbo_terms) brings one weight >= 0 per observed value of EVERY image
+    of its batch, loss_and_grads(x, eps, ..., image_weights=w) with w of shape (b, *data_dim), (b, *data_dim, C) or (b, n_pix) — masks
+    that differ from image to image: sparse scans, windows cropped at the edge of the field of view, per-frame saturated pixels or
+    exposure maps (pv_ivae_weighted_images_*).  Scope, routing and kernels are those of pixel_weights; the two combine (the
+    library gets their product).  The encoder sees x as given: x must be finite also where w = 0 (utils.weights_from_nan).  Only
+    shape and dtype are checked per call — finite, >= 0 values are the caller's promise (SVItrainer checks them on the host)."""
     supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
@@ -92,10 +108,14 @@ class IVAEEngine:
                                      # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
     pixel_weights = None             # None, or the per-observation weights of the likelihood: one contiguous float32 tensor of n_pix
                                      # values (positions x channels, channel-last), on the device once the engine is bound — pv_ivae_weighted_*
+    image_weights = False            # True: every loss_and_grads call takes image_weights=w, one weight per observed value of every
+                                     # image of the batch — pv_ivae_weighted_images_*
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
-                 particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None):
+                 particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None,
+                 image_weights: bool = False):
         self.model = model
+        self.image_weights = _image_weights_flag(image_weights)
         self.fused_channels = bool(fused_channels)
         self.kl = _kl_name(kl)
         self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
@@ -299,7 +319,7 @@ class IVAEEngine:
         layered or the bf16-class fused decoder path; renyi with the sampled KL form only."""
         # (the native one-call DP step is the one-particle, single-channel ELBO's)
         self.supports_dp_step = (type(self).supports_dp_step and self.particles == 1 and self.renyi is None
-                                 and getattr(self, "C", 1) == 1 and getattr(self, "pixel_weights", None) is None)
+                                 and getattr(self, "C", 1) == 1 and not self._weighted())
         if self.particles == 1 and self.renyi is None:
             return
         what = "particles > 1" if self.renyi is None else "renyi"
@@ -364,37 +384,69 @@ class IVAEEngine:
         dev = getattr(self, "device", None)
         return t.to(dev) if dev is not None else t.clone()
 
+    def _weighted(self) -> bool:
+        """Whether the step runs the weighted entry points (pixel_weights, image_weights or both)."""
+        return getattr(self, "pixel_weights", None) is not None or bool(getattr(self, "image_weights", False))
+
     def _check_pixel_weights(self):
-        """pixel_weights (pv_ivae_weighted_*): the one-particle ELBO of models.iVAE with its own fully connected networks, on
-        fused = 0, 1 or 2."""
-        if getattr(self, "pixel_weights", None) is None:
+        """pixel_weights (pv_ivae_weighted_*) and image_weights (pv_ivae_weighted_images_*): the one-particle ELBO of models.iVAE
+        with its own fully connected networks, on fused = 0, 1 or 2."""
+        if not self._weighted():
             return
+        kw = " / ".join(k for k, on in (("pixel_weights", getattr(self, "pixel_weights", None) is not None),
+                                        ("image_weights", getattr(self, "image_weights", False))) if on)
         if type(self) is not IVAEEngine or getattr(self, "K", 0) > 0:
-            raise ValueError("pixel_weights is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
+            raise ValueError("%s is implemented for models.iVAE only (not for %s)" % (kw, type(self.model).__name__))
         if self.conv_enc or self.ext_enc or self.ext_dec:
-            raise ValueError("pixel_weights needs the model's own fully connected encoder and decoder (no convolutional or "
-                             "user-defined networks)")
+            raise ValueError("%s needs the model's own fully connected encoder and decoder (no convolutional or "
+                             "user-defined networks)" % kw)
         if self.particles > 1 or self.renyi is not None:
-            raise ValueError("pixel_weights runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)")
+            raise ValueError("%s runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)" % kw)
         if self.fused == 3:
-            raise ValueError("pixel_weights is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
-                             "no weighted form, and training at another precision than the one asked for is worse than refusing")
+            raise ValueError("%s is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
+                             "no weighted form, and training at another precision than the one asked for is worse than refusing" % kw)
+
+    def _image_weight_tensor(self, w, b: int, n_pix: int):
+        """image_weights of one call as the library takes them: a float / bool / integer tensor or ndarray of shape (b, *data_dim)
+        (the same weight in every channel), (b, *data_dim, C) or (b, n_pix) -> one contiguous float32 device tensor (b, n_pix),
+        channel-last.  Shape and dtype only: nothing here waits for the device."""
+        try:
+            t = torch.as_tensor(w).detach()
+        except Exception as e:
+            raise ValueError("image_weights must be a tensor, an ndarray or a bool mask (got %s)" % type(w).__name__) from e
+        if not (t.is_floating_point() or t.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+            raise ValueError("image_weights must be real-valued or a bool mask (got dtype %s)" % t.dtype)
+        dd = tuple(int(d) for d in self.model.data_dim)
+        Cn = int(self.C)
+        shape = tuple(t.shape)
+        if shape == (b,) + dd and Cn > 1:
+            t = t.to(self.device, torch.float32).unsqueeze(-1).expand(b, *dd, Cn)
+        elif shape in ((b,) + dd + (Cn,), (b, n_pix)) or (Cn == 1 and shape == (b,) + dd):
+            t = t.to(self.device, torch.float32)
+        else:
+            want = "(%d, %s)" % (b, ", ".join(str(d) for d in dd))
+            if Cn > 1:
+                want += " (one weight per position, every channel), (%d, %s, %d)" % (b, ", ".join(str(d) for d in dd), Cn)
+            raise ValueError("image_weights must have shape %s or (%d, %d): one weight per observed value of every image of the "
+                             "batch (got %s)" % (want, b, n_pix, shape))
+        return t.reshape(b, n_pix).contiguous()
 
     def _plan_fused(self) -> int:
         """pv_ivae_plan.fused: the engine's `fused`, or 1 where fused_channels routes a multi-channel model to the f32 kernel —
-        and where pixel_weights route a one-channel model there (fused = 1 or 2: the weighted fused f32 kernel)."""
+        and where pixel_weights / image_weights route a one-channel model there (fused = 1 or 2: the weighted fused f32 kernel)."""
         if self.fused_channels and self.C > 1 and self.fused in (1, 2):
             return 1
-        if getattr(self, "pixel_weights", None) is not None and self.C == 1 and self.fused in (1, 2):
+        if self._weighted() and self.C == 1 and self.fused in (1, 2):
             return 1
         return int(self.fused)
 
     def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None,
-                  pixel_weights=None):
+                  pixel_weights=None, image_weights=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
         renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting.
-        pixel_weights: weights set them, False removes them, None leaves the setting."""
+        pixel_weights: weights set them, False removes them, None leaves the setting.
+        image_weights: True turns the per-image weighted step on, False off, None leaves the setting."""
         if lr is not None:
             self.lr = float(lr)
         if betas is not None:
@@ -402,11 +454,16 @@ class IVAEEngine:
         if eps is not None:
             self.adam_eps = float(eps)
         old = (self.fused, self.particles, self.renyi, self.kl, self.fused_channels)
-        old_pw = self.pixel_weights
+        old_pw, old_iw = self.pixel_weights, self.image_weights
+        if image_weights is not None:
+            new_iw = _image_weights_flag(image_weights)                       # (raises before anything is changed)
         if pixel_weights is not None:
             self.pixel_weights = self._pixel_weight_tensor(pixel_weights)     # (raises before anything is changed)
             if self.pixel_weights is not None or old_pw is not None:          # (False on an unweighted engine: nothing to reset)
                 self.ws = None
+        if image_weights is not None and new_iw != old_iw:
+            self.image_weights = new_iw
+            self.ws = None
         if fused is not None and int(fused) != self.fused:
             self.fused = int(fused)
             self.ws = None
@@ -426,7 +483,7 @@ class IVAEEngine:
             self._check_pixel_weights()
         except ValueError:
             self.fused, self.particles, self.renyi, self.kl, self.fused_channels = old
-            self.pixel_weights = old_pw
+            self.pixel_weights, self.image_weights = old_pw, old_iw
             self._check_particles()
             raise
         if self.flat is not None:
@@ -668,7 +725,7 @@ class IVAEEngine:
         p.ev_start, p.ev_stop = self.events
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
-        if what == 1 and self.pixel_weights is not None:  # the layout of the kernel family the weighted step runs
+        if what == 1 and (self.pixel_weights is not None or self.image_weights):   # the layout of the kernel family the weighted step runs
             need = _abi.lib().pv_ivae_weighted_workspace_bytes(C.byref(p))
         elif what == 1 and self.renyi is not None:       # ... plus the bound's per-image term
             need = _abi.lib().pv_ivae_renyi_workspace_bytes(C.byref(p), self.particles)
@@ -712,7 +769,7 @@ class IVAEEngine:
                        row_w: Optional[torch.Tensor] = None, row_elbo: Optional[torch.Tensor] = None,
                        dy: Optional[torch.Tensor] = None, step: bool = False,
                        class_onehot: Optional[torch.Tensor] = None, comm=None, hist_out: Optional[torch.Tensor] = None,
-                       weights_out: Optional[torch.Tensor] = None):
+                       weights_out: Optional[torch.Tensor] = None, image_weights=None):
         """Enqueues Trace_ELBO.loss_and_grads (self.kl == "analytic": TraceMeanField_ELBO's) on the current stream.  Results land in
         self.scalars (device, 4 floats) and self.grad[:n_flat]; nothing is synchronised.
         row_w (B): per-sample weights of the ELBO terms; row_elbo (B) / dy (B, c_dim): extra outputs
@@ -730,7 +787,11 @@ class IVAEEngine:
         renyi = alpha (model.engine(particles=P, renyi=alpha)): the importance-weighted bound over the same P samples
         (pv_ivae_renyi_loss_and_grads / pv_ivae_renyi_step): scalars[0] = -sum_b L_b, scalars[2] / [3] the weighted KL terms,
         scalars[1] the weighted log-likelihood plus the weights' entropy term; weights_out (P*B,), a device tensor, receives
-        the normalised weights, rows [p][b].  Same restrictions as particles > 1."""
+        the normalised weights, rows [p][b].  Same restrictions as particles > 1.
+        image_weights (an engine made with image_weights=True, and only there): this batch's weights, one per observed value of every
+        image — (b, *data_dim), (b, *data_dim, C) or (b, n_pix); float, integer or bool; tensor or ndarray
+        (pv_ivae_weighted_images_loss_and_grads / _step).  With pixel_weights as well the library gets the product.  Not with comm=,
+        row_w / row_elbo / dy / class_onehot."""
         self.ensure_bound()
         P = self.particles
         alpha = self.renyi
@@ -738,9 +799,19 @@ class IVAEEngine:
                                              or class_onehot is not None):
             raise ValueError("particles > 1 / renyi cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
         pw = self.pixel_weights
-        if pw is not None and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
-                               or class_onehot is not None):
-            raise ValueError("pixel_weights cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
+        if self.image_weights != (image_weights is not None):
+            if image_weights is None:
+                raise ValueError("this engine was made with image_weights=True: every call needs image_weights=w, the batch's weights")
+            raise ValueError("image_weights= needs an engine configured for it: model.engine(image_weights=True)")
+        if (pw is not None or image_weights is not None) and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
+                                 or class_onehot is not None):
+            raise ValueError("%s cannot be combined with comm=, row_w, row_elbo, dy or class_onehot"
+                             % ("pixel_weights" if not self.image_weights else "image_weights"))
+        iw = None
+        if image_weights is not None:                     # (shape and dtype, before anything is planned or enqueued)
+            iw = self._image_weight_tensor(image_weights, int(x.shape[0]), math.prod(int(d) for d in self.model.data_dim) * int(self.C))
+            if pw is not None:
+                iw = iw * pw                              # (b, n_pix) * (n_pix): one multiply on the device, then the per-image call
         if weights_out is not None and alpha is None:
             raise ValueError("weights_out belongs to the importance-weighted bound: model.engine(particles=P, renyi=alpha)")
         if self.conv_enc:
@@ -813,6 +884,9 @@ class IVAEEngine:
                                "pv_ivae_renyi_step")
                 elif P > 1:
                     _abi.check(_abi.lib().pv_ivae_particles_step(C.byref(p), P, _abi.current_stream()), "pv_ivae_particles_step")
+                elif iw is not None:
+                    _abi.check(_abi.lib().pv_ivae_weighted_images_step(C.byref(p), _abi.ptr(iw), _abi.current_stream()),
+                               "pv_ivae_weighted_images_step")
                 elif pw is not None:
                     _abi.check(_abi.lib().pv_ivae_weighted_step(C.byref(p), _abi.ptr(pw), _abi.current_stream()),
                                "pv_ivae_weighted_step")
@@ -825,6 +899,10 @@ class IVAEEngine:
             elif P > 1:
                 _abi.check(_abi.lib().pv_ivae_particles_loss_and_grads(C.byref(p), P, int(want_grads), _abi.current_stream()),
                            "pv_ivae_particles_loss_and_grads")
+            elif iw is not None:
+                _abi.check(_abi.lib().pv_ivae_weighted_images_loss_and_grads(C.byref(p), _abi.ptr(iw), int(want_grads),
+                                                                             _abi.current_stream()),
+                           "pv_ivae_weighted_images_loss_and_grads")
             elif pw is not None:
                 _abi.check(_abi.lib().pv_ivae_weighted_loss_and_grads(C.byref(p), _abi.ptr(pw), int(want_grads),
                                                                       _abi.current_stream()), "pv_ivae_weighted_loss_and_grads")
@@ -844,7 +922,7 @@ class IVAEEngine:
         if want_grads:
             self.grads_live = True
         self._count_bn(self._bn_enc)
-        self._keep = (x, eps, y, head, dhead, row_w, class_onehot)   # keep inputs alive until the stream has consumed them
+        self._keep = (x, eps, y, head, dhead, row_w, class_onehot, iw)   # keep inputs alive until the stream has consumed them
 
     # ------------------------------------------------------------------ user-defined decoder (torch) around the HIP guide
     def _torch_decode(self, z, y=None, angle=None, shift=None, scale=None):
@@ -1040,7 +1118,7 @@ class IVAEEngine:
     @_abi.on_device
     def uses_fused(self, batch: int) -> bool:
         """Whether loss_and_grads runs the fused persistent decoder kernel for this batch size."""
-        if self.pixel_weights is not None:
+        if self._weighted():
             return bool(_abi.lib().pv_ivae_weighted_uses_fused(C.byref(self._plan(batch))))
         return bool(_abi.lib().pv_ivae_uses_fused(C.byref(self._plan(batch))))
 

@@ -115,13 +115,15 @@ class iVAE(baseVAE):
         """Evaluates guide + model once (no gradients, no update) through the HIP library and
         returns dict(loss, ll, logpz, logqz) as python floats.  `eps` (B, z_dim) is the
         standard-normal draw of the guide; drawn on the CPU generator when omitted.
-        Replaces tracing `model`/`guide` with Pyro (models/ivae.py:165-221)."""
+        Replaces tracing `model`/`guide` with Pyro (models/ivae.py:165-221).
+        image_weights=w (an engine made with image_weights=True): the batch's per-image observation weights."""
         eng = self.engine()
         x = x.to(eng.device, torch.float32)
         if eps is None:
             eps = torch.empty(x.shape[0], self.z_dim).normal_()
+        extra = {"image_weights": kwargs["image_weights"]} if kwargs.get("image_weights", None) is not None else {}
         eng.loss_and_grads(x, eps.to(eng.device, torch.float32), kwargs.get("scale_factor", 1.),
-                           None if y is None else y.to(eng.device, torch.float32), want_grads=False)
+                           None if y is None else y.to(eng.device, torch.float32), want_grads=False, **extra)
         s = eng.scalars.cpu().tolist()
         return dict(loss=s[0], ll=s[1], logpz=s[2], logqz=s[3])
 

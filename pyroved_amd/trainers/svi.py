@@ -77,6 +77,16 @@ class SVItrainer:
             a rotation-invariant model, dead detector pixels, a gain map.  models.iVAE with its own fully connected networks, the
             one-particle ELBO (both loss strings), fp32-class precision; a ValueError elsewhere.  A one-channel model then trains
             on the weighted fused f32 decoder kernel — about the cost of fused=1, well above the default step's
+        image_weights: True — every image brings its own weights: the loader's batches carry them as their LAST tensor, (x, w) or,
+            with c_dim > 0, (x, y, w) — utils.init_dataloader(x, w) / init_dataloader(x, y, w) build such loaders.  w is
+            (n, *data_dim), (n, *data_dim, C) or (n, prod(data_dim) * C), entries finite and >= 0 (checked on the host: once per
+            data set with the device feed, per batch without it); an image whose weights are all zero contributes its KL terms
+            only.  Every log p(x_bi | z_b) of train / evaluate / step is multiplied by w_bi, normaliser included: sparse or
+            compressed-sensing scans, windows cropped at the edge of the field of view, per-frame saturated pixels, exposure
+            maps.  The encoder sees x as given, so x must be finite everywhere: for data whose missing values are marked by
+            NaN, `x, w = utils.weights_from_nan(x)` fills them and returns the 0 / 1 weights.  Scope, kernels and cost are those of
+            pixel_weights, and the two combine (w_bi * w_i); a batch with another number of tensors is a ValueError
+            
         process_group: torch.distributed group for data-parallel training (default: WORLD if initialised)
         device_feed: keep TensorDataset loaders' data on the device and gather minibatches there, in the order the
             loader's own sampler produces (default True; same numbers as iterating the loader)
@@ -129,6 +139,13 @@ class SVItrainer:
         self.engine, self.group, self._hist, self._feed_cache = None, kwargs.get("process_group", None), None, None
         self.loss_history = {"training_loss": [], "test_loss": []}
         self.current_epoch = 0
+        iw = kwargs.get("image_weights", False)
+        if iw is None:
+            iw = False
+        if not isinstance(iw, bool):
+            raise ValueError("image_weights must be True or False: the weights travel with the data, as the last tensor of every "
+                             "batch of the loader (got %s)" % type(iw).__name__)
+        self.image_weights = False
         if isinstance(loss, str) and loss not in self._LOSSES:
             raise ValueError("loss must be one of the strings %s (or a pyro.infer ELBO object); got %r"
                              % (" / ".join(repr(k) for k in self._LOSSES if k), loss))
@@ -157,8 +174,8 @@ class SVItrainer:
             if pvdist.world(self.group)[1] > 1:
                 raise ValueError("Pyro optimizer / loss objects cannot be combined with data-parallel training: replicas "
                                  "would train unsynchronised (pass optimizer=None or a dict of Adam arguments)")
-            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "rng", "device_feed", "mirror_evaluate_update")
-                   if k in kwargs]
+            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "image_weights", "rng", "device_feed",
+                               "mirror_evaluate_update") if k in kwargs]
             if bad:
                 raise ValueError("%s only apply to the HIP training path, not to Pyro optimizer / loss objects" % bad)
             pyro.clear_param_store()
@@ -191,6 +208,7 @@ class SVItrainer:
             self.engine.kl = kl
             self.engine.particles = P
             self.engine.renyi = self.alpha
+            self.image_weights = iw
         else:
             precision = kwargs.get("precision", "fp32")
             if precision not in ("fp32", "bf16"):
@@ -207,10 +225,15 @@ class SVItrainer:
             if pw is not None and pw is not False and precision == "bf16":
                 raise ValueError("pixel_weights is not implemented for precision='bf16': the bf16 throughput kernels have no "
                                  "weighted form")
+            if iw and precision == "bf16":
+                raise ValueError("image_weights is not implemented for precision='bf16': the bf16 throughput kernels have no "
+                                 "weighted form")
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
                                        renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels,
-                                       pixel_weights=False if pw is None else pw)      # (no keyword: a later trainer is unweighted)
+                                       pixel_weights=False if pw is None else pw,      # (no keyword: a later trainer is unweighted)
+                                       image_weights=iw)
+            self.image_weights = iw
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
             self.engine.reset_optimizer()          # every trainer starts a fresh Adam (svi.py:75-81)
@@ -248,13 +271,34 @@ class SVItrainer:
             return eps[x0:x0 + n]
         return eps.view(P, -1, eps.shape[-1])[:, x0:x0 + n].reshape(P * n, eps.shape[-1])
 
-    def _svi_step(self, i: int, x: torch.Tensor, y: Optional[torch.Tensor], train: bool, eps=None, shard=None,
+    def _check_weight_values(self, w: torch.Tensor) -> None:
+        """image_weights where they are on the host: finite and >= 0 (a device tensor is the caller's promise — no sync here)."""
+        if w.device.type != "cpu" or w.dtype == torch.bool or w.numel() == 0:
+            return
+        if w.is_floating_point() and not bool(torch.isfinite(w).all()):
+            raise ValueError("image_weights must be finite (found nan or inf)")
+        if bool((w < 0).any()):
+            raise ValueError("image_weights must be >= 0 (found %g)" % float(w.min()))
+
+    def _split_batch(self, data):
+        """A loader's batch -> (x, y or None, w or None).  image_weights=True: the weights are the batch's LAST tensor, (x, w) or,
+        for a class-conditioned model, (x, y, w)."""
+        if not self.image_weights:
+            return data[0], (None if len(data) == 1 else data[1]), None
+        want = 3 if int(getattr(self.model, "c_dim", 0)) > 0 else 2
+        if len(data) != want:
+            raise ValueError("image_weights=True: every batch must hold %d tensors, %s — the weights last (got %d)"
+                             % (want, "(x, y, w)" if want == 3 else "(x, w)", len(data)))
+        return data[0], (data[1] if want == 3 else None), data[-1]
+
+    def _svi_step(self, i: int, x: torch.Tensor, y: Optional[torch.Tensor], train: bool, eps=None, shard=None, w=None,
                   **kwargs) -> None:
         """SVI.step on one (global) minibatch; the loss lands in slot i of the device history.
         x / y / eps may already live on the device (device feed, _epoch_device_feed).
         shard = (lo, hi, b): x / y / eps are already THIS rank's rows [lo, hi) of a global minibatch of b samples
         (the data-parallel device feed gathers nothing else).
-        num_particles = P > 1: eps holds P rows per image, [p][b]; a shard takes rows [lo, hi) of every particle."""
+        num_particles = P > 1: eps holds P rows per image, [p][b]; a shard takes rows [lo, hi) of every particle.
+        w (image_weights=True): the minibatch's observation weights, sliced with x."""
         eng = self.engine
         beta = kwargs.get("scale_factor", 1.)          # jiVAE: scalar or [continuous, discrete] (jivae.py:161-165)
         if torch.is_tensor(beta):
@@ -296,6 +340,10 @@ class SVItrainer:
             xs = x[x0:x0 + hi - lo].to(dev, torch.float32)
             es = self._eps_rows(eps, x0, hi - lo).to(dev, torch.float32)
             ys = None if y is None else y[x0:x0 + hi - lo].to(dev, torch.float32)
+            if self.image_weights:
+                if w is None:
+                    raise ValueError("image_weights=True: the step needs the minibatch's weights")
+                extra["image_weights"] = w[x0:x0 + hi - lo]
             one_call = (direct and train and getattr(eng, "supports_step", False)
                         and not (getattr(eng, "ext_enc", False) or getattr(eng, "ext_dec", False)))
             if one_call:                              # loss, gradients and Adam in one library call (pv_ivae_step)
@@ -417,6 +465,8 @@ class SVItrainer:
         key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in tensors)
         if self._feed_cache is None or self._feed_cache[0] != key:
             dev = self.engine.device
+            if self.image_weights:
+                self._check_weight_values(tensors[-1])      # once per cached data set, where the values are on the host
             self._feed_cache = (key, [t.to(dev, torch.float32) for t in tensors])
         return self._feed_cache[1]
 
@@ -430,9 +480,12 @@ class SVItrainer:
         from torch.utils.data import DataLoader, TensorDataset
         ds = getattr(loader, "dataset", None)
         if (self._sampled_class or not self.device_feed or not isinstance(loader, DataLoader) or not isinstance(ds, TensorDataset)
-                or loader.num_workers != 0 or loader.batch_sampler is None or len(ds.tensors) not in (1, 2)
+                or loader.num_workers != 0 or loader.batch_sampler is None
+                or len(ds.tensors) not in ((2, 3) if self.image_weights else (1, 2))
                 or getattr(self.engine, "device", None) is None or self.rng != "cpu"):
             return None
+        if self.image_weights:
+            self._split_batch(ds.tensors)                      # (the batches' arity, before anything is drawn)
         batches = self._epoch_batches(loader, len(ds))         # LongTensors of sample indices, the loader's order
         if not batches:
             return 0
@@ -442,12 +495,15 @@ class SVItrainer:
             self._prefetch_perm(self._rand_n)                  # the next shuffled epoch's order, off the critical path
         dev = self.engine.device
         data = self._device_dataset(ds.tensors)
+        wdat = data[-1] if self.image_weights else None        # the weights stay on the device with the data, same indices
+        if self.image_weights:
+            data = data[:-1]
         sizes = [len(b) for b in batches]
         idx_dev = torch.cat(batches).to(dev)
         eps_dev = eps.to(dev, torch.float32)
         # minibatches are gathered a chunk of steps at a time (one index_select per ~256 MB of samples instead of one
         # small gather kernel in front of every step); a step then takes a contiguous view
-        per_sample = sum(t[0].numel() for t in data) * 4
+        per_sample = (sum(t[0].numel() for t in data) + (wdat[0].numel() if wdat is not None else 0)) * 4
         chunk = max(1, int((256 << 20) // max(per_sample * max(sizes), 1)))
         rank, world = pvdist.world(self.group)
         off, n = 0, 0
@@ -467,23 +523,26 @@ class SVItrainer:
                 idx = torch.cat(parts)
                 xs = data[0].index_select(0, idx)
                 ys = data[1].index_select(0, idx) if len(data) > 1 else None
+                wsel = wdat.index_select(0, idx) if wdat is not None else None
                 c0 = 0
                 for k, (lo, hi, bsz, r0) in enumerate(bounds):
                     w_ = hi - lo
                     e0 = P * (off + r0)                 # the step's block of P * bsz rows; the shard's rows of every particle
                     self._svi_step(n + k, xs[c0:c0 + w_], None if ys is None else ys[c0:c0 + w_], train,
-                                   eps=self._eps_rows(eps_dev[e0:e0 + P * bsz], lo, hi - lo), shard=(lo, hi, bsz), **kwargs)
+                                   eps=self._eps_rows(eps_dev[e0:e0 + P * bsz], lo, hi - lo), shard=(lo, hi, bsz),
+                                   w=None if wsel is None else wsel[c0:c0 + w_], **kwargs)
                     c0 += w_
             else:
                 idx = idx_dev[off:off + rows]
                 xs = data[0].index_select(0, idx)
                 ys = data[1].index_select(0, idx) if len(data) > 1 else None
+                wsel = wdat.index_select(0, idx) if wdat is not None else None
                 r0 = 0
                 for k in range(m):
                     bsz = sizes[n + k]
                     e0 = P * (off + r0)
                     self._svi_step(n + k, xs[r0:r0 + bsz], None if ys is None else ys[r0:r0 + bsz], train,
-                                   eps=eps_dev[e0:e0 + P * bsz], **kwargs)
+                                   eps=eps_dev[e0:e0 + P * bsz], w=None if wsel is None else wsel[r0:r0 + bsz], **kwargs)
                     r0 += bsz
             off += rows
             n += m
@@ -506,7 +565,11 @@ class SVItrainer:
         if n is None:
             n = 0
             for data in loader:
-                if len(data) == 1:  # VAE mode
+                if self.image_weights:  # (x, w) or (x, y, w): the weights are sliced as x is
+                    x_, y_, w_ = self._split_batch(data)
+                    self._check_weight_values(w_)
+                    self._svi_step(n, x_, y_, train, w=w_, **kwargs)
+                elif len(data) == 1:  # VAE mode
                     self._svi_step(n, data[0], None, train, **kwargs)
                 else:  # VED or cVAE mode
                     self._svi_step(n, data[0], data[1], train, **kwargs)

@@ -5,6 +5,7 @@ Behaviour contract kept from the reference (it defines the data order parity dep
 a `torch.Generator(device)` handed to the loader only when `device=` is passed.  SVItrainer recognises loaders
 built here (plain TensorDataset + standard samplers) and feeds them from device memory (trainers/svi.py).
 """
+import math
 from typing import Iterator, Tuple
 
 import torch
@@ -23,6 +24,25 @@ def init_dataloader(*args: torch.Tensor, random_sampler: bool = False, shuffle: 
     else:
         opts["shuffle"] = shuffle
     return DataLoader(ds, **opts)
+
+
+def weights_from_nan(x, fill: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Missing values marked by NaN -> (x_filled, w): x with every NaN replaced by `fill`, and w of x's shape and (floating)
+    dtype with 0 where x was NaN and 1 elsewhere.  The front door of SVItrainer(model, image_weights=True) for NaN-marked data:
+    the encoder sees x as given, so x itself must be finite everywhere — `fill` is what the encoder sees at the missing
+    positions; the likelihood ignores them (weight 0).  x: a tensor or an ndarray; neither is modified.
+
+        x, w = weights_from_nan(scan)                      # scan: (n, *data_dim) with NaN where nothing was measured
+        loader = init_dataloader(x, w, batch_size=64)      # the weights travel as the batches' last tensor
+        trainer = SVItrainer(model, image_weights=True)"""
+    t = torch.as_tensor(x)
+    if not t.is_floating_point():
+        t = t.to(torch.float32)
+    if not math.isfinite(float(fill)):
+        raise ValueError("fill must be finite (got %r): the encoder reads the filled values" % (fill,))
+    missing = torch.isnan(t)
+    w = (~missing).to(t.dtype)
+    return torch.where(missing, torch.full_like(t, float(fill)), t), w
 
 
 def iter_batches(*args: torch.Tensor, batch_size: int = 100) -> Iterator[Tuple[torch.Tensor, ...]]:
