@@ -329,6 +329,18 @@ int pv_experiments_build(void);
  *   bit does nothing: a one-channel plan with it is byte for byte the fused == 1 plan without it.  pv_ivae_particles_* and
  *   pv_ivae_renyi_* keep refusing fused == 1.  No reference counterpart (the reference has one code path). */
 #define PV_PLAN_FUSED_CHANNELS 256
+/* PV_PLAN_FAST_WEIGHTS (pv_ivae_plan; a new bit of `flags`, no layout change, no version bump): the weighted entry points
+ *   (pv_ivae_weighted_* / pv_ivae_weighted_images_*, below) keep the plan's `fused` — 2: the bf16 three-product build of the 4-wave
+ *   fused decoder kernel, 3: its plain-bf16 build — and run that kernel's WEIGHTED instances instead of the fused f32 kernel's.
+ *   Takes effect only for a plan with ALL of: one channel, the architecture the fused kernel is specialised for
+ *   (pv_ivae_uses_fused), fused == 2 or 3 and dec_kernel == 0 or 1.  The call then runs the plan with dec_kernel = 1 (the 4-wave
+ *   kernel at every size, for training and forward-only launches alike, as Poisson plans on fused == 2 already do) and
+ *   PV_PLAN_NO_ENC_FOLD (the guide as its own launch).  Both builds carry fp32's exponent range, so weights of any magnitude are
+ *   safe; results are of fp32 class with fused == 2 and of the bf16 throughput precision with fused == 3.
+ *   With the bit set and the conditions not met: fused == 2 routes as without the bit; fused == 3 stays PV_EINVAL; dec_kernel > 1
+ *   is PV_EINVAL (the fp16 builds and the 8-wave kernel have no weighted form).  The unweighted entry points ignore the bit: with
+ *   it pv_ivae_loss_and_grads / pv_ivae_step run exactly what they run without it.  No reference counterpart. */
+#define PV_PLAN_FAST_WEIGHTS 512
 
 /* Bytes of workspace pv_ivae_* calls need for this plan (depends on batch, n_pix,
  * layer widths).  Returns < 0 on an unsupported plan. */
@@ -454,10 +466,15 @@ int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float al
  *     the bf16 throughput kernels have no weighted form, and a weighted one-channel step costs what the fused == 1 step costs
  *     (DESIGN.md 4.13 has the measured figures);
  *   fused == 1 or 2, 2 .. PV_MAX_CHANNELS channels               as unweighted: the fused f32 kernel with PV_PLAN_FUSED_CHANNELS
- *     and fused == 1, the layer-by-layer kernels otherwise.
+ *     and fused == 1, the layer-by-layer kernels otherwise;
+ *   PV_PLAN_FAST_WEIGHTS, fused == 2 or 3, one channel, such a    the weighted instances of the 4-wave bf16-class fused decoder
+ *     decoder, dec_kernel 0 or 1                                 kernel (fused == 2: three bf16 products, fp32-class results;
+ *     fused == 3: plain bf16), run as dec_kernel = 1 with PV_PLAN_NO_ENC_FOLD; pv_ivae_weighted_uses_fused is 1 and the workspace
+ *     is that plan's.  With the bit and fused == 2 on any other plan: the rows above.  With the bit and dec_kernel > 1: PV_EINVAL.
  * Scope: the one-particle ELBO in either kl_mode of the fc-encoder iVAE — spatial or vanilla decoder, 1 .. PV_MAX_CHANNELS
  * channels, with or without c_dim, every likelihood.  PV_EINVAL (the workspace query too; pv_ivae_weighted_uses_fused: 0) for
- * discrete_dim > 0, a convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 3.  There
+ * discrete_dim > 0, a convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 3 (unless
+ * PV_PLAN_FAST_WEIGHTS takes effect, above).  There
  * is no weighted form of pv_ivae_particles_*, pv_ivae_renyi_*, pv_ved_*, the semi-supervised calls or pv_ivae_dp_step (a
  * data-parallel caller reduces [gradients | scalars] itself: the loss stays a sum over images). */
 int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan);                        /* <0 unsupported */

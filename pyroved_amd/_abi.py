@@ -20,6 +20,7 @@ PV_PLAN_CONV_X3 = 64
 PV_PLAN_ENC_TILED = 32
 PV_PLAN_GENERIC_TILE_LOOP = 128
 PV_PLAN_FUSED_CHANNELS = 256         # several channels per position on the fused f32 decoder kernel (with fused == 1)
+PV_PLAN_FAST_WEIGHTS = 512           # weighted steps on the 4-wave bf16-class fused decoder kernel's weighted instances (fused 2 / 3)
 PV_MAX_LAYERS = 8
 PV_MAX_CHANNELS = 8         # channels per grid position of a spatial decoder (pv_ivae_plan.out.out_dim)
 
@@ -233,6 +234,15 @@ def lib():
             raise PvError("pyroved_amd: ABI version mismatch (library %d, binding %d)" % (v, PV_ABI_VERSION))
         _lib = handle
     return _lib
+
+
+def weighted_decoder_kernel_name(plan, per_image, grads):
+    """The decoder kernel a weighted call of `plan` launches, as rocprofv3 prints it: pv_debug_weighted_decoder_kernel_name, a
+    test hook the library exports outside include/pyroved_amd.h (so not in SIGNATURES).  '' for a plan the weighted calls refuse."""
+    fn = lib().pv_debug_weighted_decoder_kernel_name
+    fn.restype = C.c_char_p
+    fn.argtypes = [C.POINTER(pv_ivae_plan), C.c_int, C.c_int]
+    return fn(C.byref(plan), int(bool(per_image)), int(bool(grads))).decode()
 
 
 def check(code, what):

@@ -1027,8 +1027,15 @@ int fused_decoder_launch(FusedStep& st) {
   const pv_ivae_plan* p = st.p;
   const bool timed = p->ev_start && p->ev_stop;
   if (timed) (void)hipEventRecord((hipEvent_t)p->ev_start, st.s);
-  if (p->fused >= 2) PV_TRY(pv_sdec_fused_bf16_launch(st.f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
-                                                      (st.own_chain() && !st.fold) ? &st.ef : nullptr));
+  if (p->fused >= 2) {
+    // (weighted steps on the bf16-class kernels — weighted_route with PV_PLAN_FAST_WEIGHTS: the weights ride in the slot of `park`,
+    //  which no 4-wave launch reads; the routed plan's dec_kernel = 1 keeps every launch on the 4-wave kernel)
+    PvFused f = st.f;
+    if (st.L.pw) f.park = const_cast<float*>(st.L.pw);
+    PV_TRY(pv_sdec_fused_bf16_launch(f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
+                                     (st.own_chain() && !st.fold) ? &st.ef : nullptr,
+                                     !st.L.pw ? 0 : st.L.pw_img ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED));
+  }
   else if (plan_fused_mc(p) || st.L.pw) {
     // several channels per row: the f32 kernel's sibling, then (training) the sums of channels 1 .. C-1 of d(wo), d(bo) into the
     // flat gradient — in front of every launch that reads it, the one that applies Adam included
@@ -1581,17 +1588,33 @@ extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
 // ---- per-observation weights of the likelihood (v17, added without a layout change; include/pyroved_amd.h) ----
 // loss = -( sum_b sum_i w_i log p(x_bi | z_b) + beta sum_b [log p(z_b) - log q(z_b | x_b)] ), w (n_pix) shared by all images.
 // Scope: the one-particle ELBO (either KL form) of the fc-encoder iVAE, spatial or vanilla decoder, every likelihood
+// PV_PLAN_FAST_WEIGHTS takes effect: one channel, the fused kernels' architecture, a bf16-class `fused`, no build asked for by name
+// but the 4-wave bf16 one (dec_kernel 1) — the weighted instances of pv_sdec_fused_bf16.hip's 4-wave kernel take the decoder
+static bool weighted_fast(const pv_ivae_plan* p) {
+  return (p->flags & PV_PLAN_FAST_WEIGHTS) && p->coord_dim > 0 && p->out.out_dim == 1 && pv_sdec_fused_supported(p) &&
+         (p->fused == 2 || p->fused == 3) && (p->dec_kernel == 0 || p->dec_kernel == 1);
+}
 static bool weighted_scope(const pv_ivae_plan* p) {
-  return valid_plan(p) && p->discrete_dim == 0 && p->n_enc_ops == 0 && !p->ext_encoder && !p->ext_decoder && !p->row_w &&
-         !p->row_elbo && !p->dy && !p->class_onehot && p->fused != 3;
+  if (!(valid_plan(p) && p->discrete_dim == 0 && p->n_enc_ops == 0 && !p->ext_encoder && !p->ext_decoder && !p->row_w &&
+        !p->row_elbo && !p->dy && !p->class_onehot))
+    return false;
+  if ((p->flags & PV_PLAN_FAST_WEIGHTS) && p->dec_kernel > 1) return false;      // (the fp16 builds, the 8-wave kernel: no weighted form)
+  return p->fused != 3 || weighted_fast(p);
 }
 // The plan a weighted call runs: the caller's with `fused` rewritten to the kernel family that has a weighted form — 1 where the
 // weighted instances of the fused f32 kernel take the decoder (one channel asked with fused 1 or 2: fused = 2 promises fp32-class
 // results and the f32 kernel delivers them; several channels as the unweighted plan decides: PV_PLAN_FUSED_CHANNELS and fused == 1),
-// 0 (the layer-by-layer kernels) everywhere else.  The fp16-piece / bf16 decoder kernels have no weighted form
+// 0 (the layer-by-layer kernels) everywhere else.  The fp16-piece decoder kernels and the 8-wave bf16 kernel have no weighted form;
+// the 4-wave kernel's bf16 builds have one, taken on request (weighted_fast): `fused` stays, dec_kernel = 1 names that kernel for
+// every launch of the step at every size, and the guide keeps a launch of its own (the kernel that could host it is the 8-wave one)
 // (per_image: pv_ivae_weighted_images_* — the same routing over the per-image instances' list, which today is the same list)
 static pv_ivae_plan weighted_route(const pv_ivae_plan* p, bool per_image = false) {
   pv_ivae_plan q = *p;
+  if (weighted_fast(p)) {
+    q.dec_kernel = 1;
+    q.flags |= PV_PLAN_NO_ENC_FOLD;
+    return q;
+  }
   if (q.fused == 2 && q.coord_dim > 0 && q.out.out_dim == 1) q.fused = 1;
   if (!(q.fused == 1 && pv_sdec_fused_mc_weighted_supported(&q, per_image) && plan_fused_ok(&q))) q.fused = 0;
   return q;
@@ -1606,7 +1629,19 @@ extern "C" int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan) {
 extern "C" int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan) {
   if (!weighted_scope(plan)) return 0;
   const pv_ivae_plan q = weighted_route(plan);
-  return q.fused == 1 ? 1 : 0;
+  return (q.fused == 1 || weighted_fast(plan)) ? 1 : 0;
+}
+// test hook (not in include/), in the style of pv_debug_decoder_kernel_name: the decoder kernel a weighted call of the plan launches,
+// spelled the way rocprofv3 prints it (per_image: pv_ivae_weighted_images_*; grads: the gradient call / the forward-only one)
+extern "C" const char* pv_debug_weighted_decoder_kernel_name(const pv_ivae_plan* plan, int per_image, int grads) {
+  if (!weighted_scope(plan)) return "";
+  if (weighted_fast(plan)) return pv_sdec_fused_bf16_wt_kernel_name(plan->fused == 2, grads, plan->lik);
+  const pv_ivae_plan q = weighted_route(plan, per_image != 0);
+  if (q.fused != 1) return "pv_gemm_kernel (layer-by-layer path)";
+  static thread_local char buf[96];
+  snprintf(buf, sizeof buf, "void pv_sdec_fused_mc_kernel<%s, %d, %d>(PvFused)", grads ? "true" : "false", (int)plan_C(&q),
+           per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED);
+  return buf;
 }
 extern "C" int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream) {
   if (!pixel_w) return pv_ivae_loss_and_grads(plan, want_grads, stream);

@@ -51,6 +51,9 @@ struct PvFused {
                          //   and with them every kernel that takes a PvFused its argument layout, hidden arguments included
   };
   void* park;            // 8-wave split-precision kernel only: pv_sdec_fused_w8x3_park_bytes(grid) of per-wave parking slots
+                         //   — and, no 4-wave launch reading it, the slot the WEIGHTED 4-wave launches of pv_sdec_fused_bf16.hip
+                         //   (pv_sdec_fused_bf16_launch(..., weighted)) take for their per-observation weights: (N) floats shared by
+                         //   all samples or (M) in the layout of x.  They need wimg, so `pw` above is not theirs to use
   int64_t M;             // rows
   int64_t units;         // M / FD_UNIT
   int N, cd, B, lik, sigmoid_out, kmax;
@@ -174,8 +177,14 @@ int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, bool x3, hipStream_t s
 struct PvFbPrep;
 PvFbPrep pv_sdec_fused_bf16_prep_args(const PvFused& f, bool grads, bool x3);
 bool pv_sdec_fused_w8_qswap();          // the 8-wave plain-bf16 kernel's images are in the q-swapped column order (pv_fb_layout.h)
+// weighted (PV_FDM_W_SHARED / PV_FDM_W_IMAGES; pv_ivae_weighted_* with PV_PLAN_FAST_WEIGHTS): the weighted instances of the 4-wave
+// kernel's bf16 builds; the weights — (N), or (M) in the layout of x — travel in f.park.  PV_EINVAL where
+// pv_sdec_fused_bf16_weighted_ok(x3, f.units, f.sel) is false, or with fold, f.sw or f.x_units set
 int pv_sdec_fused_bf16_launch(const PvFused& f, int grid, bool grads, bool x3, hipStream_t s, const PvEncFold* fold = nullptr,
-                              const PvEncFold* chain = nullptr);      // chain: the 4-wave kernels' own-sample epilogue (PvEncFold::chain)
+                              const PvEncFold* chain = nullptr,      // chain: the 4-wave kernels' own-sample epilogue (PvEncFold::chain)
+                              int weighted = 0);
+bool pv_sdec_fused_bf16_weighted_ok(bool x3, int64_t units, int sel);
+const char* pv_sdec_fused_bf16_wt_kernel_name(bool x3, int grads, int lik);      // (as rocprofv3 prints it)
 int pv_sdec_fused_w8_launch(const PvFused& f, int grid, bool grads, hipStream_t s, const PvEncFold* fold = nullptr);
 // the 8-wave split-precision kernel (pv_sdec_fused_w8x3.hip; images pre-scaled by 2 log2(e) like the plain 8-wave kernel's)
 int pv_sdec_fused_w8x3_launch(const PvFused& f, int grid, bool grads, hipStream_t s, int waves);   // waves: 8 or 4

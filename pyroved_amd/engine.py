@@ -85,7 +85,12 @@ class IVAEEngine:
     that differ from image to image: sparse scans, windows cropped at the edge of the field of view, per-frame saturated pixels or
     exposure maps (pv_ivae_weighted_images_*).  Scope, routing and kernels are those of pixel_weights; the two combine (the
     library gets their product).  The encoder sees x as given: x must be finite also where w = 0 (utils.weights_from_nan).  Only
-    shape and dtype are checked per call — finite, >= 0 values are the caller's promise (SVItrainer checks them on the host)."""
+    shape and dtype are checked per call — finite, >= 0 values are the caller's promise (SVItrainer checks them on the host).
+    fast_weights=True (with pixel_weights and / or image_weights, fused = 2 or 3): the weighted step keeps the bf16-class decoder —
+    the weighted instances of the 4-wave fused kernel's bf16 three-product build (fused = 2, fp32-class results) or plain-bf16 build
+    (fused = 3 / precision='bf16', which is refused without the keyword) — instead of the fused f32 kernel (PV_PLAN_FAST_WEIGHTS).
+    For a one-channel spatial decoder of two tanh layers of 128 with positions a multiple of 16; with fused = 2 every other model
+    keeps the routing above, with fused = 3 it is refused."""
     supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
@@ -110,12 +115,14 @@ class IVAEEngine:
                                      # values (positions x channels, channel-last), on the device once the engine is bound — pv_ivae_weighted_*
     image_weights = False            # True: every loss_and_grads call takes image_weights=w, one weight per observed value of every
                                      # image of the batch — pv_ivae_weighted_images_*
+    fast_weights = False             # PV_PLAN_FAST_WEIGHTS: weighted steps on the 4-wave bf16-class fused decoder kernel (fused = 2 or 3)
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
                  particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None,
-                 image_weights: bool = False):
+                 image_weights: bool = False, fast_weights: bool = False):
         self.model = model
         self.image_weights = _image_weights_flag(image_weights)
+        self.fast_weights = bool(fast_weights)
         self.fused_channels = bool(fused_channels)
         self.kl = _kl_name(kl)
         self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
@@ -138,6 +145,7 @@ class IVAEEngine:
         self._check_particles()
         self._check_fused_channels()
         self._check_pixel_weights()
+        self._check_fast_weights()
         self.bind()
 
     # ------------------------------------------------------------------ structure
@@ -402,9 +410,51 @@ class IVAEEngine:
                              "user-defined networks)" % kw)
         if self.particles > 1 or self.renyi is not None:
             raise ValueError("%s runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)" % kw)
-        if self.fused == 3:
+        if self.fused == 3 and not self.fast_weights:
             raise ValueError("%s is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
                              "no weighted form, and training at another precision than the one asked for is worse than refusing" % kw)
+
+    def _fast_weights_blocker(self) -> Optional[str]:
+        """None where the weighted 4-wave bf16-class decoder kernel takes this model; otherwise the condition that fails."""
+        m, dec = self.model, self.model.decoder
+        if int(getattr(self, "C", 1)) != 1:
+            return "the model has %d channels (the kernel computes one)" % self.C
+        if m.coord == 0 or not isinstance(dec, sDecoderNet):
+            return "the decoder is the vanilla fully connected one (the kernel is the spatial decoder's)"
+        lins = _linears(dec.fc_layers)
+        if (len(lins) != 2 or any(l.in_features != 128 or l.out_features != 128 or l.bias is None for l in lins)
+                or dec.activation != "tanh" or dec.coord_latent.fc_coord.out_features != 128):
+            return ("the decoder is not two tanh layers of 128 (hidden_dim_d=[128, 128], activation='tanh'): it has %s, activation %r"
+                    % ([l.out_features for l in lins], dec.activation))
+        n_pos = math.prod(int(d) for d in m.data_dim)
+        if n_pos % 16 != 0:
+            return "the grid has %d positions, not a multiple of 16" % n_pos
+        return None
+
+    def _check_fast_weights(self):
+        """fast_weights=True asks for the weighted instances of the 4-wave bf16-class decoder kernel: a weighted engine on fused = 2
+        or 3.  fused = 3 promises that kernel family, so a model it does not take is refused; fused = 2 promises fp32-class results,
+        which the weighted fused f32 / layer-by-layer kernels deliver as well, so such a model keeps that routing."""
+        if not self.fast_weights:
+            return
+        if not self._weighted():
+            raise ValueError("fast_weights=True selects the kernel of a WEIGHTED step: it needs pixel_weights and / or image_weights")
+        if self.fused in (0, 1):
+            raise ValueError("fast_weights=True contradicts fused=%d (%s): it selects the bf16-class fused decoder kernels, use "
+                             "fused=2 or fused=3 (precision='bf16')"
+                             % (self.fused, "the layer-by-layer kernels" if self.fused == 0 else "the f32 fused kernel"))
+        why = self._fast_weights_blocker()
+        if self.fused == 3 and why is not None:
+            raise ValueError("fast_weights=True with fused=3 (precision='bf16') needs a model the weighted bf16 decoder kernel "
+                             "takes, and %s" % why)
+        if getattr(self, "dec_kernel", 0) not in (0, 1) and why is None:
+            raise ValueError("fast_weights=True runs the 4-wave bf16 decoder kernel (dec_kernel 0 or 1), not dec_kernel=%d"
+                             % self.dec_kernel)
+
+    def _fast_weights_on(self) -> bool:
+        """Whether the weighted step runs the weighted bf16-class kernel (the plan then carries PV_PLAN_FAST_WEIGHTS and keeps `fused`)."""
+        return (bool(getattr(self, "fast_weights", False)) and self._weighted() and self.fused in (2, 3)
+                and self._fast_weights_blocker() is None)
 
     def _image_weight_tensor(self, w, b: int, n_pix: int):
         """image_weights of one call as the library takes them: a float / bool / integer tensor or ndarray of shape (b, *data_dim)
@@ -433,20 +483,24 @@ class IVAEEngine:
 
     def _plan_fused(self) -> int:
         """pv_ivae_plan.fused: the engine's `fused`, or 1 where fused_channels routes a multi-channel model to the f32 kernel —
-        and where pixel_weights / image_weights route a one-channel model there (fused = 1 or 2: the weighted fused f32 kernel)."""
+        and where pixel_weights / image_weights route a one-channel model there (fused = 1 or 2: the weighted fused f32 kernel) unless
+        fast_weights keeps it on the bf16-class kernels."""
         if self.fused_channels and self.C > 1 and self.fused in (1, 2):
             return 1
+        if self._fast_weights_on():
+            return int(self.fused)
         if self._weighted() and self.C == 1 and self.fused in (1, 2):
             return 1
         return int(self.fused)
 
     def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None,
-                  pixel_weights=None, image_weights=None):
+                  pixel_weights=None, image_weights=None, fast_weights=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
         renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting.
         pixel_weights: weights set them, False removes them, None leaves the setting.
-        image_weights: True turns the per-image weighted step on, False off, None leaves the setting."""
+        image_weights: True turns the per-image weighted step on, False off, None leaves the setting.
+        fast_weights: True / False switches the weighted step to / from the bf16-class decoder kernels, None leaves the setting."""
         if lr is not None:
             self.lr = float(lr)
         if betas is not None:
@@ -454,7 +508,10 @@ class IVAEEngine:
         if eps is not None:
             self.adam_eps = float(eps)
         old = (self.fused, self.particles, self.renyi, self.kl, self.fused_channels)
-        old_pw, old_iw = self.pixel_weights, self.image_weights
+        old_pw, old_iw, old_fw = self.pixel_weights, self.image_weights, self.fast_weights
+        if fast_weights is not None and bool(fast_weights) != self.fast_weights:
+            self.fast_weights = bool(fast_weights)
+            self.ws = None
         if image_weights is not None:
             new_iw = _image_weights_flag(image_weights)                       # (raises before anything is changed)
         if pixel_weights is not None:
@@ -481,9 +538,10 @@ class IVAEEngine:
             self._check_kl()
             self._check_fused_channels()
             self._check_pixel_weights()
+            self._check_fast_weights()
         except ValueError:
             self.fused, self.particles, self.renyi, self.kl, self.fused_channels = old
-            self.pixel_weights, self.image_weights = old_pw, old_iw
+            self.pixel_weights, self.image_weights, self.fast_weights = old_pw, old_iw, old_fw
             self._check_particles()
             raise
         if self.flat is not None:
@@ -612,6 +670,7 @@ class IVAEEngine:
                 (0 if getattr(self, "enc_per_image", True) else _abi.PV_PLAN_ENC_TILED) |
                 (0 if getattr(self, "full_tile_loop", True) else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
                 (_abi.PV_PLAN_FUSED_CHANNELS if (getattr(self, "fused_channels", False) and getattr(self, "C", 1) > 1) else 0) |
+                (_abi.PV_PLAN_FAST_WEIGHTS if self._fast_weights_on() else 0) |
                 (_abi.PV_PLAN_CONV_X3 if getattr(self, "conv_x3", False) else 0))
 
     def ensure_bound(self):

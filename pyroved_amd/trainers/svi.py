@@ -87,6 +87,12 @@ class SVItrainer:
             NaN, `x, w = utils.weights_from_nan(x)` fills them and returns the 0 / 1 weights.  Scope, kernels and cost are those of
             pixel_weights, and the two combine (w_bi * w_i); a batch with another number of tensors is a ValueError
             
+        fast_weights: True (with pixel_weights and / or image_weights) — the weighted step stays on the bf16-class fused decoder:
+            the weighted instances of its 4-wave kernel, three bf16 products at precision="fp32" (fp32-class results), plain bf16
+            at precision="bf16", which is refused with weights otherwise.  For one-channel models whose spatial decoder is two tanh
+            layers of 128 over a number of grid positions that is a multiple of 16: at precision="fp32" other models keep the
+            routing above, at precision="bf16" they are a ValueError that names the condition.  A ValueError without weights and
+            with fused=0 or 1 (DESIGN.md 4.16 has the measured cost of a weighted step on each route)
         process_group: torch.distributed group for data-parallel training (default: WORLD if initialised)
         device_feed: keep TensorDataset loaders' data on the device and gather minibatches there, in the order the
             loader's own sampler produces (default True; same numbers as iterating the loader)
@@ -174,7 +180,7 @@ class SVItrainer:
             if pvdist.world(self.group)[1] > 1:
                 raise ValueError("Pyro optimizer / loss objects cannot be combined with data-parallel training: replicas "
                                  "would train unsynchronised (pass optimizer=None or a dict of Adam arguments)")
-            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "image_weights", "rng", "device_feed",
+            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "image_weights", "fast_weights", "rng", "device_feed",
                                "mirror_evaluate_update") if k in kwargs]
             if bad:
                 raise ValueError("%s only apply to the HIP training path, not to Pyro optimizer / loss objects" % bad)
@@ -222,17 +228,22 @@ class SVItrainer:
                                  "exists, and training at another precision than the one asked for is worse than refusing"
                                  % model.channels)
             pw = kwargs.get("pixel_weights", None)
-            if pw is not None and pw is not False and precision == "bf16":
+            fw = kwargs.get("fast_weights", False)
+            if fw is None:
+                fw = False
+            if not isinstance(fw, bool):
+                raise ValueError("fast_weights must be True or False (got %s)" % type(fw).__name__)
+            if pw is not None and pw is not False and precision == "bf16" and not fw:
                 raise ValueError("pixel_weights is not implemented for precision='bf16': the bf16 throughput kernels have no "
                                  "weighted form")
-            if iw and precision == "bf16":
+            if iw and precision == "bf16" and not fw:
                 raise ValueError("image_weights is not implemented for precision='bf16': the bf16 throughput kernels have no "
                                  "weighted form")
             self.engine = model.engine(lr=adam["lr"], betas=adam["betas"], eps=adam["eps"],
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
                                        renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels,
                                        pixel_weights=False if pw is None else pw,      # (no keyword: a later trainer is unweighted)
-                                       image_weights=iw)
+                                       image_weights=iw, fast_weights=fw)
             self.image_weights = iw
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
