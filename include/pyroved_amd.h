@@ -14,6 +14,14 @@
  *    weights use torch.nn.Linear layout (out_features, in_features), row-major;
  *  - the caller owns every buffer (including the workspace); the library never
  *    allocates device memory, never frees, never keeps a pointer past the call;
+ *  - the workspace (`ws`, `ws_bytes` of every plan) is scratch: on entry it may hold ANYTHING (the library zero-fills what it
+ *    sums over and reads no flag, index or count it has not written in the same call), the size its query returns is enough,
+ *    a smaller `ws_bytes` is PV_EWS before anything is enqueued, and nothing is kept in it from one call to the next — except
+ *    inside the three documented pairs, where it must stay untouched between the two calls: pv_ivae_guide ->
+ *    pv_ivae_guide_backward, pv_convnet_forward -> pv_convnet_backward, pv_mlp_forward -> pv_mlp_backward.  `ws` must be
+ *    aligned to 256 bytes: every region is carved at a multiple of 256 bytes from it and read with 16-byte vector accesses
+ *    (hipMalloc and torch's allocator give at least that).  The size queries need no `ws` (tests/test_gpu_workspace_contract.py,
+ *    tests/test_workspace_contract_cpu.py hold the library to all of this);
  *  - all work is enqueued asynchronously on `stream` (a hipStream_t passed as
  *    void*); no implicit device synchronisation; safe inside stream capture;
  *  - return value: 0 on success, otherwise a hipError_t (>0) or a PV_E* code (<0);
