@@ -403,6 +403,45 @@ int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, void* strea
  * so plan->grads holds the zeroed gradients of pyro's zero_grads afterwards.  Needs adam_m / adam_v / adam_step. */
 int pv_ivae_step(const pv_ivae_plan* plan, void* stream);
 
+/* ---- (v17, new entry points, no layout change) the step's OBJECTIVE as one descriptor next to the plan ------------------------
+ * Which bound, over how many samples, with which observation weights: one struct, read by one workspace query and two calls.
+ * The recommended spelling for new callers; every pv_ivae_particles_* / _renyi_* / _weighted_* / _weighted_images_* function below
+ * (and pv_ivae_loss_and_grads / pv_ivae_step above) fills this descriptor and runs the same code, so results are theirs bit for
+ * bit.  The sections below keep each objective's mathematics; SCOPE is stated here, once. */
+#define PV_BOUND_ELBO       0    /* Trace_ELBO / TraceMeanField_ELBO (plan->kl_mode)                                          */
+#define PV_BOUND_RENYI      1    /* RenyiELBO(alpha, num_particles)                                                           */
+#define PV_OBS_W_NONE       0
+#define PV_OBS_W_SHARED     1    /* obs_w: n_pix floats, shared by all images                                                 */
+#define PV_OBS_W_PER_IMAGE  2    /* obs_w: batch * n_pix floats in the layout of plan->x                                      */
+typedef struct pv_ivae_objective {
+  int32_t num_particles;         /* >= 1                                                                                      */
+  int32_t bound;                 /* PV_BOUND_*                                                                                */
+  float   alpha;                 /* PV_BOUND_RENYI only: finite, != 1 (the workspace query does not read it)                  */
+  int32_t obs_w_kind;            /* PV_OBS_W_*                                                                                */
+  const float* obs_w;            /* DEVICE weights (obs_w_kind != PV_OBS_W_NONE); read by the two calls, not by the query     */
+  float*  weights_out;           /* DEVICE, optional, num_particles * batch floats; PV_BOUND_RENYI only                       */
+} pv_ivae_objective;
+/* A NULL objective is {1, PV_BOUND_ELBO, -, PV_OBS_W_NONE, -, NULL}: the query is pv_ivae_workspace_bytes_for(plan, PV_WS_STEP),
+ * the calls are pv_ivae_loss_and_grads / pv_ivae_step.
+ *
+ *   objective                                   scope (plans outside it: PV_EINVAL, from the query too)
+ *   ------------------------------------------  -----------------------------------------------------------------------------
+ *   {1, ELBO, NONE}                             every plan of pv_ivae_loss_and_grads / pv_ivae_step
+ *   {P > 1, ELBO, NONE}                         "fc iVAE": discrete_dim == 0, no convolutional or external encoder / decoder, no
+ *                                               row_w / row_elbo / dy / class_onehot; spatial or vanilla decoder, with or without
+ *                                               c_dim, every likelihood, both kl_mode values — and fused = 0, 2 or 3 (not 1)
+ *   {1 <= P <= 1024, RENYI, alpha}               the row above AT EVERY P (P == 1 too), and kl_mode == PV_KL_SAMPLED; alpha finite
+ *                                               and != 1 (checked by the two calls)
+ *   {1, ELBO, SHARED | PER_IMAGE}               "fc iVAE" as above with 1 .. PV_MAX_CHANNELS channels, and fused = 0, 1 or 2 — or
+ *                                               3 where PV_PLAN_FAST_WEIGHTS takes effect; with that bit, dec_kernel <= 1
+ *   PV_EINVAL whatever the plan (all three functions, before any pointer is read):
+ *     num_particles < 1; an unknown bound or obs_w_kind; obs_w_kind != NONE with num_particles > 1 or RENYI (no kernel weighs
+ *     both); weights_out != NULL with ELBO; and, in the two calls only, obs_w_kind != NONE with obs_w == NULL.
+ * There is no descriptor for pv_ved_*, the semi-supervised calls or pv_ivae_dp_step. */
+int64_t pv_ivae_objective_workspace_bytes(const pv_ivae_plan* plan, const pv_ivae_objective* objective);   /* PV_WS_STEP layout; <0 unsupported */
+int pv_ivae_objective_loss_and_grads(const pv_ivae_plan* plan, const pv_ivae_objective* objective, int want_grads, void* stream);
+int pv_ivae_objective_step(const pv_ivae_plan* plan, const pv_ivae_objective* objective, void* stream);    /* + Adam, as pv_ivae_step */
+
 /* ---- (v17, added without a layout change) the multi-particle ELBO ------------------------------------------------------------
  * pyro.infer.Trace_ELBO(num_particles=P) / TraceMeanField_ELBO(num_particles=P): for images x_b, b < B, and draws eps_pb, p < P,
  *   z_pb = mu_b + sigma_b eps_pb
@@ -416,13 +455,11 @@ int pv_ivae_step(const pv_ivae_plan* plan, void* stream);
  *   scalars keep their slots and scalars[0] = -(scalars[1] + scalars[2] - scalars[3]): each holds the mean over particles of
  *          the term it holds in the one-particle step;
  *   ws     sized by pv_ivae_particles_workspace_bytes (the PV_WS_STEP layout for P particles).
- * num_particles == 1 forwards to pv_ivae_workspace_bytes_for(plan, PV_WS_STEP) / pv_ivae_loss_and_grads / pv_ivae_step (the same
- * launches, the guide folded into the decoder launch where pv_ivae_guide_folds says so); num_particles < 1 is PV_EINVAL.
+ * These are the objective {num_particles, PV_BOUND_ELBO, PV_OBS_W_NONE} (pv_ivae_objective above: scope and PV_EINVAL).
+ * num_particles == 1 is the plain objective: pv_ivae_workspace_bytes_for(plan, PV_WS_STEP) / pv_ivae_loss_and_grads / pv_ivae_step
+ * (the same launches, the guide folded into the decoder launch where pv_ivae_guide_folds says so).
  * For P > 1 the guide never folds into the decoder launch, and every sum over particles runs in a fixed order (no float
- * atomics): a step is bit-reproducible run to run.
- * Scope for P > 1: the fc-encoder iVAE (spatial 1-D / 2-D or vanilla decoder, with or without c_dim, every likelihood, both
- * kl_mode values) with fused = 0, 2 or 3.  PV_EINVAL — from the workspace query too — for discrete_dim > 0 (jiVAE), a
- * convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 1. */
+ * atomics): a step is bit-reproducible run to run. */
 int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles);   /* PV_WS_STEP layout; <0 unsupported */
 int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream);
 int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream);    /* + Adam, as pv_ivae_step */
@@ -445,9 +482,9 @@ int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void
  * On the fused decoder (fused = 2, 3) a gradient step runs the decoder forward twice — once without gradients for the weights,
  * once with them — because that kernel fuses forward and backward; the loss is the first forward's.  Every sum over particles
  * runs in ascending p without atomics: a step is bit-reproducible.
- * num_particles == 1 forwards to the one-particle entry points, bit for bit (weights_out <- 1).
- * PV_EINVAL, at every num_particles and from the workspace query too: alpha == 1 or not finite, num_particles < 1 or > 1024,
- * kl_mode != PV_KL_SAMPLED (the analytic KL has no per-sample weight), and every plan the multi-particle entry points refuse. */
+ * These are the objective {num_particles, PV_BOUND_RENYI, alpha, PV_OBS_W_NONE, -, weights_out} (pv_ivae_objective above: scope
+ * and PV_EINVAL; the analytic KL has no per-sample weight).  num_particles == 1 runs the one-particle launches, bit for bit
+ * (weights_out <- 1). */
 int64_t pv_ivae_renyi_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles);
 int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, float alpha, int want_grads, float* weights_out,
                                  void* stream);
@@ -465,7 +502,8 @@ int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float al
  *   plan      the one-particle step's; loc (optional) is NOT weighted, the encoder sees x as given; the pointer travels next
  *             to the plan, the struct is unchanged.
  *   ws        sized by pv_ivae_weighted_workspace_bytes (a PV_WS_STEP layout of the kernel family that runs, below).
- * pixel_w == NULL forwards to pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
+ * These are the objective {1, PV_BOUND_ELBO, -, PV_OBS_W_SHARED, pixel_w} (pv_ivae_objective above: scope and PV_EINVAL);
+ * pixel_w == NULL is PV_OBS_W_NONE, pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
  * Which kernels run (pv_ivae_weighted_uses_fused: 1 for the fused f32 kernel, 0 for the layer-by-layer kernels):
  *   fused == 0, or a decoder the fused f32 kernels are not written for (pv_ivae_uses_fused's architecture: hidden [128, 128],
  *     tanh, positions a multiple of 16, coord_dim > 0)          the layer-by-layer kernels;
@@ -479,12 +517,8 @@ int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float al
  *     decoder, dec_kernel 0 or 1                                 kernel (fused == 2: three bf16 products, fp32-class results;
  *     fused == 3: plain bf16), run as dec_kernel = 1 with PV_PLAN_NO_ENC_FOLD; pv_ivae_weighted_uses_fused is 1 and the workspace
  *     is that plan's.  With the bit and fused == 2 on any other plan: the rows above.  With the bit and dec_kernel > 1: PV_EINVAL.
- * Scope: the one-particle ELBO in either kl_mode of the fc-encoder iVAE — spatial or vanilla decoder, 1 .. PV_MAX_CHANNELS
- * channels, with or without c_dim, every likelihood.  PV_EINVAL (the workspace query too; pv_ivae_weighted_uses_fused: 0) for
- * discrete_dim > 0, a convolutional or external encoder / decoder, row_w / row_elbo / dy / class_onehot, and fused == 3 (unless
- * PV_PLAN_FAST_WEIGHTS takes effect, above).  There
- * is no weighted form of pv_ivae_particles_*, pv_ivae_renyi_*, pv_ved_*, the semi-supervised calls or pv_ivae_dp_step (a
- * data-parallel caller reduces [gradients | scalars] itself: the loss stays a sum over images). */
+ * pv_ivae_weighted_uses_fused is 0 for a plan outside the scope.  There is no weighted form of pv_ved_*, the semi-supervised
+ * calls or pv_ivae_dp_step (a data-parallel caller reduces [gradients | scalars] itself: the loss stays a sum over images). */
 int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan);                        /* <0 unsupported */
 int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan);
 int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream);
@@ -502,8 +536,9 @@ int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* 
  *   plan      the one-particle step's; loc (optional) is NOT weighted, and the encoder sees x as given — x must be finite
  *             everywhere, also where w == 0.
  *   ws        sized by pv_ivae_weighted_workspace_bytes.
- * image_w == NULL forwards to pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
- * Kernels, scope and PV_EINVAL are those of pv_ivae_weighted_*: every channel count has a per-image instance of the fused f32
+ * These are the objective {1, PV_BOUND_ELBO, -, PV_OBS_W_PER_IMAGE, image_w} (pv_ivae_objective above: scope and PV_EINVAL);
+ * image_w == NULL is PV_OBS_W_NONE, pv_ivae_loss_and_grads / pv_ivae_step: the same launches, bit for bit.
+ * The kernels are those of pv_ivae_weighted_*: every channel count has a per-image instance of the fused f32
  * kernel, so pv_ivae_weighted_workspace_bytes and pv_ivae_weighted_uses_fused answer for these calls too.  The kernels read the
  * weight at the index they read x at; with the shared weights repeated per image the layer-by-layer kernels give the bits of
  * pv_ivae_weighted_* (the fused kernel's instances differ: DESIGN.md 4.15). */

@@ -87,6 +87,16 @@ class pv_ivae_plan(C.Structure):
     ]
 
 
+# the step's objective next to the plan (include/pyroved_amd.h: pv_ivae_objective)
+PV_BOUND_ELBO, PV_BOUND_RENYI = 0, 1
+PV_OBS_W_NONE, PV_OBS_W_SHARED, PV_OBS_W_PER_IMAGE = 0, 1, 2
+
+
+class pv_ivae_objective(C.Structure):
+    _fields_ = [("num_particles", C.c_int32), ("bound", C.c_int32), ("alpha", C.c_float), ("obs_w_kind", C.c_int32),
+                ("obs_w", C.c_void_p), ("weights_out", C.c_void_p)]
+
+
 class pv_ved_plan(C.Structure):
     _fields_ = [
         ("batch", C.c_int32), ("ndim_in", C.c_int32), ("ndim_out", C.c_int32),
@@ -154,6 +164,10 @@ SIGNATURES = {
                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "pv_ivae_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_void_p]),
+    # the objective as one descriptor (v17, added without a layout change): what every family below forwards to
+    "pv_ivae_objective_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan), C.POINTER(pv_ivae_objective)]),
+    "pv_ivae_objective_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.POINTER(pv_ivae_objective), C.c_int, C.c_void_p]),
+    "pv_ivae_objective_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.POINTER(pv_ivae_objective), C.c_void_p]),
     # the multi-particle ELBO (v17, added without a layout change)
     "pv_ivae_particles_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan), C.c_int32]),
     "pv_ivae_particles_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_int, C.c_void_p]),

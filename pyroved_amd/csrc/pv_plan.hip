@@ -62,15 +62,20 @@ struct Layout {
   // multi-particle ELBO (pv_ivae_particles_*): P decoder samples per image ordered [p][b]; z, tp, zy, hz, sw, llkb hold P*B rows.
   // The count travels here, not in the ABI struct; 1 everywhere else
   int P;
-  // importance-weighted (Renyi) bound (pv_ivae_renyi_*; pv_particles.h: pv_renyi_weights): sw is filled with the softmax weights.
-  // Like P, these travel here
-  bool renyi; float r_alpha; float* r_c; float* r_wout;     // c_b (B); the caller's optional (P*B) copy of the weights
+  // importance-weighted (Renyi) bound with P > 1 (pv_particles.h: pv_renyi_weights): sw is filled with the softmax weights, and
+  // c_b (B) gets room behind everything else
+  bool renyi; float* r_c;
   double* pl_part;                                          // Poisson plans: pv_poisson_lognorm's partial sums (PV_POISSON_PARTS doubles)
-  // per-observation weights of the likelihood (pv_ivae_weighted_*): (n_pix) floats shared by all images, or null.  Like P, the
-  // pointer travels here, set by the entry point after carve(); the layout itself does not depend on it
-  const float* pw;
-  bool pw_img;              // pv_ivae_weighted_images_*: pw is (batch * n_pix), one weight per observation of every image (the layout of x)
   int64_t total;
+};
+
+// What the launches read of the step's objective (include/pyroved_amd.h: pv_ivae_objective) that does NOT decide the layout — the
+// call arguments next to the Layout (L.P and L.renyi do decide it and live there).  Filled by resolve(), below
+struct ObjArgs {
+  float alpha = 0.0f; float* wout = nullptr;   // Renyi bound (L.renyi): its order; the caller's optional (P*B) copy of the weights
+  const float* pw = nullptr;                   // per-observation weights of the likelihood: (n_pix) floats shared by all images, or null
+  bool pw_img = false;                         // ... (batch * n_pix) instead: one weight per observation of every image (the layout of x)
+  int fdm() const { return !pw ? 0 : pw_img ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED; }   // the fused decoder kernels' weighted instance
 };
 
 // jiVAE (discrete_dim = K > 0): K decoder samples per input, ordered [k][b]; head = [mu | softplus input | class logits]
@@ -152,9 +157,8 @@ bool valid_plan(const pv_ivae_plan* p) {
 void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1,
            bool renyi = false) {
   Carver c{base, 0};
-  L.pw = nullptr; L.pw_img = false;
   L.P = inference_only ? 1 : P;
-  L.renyi = renyi && L.P > 1; L.r_alpha = 0.0f; L.r_wout = nullptr;
+  L.renyi = renyi && L.P > 1;
   // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
   const int64_t B = p->batch, N = encode_only ? 0 : plan_pos(p), z = p->z_dim, Cn = plan_C(p);
   const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
@@ -770,11 +774,11 @@ PvParticleBwd particle_bwd_desc(const pv_ivae_plan* p, const Layout& L) {
   return pb;
 }
 // the Renyi bound's weights from the P samples' log-likelihoods in L.llkb: sw, the image's KL row, c_b
-int renyi_weights(const pv_ivae_plan* p, const Layout& L, hipStream_t s) {
+int renyi_weights(const pv_ivae_plan* p, const Layout& L, const ObjArgs& o, hipStream_t s) {
   PvRenyiWeights r{};
   r.llkb = L.llkb; r.z = L.z; r.eps = p->eps; r.z_scale = L.z_scale;
-  r.sw = L.sw; r.weights_out = L.r_wout; r.kl_part = L.kl_part; r.c = L.r_c;
-  r.B = (int)p->batch; r.P = L.P; r.z_dim = p->z_dim; r.beta = p->beta; r.alpha = L.r_alpha;
+  r.sw = L.sw; r.weights_out = o.wout; r.kl_part = L.kl_part; r.c = L.r_c;
+  r.B = (int)p->batch; r.P = L.P; r.z_dim = p->z_dim; r.beta = p->beta; r.alpha = o.alpha;
   return pv_renyi_weights(r, s);
 }
 // the scopes of pv_ivae_particles_*: the fc-encoder iVAE (spatial or vanilla decoder, with or without c_dim), layered or on the
@@ -811,7 +815,7 @@ static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L) {
 // ---- loss_and_grads with the fused persistent spatial-decoder kernel (pv_sdec_fused.hip), step by step ----
 // what the steps hand to one another
 struct FusedStep {
-  const pv_ivae_plan* p; const Layout& L; bool grads; hipStream_t s;
+  const pv_ivae_plan* p; const Layout& L; const ObjArgs& o; bool grads; hipStream_t s;
   const float* zin; int64_t ldz;                     // the decoder's latent input: z's content columns, or the materialised concatenation
   int rec_fmt;                                       // the record format the decoder launch writes (pv_sdec_fused.h PV_REC_*)
   PvFused f{};                                       // the decoder launch's arguments
@@ -1031,21 +1035,19 @@ int fused_decoder_launch(FusedStep& st) {
     // (weighted steps on the bf16-class kernels — weighted_route with PV_PLAN_FAST_WEIGHTS: the weights ride in the slot of `park`,
     //  which no 4-wave launch reads; the routed plan's dec_kernel = 1 keeps every launch on the 4-wave kernel)
     PvFused f = st.f;
-    if (st.L.pw) f.park = const_cast<float*>(st.L.pw);
+    if (st.o.pw) f.park = const_cast<float*>(st.o.pw);
     PV_TRY(pv_sdec_fused_bf16_launch(f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
-                                     (st.own_chain() && !st.fold) ? &st.ef : nullptr,
-                                     !st.L.pw ? 0 : st.L.pw_img ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED));
+                                     (st.own_chain() && !st.fold) ? &st.ef : nullptr, st.o.fdm()));
   }
-  else if (plan_fused_mc(p) || st.L.pw) {
+  else if (plan_fused_mc(p) || st.o.pw) {
     // several channels per row: the f32 kernel's sibling, then (training) the sums of channels 1 .. C-1 of d(wo), d(bo) into the
     // flat gradient — in front of every launch that reads it, the one that applies Adam included
-    // (weighted steps, st.L.pw: its weighted instances at every channel count — the entry point routed the plan here,
+    // (weighted steps, st.o.pw: its weighted instances at every channel count — the entry point routed the plan here,
     //  weighted_route; with one channel there is nothing for the second launch to sum)
     PvFused f = st.f;
     f.wimg = nullptr; f.park = nullptr;
-    if (st.L.pw) f.pw = st.L.pw;
-    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s,
-                                   !st.L.pw ? 0 : st.L.pw_img ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED));
+    if (st.o.pw) f.pw = st.o.pw;
+    PV_TRY(pv_sdec_fused_mc_launch(f, (int)plan_C(p), st.L.f_grid, st.grads, st.s, st.o.fdm()));
     if (st.grads && plan_C(p) > 1) PV_TRY(pv_sdec_fused_mc_reduce_out(st.L.f_part, st.L.f_grid, p->grads, p->out.w_off, p->out.b_off, (int)plan_C(p), st.s));
   }
   else PV_TRY(pv_sdec_fused_launch(st.f, st.L.f_grid, st.grads, st.s));
@@ -1069,7 +1071,7 @@ int fused_close_forward(const FusedStep& st) {
     pf.llrow = L.llrow; pf.M = L.rows; pf.N = (int)N; pf.kmax = 1; pf.fwd_only = 1;
     if (L.renyi) {                                   // ... with the bound's weights: llb[b] = sum_p w_pb ll_pb + c_b
       PV_TRY(pv_segsum(L.llrow, step_S(p, L), N, L.llkb, s));
-      PV_TRY(renyi_weights(p, L, s));
+      PV_TRY(renyi_weights(p, L, st.o, s));
       pf.llkb = L.llkb;
     }
     PV_TRY(pv_particle_bwd(pf, s));
@@ -1098,7 +1100,7 @@ int fused_renyi_forward(const FusedStep& st) {
   PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, x3, s));
   if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, x3, s));
   PV_TRY(pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s));
-  return renyi_weights(p, L, s);
+  return renyi_weights(p, L, st.o, s);
 }
 
 int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
@@ -1127,13 +1129,13 @@ int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
 }
 
 // the step's launch sequence
-int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s,
+int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, const ObjArgs& obj, int want_grads, hipStream_t s,
                          const PvAdamFuse* adam = nullptr, bool* adam_done = nullptr) {
   const int64_t K = plan_K(p), lat_in = plan_lat_in(p);
   if (p->fc_latent.in_dim != lat_in) return PV_EINVAL;
   if (K > 0 && !L.enc_compact) return PV_EINVAL;
   const bool cat_in = p->c_dim > 0 || K > 0;         // the decoder's latent input is a materialised concatenation
-  FusedStep st{p, L, want_grads != 0, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
+  FusedStep st{p, L, obj, want_grads != 0, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
                p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, plan_sel(p)) : PV_REC_ROWMAJOR};
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
@@ -1143,7 +1145,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, int want_grads,
   return want_grads ? fused_close(st, adam, adam_done) : fused_close_forward(st);
 }
 
-int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grads, hipStream_t s) {
+int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, const ObjArgs& obj, int want_grads, hipStream_t s) {
   const int64_t K = plan_K(p);
   // N: rows per sample of the spatial decoder (positions; Cn channels each) or the vanilla decoder's output width
   const int64_t B = p->batch, N = plan_pos(p), Cn = plan_C(p), R = L.rows, z = p->z_dim;
@@ -1184,7 +1186,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     o.dpre = (want_grads && !renyi) ? cur : nullptr; o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = R; o.H = Hl;
     o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
     o.sw = reps > 1 ? L.sw : p->row_w; o.N = (int)N; o.xmod = reps > 1 ? B * N : 0;
-    o.pw = L.pw; o.pw_img = L.pw_img ? 1 : 0;
+    o.pw = obj.pw; o.pw_img = obj.pw_img ? 1 : 0;
     PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
   } else {
     // oth <- dL/dlogits (R, N); jiVAE: one pass per enumerated class against the same observations, rows then
@@ -1193,7 +1195,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
     for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
                          p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s,
-                         L.pw, N, L.pw_img));
+                         obj.pw, N, obj.pw_img));
     if (reps > 1 && want_grads && !renyi) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
@@ -1209,7 +1211,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, int want_grad
   } else if (P > 1) {                                // llb[b] = sum_p sw ll_pb
     PV_TRY(pv_segsum(L.llrow, S, N, L.llkb, s));
     if (renyi) {
-      PV_TRY(renyi_weights(p, L, s));
+      PV_TRY(renyi_weights(p, L, obj, s));
       if (want_grads && p->coord_dim > 0) {            // the second likelihood pass: dL/dpre and the output layer's partials
         o.dpre = cur; o.llrow = nullptr; o.loc = nullptr;
         PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
@@ -1454,50 +1456,14 @@ extern "C" int pv_debug_ivae_conv_trace(const pv_ivae_plan* plan, int64_t* out) 
   return 0;
 }
 
-// the Renyi bound's arguments next to the plan (null: the ELBO)
-struct RenyiArgs { float alpha; float* weights_out; };
-static void set_renyi(Layout& L, const RenyiArgs* rn) {
-  if (L.renyi) { L.r_alpha = rn->alpha; L.r_wout = rn->weights_out; }
-}
-
 // Poisson plans: the data-only normaliser C = sum lgamma(x + 1) into the finished scalars ([1] -= C, [0] += C): two small trailing
 // launches on the caller's stream (partial sums, then their fixed-order sum), after the step's own launches and before anything
 // reads the scalars.  The same
 // correction for every objective (C does not depend on the latent sample).  The sampled-class jiVAE objective is the exception:
 // its score-function term needs the per-image value, which went into llkb in front of pv_jiv_combine_sampled (nothing to do here).
-static int poisson_lognorm(const pv_ivae_plan* plan, const Layout& L, hipStream_t s) {
+static int poisson_lognorm(const pv_ivae_plan* plan, const Layout& L, const ObjArgs& o, hipStream_t s) {
   if (plan->lik != PV_LIK_POISSON_LOG || (plan_K(plan) > 0 && plan->class_onehot)) return 0;
-  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s, L.pw, plan->n_pix,
-                            L.pw_img);
-}
-
-// P: particles of the ELBO estimate (1: pv_ivae_loss_and_grads itself)
-// pw: per-observation weights (pv_ivae_weighted_*: `plan` is then the routed copy, weighted_route) or null; pw_img: one per
-// observation of every image (pv_ivae_weighted_images_*)
-static int loss_and_grads_impl(const pv_ivae_plan* plan, int P, int want_grads, void* stream, const RenyiArgs* rn = nullptr,
-                               const float* pw = nullptr, bool pw_img = false) {
-  if (plan && plan->ext_decoder) return PV_EINVAL;      // (pv_ivae_guide / pv_ivae_guide_backward)
-  if (!valid_plan(plan) || !plan->params || !plan->x || !plan->eps || !plan->scalars || !plan->ws) return PV_EINVAL;
-  if (want_grads && !plan->grads) return PV_EINVAL;
-  if (plan->ext_encoder && (!plan->ext_head || (want_grads && !plan->ext_dhead))) return PV_EINVAL;
-  if (plan->coord_dim > 0 && !plan->grid) return PV_EINVAL;
-  if (P < 1 || (P > 1 && !particles_supported(plan))) return PV_EINVAL;
-  Layout L;
-  carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
-  set_renyi(L, rn);
-  L.pw = pw; L.pw_img = pw && pw_img;
-  if (plan->ws_bytes < L.total) return PV_EWS;
-  hipStream_t s = (hipStream_t)stream;
-  // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
-  // cannot run it with invariances (models/jivae.py:181-189) — and only the layer-by-layer path implements it
-  if (plan->class_onehot && (L.fused || plan->coord_dim > 0)) return PV_EINVAL;
-  if (L.fused) PV_TRY(loss_and_grads_fused(plan, L, want_grads, s));
-  else PV_TRY(loss_and_grads_layered(plan, L, want_grads, s));
-  return poisson_lognorm(plan, L, s);
-}
-extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, void* stream) {
-  PV_RANGE("pv_ivae_loss_and_grads");
-  return loss_and_grads_impl(plan, 1, want_grads, stream);
+  return pv_poisson_lognorm(plan->x, (int64_t)plan->batch * plan->n_pix, L.pl_part, plan->scalars, s, o.pw, plan->n_pix, o.pw_img);
 }
 
 // ---- external decoder (plan->ext_decoder): the library's half of the step works on a copy of the plan whose decoder is
@@ -1546,45 +1512,6 @@ extern "C" int pv_ivae_guide_backward(const pv_ivae_plan* plan, int want_grads, 
   return latent_encoder_bwd(&q, L, q.z_dim, 4, 1, s);
 }
 
-// SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
-// gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
-// pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
-static int step_impl(const pv_ivae_plan* plan, int P, void* stream, const RenyiArgs* rn = nullptr, const float* pw = nullptr,
-                     bool pw_img = false) {
-  if (P < 1 || (P > 1 && !(valid_plan(plan) && particles_supported(plan)))) return PV_EINVAL;
-  if (plan && !plan->ext_decoder && valid_plan(plan) && plan->params && plan->x && plan->eps && plan->scalars && plan->ws &&
-      plan->grads && plan->adam_m && plan->adam_v && plan->adam_step >= 1 && plan->n_params > 0 &&
-      !(plan->coord_dim > 0 && !plan->grid) && !plan->ext_encoder &&
-      // extra outputs (dy, row_elbo) are computed AFTER the encoder backward from the first-layer weights: with Adam
-      // riding in that launch they would see the updated weights — such plans take the two-call sequence below
-      !plan->dy && !plan->row_elbo) {
-    Layout L;
-    carve(plan, (char*)plan->ws, L, false, false, P, rn != nullptr);
-    set_renyi(L, rn);
-    L.pw = pw; L.pw_img = pw && pw_img;
-    if (plan->ws_bytes < L.total) return PV_EWS;
-    if (L.fused && (L.enc_compact || L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
-      const double bc1 = 1.0 - pow((double)plan->adam_beta1, (double)plan->adam_step);
-      const double bc2 = 1.0 - pow((double)plan->adam_beta2, (double)plan->adam_step);
-      const PvAdamFuse ad{plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->adam_beta1,
-                          plan->adam_beta2, plan->adam_eps, (float)((double)plan->lr / bc1), (float)sqrt(bc2)};
-      bool done = false;
-      PV_TRY(loss_and_grads_fused(plan, L, 1, (hipStream_t)stream, &ad, &done));
-      PV_TRY(poisson_lognorm(plan, L, (hipStream_t)stream));
-      if (done) return 0;
-      return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
-                          plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
-    }
-  }
-  PV_TRY(loss_and_grads_impl(plan, P, 1, stream, rn, pw, pw_img));
-  return pv_adam_step(plan->params, plan->grads, plan->adam_m, plan->adam_v, plan->n_params, plan->lr,
-                      plan->adam_beta1, plan->adam_beta2, plan->adam_eps, plan->adam_step, stream);
-}
-extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
-  PV_RANGE("pv_ivae_step");
-  return step_impl(plan, 1, stream);
-}
-
 // ---- per-observation weights of the likelihood (v17, added without a layout change; include/pyroved_amd.h) ----
 // loss = -( sum_b sum_i w_i log p(x_bi | z_b) + beta sum_b [log p(z_b) - log q(z_b | x_b)] ), w (n_pix) shared by all images.
 // Scope: the one-particle ELBO (either KL form) of the fc-encoder iVAE, spatial or vanilla decoder, every likelihood
@@ -1619,13 +1546,6 @@ static pv_ivae_plan weighted_route(const pv_ivae_plan* p, bool per_image = false
   if (!(q.fused == 1 && pv_sdec_fused_mc_weighted_supported(&q, per_image) && plan_fused_ok(&q))) q.fused = 0;
   return q;
 }
-extern "C" int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan) {
-  if (!weighted_scope(plan)) return PV_EINVAL;
-  const pv_ivae_plan q = weighted_route(plan);
-  Layout L;
-  carve(&q, nullptr, L);
-  return L.total;
-}
 extern "C" int pv_ivae_weighted_uses_fused(const pv_ivae_plan* plan) {
   if (!weighted_scope(plan)) return 0;
   const pv_ivae_plan q = weighted_route(plan);
@@ -1643,92 +1563,191 @@ extern "C" const char* pv_debug_weighted_decoder_kernel_name(const pv_ivae_plan*
            per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED);
   return buf;
 }
-extern "C" int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream) {
-  if (!pixel_w) return pv_ivae_loss_and_grads(plan, want_grads, stream);
-  PV_RANGE("pv_ivae_weighted_loss_and_grads");
-  if (!weighted_scope(plan)) return PV_EINVAL;
-  const pv_ivae_plan q = weighted_route(plan);
-  return loss_and_grads_impl(&q, 1, want_grads, stream, nullptr, pixel_w);
-}
-extern "C" int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* stream) {
-  if (!pixel_w) return pv_ivae_step(plan, stream);
-  PV_RANGE("pv_ivae_weighted_step");
-  if (!weighted_scope(plan)) return PV_EINVAL;
-  const pv_ivae_plan q = weighted_route(plan);
-  return step_impl(&q, 1, stream, nullptr, pixel_w);
-}
-
-// ---- one weight per observation of every image (v17, added without a layout change; include/pyroved_amd.h) ----
-// loss = -( sum_b sum_i w_bi log p(x_bi | z_b) + beta sum_b [...] ), image_w (batch * n_pix) in the layout of plan->x.  Scope,
-// routing and workspace are pv_ivae_weighted_*'s (every per-image instance of the fused f32 kernel exists, so
-// pv_ivae_weighted_workspace_bytes / pv_ivae_weighted_uses_fused answer for these calls too); the kernels read the weight at the
-// index they read x at
-extern "C" int pv_ivae_weighted_images_loss_and_grads(const pv_ivae_plan* plan, const float* image_w, int want_grads, void* stream) {
-  if (!image_w) return pv_ivae_loss_and_grads(plan, want_grads, stream);
-  PV_RANGE("pv_ivae_weighted_images_loss_and_grads");
-  if (!weighted_scope(plan)) return PV_EINVAL;
-  const pv_ivae_plan q = weighted_route(plan, true);
-  return loss_and_grads_impl(&q, 1, want_grads, stream, nullptr, image_w, true);
-}
-extern "C" int pv_ivae_weighted_images_step(const pv_ivae_plan* plan, const float* image_w, void* stream) {
-  if (!image_w) return pv_ivae_step(plan, stream);
-  PV_RANGE("pv_ivae_weighted_images_step");
-  if (!weighted_scope(plan)) return PV_EINVAL;
-  const pv_ivae_plan q = weighted_route(plan, true);
-  return step_impl(&q, 1, stream, nullptr, image_w, true);
-}
-
-// ---- the multi-particle ELBO (v17, added without a layout change; include/pyroved_amd.h) ----
-extern "C" int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
-  if (num_particles < 1) return PV_EINVAL;
-  if (num_particles == 1) return pv_ivae_workspace_bytes_for(plan, PV_WS_STEP);
-  if (!valid_plan(plan) || !particles_supported(plan)) return PV_EINVAL;
-  Layout L;
-  carve(plan, nullptr, L, false, false, num_particles);
-  return L.total;
-}
-extern "C" int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream) {
-  PV_RANGE("pv_ivae_particles_loss_and_grads");
-  return loss_and_grads_impl(plan, num_particles, want_grads, stream);
-}
-extern "C" int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream) {
-  PV_RANGE("pv_ivae_particles_step");
-  return step_impl(plan, num_particles, stream);
-}
 
 // ---- the importance-weighted (Renyi / IWAE) bound (v17, added without a layout change; include/pyroved_amd.h) ----
-// everything the multi-particle entry points refuse, at every P; the sampled KL form only (the analytic one has no per-sample weight)
+// everything the multi-particle objective refuses, at every P; the sampled KL form only (the analytic one has no per-sample weight)
 static bool renyi_ok(const pv_ivae_plan* plan, int32_t P, float alpha) {
   return P >= 1 && P <= PV_RENYI_MAX_P && std::isfinite(alpha) && alpha != 1.0f && valid_plan(plan) && particles_supported(plan) &&
          plan->kl_mode == PV_KL_SAMPLED;
 }
-extern "C" int64_t pv_ivae_renyi_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
-  if (!renyi_ok(plan, num_particles, 0.0f)) return PV_EINVAL;
-  if (num_particles == 1) return pv_ivae_workspace_bytes_for(plan, PV_WS_STEP);
-  Layout L;
-  carve(plan, nullptr, L, false, false, num_particles, true);
-  return L.total;
+
+// ---- one resolution of (plan, objective) behind the workspace query and the two calls (include/pyroved_amd.h: pv_ivae_objective) ----
+struct Resolved {
+  const pv_ivae_plan* plan; pv_ivae_plan routed;   // the plan to run: the caller's, or the copy a route made (`routed`)
+  Layout L; ObjArgs o;
+  float* ones;                                      // Renyi bound with ONE particle: the caller's weights_out — the bound is the ELBO,
+};                                                  // the one weight per image is 1, written behind the step's launches
+// Validates the descriptor alone and against the plan, routes, carves; PV_EINVAL before any
+// pointer is touched.  call == false: the workspace query (offsets only: r.L.total), call == true: a call that runs — the plan's
+// buffers are checked as well (want_grads: the gradient buffers too), the workspace's size last (PV_EWS).
+static int resolve(const pv_ivae_plan* plan, const pv_ivae_objective& d, bool call, int want_grads, Resolved& r) {
+  const int P = d.num_particles;
+  const bool renyi = d.bound == PV_BOUND_RENYI, per_image = d.obs_w_kind == PV_OBS_W_PER_IMAGE;
+  const bool weighted = d.obs_w_kind == PV_OBS_W_SHARED || per_image;
+  if ((!renyi && d.bound != PV_BOUND_ELBO) || (!weighted && d.obs_w_kind != PV_OBS_W_NONE) || P < 1) return PV_EINVAL;
+  // combinations no kernel path exists for: weights with several particles or the Renyi bound; the bound's output without the bound
+  if ((weighted && (P > 1 || renyi)) || (!renyi && d.weights_out) || (call && weighted && !d.obs_w)) return PV_EINVAL;
+  if (renyi && !renyi_ok(plan, P, call ? d.alpha : 0.0f)) return PV_EINVAL;      // (the query does not see alpha)
+  r.plan = plan;
+  if (weighted) {
+    if (!weighted_scope(plan)) return PV_EINVAL;
+    r.routed = weighted_route(plan, per_image);
+    r.plan = &r.routed;
+  } else if (plan && plan->ext_decoder) {           // only the guide half runs in the library (pv_ivae_guide / pv_ivae_guide_backward):
+    if (call || ext_decoder_channels(plan)) return PV_EINVAL;                     // no step, and PV_WS_STEP is that half's layout
+    r.routed = guide_plan(plan);
+    r.plan = &r.routed;
+  }
+  const pv_ivae_plan* p = r.plan;
+  // (a weighted route's copy — the caller's plan passed weighted_scope — is validated by the calls only: a dec_kernel naming a
+  //  bf16-class build is PV_EINVAL on the f32 kernel the route chose, while the query has always answered with that plan's size)
+  if (((call || !weighted) && !valid_plan(p)) || (P > 1 && !particles_supported(p))) return PV_EINVAL;
+  if (call) {
+    if (!p->params || !p->x || !p->eps || !p->scalars || !p->ws || (want_grads && !p->grads)) return PV_EINVAL;
+    if (p->ext_encoder && (!p->ext_head || (want_grads && !p->ext_dhead))) return PV_EINVAL;
+    if (p->coord_dim > 0 && !p->grid) return PV_EINVAL;
+  }
+  carve(p, call ? (char*)p->ws : nullptr, r.L, false, false, P, renyi);
+  if (call && p->ws_bytes < r.L.total) return PV_EWS;
+  r.o = ObjArgs{};
+  if (r.L.renyi) { r.o.alpha = d.alpha; r.o.wout = d.weights_out; }
+  if (weighted) { r.o.pw = d.obs_w; r.o.pw_img = per_image; }
+  r.ones = (renyi && P == 1) ? d.weights_out : nullptr;
+  return 0;
 }
-// P = 1: the bound is the ELBO and the one weight per image is 1
-static int renyi_one_particle_weights(const pv_ivae_plan* plan, float* weights_out, void* stream) {
-  if (!weights_out) return 0;
-  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)weights_out, 0x3f800000 /* 1.0f */, (size_t)plan->batch, (hipStream_t)stream);
+static int one_particle_weights(const Resolved& r, void* stream) {
+  if (!r.ones) return 0;
+  const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)r.ones, 0x3f800000 /* 1.0f */, (size_t)r.plan->batch, (hipStream_t)stream);
   return e == hipSuccess ? 0 : (int)e;
+}
+
+static int64_t workspace_bytes_impl(const pv_ivae_plan* plan, const pv_ivae_objective& d) {
+  Resolved r;
+  const int e = resolve(plan, d, false, 0, r);
+  return e ? e : r.L.total;
+}
+
+// the step's launches without the optimizer
+static int launches(const Resolved& r, int want_grads, hipStream_t s) {
+  const pv_ivae_plan* p = r.plan;
+  // the sampled-class objective (Trace_ELBO on a drawn class) exists for the vanilla decoder only — the reference's own model
+  // cannot run it with invariances (models/jivae.py:181-189) — and only the layer-by-layer path implements it
+  if (p->class_onehot && (r.L.fused || p->coord_dim > 0)) return PV_EINVAL;
+  if (r.L.fused) PV_TRY(loss_and_grads_fused(p, r.L, r.o, want_grads, s));
+  else PV_TRY(loss_and_grads_layered(p, r.L, r.o, want_grads, s));
+  return poisson_lognorm(p, r.L, r.o, s);
+}
+static int loss_and_grads_impl(const pv_ivae_plan* plan, const pv_ivae_objective& d, int want_grads, void* stream) {
+  Resolved r;
+  PV_TRY(resolve(plan, d, true, want_grads, r));
+  PV_TRY(launches(r, want_grads, (hipStream_t)stream));
+  return one_particle_weights(r, stream);
+}
+
+// SVI.step in one call.  On the fused-decoder path with the compact encoder or a conv encoder the Adam update rides in the last
+// gradient launch (pv_wgrad.hip: every element is updated by whoever finalises its gradient; bit-identical to
+// pv_ivae_loss_and_grads + pv_adam_step, one launch fewer); everywhere else it is exactly that pair of calls.
+static int step_impl(const pv_ivae_plan* plan, const pv_ivae_objective& d, void* stream) {
+  Resolved r;
+  PV_TRY(resolve(plan, d, true, 1, r));
+  const pv_ivae_plan* p = r.plan;
+  hipStream_t s = (hipStream_t)stream;
+  bool done = false;
+  // extra outputs (dy, row_elbo) are computed AFTER the encoder backward from the first-layer weights: with Adam
+  // riding in that launch they would see the updated weights — such plans take the two-call sequence
+  if (p->adam_m && p->adam_v && p->adam_step >= 1 && p->n_params > 0 && !p->ext_encoder && !p->dy && !p->row_elbo &&
+      r.L.fused && (r.L.enc_compact || r.L.enc_conv)) {  // (conv encoder: in the launch of fc_latent's weight gradient, the step's last)
+    const double bc1 = 1.0 - pow((double)p->adam_beta1, (double)p->adam_step);
+    const double bc2 = 1.0 - pow((double)p->adam_beta2, (double)p->adam_step);
+    const PvAdamFuse ad{p->params, p->grads, p->adam_m, p->adam_v, p->n_params, p->adam_beta1,
+                        p->adam_beta2, p->adam_eps, (float)((double)p->lr / bc1), (float)sqrt(bc2)};
+    PV_TRY(loss_and_grads_fused(p, r.L, r.o, 1, s, &ad, &done));
+    PV_TRY(poisson_lognorm(p, r.L, r.o, s));
+  } else {
+    PV_TRY(launches(r, 1, s));
+  }
+  if (!done)
+    PV_TRY(pv_adam_step(p->params, p->grads, p->adam_m, p->adam_v, p->n_params, p->lr, p->adam_beta1, p->adam_beta2, p->adam_eps,
+                        p->adam_step, stream));
+  return one_particle_weights(r, stream);
+}
+
+// ---- the entry points: every public function opens its own range and hands its objective to the three functions above ----
+// (a null descriptor is the plain one-particle ELBO)
+static const pv_ivae_objective plain_obj = {1, PV_BOUND_ELBO, 0.0f, PV_OBS_W_NONE, nullptr, nullptr};
+static pv_ivae_objective particles_obj(int32_t P) { return {P, PV_BOUND_ELBO, 0.0f, PV_OBS_W_NONE, nullptr, nullptr}; }
+static pv_ivae_objective renyi_obj(int32_t P, float alpha, float* weights_out) {
+  return {P, PV_BOUND_RENYI, alpha, PV_OBS_W_NONE, nullptr, weights_out};
+}
+// (a null weight pointer is the plain call)
+static pv_ivae_objective weights_obj(int kind, const float* w) { return {1, PV_BOUND_ELBO, 0.0f, w ? kind : PV_OBS_W_NONE, w, nullptr}; }
+
+extern "C" int64_t pv_ivae_objective_workspace_bytes(const pv_ivae_plan* plan, const pv_ivae_objective* objective) {
+  return workspace_bytes_impl(plan, objective ? *objective : plain_obj);
+}
+extern "C" int pv_ivae_objective_loss_and_grads(const pv_ivae_plan* plan, const pv_ivae_objective* objective, int want_grads,
+                                                void* stream) {
+  PV_RANGE("pv_ivae_objective_loss_and_grads");
+  return loss_and_grads_impl(plan, objective ? *objective : plain_obj, want_grads, stream);
+}
+extern "C" int pv_ivae_objective_step(const pv_ivae_plan* plan, const pv_ivae_objective* objective, void* stream) {
+  PV_RANGE("pv_ivae_objective_step");
+  return step_impl(plan, objective ? *objective : plain_obj, stream);
+}
+
+extern "C" int pv_ivae_loss_and_grads(const pv_ivae_plan* plan, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_loss_and_grads");
+  return loss_and_grads_impl(plan, plain_obj, want_grads, stream);
+}
+extern "C" int pv_ivae_step(const pv_ivae_plan* plan, void* stream) {
+  PV_RANGE("pv_ivae_step");
+  return step_impl(plan, plain_obj, stream);
+}
+
+extern "C" int64_t pv_ivae_particles_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
+  return workspace_bytes_impl(plan, particles_obj(num_particles));
+}
+extern "C" int pv_ivae_particles_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_particles_loss_and_grads");
+  return loss_and_grads_impl(plan, particles_obj(num_particles), want_grads, stream);
+}
+extern "C" int pv_ivae_particles_step(const pv_ivae_plan* plan, int32_t num_particles, void* stream) {
+  PV_RANGE("pv_ivae_particles_step");
+  return step_impl(plan, particles_obj(num_particles), stream);
+}
+
+extern "C" int64_t pv_ivae_renyi_workspace_bytes(const pv_ivae_plan* plan, int32_t num_particles) {
+  return workspace_bytes_impl(plan, renyi_obj(num_particles, 0.0f, nullptr));
 }
 extern "C" int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles, float alpha, int want_grads,
                                             float* weights_out, void* stream) {
   PV_RANGE("pv_ivae_renyi_loss_and_grads");
-  if (!renyi_ok(plan, num_particles, alpha)) return PV_EINVAL;
-  const RenyiArgs rn{alpha, weights_out};
-  PV_TRY(loss_and_grads_impl(plan, num_particles, want_grads, stream, num_particles > 1 ? &rn : nullptr));
-  return num_particles == 1 ? renyi_one_particle_weights(plan, weights_out, stream) : 0;
+  return loss_and_grads_impl(plan, renyi_obj(num_particles, alpha, weights_out), want_grads, stream);
 }
 extern "C" int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream) {
   PV_RANGE("pv_ivae_renyi_step");
-  if (!renyi_ok(plan, num_particles, alpha)) return PV_EINVAL;
-  const RenyiArgs rn{alpha, weights_out};
-  PV_TRY(step_impl(plan, num_particles, stream, num_particles > 1 ? &rn : nullptr));
-  return num_particles == 1 ? renyi_one_particle_weights(plan, weights_out, stream) : 0;
+  return step_impl(plan, renyi_obj(num_particles, alpha, weights_out), stream);
+}
+
+// (the query of both weighted families: it never sees the pointer, and the per-image instances' list is the shared ones')
+extern "C" int64_t pv_ivae_weighted_workspace_bytes(const pv_ivae_plan* plan) {
+  return workspace_bytes_impl(plan, pv_ivae_objective{1, PV_BOUND_ELBO, 0.0f, PV_OBS_W_SHARED, nullptr, nullptr});
+}
+extern "C" int pv_ivae_weighted_loss_and_grads(const pv_ivae_plan* plan, const float* pixel_w, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_weighted_loss_and_grads");
+  return loss_and_grads_impl(plan, weights_obj(PV_OBS_W_SHARED, pixel_w), want_grads, stream);
+}
+extern "C" int pv_ivae_weighted_step(const pv_ivae_plan* plan, const float* pixel_w, void* stream) {
+  PV_RANGE("pv_ivae_weighted_step");
+  return step_impl(plan, weights_obj(PV_OBS_W_SHARED, pixel_w), stream);
+}
+extern "C" int pv_ivae_weighted_images_loss_and_grads(const pv_ivae_plan* plan, const float* image_w, int want_grads, void* stream) {
+  PV_RANGE("pv_ivae_weighted_images_loss_and_grads");
+  return loss_and_grads_impl(plan, weights_obj(PV_OBS_W_PER_IMAGE, image_w), want_grads, stream);
+}
+extern "C" int pv_ivae_weighted_images_step(const pv_ivae_plan* plan, const float* image_w, void* stream) {
+  PV_RANGE("pv_ivae_weighted_images_step");
+  return step_impl(plan, weights_obj(PV_OBS_W_PER_IMAGE, image_w), stream);
 }
 
 extern "C" int pv_ivae_encode(const pv_ivae_plan* plan, float* z_loc, float* z_scale, void* stream) {

@@ -761,7 +761,18 @@ class IVAEEngine:
         p.grid = self.grid.data_ptr() if self.grid is not None else None
         p.scalars = self.scalars.data_ptr()
         p.lr, p.adam_beta1, p.adam_beta2, p.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
+        self._objective = self._objective_desc()       # (rebuilt wherever the static plan is: bind, configure)
         return p
+
+    def _objective_desc(self) -> _abi.pv_ivae_objective:
+        """The step's objective as the library takes it (pv_ivae_objective), from the engine's settings; the two device pointers
+        (obs_w, weights_out) are written per call.  Per-image weights carry the shared ones as a factor, so they win the kind."""
+        o = _abi.pv_ivae_objective()
+        o.num_particles = self.particles
+        o.bound, o.alpha = (_abi.PV_BOUND_ELBO, 0.0) if self.renyi is None else (_abi.PV_BOUND_RENYI, self.renyi)
+        o.obs_w_kind = (_abi.PV_OBS_W_PER_IMAGE if self.image_weights else
+                        _abi.PV_OBS_W_SHARED if self.pixel_weights is not None else _abi.PV_OBS_W_NONE)
+        return o
 
     def _plan(self, batch: int, beta: float = 1.0, what: int = 1) -> _abi.pv_ivae_plan:
         """what: 1 = training step, 2 = encode, 3 = decode (PV_WS_*): the workspace grows to what that call needs."""
@@ -784,12 +795,8 @@ class IVAEEngine:
         p.ev_start, p.ev_stop = self.events
         ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
-        if what == 1 and (self.pixel_weights is not None or self.image_weights):   # the layout of the kernel family the weighted step runs
-            need = _abi.lib().pv_ivae_weighted_workspace_bytes(C.byref(p))
-        elif what == 1 and self.renyi is not None:       # ... plus the bound's per-image term
-            need = _abi.lib().pv_ivae_renyi_workspace_bytes(C.byref(p), self.particles)
-        elif what == 1 and self.particles > 1:           # the training step's layout for P decoder samples per image
-            need = _abi.lib().pv_ivae_particles_workspace_bytes(C.byref(p), self.particles)
+        if what == 1:                                    # the training step's layout for this engine's objective
+            need = _abi.lib().pv_ivae_objective_workspace_bytes(C.byref(p), C.byref(self._objective))
         else:
             need = _abi.lib().pv_ivae_workspace_bytes_for(C.byref(p), what)
         if need < 0:
@@ -831,6 +838,8 @@ class IVAEEngine:
                        weights_out: Optional[torch.Tensor] = None, image_weights=None):
         """Enqueues Trace_ELBO.loss_and_grads (self.kl == "analytic": TraceMeanField_ELBO's) on the current stream.  Results land in
         self.scalars (device, 4 floats) and self.grad[:n_flat]; nothing is synchronised.
+        The engine's objective goes to the library as one descriptor (self._objective: pv_ivae_objective_loss_and_grads /
+        pv_ivae_objective_step); the entry points named below are the ones that descriptor stands for.
         row_w (B): per-sample weights of the ELBO terms; row_elbo (B) / dy (B, c_dim): extra outputs
         (include/pyroved_amd.h: pv_ivae_plan.row_w / row_elbo / dy).
         step=True: the whole SVI.step — the Adam update follows in the same library call (pv_ivae_step; on the fused
@@ -854,18 +863,18 @@ class IVAEEngine:
         self.ensure_bound()
         P = self.particles
         alpha = self.renyi
-        if (P > 1 or alpha is not None) and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
-                                             or class_onehot is not None):
-            raise ValueError("particles > 1 / renyi cannot be combined with comm=, row_w, row_elbo, dy or class_onehot")
         pw = self.pixel_weights
+        extras = comm is not None or row_w is not None or row_elbo is not None or dy is not None or class_onehot is not None
+        # (weights that do not match the engine's image_weights setting are refused for that, below)
+        weighted = (pw is not None or image_weights is not None) and self.image_weights == (image_weights is not None)
+        if extras and (P > 1 or alpha is not None or weighted):
+            raise ValueError("%s cannot be combined with comm=, row_w, row_elbo, dy or class_onehot"
+                             % ("particles > 1 / renyi" if (P > 1 or alpha is not None) else
+                                "pixel_weights" if not self.image_weights else "image_weights"))
         if self.image_weights != (image_weights is not None):
             if image_weights is None:
                 raise ValueError("this engine was made with image_weights=True: every call needs image_weights=w, the batch's weights")
             raise ValueError("image_weights= needs an engine configured for it: model.engine(image_weights=True)")
-        if (pw is not None or image_weights is not None) and (comm is not None or row_w is not None or row_elbo is not None or dy is not None
-                                 or class_onehot is not None):
-            raise ValueError("%s cannot be combined with comm=, row_w, row_elbo, dy or class_onehot"
-                             % ("pixel_weights" if not self.image_weights else "image_weights"))
         iw = None
         if image_weights is not None:                     # (shape and dtype, before anything is planned or enqueued)
             iw = self._image_weight_tensor(image_weights, int(x.shape[0]), math.prod(int(d) for d in self.model.data_dim) * int(self.C))
@@ -929,6 +938,9 @@ class IVAEEngine:
         if class_onehot is not None and self.K <= 0:
             raise ValueError("class_onehot needs a model with a discrete latent (models.jiVAE)")
         p.class_onehot = class_onehot.data_ptr() if class_onehot is not None else None
+        obj = self._objective
+        obj.obs_w = (iw if iw is not None else pw).data_ptr() if (iw is not None or pw is not None) else None
+        obj.weights_out = weights_out.data_ptr() if weights_out is not None else None
         try:
             if step:
                 p.lr, p.adam_beta1, p.adam_beta2, p.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
@@ -938,36 +950,13 @@ class IVAEEngine:
                         _abi.require_device(hist_out, "hist_out")
                     _abi.check(_abi.lib().pv_ivae_dp_step(C.byref(p), comm.handle, _abi.ptr(hist_out), _abi.current_stream()),
                                "pv_ivae_dp_step")
-                elif alpha is not None:
-                    _abi.check(_abi.lib().pv_ivae_renyi_step(C.byref(p), P, alpha, _abi.ptr(weights_out), _abi.current_stream()),
-                               "pv_ivae_renyi_step")
-                elif P > 1:
-                    _abi.check(_abi.lib().pv_ivae_particles_step(C.byref(p), P, _abi.current_stream()), "pv_ivae_particles_step")
-                elif iw is not None:
-                    _abi.check(_abi.lib().pv_ivae_weighted_images_step(C.byref(p), _abi.ptr(iw), _abi.current_stream()),
-                               "pv_ivae_weighted_images_step")
-                elif pw is not None:
-                    _abi.check(_abi.lib().pv_ivae_weighted_step(C.byref(p), _abi.ptr(pw), _abi.current_stream()),
-                               "pv_ivae_weighted_step")
                 else:
-                    _abi.check(_abi.lib().pv_ivae_step(C.byref(p), _abi.current_stream()), "pv_ivae_step")
+                    _abi.check(_abi.lib().pv_ivae_objective_step(C.byref(p), C.byref(obj), _abi.current_stream()),
+                               "pv_ivae_objective_step")
                 self.adam_t += 1
-            elif alpha is not None:
-                _abi.check(_abi.lib().pv_ivae_renyi_loss_and_grads(C.byref(p), P, alpha, int(want_grads), _abi.ptr(weights_out),
-                                                                   _abi.current_stream()), "pv_ivae_renyi_loss_and_grads")
-            elif P > 1:
-                _abi.check(_abi.lib().pv_ivae_particles_loss_and_grads(C.byref(p), P, int(want_grads), _abi.current_stream()),
-                           "pv_ivae_particles_loss_and_grads")
-            elif iw is not None:
-                _abi.check(_abi.lib().pv_ivae_weighted_images_loss_and_grads(C.byref(p), _abi.ptr(iw), int(want_grads),
-                                                                             _abi.current_stream()),
-                           "pv_ivae_weighted_images_loss_and_grads")
-            elif pw is not None:
-                _abi.check(_abi.lib().pv_ivae_weighted_loss_and_grads(C.byref(p), _abi.ptr(pw), int(want_grads),
-                                                                      _abi.current_stream()), "pv_ivae_weighted_loss_and_grads")
             else:
-                _abi.check(_abi.lib().pv_ivae_loss_and_grads(C.byref(p), int(want_grads), _abi.current_stream()),
-                           "pv_ivae_loss_and_grads")
+                _abi.check(_abi.lib().pv_ivae_objective_loss_and_grads(C.byref(p), C.byref(obj), int(want_grads),
+                                                                       _abi.current_stream()), "pv_ivae_objective_loss_and_grads")
         finally:
             p.scalars = self.scalars.data_ptr()
             p.ext_head = p.ext_dhead = None

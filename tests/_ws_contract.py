@@ -321,12 +321,8 @@ def ivae_query(eng, batch, what=1, beta=1.0):
         ws = eng.ws
         p = eng._plan(batch, beta, what) if what == 1 else eng._plan(batch, what=what)
         eng.ws = ws                                     # (_plan may not replace what is installed; keep it in any case)
-        if what == 1 and eng._weighted():
-            return lib.pv_ivae_weighted_workspace_bytes(C.byref(p))
-        if what == 1 and eng.renyi is not None:
-            return lib.pv_ivae_renyi_workspace_bytes(C.byref(p), eng.particles)
-        if what == 1 and eng.particles > 1:
-            return lib.pv_ivae_particles_workspace_bytes(C.byref(p), eng.particles)
+        if what == 1:                                   # (the training step: the one query of the engine's objective)
+            return lib.pv_ivae_objective_workspace_bytes(C.byref(p), C.byref(eng._objective))
         return lib.pv_ivae_workspace_bytes_for(C.byref(p), what)
     return q
 
