@@ -66,7 +66,23 @@ enum pv_lik { PV_LIK_BERNOULLI = 0, PV_LIK_GAUSSIAN = 1, PV_LIK_CBERNOULLI = 2 /
    * kernel at every size (what dec_kernel == 1 names): the fp16 builds that path otherwise takes from 16 384 decoder rows
    * up stage a per-row power of two of dL/dlogit as fp16, which holds |rate - x| < 32768 only; dec_kernel 21 / 28 with
    * this likelihood is PV_EINVAL. */
-  PV_LIK_POISSON_LOG = 3 };
+  PV_LIK_POISSON_LOG = 3,
+  /* (v17: a new enum value, no struct layout changes) Categorical over the C values of a position, for label maps (one-hot or
+   * soft labels, x >= 0, channel-last): the decoder's C outputs of a position are logits a.  With lse = logsumexp_c a_c (maximum
+   * subtracted, fp32) and p_c = exp(a_c - lse):
+   *   log p(x | a)   = sum_c x_c (a_c - lse)             (= OneHotCategorical(logits=a).log_prob(x) for one-hot x; no multinomial
+   *                                                       coefficient: it is 0 for one-hot x and depends on the data only otherwise)
+   *   d(-log p)/da_k = p_k (sum_c x_c) - x_k
+   *   loc (decode, loc_out) = p                          (the class probabilities)
+   * log p_c is a_c - lse, never log(p_c): a class whose probability underflows under an observation of 0 contributes exactly 0.
+   * Observation weights (pv_ivae_weighted_*) multiply each term x_c log p_c: w_c x_c takes the place of x_c in both formulas.
+   * Scope: the iVAE plan with the library's own fully connected encoder and decoder and C = 2 .. PV_MAX_CHANNELS classes:
+   * coord_dim > 0 with out.out_dim = C (the layer-by-layer kernels, or the fused f32 kernel's categorical instances with fused == 1
+   * and PV_PLAN_FUSED_CHANNELS), or coord_dim == 0 with out._pad = C (the vanilla decoder's n_pix = positions * C outputs are
+   * grouped C at a time; out._pad is ignored for every other plan).  Needs sigmoid_out == 0, discrete_dim == 0, no convolutional
+   * or external encoder, no external decoder, no row_w / row_elbo / dy; decoder_sig is ignored.  Everything else — and this value in a
+   * pv_ved_plan — is PV_EINVAL from every entry point before any pointer is read. */
+  PV_LIK_CATEGORICAL = 4 };
 
 /* (v17) the form of the KL term between the guide q(z|x) = N(mu, sigma) and the N(0, 1) prior (pv_ivae_plan.kl_mode,
  * pv_ved_plan.kl_mode).  z = mu + sigma * eps is drawn once per sample for the likelihood either way.
@@ -163,7 +179,8 @@ typedef struct pv_ivae_plan {
   pv_layer out;                    /* decoder.out (fc.py:186 / fc.py:140).  coord_dim > 0: out_dim = C, the channels per grid
                                       position, 1 .. PV_MAX_CHANNELS, weight (C, in_dim); C > 1 runs the layer-by-layer kernels
                                       whatever `fused` asks for (but fused == 1 with PV_PLAN_FUSED_CHANNELS) and is refused with discrete_dim, row_w / row_elbo / dy, a conv or
-                                      external encoder and an external decoder.  coord_dim == 0: out_dim = n_pix */
+                                      external encoder and an external decoder.  coord_dim == 0: out_dim = n_pix — and, with
+                                      lik == PV_LIK_CATEGORICAL only, out._pad = C, the classes per position (enum pv_lik) */
   /* ---- optional convolutional encoder: iVAE.set_encoder(convEncoderNet(data_dim, latent_dim=z_dim))
    * (models/base.py:173-177, nets/conv.py:24-64).  n_enc_ops > 0: `enc` / n_enc are ignored, the encoder is this
    * op sequence over x viewed as (B, 1, *enc_in_dim), and `head` is features2latent.fc_latent (in_dim = C *
@@ -434,6 +451,10 @@ typedef struct pv_ivae_objective {
  *                                               and != 1 (checked by the two calls)
  *   {1, ELBO, SHARED | PER_IMAGE}               "fc iVAE" as above with 1 .. PV_MAX_CHANNELS channels, and fused = 0, 1 or 2 — or
  *                                               3 where PV_PLAN_FAST_WEIGHTS takes effect; with that bit, dec_kernel <= 1
+ *   any of the above, lik == PV_LIK_CATEGORICAL   "fc iVAE" with 2 .. PV_MAX_CHANNELS classes per position and sigmoid_out == 0 (enum
+ *                                               pv_lik): the row's scope within that — P > 1 and RENYI on the layer-by-layer kernels
+ *                                               (fused = 0, 2, 3 all run them for several channels), weights on them or, with
+ *                                               fused == 1 and PV_PLAN_FUSED_CHANNELS, on the fused f32 kernel's categorical instances
  *   PV_EINVAL whatever the plan (all three functions, before any pointer is read):
  *     num_particles < 1; an unknown bound or obs_w_kind; obs_w_kind != NONE with num_particles > 1 or RENYI (no kernel weighs
  *     both); weights_out != NULL with ELBO; and, in the two calls only, obs_w_kind != NONE with obs_w == NULL.

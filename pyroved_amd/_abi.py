@@ -27,6 +27,17 @@ PV_MAX_CHANNELS = 8         # channels per grid position of a spatial decoder (p
 # enum pv_act / pv_lik (include/pyroved_amd.h)
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2, "lrelu": 3, "softplus": 4, "gelu": 5, "sigmoid": 6}
 LIK = {"bernoulli": 0, "gaussian": 1, "continuous_bernoulli": 2, "poisson_log": 3}
+# ... and the likelihoods that score the C values of a position JOINTLY (enum pv_lik as well).  Kept apart from LIK, the per-value
+# likelihoods every engine takes: only the iVAE engine resolves these (lik_code), so VED, the semi-supervised models and jiVAE
+# refuse them with the messages their `name not in LIK` tests already have
+PV_LIK_CATEGORICAL = 4
+LIK_JOINT = {"categorical": PV_LIK_CATEGORICAL}
+
+
+def lik_code(name):
+    """enum pv_lik of a sampler name for the iVAE engine: a per-value likelihood (LIK) or a joint one (LIK_JOINT)."""
+    return LIK[name] if name in LIK else LIK_JOINT[name]
+
 # enum pv_kl_mode: the sampled log q - log p of Trace_ELBO / the closed-form KL of TraceMeanField_ELBO
 KL = {"sampled": 0, "analytic": 1}
 
@@ -257,6 +268,15 @@ def weighted_decoder_kernel_name(plan, per_image, grads):
     fn.restype = C.c_char_p
     fn.argtypes = [C.POINTER(pv_ivae_plan), C.c_int, C.c_int]
     return fn(C.byref(plan), int(bool(per_image)), int(bool(grads))).decode()
+
+
+def categorical_decoder_kernel_name(plan, weighted, grads):
+    """The decoder kernel a call of a categorical `plan` launches (pv_debug_categorical_decoder_kernel_name, a test hook outside
+    include/pyroved_amd.h): weighted 0 the unweighted calls, 1 shared weights, 2 per-image weights.  '' for a refused plan."""
+    fn = lib().pv_debug_categorical_decoder_kernel_name
+    fn.restype = C.c_char_p
+    fn.argtypes = [C.POINTER(pv_ivae_plan), C.c_int, C.c_int]
+    return fn(C.byref(plan), int(weighted), int(bool(grads))).decode()
 
 
 def check(code, what):

@@ -439,108 +439,26 @@ int pv_out_lik(const PvOutLik& p, hipStream_t s) {
 // row: it reads x[row * C + c] (one coalesced read), evaluates the likelihood once and writes loc[row * C + c]; dL/da_c reaches the
 // other lanes through a read of lane c.  The waves' partials leave through the one red[] buffer, a channel at a time.
 //   part_dwo (blocks, C * H)   part_dbo (blocks, C)   x null: observations of 0 (forward-only decode)
-template <int C>
-__global__ __launch_bounds__(256) void pv_out_lik_mc_kernel(PvOutLik p) {
-  static_assert(C >= 2 && C <= PV_MAX_CHANNELS, "channels per row");
-  __shared__ float red[4][64 * OL_MAXJ];
-  __shared__ float redb[4][PV_MAX_CHANNELS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int H = p.H;
-  float wo[C][OL_MAXJ], acc[C][OL_MAXJ];
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-#pragma unroll
-    for (int jj = 0; jj < OL_MAXJ; ++jj) {
-      const int j = lane + 64 * jj;
-      wo[c][jj] = j < H ? p.wo[c * H + j] : 0.0f;
-      acc[c][jj] = 0.0f;
-    }
-  }
-  const float bo = (p.bo && lane < C) ? p.bo[lane] : 0.0f;
-  float accb = 0.0f;                                  // lane c: sum over the wave's rows of dL/da_c
-  const int64_t rbeg = (int64_t)blockIdx.x * OL_ROWS + wave * (OL_ROWS / 4);
-  for (int i = 0; i < OL_ROWS / 4; ++i) {
-    const int64_t row = rbeg + i;
-    if (row >= p.M) break;
-    const float* hr = p.h + row * p.ldh;
-    float hv[OL_MAXJ];
-#pragma unroll
-    for (int jj = 0; jj < OL_MAXJ; ++jj) {
-      const int j = lane + 64 * jj;
-      hv[jj] = j < H ? hr[j] : 0.0f;
-    }
-    // (the lane index made opaque per row: hoisted out of the row loop, the C masks of `lane == c` would be scalar spills)
-    int lv = lane;
-    asm volatile("" : "+v"(lv));
-    float a = 0.0f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      float dot = 0.0f;
-#pragma unroll
-      for (int jj = 0; jj < OL_MAXJ; ++jj) dot += hv[jj] * wo[c][jj];
-      dot = pv_wave_sum(dot);
-      if (lv == c) a = dot;
-    }
-    a += bo;
-    float ll = 0.0f, dlda = 0.0f, locv = 0.0f;
-    if (lane < C) {
-      const float x = p.x ? p.x[(p.xmod > 0 ? row % p.xmod : row) * C + lane] : 0.0f;
-      pv_lik_any(a, x, p.lik, p.sigmoid_out, p.sig, ll, dlda, locv);
-      if (p.loc) p.loc[row * C + lane] = locv;
-      if (p.pw) {                                        // per-observation weight (pv_ivae_weighted_*)
-        const float w = p.pw[(p.pw_img ? row : row % p.N) * C + lane];
-        ll *= w;
-        dlda *= w;
-      }
-      if (p.sw) dlda *= p.sw[row / p.N];
-    }
-    if (p.llrow) {
-      float s = 0.0f;
-#pragma unroll
-      for (int c = 0; c < C; ++c) s += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ll), c));
-      if (lane == 0) p.llrow[row] = s;
-    }
-    if (p.dpre) {
-      float d[C];
-#pragma unroll
-      for (int c = 0; c < C; ++c) d[c] = __shfl(dlda, c);      // (vector registers: eight more scalars would spill)
-      float* dr = p.dpre + row * p.ldh;
-      const float* pr_ = p.hpre ? p.hpre + row * p.ldh : nullptr;
-#pragma unroll
-      for (int jj = 0; jj < OL_MAXJ; ++jj) {
-        const int j = lane + 64 * jj;
-        if (j < H) {
-          float g = 0.0f;
-#pragma unroll
-          for (int c = 0; c < C; ++c) {
-            g += d[c] * wo[c][jj];
-            acc[c][jj] += d[c] * hv[jj];
-          }
-          dr[j] = g * pv_act_grad2(hv[jj], pr_ ? pr_[j] : 0.0f, p.act_last);
-        }
-      }
-      accb += dlda;
-    }
-  }
-  if (!p.dpre) return;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-#pragma unroll
-    for (int jj = 0; jj < OL_MAXJ; ++jj) red[wave][lane + 64 * jj] = acc[c][jj];
-    __syncthreads();
-    for (int j = threadIdx.x; j < H; j += 256)
-      p.part_dwo[((int64_t)blockIdx.x * C + c) * H + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
-    __syncthreads();
-  }
-  if (lane < C) redb[wave][lane] = accb;
-  __syncthreads();
-  if (threadIdx.x < C)
-    p.part_dbo[(int64_t)blockIdx.x * C + threadIdx.x] =
-        (redb[0][threadIdx.x] + redb[1][threadIdx.x]) + (redb[2][threadIdx.x] + redb[3][threadIdx.x]);
-}
+// CAT (PV_LIK_CATEGORICAL: pv_out_lik_mc_cat_kernel<C>, from the same text — pv_out_lik_mc_body.inc — included a second time): the C values of a row are ONE
+// observation on the simplex.  Lane c holds a_c; the maximum, sum_c exp(a_c - max) and sum_c xw_c are taken over lanes 0 .. C-1 in
+// ascending c (the llrow sum's lane reads), then  ll_c = xw_c (a_c - lse),  dL/da_c = p_c sum_c xw_c - xw_c,  loc_c = p_c, with
+// xw_c = w_c x_c the weighted observation (w = 1 without weights).  The weights enter first, then p.sw, as in the per-value form
+#define OLM_KERNEL pv_out_lik_mc_kernel
+#define OLM_CAT 0
+#include "pv_out_lik_mc_body.inc"
+#undef OLM_KERNEL
+#undef OLM_CAT
+#define OLM_KERNEL pv_out_lik_mc_cat_kernel
+#define OLM_CAT 1
+#include "pv_out_lik_mc_body.inc"
+#undef OLM_KERNEL
+#undef OLM_CAT
 
 template <int C> static void out_lik_mc_launch(const PvOutLik& p, hipStream_t s) {
-  hipLaunchKernelGGL(pv_out_lik_mc_kernel<C>, dim3((unsigned)pv_out_lik_blocks(p.M)), dim3(256), 0, s, p);
+  if (p.lik == PV_LIK_CATEGORICAL)
+    hipLaunchKernelGGL(pv_out_lik_mc_cat_kernel<C>, dim3((unsigned)pv_out_lik_blocks(p.M)), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(pv_out_lik_mc_kernel<C>, dim3((unsigned)pv_out_lik_blocks(p.M)), dim3(256), 0, s, p);
 }
 
 int pv_out_lik_mc(const PvOutLik& p, int C, hipStream_t s) {
@@ -1435,14 +1353,69 @@ int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik,
   return 0;
 }
 
+// PV_LIK_CATEGORICAL on the vanilla decoder's logits: the C consecutive values of a position are one observation on the simplex
+// (pv_out_lik_mc_cat_kernel<C>'s arithmetic, c ascending).  One thread per position; the per-element outputs have pv_lik_elem's
+// layout, so the sums and the output layer's backward behind them are unchanged.  x null: observations of 0
+template <int C>
+__global__ void pv_lik_elem_cat_kernel(const float* __restrict__ a, const float* __restrict__ x, int64_t G, float* __restrict__ loc,
+                                       float* __restrict__ llrow, float* __restrict__ dlda, const float* __restrict__ pw,
+                                       int64_t per) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = g * C;
+    float av[C], xw[C];
+    float mx = -INFINITY, sx = 0.0f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      av[c] = a[e0 + c];
+      xw[c] = x ? x[e0 + c] : 0.0f;
+      if (pw) xw[c] *= pw[per > 0 ? (e0 + c) % per : e0 + c];   // (per == 0: one weight per element)
+      mx = fmaxf(mx, av[c]);
+      sx += xw[c];
+    }
+    float ev[C], se = 0.0f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { ev[c] = expf(av[c] - mx); se += ev[c]; }
+    const float lse = mx + logf(se);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float pc = ev[c] / se;
+      if (loc) loc[e0 + c] = pc;
+      if (llrow) llrow[e0 + c] = xw[c] * (av[c] - lse);
+      if (dlda) dlda[e0 + c] = pc * sx - xw[c];
+    }
+  }
+}
+
+template <int C>
+static void lik_elem_cat_launch(const float* a, const float* x, int64_t G, float* loc, float* llrow, float* dlda, hipStream_t s,
+                                const float* pw, int64_t per) {
+  int blocks = (int)((G + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pv_lik_elem_cat_kernel<C>, dim3(blocks), dim3(256), 0, s, a, x, G, loc, llrow, dlda, pw, per);
+}
+
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s, const float* pw, int64_t per, bool pw_img) {
+                float* llrow, float* dlda, hipStream_t s, const float* pw, int64_t per, bool pw_img, int group) {
   int blocks = (int)((M + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) return 0;
   if (pw && !pw_img && per < 1) return PV_EINVAL;
   if (pw_img) per = 0;                                   // (the kernels' sign for "one weight per element")
-  if (lik == PV_LIK_POISSON_LOG) {
+  if ((lik == PV_LIK_CATEGORICAL) != (group > 1)) return PV_EINVAL;
+  if (lik == PV_LIK_CATEGORICAL) {
+    if (M % group != 0 || (per > 0 && per % group != 0)) return PV_EINVAL;
+    const int64_t G = M / group;
+    switch (group) {
+      case 2: lik_elem_cat_launch<2>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 3: lik_elem_cat_launch<3>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 4: lik_elem_cat_launch<4>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 5: lik_elem_cat_launch<5>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 6: lik_elem_cat_launch<6>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 7: lik_elem_cat_launch<7>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      case 8: lik_elem_cat_launch<8>(a, x, G, loc, llrow, dlda, s, pw, per); break;
+      default: return PV_EINVAL;
+    }
+  } else if (lik == PV_LIK_POISSON_LOG) {
     hipLaunchKernelGGL(pv_lik_elem_poisson_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, loc, llrow, dlda, pw, per);
   } else {
     hipLaunchKernelGGL(pv_lik_elem_kernel, dim3(blocks), dim3(256), 0, s, a, x, M, lik, sigmoid_out, sig, loc, llrow, dlda, pw, per);

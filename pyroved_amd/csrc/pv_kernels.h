@@ -240,7 +240,11 @@ int pv_rec_wgrad(const float* part, int grid, float* G, const PvFusedOffsets& o,
 int pv_lik_rows(const float* a, const float* x, int64_t B, int64_t per, int lik, int sigmoid_out, float sig, float* loc,
                 float* dlda, float* llb, hipStream_t s, const float* pw = nullptr);
 int pv_lik_elem(const float* a, const float* x, int64_t M, int lik, int sigmoid_out, float sig, float* loc,
-                float* llrow, float* dlda, hipStream_t s, const float* pw = nullptr, int64_t per = 0, bool pw_img = false);
+                float* llrow, float* dlda, hipStream_t s, const float* pw = nullptr, int64_t per = 0, bool pw_img = false,
+                int group = 1);
+// (group: PV_LIK_CATEGORICAL only — the C = 2 .. PV_MAX_CHANNELS consecutive logits of a position are one observation on the simplex,
+//  M % C == 0; one thread per position walks them: ll_c = xw_c (a_c - lse), dL/da_c = p_c sum_c xw_c - xw_c, loc_c = p_c, xw = w x.
+//  x null: observations of 0, the forward-only decode.  The per-value likelihoods take group == 1)
 
 // The Poisson (log link) likelihood's data-only normaliser C = sum_i lgamma(x[i] + 1) over the call's n observations, applied to the
 // finished scalars: scalars[1] -= C, scalars[0] += C.  Two launches: up to PV_POISSON_PARTS workgroups each sum a contiguous chunk

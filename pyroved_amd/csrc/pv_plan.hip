@@ -95,6 +95,11 @@ static inline int plan_conv_mode(const pv_ivae_plan* p) {
 // the grid, the row chunks and the per-sample segment sums run over the positions.  Vanilla decoders: C = 1, positions = n_pix
 static inline int64_t plan_C(const pv_ivae_plan* p) { return p->coord_dim > 0 ? p->out.out_dim : 1; }
 static inline int64_t plan_pos(const pv_ivae_plan* p) { return p->n_pix / plan_C(p); }
+// PV_LIK_CATEGORICAL: the classes per position — the spatial decoder's channels, or the group width a vanilla plan names in out._pad
+// (its decoder's n_pix outputs are channel-last, C consecutive logits per position); 1 for every per-value likelihood
+static inline int plan_group(const pv_ivae_plan* p) {
+  return p->lik != PV_LIK_CATEGORICAL ? 1 : (p->coord_dim > 0 ? p->out.out_dim : p->out._pad);
+}
 // The fused persistent decoder kernel a plan runs on, if any: the one-channel kernels (every `fused` mode) or the f32 kernel's
 // multi-channel sibling (pv_sdec_fused_mc.hip: PV_PLAN_FUSED_CHANNELS with fused == 1 and 2 .. PV_MAX_CHANNELS channels).  The two
 // predicates exclude each other (out.out_dim == 1 / >= 2)
@@ -131,9 +136,15 @@ bool valid_plan(const pv_ivae_plan* p) {
   if (p->discrete_dim > 0 && p->c_dim != 0) return false;                            // jiVAE: no conditioning vector
   if ((p->row_w || p->row_elbo || p->dy) && (p->discrete_dim > 0 || p->n_enc_ops > 0 || p->ext_encoder)) return false;
   if (p->dy && p->c_dim == 0) return false;
-  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI && p->lik != PV_LIK_POISSON_LOG)
+  if (p->lik != PV_LIK_BERNOULLI && p->lik != PV_LIK_GAUSSIAN && p->lik != PV_LIK_CBERNOULLI && p->lik != PV_LIK_POISSON_LOG &&
+      p->lik != PV_LIK_CATEGORICAL)
     return false;
-  if (p->lik == PV_LIK_POISSON_LOG) {
+  if (p->lik == PV_LIK_CATEGORICAL) {
+    // the C logits of a position are one observation: 2 .. PV_MAX_CHANNELS classes, no output sigmoid, the fc-encoder iVAE alone
+    const int C = plan_group(p);
+    if (C < 2 || C > PV_MAX_CHANNELS || p->n_pix % C != 0 || p->sigmoid_out) return false;
+    if (p->discrete_dim > 0 || p->n_enc_ops > 0 || p->ext_encoder || p->ext_decoder || p->row_w || p->row_elbo || p->dy) return false;
+  } else if (p->lik == PV_LIK_POISSON_LOG) {
     if (p->sigmoid_out) return false;                               // the decoder's output is the log-rate
     if (p->row_w || p->row_elbo || p->dy) return false;             // (per-image outputs would need the per-image normaliser)
     if (p->fused == 2 && p->dec_kernel > 1) return false;           // (the fp16 builds: plan_sel)
@@ -1195,7 +1206,7 @@ int loss_and_grads_layered(const pv_ivae_plan* p, const Layout& L, const ObjArgs
     for (int64_t k = 0; k < reps; ++k)
       PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig,
                          p->loc ? p->loc + k * B * N : nullptr, L.llrow + k * B * N, want_grads ? oth + k * B * N : nullptr, s,
-                         obj.pw, N, obj.pw_img));
+                         obj.pw, N, obj.pw_img, plan_group(p)));
     if (reps > 1 && want_grads && !renyi) PV_TRY(pv_scale_rows(oth, L.sw, R, N, s));
     if (K == 0 && p->row_w && want_grads) PV_TRY(pv_scale_rows(oth, p->row_w, R, N, s));
   }
@@ -1329,12 +1340,18 @@ static pv_ivae_plan decode_plan(const pv_ivae_plan* plan) {
 }
 
 static pv_ivae_plan guide_plan(const pv_ivae_plan* plan);
-// several channels per position with an external decoder: refused (the guide plan below no longer knows the decoder)
-static bool ext_decoder_channels(const pv_ivae_plan* plan) { return plan->ext_decoder && plan->coord_dim > 0 && plan->out.out_dim > 1; }
+// several channels per position with an external decoder: refused (the guide plan below no longer knows the decoder); the
+// categorical likelihood, which exists for several channels only, likewise (the guide plan would replace it by a per-value one)
+static bool ext_decoder_channels(const pv_ivae_plan* plan) {
+  return plan->ext_decoder && ((plan->coord_dim > 0 && plan->out.out_dim > 1) || plan->lik == PV_LIK_CATEGORICAL);
+}
 
 // the likelihood branch a forward-only launch borrows to turn logits into `loc`: the Gaussian one (sigmoid(a) or a) for every
-// likelihood whose mean is that; the Poisson's own for its rate exp(min(a, 30))
-static int loc_lik(const pv_ivae_plan* lay) { return lay->lik == PV_LIK_POISSON_LOG ? PV_LIK_POISSON_LOG : PV_LIK_GAUSSIAN; }
+// likelihood whose mean is that; the Poisson's own for its rate exp(min(a, 30)); the categorical's own for the class
+// probabilities softmax(a)
+static int loc_lik(const pv_ivae_plan* lay) {
+  return (lay->lik == PV_LIK_POISSON_LOG || lay->lik == PV_LIK_CATEGORICAL) ? lay->lik : PV_LIK_GAUSSIAN;
+}
 
 // ---- forward-only decode on the fused spatial-decoder kernel (models/base.py:145-171) ----
 // decode(z, angle, shift, scale) of an invariant model whose decoder the fused kernel is specialised for: the per-sample
@@ -1561,6 +1578,23 @@ extern "C" const char* pv_debug_weighted_decoder_kernel_name(const pv_ivae_plan*
   static thread_local char buf[96];
   snprintf(buf, sizeof buf, "void pv_sdec_fused_mc_kernel<%s, %d, %d>(PvFused)", grads ? "true" : "false", (int)plan_C(&q),
            per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED);
+  return buf;
+}
+
+// test hook (not in include/), in the same style: the decoder kernel a call of a PV_LIK_CATEGORICAL plan launches — weighted: 0 the
+// unweighted entry points, 1 pv_ivae_weighted_*, 2 pv_ivae_weighted_images_*; '' for a plan those calls refuse
+extern "C" const char* pv_debug_categorical_decoder_kernel_name(const pv_ivae_plan* plan, int weighted, int grads) {
+  if (!plan || weighted < 0 || weighted > 2 || plan->lik != PV_LIK_CATEGORICAL) return "";
+  if (weighted ? !weighted_scope(plan) : !valid_plan(plan)) return "";
+  const pv_ivae_plan q = weighted ? weighted_route(plan, weighted == 2) : *plan;
+  static thread_local char buf[160];
+  if (!(q.fused == 1 && plan_fused_mc(&q))) {            // the likelihood launch of the layer-by-layer path
+    if (q.coord_dim > 0) snprintf(buf, sizeof buf, "void pv_out_lik_mc_cat_kernel<%d>(PvOutLik) (layer-by-layer path)", plan_group(&q));
+    else snprintf(buf, sizeof buf, "void pv_lik_elem_cat_kernel<%d>(float const*, float const*, long, float*, float*, float*, float const*, long) "
+                  "(layer-by-layer path)", plan_group(&q));
+    return buf;
+  }
+  snprintf(buf, sizeof buf, "void pv_sdec_fused_mc_cat_kernel<%s, %d, %d>(PvFused)", grads ? "true" : "false", (int)plan_C(&q), weighted);
   return buf;
 }
 
@@ -1802,5 +1836,6 @@ extern "C" int pv_ivae_decode(const pv_ivae_plan* plan, const float* z, float an
     if (plan_C(plan) > 1) { o.x = nullptr; return pv_out_lik_mc(o, (int)plan_C(plan), s); }
     return pv_out_lik(o, s);
   }
-  return pv_lik_elem(L.logits, L.logits, B * N, loc_lik(plan), plan->sigmoid_out, 1.0f, loc, nullptr, nullptr, s);
+  return pv_lik_elem(L.logits, plan->lik == PV_LIK_CATEGORICAL ? nullptr : L.logits, B * N, loc_lik(plan), plan->sigmoid_out, 1.0f, loc,
+                     nullptr, nullptr, s, nullptr, 0, false, plan_group(plan));
 }

@@ -217,7 +217,18 @@ class IVAEEngine:
         if m.coord == 0 and not isinstance(dec, fcDecoderNet):
             raise UnsupportedModel("vanilla models need fcDecoderNet")
         name = m.sampler_d.name
-        if name not in _abi.LIK:
+        if name in _abi.LIK_JOINT:
+            # the joint likelihood over a position's channels: models.iVAE with its own fully connected networks alone (the
+            # per-value tests of every other engine, `name not in _abi.LIK`, refuse it with their own messages)
+            if type(self) is not IVAEEngine or self.K > 0 or self.conv_enc:
+                raise UnsupportedModel("sampler_d=%r is implemented for models.iVAE with its own fully connected encoder and "
+                                       "decoder only (not for %s)" % (name, type(m).__name__))
+            if self.C < 2:
+                raise UnsupportedModel("sampler_d=%r needs channels >= 2, the classes per position (got channels=%d)"
+                                       % (name, self.C))
+            if dec.sigmoid_out:
+                raise UnsupportedModel("%s likelihood needs sigmoid_d=False (the decoder's outputs are the class logits)" % name)
+        elif name not in _abi.LIK:
             raise UnsupportedModel("decoder sampler %r is not implemented in the HIP path yet" % name)
         if name in ("bernoulli", "continuous_bernoulli") and not dec.sigmoid_out:
             raise UnsupportedModel("%s likelihood needs sigmoid_d=True" % name)
@@ -721,7 +732,7 @@ class IVAEEngine:
             p.t_prior[1] = tpl[1] if len(tpl) > 1 else tpl[0]
         sp = getattr(m, "sc_prior", None)
         p.sc_prior = float(sp) if sp is not None else 0.0
-        p.lik = _abi.LIK[m.sampler_d.name]
+        p.lik = _abi.lik_code(m.sampler_d.name)
         p.sigmoid_out = int(getattr(dec, "sigmoid_out", True))
         p.decoder_sig = m.sampler_d.decoder_sig
         p.ext_decoder = int(self.ext_dec)
@@ -753,6 +764,8 @@ class IVAEEngine:
             for j, i in enumerate(idx):
                 p.dec[j] = self._layer("decoder.fc_layers.%d" % i, dec.fc_layers[i], dec.activation)
             p.out = self._layer("decoder.out", dec.out, None)
+            if p.lik == _abi.PV_LIK_CATEGORICAL and p.coord_dim == 0:
+                p.out._pad = self.C                    # the vanilla decoder's outputs are grouped C at a time (enum pv_lik's comment)
         p.params = self.flat.data_ptr()
         p.grads = self.grad.data_ptr()
         p.adam_m = self.m.data_ptr()

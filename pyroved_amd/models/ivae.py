@@ -44,7 +44,12 @@ class iVAE(baseVAE):
         hidden_dim_e / hidden_dim_d: hidden layer widths of encoder / decoder (default [128, 128])
         activation: 'tanh' (default), 'lrelu', 'softplus', 'relu', 'gelu'
         sampler_d: 'bernoulli' (default), 'continuous_bernoulli', 'gaussian', or 'poisson_log' for count data: a Poisson
-            whose log-rate is the decoder's output (needs sigmoid_d=False; decode / manifold2d return the rate)
+            whose log-rate is the decoder's output (needs sigmoid_d=False; decode / manifold2d return the rate), or
+            'categorical' for label maps (channels=C >= 2, sigmoid_d=False): the C values of a position are ONE observation
+            on the simplex — one-hot labels (utils.onehot_channels) or soft ones — and the decoder's C outputs its logits:
+            log p(x | z) = sum over positions of sum_c x_c log softmax(a)_c (no multinomial coefficient: 0 for one-hot x,
+            data-only otherwise); decode / manifold2d return the class probabilities.  Observation weights multiply each
+            term x_c log p_c.  iVAE with its own fully connected networks only
         sigmoid_d: sigmoid at the decoder output (default True)
         seed: seed used in torch.manual_seed(seed)
         channels: values per grid position, 1 .. 8 (default 1).  With C > 1 the data is channel-last, x of shape
@@ -79,6 +84,13 @@ class iVAE(baseVAE):
          ) -> None:
         args = (data_dim, invariances)
         super(iVAE, self).__init__(*args, channels=channels, **kwargs)
+        if sampler_d == "categorical":
+            # one observation per position: its C values are class logits, so there must be classes and no output sigmoid
+            if self.channels < 2:
+                raise ValueError("sampler_d='categorical' needs channels >= 2, the number of classes per position "
+                                 "(got channels=%d)" % self.channels)
+            if sigmoid_d:
+                raise ValueError("sampler_d='categorical' needs sigmoid_d=False (the decoder's outputs are the class logits)")
 
         # same RNG consumption as the reference (models/ivae.py:140-154): seed, then the
         # encoder's Linear layers, then the decoder's, all on the CPU generator
@@ -102,7 +114,7 @@ class iVAE(baseVAE):
                 full_dim, latent_dim, c_dim, hidden_dim_d,
                 activation, sigmoid_out=sigmoid_d
             )
-        self.sampler_d = get_sampler(sampler_d, **kwargs)
+        self.sampler_d = get_sampler(sampler_d, **{**kwargs, "channels": C})
 
         self.z_dim = latent_dim + self.coord
         self.c_dim = c_dim

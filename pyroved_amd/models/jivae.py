@@ -23,6 +23,7 @@ from .base import baseVAE
 from .ivae import _plot_manifold
 from ..nets import fcDecoderNet, jfcEncoderNet, sDecoderNet
 from ..utils import get_sampler, set_deterministic_mode, to_onehot
+from ..utils.prob import only_ivae_sampler
 
 
 class jiVAE(baseVAE):
@@ -64,6 +65,7 @@ class jiVAE(baseVAE):
         self.decoder = dnet(
             data_dim, latent_dim, discrete_dim, hidden_dim_d,
             activation, sigmoid_out=sigmoid_d, unflat=False)
+        only_ivae_sampler(sampler_d, type(self).__name__)
         self.sampler_d = get_sampler(sampler_d, **kwargs)
         self.z_dim = latent_dim + self.coord
         self.discrete_dim = discrete_dim

@@ -17,6 +17,7 @@ from .ivae import _plot_manifold
 from ..nets import fcDecoderNet, fcEncoderNet, sDecoderNet, fcClassifierNet, fcRegressorNet
 from ..utils import (get_sampler, set_deterministic_mode, to_onehot, iter_batches, generate_latent_grid,
                      generate_latent_grid_traversal)
+from ..utils.prob import only_ivae_sampler
 
 tt = torch.tensor
 
@@ -33,6 +34,7 @@ class _ssBase(baseVAE):
         self.encoder_y = label_net(data_dim, label_dim, hidden_dim_y, activation)
         dnet = sDecoderNet if 0 < self.coord < 5 else fcDecoderNet
         self.decoder = dnet(data_dim, latent_dim, label_dim, hidden_dim_d, activation, sigmoid_out=sigmoid_d, unflat=False)
+        only_ivae_sampler(sampler_d, type(self).__name__)
         self.sampler_d = get_sampler(sampler_d, **kwargs)
         self.z_dim = latent_dim + self.coord
         self.c_dim = label_dim               # the label vector is the conditioning input of encoder_z and decoder

@@ -14,6 +14,7 @@ import torch
 from .base import baseVAE
 from ..nets.conv import convEncoderNet, convDecoderNet
 from ..utils import get_sampler, iter_batches, set_deterministic_mode
+from ..utils.prob import only_ivae_sampler
 
 
 class VED(baseVAE):
@@ -56,6 +57,7 @@ class VED(baseVAE):
         self.encoder_z = convEncoderNet(input_dim, latent_dim, input_channels, hidden_dim_e, batchnorm, activation)
         self.decoder = convDecoderNet(latent_dim, output_dim, output_channels, hidden_dim_d, batchnorm, activation,
                                       sigmoid_d)
+        only_ivae_sampler(sampler_d, type(self).__name__)
         self.sampler_d = get_sampler(sampler_d, **kwargs)
         self.z_dim = latent_dim
         self.c_dim = 0

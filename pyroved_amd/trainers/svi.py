@@ -70,7 +70,10 @@ class SVItrainer:
             decoder kernel's multi-channel form instead of the layer-by-layer kernels they otherwise take whatever `fused`
             says (default False; fp32-class results; decoders of hidden size [128, 128] with tanh and a number of grid
             positions that is a multiple of 16 — others keep the layered kernels).  A ValueError with num_particles > 1,
-            loss="RenyiELBO", fused=0, fused=3 or precision="bf16".  Changes nothing for a single-channel model
+            loss="RenyiELBO", fused=0, fused=3 or precision="bf16".  Changes nothing for a single-channel model.  A model with
+            sampler_d="categorical" (label maps: the C channels of a position are one categorical observation) trains wherever a
+            multi-channel Bernoulli model does — every loss and num_particles on the layer-by-layer kernels, and with this keyword
+            on the kernel's categorical instances
         pixel_weights: per-observation weights of the likelihood, shared by all images: a tensor, ndarray or bool mask of shape
             data_dim (the same weight in every channel of a multi-channel model) or (*data_dim, C); entries >= 0, not all zero.
             Every log p(x_bi | z_b) of train / evaluate is multiplied by w_i (its normaliser included) — a circular aperture for

@@ -45,6 +45,22 @@ def weights_from_nan(x, fill: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
     return torch.where(missing, torch.full_like(t, float(fill)), t), w
 
 
+def onehot_channels(labels, num_classes: int) -> torch.Tensor:
+    """Integer label images (n, *dims) -> channel-last float32 one-hot (n, *dims, num_classes): the data of
+    iVAE(data_dim, ..., channels=num_classes, sampler_d="categorical", sigmoid_d=False).  labels: a tensor or an ndarray of an
+    integer dtype with every entry in 0 .. num_classes - 1 (ValueError otherwise); it is not modified."""
+    t = torch.as_tensor(labels)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError("labels must have an integer dtype (got %s)" % t.dtype)
+    if isinstance(num_classes, bool) or int(num_classes) != num_classes or num_classes < 1:
+        raise ValueError("num_classes must be a positive int (got %r)" % (num_classes,))
+    t = t.to(torch.int64)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= num_classes):
+        raise ValueError("labels must lie in 0 .. %d (got %d .. %d)" % (num_classes - 1, int(t.min()), int(t.max())))
+    out = torch.zeros(*t.shape, int(num_classes), dtype=torch.float32)
+    return out.scatter_(-1, t.unsqueeze(-1), 1.0)
+
+
 def iter_batches(*args: torch.Tensor, batch_size: int = 100) -> Iterator[Tuple[torch.Tensor, ...]]:
     """The batches `init_dataloader(*args, shuffle=False, batch_size=...)` yields — same boundaries, same order, the last
     one partial — as views of the callers' tensors.  The inference loops (encode / decode / predict / classifier) walk
