@@ -511,6 +511,44 @@ int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t num_particles
                                  void* stream);
 int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream);   /* + Adam */
 
+/* ---- (v17, new entry points, no layout change) held-out log-evidence: log p^(x_b) per image ----------------------------------
+ * The K-sample importance-weighted estimate every VAE paper reports as its test metric ("IWAE-5000"), at beta = 1:
+ *   lw_kb      = log p(x_b | z_kb [, y_b]) + log N(z_kb; 0, 1) - log N(z_kb; mu_b, sigma_b),   z_kb = mu_b + sigma_b eps_kb
+ *   log p^(x_b) = logsumexp_k lw_kb - log K,     ESS_b = (sum_k e^lw_kb)^2 / sum_k e^(2 lw_kb)   in [1, K]
+ * streamed over chunks of P <= 1024 particles against a running state per image, DEVICE (B, 4) floats {m, s, q, unused},
+ * 16-byte aligned:  m = the largest lw so far,  s = sum e^(lw - m),  q = sum e^(2 (lw - m)).  A chunk rescales s by
+ * e^(m_old - m_new) and q by its square, then adds its terms in ascending p; log p^ = m + log s - log K, ESS = s^2 / q.
+ * One thread per image, no float atomics: a run is bit-reproducible.  A term whose e^(lw - m) underflows adds exactly 0;
+ * lw = -inf for every particle of an image is not expected (it gives NaN).
+ * lw includes every normaliser a log_prob has: the Gaussian's -log sig - log sqrt(2 pi), the continuous Bernoulli's log C, the
+ * categorical's log-softmax and the Poisson's -sum_i lgamma(x_bi + 1) PER IMAGE.
+ *
+ * pv_logmeanexp_update / _finish work on any DEVICE (P, B) table of log-weights, rows [p][b]:
+ *   first != 0  the state is initialised from this chunk: what it held is never read.
+ *   K_total     the particles accumulated over all chunks;  ess may be NULL.
+ *   PV_EINVAL: a NULL lw / state / log_mean, P < 1, B < 1, K_total < 1, a state that is not 16-byte aligned.
+ *
+ * pv_ivae_evidence_accumulate adds one chunk of P particles of the plan's batch.  It takes the plan as the objective
+ * {P, PV_BOUND_RENYI} does — eps (P*B, z_dim) ordered [p][b]; y with c_dim > 0 — and runs that objective's forward-only
+ * launches: the guide once, the expansion into P*B samples, the decoder launch the plan's `fused` selects, ll per sample; then
+ * the log-weights (the device function pv_ivae_renyi_* forms them with: a one-chunk evidence IS the alpha = 0 bound's L_b) and
+ * the state update.
+ *   beta     used as given; the evidence is beta = 1.
+ *   kl_mode  not consulted: a log-weight is a sampled quantity (PV_KL_SAMPLED runs).
+ *   z_loc / z_scale are written if set; scalars, loc, grads and adam_* are neither read nor written.
+ *   ws       sized by pv_ivae_evidence_workspace_bytes(plan, P): a forward-only layout (no gradient buffers of the layer-by-layer
+ *            path), exact size, any prior content.
+ * Scope: what {P, PV_BOUND_RENYI} accepts — the fc-encoder iVAE, spatial or vanilla decoder, with or without c_dim, every
+ * likelihood, 1 .. PV_MAX_CHANNELS channels (several: the layer-by-layer kernels), fused 0, 2 or 3 — at every P in 1 .. 1024.
+ * PV_EINVAL from the query and the call, before any pointer is read: discrete_dim > 0, conv or external networks, row_w /
+ * row_elbo / dy / class_onehot, fused == 1, P out of range, (the call) a NULL state or a missing params / x / eps / ws / y / grid.
+ * PV_EWS as elsewhere. */
+int pv_logmeanexp_update(const float* lw /* (P, B) */, int32_t P, int32_t B, float* state, int first, void* stream);
+int pv_logmeanexp_finish(const float* state, int32_t B, int64_t K_total, float* log_mean /* (B) */, float* ess /* (B) or NULL */,
+                         void* stream);
+int64_t pv_ivae_evidence_workspace_bytes(const pv_ivae_plan* plan, int32_t P);          /* <0 unsupported */
+int pv_ivae_evidence_accumulate(const pv_ivae_plan* plan, int32_t P, float* state, int first, void* stream);
+
 /* ---- (v17, new entry points, no layout change) per-observation weights (masks) of the likelihood ----------------------------
  * A circular aperture for a rotation-invariant model, dead or hot detector pixels, a per-pixel gain or exposure map: one
  * factor per observed value,

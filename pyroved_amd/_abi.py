@@ -186,6 +186,11 @@ SIGNATURES = {
     "pv_ivae_renyi_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan), C.c_int32]),
     "pv_ivae_renyi_loss_and_grads": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "pv_ivae_renyi_step": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    # held-out log-evidence per image (v17, added without a layout change)
+    "pv_logmeanexp_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
+    "pv_logmeanexp_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pv_ivae_evidence_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan), C.c_int32]),
+    "pv_ivae_evidence_accumulate": (C.c_int, [C.POINTER(pv_ivae_plan), C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     # per-observation weights of the likelihood (v17, added without a layout change)
     "pv_ivae_weighted_workspace_bytes": (C.c_int64, [C.POINTER(pv_ivae_plan)]),
     "pv_ivae_weighted_uses_fused": (C.c_int, [C.POINTER(pv_ivae_plan)]),

@@ -79,3 +79,28 @@ struct PvRenyiWeights {
   float beta, alpha;
 };
 int pv_renyi_weights(const PvRenyiWeights& r, hipStream_t s);
+
+// one sample's log-weight lw_pb = ll_pb + beta (log p(z_pb) - log q(z_pb | x_b)), the arithmetic shared by pv_renyi_weights and the
+// evidence estimate (pv_evidence_lw) so that both form the same bits: one latent coordinate's two terms (a lane walks
+// i = t, t + 64, ..; the wave's sums follow, pv_wave_sum, scaled by beta), and the sum.  Pure functions of values: the callers keep
+// their own loops and index arithmetic, so that pv_renyi_weights_kernel compiles to the instructions it had before the functions
+// existed (scripts/compare_kernel_asm.py --source pv_particles.hip)
+__device__ __forceinline__ float pv_lw_logq(float e, float sig) { return -(e * e) / 2.0f - logf(sig) - LOG_SQRT_2PI; }   // Normal(mu, sig).log_prob(mu + sig eps)
+__device__ __forceinline__ float pv_lw_logp(float z) { return -(z * z) / 2.0f - LOG_SQRT_2PI; }                          // Normal(0, 1).log_prob(z)
+__device__ __forceinline__ float pv_log_weight(float ll, float lp, float lq) { return ll + (lp - lq); }
+
+// ---- held-out log-evidence: log p^(x_b) = logsumexp_k lw_kb - log K, streamed over chunks of P <= PV_RENYI_MAX_P particles ----
+// lw[p B + b] = pv_log_weight(llkb[p B + b], ...) for the chunk's P samples of every image: one wave per image
+struct PvEvidenceLw {
+  const float* llkb;                // (P*B) log p(x_b | z_pb), every normaliser included
+  const float* z; const float* eps; // (P*B, z_dim)
+  const float* z_scale;             // (B, z_dim)
+  float* lw;                        // (P*B)
+  int B, P, z_dim;
+  float beta;
+};
+int pv_evidence_lw(const PvEvidenceLw& e, hipStream_t s);
+// the Poisson likelihood's per-image normaliser on P samples: llkb[p B + b] -= sum_i lgamma(x[b N + i] + 1), p < P (the sibling of
+// pv_poisson_lognorm_rows without its K <= 256; the same float64 sum)
+int pv_poisson_lognorm_particles(const float* x, int64_t B, int64_t N, float* llkb, int P, hipStream_t s);
+// (pv_logmeanexp_update / pv_logmeanexp_finish, the running state per image: include/pyroved_amd.h)

@@ -264,15 +264,15 @@ __global__ __launch_bounds__(64) void pv_renyi_weights_kernel(PvRenyiWeights r) 
     float lp = 0.0f, lq = 0.0f;
     for (int i = t; i < zd; i += 64) {
       const float z = r.z[s * zd + i], e = r.eps[s * zd + i], sig = r.z_scale[(int64_t)b * zd + i];
-      lq += -(e * e) / 2.0f - logf(sig) - LOG_SQRT_2PI;      // Normal(mu, sig).log_prob(mu + sig eps)
-      lp += -(z * z) / 2.0f - LOG_SQRT_2PI;
+      lq += pv_lw_logq(e, sig);
+      lp += pv_lw_logp(z);
     }
     lp = r.beta * pv_wave_sum(lp);
     lq = r.beta * pv_wave_sum(lq);
     if (t == 0) {
       sh_lp[p] = lp;
       sh_lq[p] = lq;
-      sh_a[p] = oma * (r.llkb[s] + (lp - lq));
+      sh_a[p] = oma * pv_log_weight(r.llkb[s], lp, lq);
     }
   }
   if (t != 0) return;                                  // (thread 0 reads back what it wrote: no barrier)
@@ -300,6 +300,101 @@ int pv_renyi_weights(const PvRenyiWeights& r, hipStream_t s) {
   if (r.B < 1 || r.P < 1 || r.P > PV_RENYI_MAX_P || r.z_dim < 1 || !std::isfinite(r.alpha) || r.alpha == 1.0f) return PV_EINVAL;
   if (!r.llkb || !r.z || !r.eps || !r.z_scale || !r.sw || !r.kl_part || !r.c) return PV_EINVAL;
   hipLaunchKernelGGL(pv_renyi_weights_kernel, dim3(r.B), dim3(64), 0, s, r);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- held-out log-evidence (pv_particles.h; include/pyroved_amd.h: pv_ivae_evidence_accumulate) ----
+__global__ __launch_bounds__(64) void pv_evidence_lw_kernel(PvEvidenceLw e) {
+  const int b = blockIdx.x, t = threadIdx.x, zd = e.z_dim;
+  for (int p = 0; p < e.P; ++p) {
+    const int64_t s = (int64_t)p * e.B + b;
+    float lp = 0.0f, lq = 0.0f;
+    for (int i = t; i < zd; i += 64) {
+      const float z = e.z[s * zd + i], ep = e.eps[s * zd + i], sig = e.z_scale[(int64_t)b * zd + i];
+      lq += pv_lw_logq(ep, sig);
+      lp += pv_lw_logp(z);
+    }
+    lp = e.beta * pv_wave_sum(lp);
+    lq = e.beta * pv_wave_sum(lq);
+    if (t == 0) e.lw[s] = pv_log_weight(e.llkb[s], lp, lq);
+  }
+}
+int pv_evidence_lw(const PvEvidenceLw& e, hipStream_t s) {
+  if (e.B < 1 || e.P < 1 || e.P > PV_RENYI_MAX_P || e.z_dim < 1) return PV_EINVAL;
+  if (!e.llkb || !e.z || !e.eps || !e.z_scale || !e.lw) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_evidence_lw_kernel, dim3(e.B), dim3(64), 0, s, e);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void pv_poisson_lognorm_particles_kernel(const float* __restrict__ x, int64_t N, float* __restrict__ llkb,
+                                                                           int64_t B, int P) {
+  __shared__ double sm[4];
+  const float* xb = x + (int64_t)blockIdx.x * N;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += 256) acc += (double)lgammaf(xb[i] + 1.0f);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  const double c = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  for (int p = threadIdx.x; p < P; p += 256) {
+    float* d = llkb + (int64_t)p * B + blockIdx.x;
+    *d = (float)((double)*d - c);
+  }
+}
+int pv_poisson_lognorm_particles(const float* x, int64_t B, int64_t N, float* llkb, int P, hipStream_t s) {
+  if (!x || !llkb || B <= 0 || N <= 0 || P < 1) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_poisson_lognorm_particles_kernel, dim3((unsigned)B), dim3(256), 0, s, x, N, llkb, B, P);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+// the running state per image, {m, s, q, unused}: one thread per image walks the chunk's P log-weights in ascending p — the chunk's
+// maximum first, then the sums against max(m_old, chunk maximum).  first != 0: the state is written, never read
+#define PV_LME_THREADS 256
+__global__ __launch_bounds__(PV_LME_THREADS) void pv_logmeanexp_update_kernel(const float* __restrict__ lw, int P, int B,
+                                                                              float* __restrict__ state, int first) {
+  const int b = blockIdx.x * PV_LME_THREADS + threadIdx.x;
+  if (b >= B) return;
+  float m = lw[b];
+  for (int p = 1; p < P; ++p) m = fmaxf(m, lw[(int64_t)p * B + b]);
+  float sum = 0.0f, sq = 0.0f;
+  float4* st = reinterpret_cast<float4*>(state) + b;
+  if (!first) {
+    const float4 o = *st;
+    m = fmaxf(m, o.x);
+    const float r = expf(o.x - m);                     // (1 when the maximum stays; an underflow leaves exactly 0)
+    sum = o.y * r;
+    sq = o.z * (r * r);
+  }
+  for (int p = 0; p < P; ++p) {
+    const float e = expf(lw[(int64_t)p * B + b] - m);
+    sum += e;
+    sq += e * e;
+  }
+  *st = float4{m, sum, sq, 0.0f};
+}
+__global__ __launch_bounds__(PV_LME_THREADS) void pv_logmeanexp_finish_kernel(const float* __restrict__ state, int B, float log_k,
+                                                                              float* __restrict__ log_mean, float* __restrict__ ess) {
+  const int b = blockIdx.x * PV_LME_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const float4 o = reinterpret_cast<const float4*>(state)[b];
+  log_mean[b] = o.x + (logf(o.y) - log_k);
+  if (ess) ess[b] = (o.y * o.y) / o.z;
+}
+
+extern "C" int pv_logmeanexp_update(const float* lw, int32_t P, int32_t B, float* state, int first, void* stream) {
+  if (!lw || !state || P < 1 || B < 1 || ((uintptr_t)state & 15) != 0) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_logmeanexp_update_kernel, dim3((B + PV_LME_THREADS - 1) / PV_LME_THREADS), dim3(PV_LME_THREADS), 0,
+                     (hipStream_t)stream, lw, P, B, state, first);
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int pv_logmeanexp_finish(const float* state, int32_t B, int64_t K_total, float* log_mean, float* ess, void* stream) {
+  if (!state || !log_mean || B < 1 || K_total < 1 || ((uintptr_t)state & 15) != 0) return PV_EINVAL;
+  hipLaunchKernelGGL(pv_logmeanexp_finish_kernel, dim3((B + PV_LME_THREADS - 1) / PV_LME_THREADS), dim3(PV_LME_THREADS), 0,
+                     (hipStream_t)stream, state, B, (float)log((double)K_total), log_mean, ess);
   PV_LAUNCH_CHECK();
   return 0;
 }

@@ -66,6 +66,9 @@ struct Layout {
   // c_b (B) gets room behind everything else
   bool renyi; float* r_c;
   double* pl_part;                                          // Poisson plans: pv_poisson_lognorm's partial sums (PV_POISSON_PARTS doubles)
+  // held-out log-evidence (pv_ivae_evidence_accumulate): the multi-particle layout at EVERY P (P == 1 too: sw, llkb and the expansion),
+  // without the buffers only a backward pass touches, and the chunk's (P, B) log-weights behind everything else
+  bool ev; float* ev_lw;
   int64_t total;
 };
 
@@ -165,15 +168,18 @@ bool valid_plan(const pv_ivae_plan* p) {
 // encode_only (with inference_only): none of the decoder's per-row buffers is touched, so they get no room
 // P > 1 (training step only): the multi-particle ELBO's layout; P == 1 is byte for byte the one-particle layout
 // renyi (with P > 1): room for c_b at the very end, behind the multi-particle layout, which is unchanged
+// evidence (training-step form only, never with renyi): Layout::ev — a forward-only layout of its own, no other query's size moves
 void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = false, bool encode_only = false, int P = 1,
-           bool renyi = false) {
+           bool renyi = false, bool evidence = false) {
   Carver c{base, 0};
   L.P = inference_only ? 1 : P;
   L.renyi = renyi && L.P > 1;
+  L.ev = evidence && !inference_only;
+  const bool bwd = !L.ev;                            // room for what only a backward pass reads or writes
   // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
   const int64_t B = p->batch, N = encode_only ? 0 : plan_pos(p), z = p->z_dim, Cn = plan_C(p);
   const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
-  const bool multi = K > 0 || L.P > 1;              // several decoder samples per input
+  const bool multi = K > 0 || L.P > 1 || L.ev;      // several decoder samples per input
   L.rows = p->coord_dim > 0 ? S * N : S;
   const int64_t R = L.rows;
   L.xin = p->c_dim > 0 ? c.take(B * (p->n_pix + p->c_dim)) : nullptr;
@@ -271,12 +277,12 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     L.rows_per_chunk = (int)((N + nchunk - 1) / nchunk);
     if (L.rows_per_chunk < 1) L.rows_per_chunk = 1;
     L.nchunk = (int)((N + L.rows_per_chunk - 1) / L.rows_per_chunk);
-    L.part_hz = c.take(S * L.nchunk * H0);
-    L.part_wc = c.take(S * L.nchunk * H0 * p->coord_dim);
-    L.part_tp = c.take(S * L.nchunk * 4);
-    L.dhz = c.take(S * H0);
-    L.dtp = c.take(S * 4);
-    L.dzc = c.take(S * lat_in);
+    L.part_hz = bwd ? c.take(S * L.nchunk * H0) : nullptr;
+    L.part_wc = bwd ? c.take(S * L.nchunk * H0 * p->coord_dim) : nullptr;
+    L.part_tp = bwd ? c.take(S * L.nchunk * 4) : nullptr;
+    L.dhz = bwd ? c.take(S * H0) : nullptr;
+    L.dtp = bwd ? c.take(S * 4) : nullptr;
+    L.dzc = bwd ? c.take(S * lat_in) : nullptr;
     upd(gemm_ws_need(S, H0, lat_in));          // hz
     upd(gemm_ws_need(H0, lat_in, S));          // dWz
     upd(gemm_ws_need(S, lat_in, H0));          // dzc
@@ -286,7 +292,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     L.llrow = c.take(S * N);
     L.part_dwo = L.part_dbo = L.part_hz = L.part_wc = L.part_tp = L.dhz = L.dtp = nullptr;
     L.nchunk = L.rows_per_chunk = 0;
-    L.dzc = c.take(S * lat_in);
+    L.dzc = bwd ? c.take(S * lat_in) : nullptr;
     if (N > maxd) maxd = N;
     upd(gemm_ws_need(S, N, p->out.in_dim));
     upd(gemm_ws_need(N, p->out.in_dim, S));
@@ -297,8 +303,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.row_ll = c.take(B);
   L.llkb = multi ? c.take(S) : nullptr;
   L.jfix = K > 0 ? c.take(4) : nullptr;
-  L.dbuf[0] = L.fused ? nullptr : c.take(R * maxd);
-  L.dbuf[1] = L.fused ? nullptr : c.take(R * maxd);
+  L.dbuf[0] = (L.fused || !bwd) ? nullptr : c.take(R * maxd);
+  L.dbuf[1] = (L.fused || !bwd) ? nullptr : c.take(R * maxd);
   // scratch: the largest split-K / colsum requirement of any single call
   upd(cnd.scratch);
   for (int i = 0; i < n_enc; ++i) {
@@ -329,7 +335,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   }
   L.r_c = L.renyi ? c.take(B) : nullptr;           // (behind everything else: the multi-particle layout's offsets stay)
   // (at the very end, training layouts of Poisson plans only: every other offset is what it was)
-  L.pl_part = (p->lik == PV_LIK_POISSON_LOG && !inference_only) ? reinterpret_cast<double*>(c.take(2 * PV_POISSON_PARTS)) : nullptr;
+  L.pl_part = (p->lik == PV_LIK_POISSON_LOG && !inference_only && bwd) ? reinterpret_cast<double*>(c.take(2 * PV_POISSON_PARTS)) : nullptr;
+  L.ev_lw = L.ev ? c.take(S) : nullptr;
   L.total = c.off;
 }
 
@@ -892,7 +899,7 @@ int fused_guide(FusedStep& st) {
   const float* Wz = p->params + p->fc_latent.w_off;
   st.kl_n = L.kl_blocks;
   st.kl_part = L.enc_compact;
-  if (L.P > 1) {
+  if (L.P > 1 || L.ev) {
     // multi-particle: the guide never rides in the decoder launch; the encoder once, the expansion writes hz for the P*B samples
     if (p->fused < 2) return PV_EINVAL;
     if (L.enc_compact) {
@@ -1761,6 +1768,83 @@ extern "C" int pv_ivae_renyi_loss_and_grads(const pv_ivae_plan* plan, int32_t nu
 extern "C" int pv_ivae_renyi_step(const pv_ivae_plan* plan, int32_t num_particles, float alpha, float* weights_out, void* stream) {
   PV_RANGE("pv_ivae_renyi_step");
   return step_impl(plan, renyi_obj(num_particles, alpha, weights_out), stream);
+}
+
+// ---- held-out log-evidence (v17, added without a layout change; include/pyroved_amd.h) ----
+// One chunk of P particles of the plan's batch: the launches of the {P, PV_BOUND_RENYI} forward-only call up to the per-sample ll,
+// then — instead of the bound's weights and scalars — the chunk's log-weights and the running state per image.
+// Scope: what that objective accepts, at every P in 1 .. PV_RENYI_MAX_P; the plan's kl_mode is not consulted (a log-weight is a
+// sampled quantity) and runs as PV_KL_SAMPLED; loc is ignored.
+static bool evidence_ok(const pv_ivae_plan* plan, int32_t P) {
+  return P >= 1 && P <= PV_RENYI_MAX_P && valid_plan(plan) && particles_supported(plan);
+}
+static pv_ivae_plan evidence_plan(const pv_ivae_plan* plan) {
+  pv_ivae_plan q = *plan;
+  q.kl_mode = PV_KL_SAMPLED; q.loc = nullptr;
+  return q;
+}
+// the P*B samples' log p(x_b | z_pb) into L.llkb, layer by layer ...
+static int evidence_ll_layered(const pv_ivae_plan* p, const Layout& L, hipStream_t s) {
+  const int64_t B = p->batch, N = plan_pos(p), Cn = plan_C(p), z = p->z_dim, S = step_S(p, L), lat_in = plan_lat_in(p);
+  const int nd = p->n_dec;
+  PV_TRY(particle_guide(p, L, s, nullptr, 0.0f, nullptr));
+  const bool cat_in = p->c_dim > 0;
+  const float* zin = cat_in ? L.zy : (p->coord_dim > 0 ? L.z + (z - p->latent_dim) : L.z);
+  PV_TRY(decoder_hidden_fwd(p, L, zin, cat_in ? lat_in : z, lat_in, s));
+  if (p->coord_dim > 0) {
+    PvOutLik o{};
+    o.h = L.dact[nd - 1]; o.hpre = L.dpre_[nd - 1]; o.ldh = p->dec[nd - 1].out_dim; o.wo = p->params + p->out.w_off;
+    o.bo = bias_of(p->params, p->out); o.x = p->x; o.llrow = L.llrow;
+    o.part_dwo = L.part_dwo; o.part_dbo = L.part_dbo; o.M = L.rows; o.H = p->dec[nd - 1].out_dim;
+    o.lik = p->lik; o.sigmoid_out = p->sigmoid_out; o.act_last = p->dec[nd - 1].act; o.sig = p->decoder_sig;
+    o.sw = L.sw; o.N = (int)N; o.xmod = B * N;
+    PV_TRY(Cn > 1 ? pv_out_lik_mc(o, (int)Cn, s) : pv_out_lik(o, s));
+  } else {
+    for (int64_t k = 0; k < L.P; ++k)                // one pass per particle against the same observations
+      PV_TRY(pv_lik_elem(L.logits + k * B * N, p->x, B * N, p->lik, p->sigmoid_out, p->decoder_sig, nullptr, L.llrow + k * B * N,
+                         nullptr, s, nullptr, N, false, plan_group(p)));
+  }
+  return pv_segsum(L.llrow, S, N, L.llkb, s);
+}
+// ... or with the forward-only launch of the bf16-class fused decoder kernels (fused 2 / 3), which leaves rows
+static int evidence_ll_fused(const pv_ivae_plan* p, const Layout& L, hipStream_t s) {
+  const int64_t lat_in = plan_lat_in(p);
+  if (p->fc_latent.in_dim != lat_in) return PV_EINVAL;
+  const bool cat_in = p->c_dim > 0;
+  const ObjArgs obj{};
+  FusedStep st{p, L, obj, false, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
+               pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, plan_sel(p))};
+  fused_decoder_args(st);
+  PV_TRY(fused_guide(st));
+  PV_TRY(fused_decoder_launch(st));
+  return pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s);
+}
+
+extern "C" int64_t pv_ivae_evidence_workspace_bytes(const pv_ivae_plan* plan, int32_t P) {
+  if (!evidence_ok(plan, P)) return PV_EINVAL;
+  const pv_ivae_plan q = evidence_plan(plan);
+  Layout L;
+  carve(&q, nullptr, L, false, false, P, false, true);
+  return L.total;
+}
+extern "C" int pv_ivae_evidence_accumulate(const pv_ivae_plan* plan, int32_t P, float* state, int first, void* stream) {
+  PV_RANGE("pv_ivae_evidence_accumulate");
+  if (!evidence_ok(plan, P) || !state) return PV_EINVAL;
+  const pv_ivae_plan q = evidence_plan(plan);
+  const pv_ivae_plan* p = &q;
+  if (!p->params || !p->x || !p->eps || !p->ws || (p->c_dim > 0 && !p->y) || (p->coord_dim > 0 && !p->grid)) return PV_EINVAL;
+  Layout L;
+  carve(p, (char*)p->ws, L, false, false, P, false, true);
+  if (p->ws_bytes < L.total) return PV_EWS;
+  hipStream_t s = (hipStream_t)stream;
+  PV_TRY(L.fused ? evidence_ll_fused(p, L, s) : evidence_ll_layered(p, L, s));
+  // every normaliser a log_prob has: the Poisson's data-only one is not in the rows the decoder launches leave
+  if (p->lik == PV_LIK_POISSON_LOG) PV_TRY(pv_poisson_lognorm_particles(p->x, p->batch, p->n_pix, L.llkb, P, s));
+  PvEvidenceLw e{};
+  e.llkb = L.llkb; e.z = L.z; e.eps = p->eps; e.z_scale = L.z_scale; e.lw = L.ev_lw;
+  e.B = (int)p->batch; e.P = P; e.z_dim = p->z_dim; e.beta = p->beta;
+  PV_TRY(pv_evidence_lw(e, s));
+  return pv_logmeanexp_update(L.ev_lw, P, (int32_t)p->batch, state, first, stream);
 }
 
 // (the query of both weighted families: it never sees the pointer, and the per-image instances' list is the shared ones')

@@ -113,6 +113,8 @@ class IVAEEngine:
                                      # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
     pixel_weights = None             # None, or the per-observation weights of the likelihood: one contiguous float32 tensor of n_pix
                                      # values (positions x channels, channel-last), on the device once the engine is bound — pv_ivae_weighted_*
+    _ev_ws = None                    # log_evidence_chunk: the evidence workspace (grows to the largest layout asked for) and the
+    _ev_need = None                  # sizes the library answered, per (batch, P, fused)
     image_weights = False            # True: every loss_and_grads call takes image_weights=w, one weight per observed value of every
                                      # image of the batch — pv_ivae_weighted_images_*
     fast_weights = False             # PV_PLAN_FAST_WEIGHTS: weighted steps on the 4-wave bf16-class fused decoder kernel (fused = 2 or 3)
@@ -1157,6 +1159,79 @@ class IVAEEngine:
         if alpha is not None:
             return z_loc, z_scale, alpha
         return z_loc, z_scale
+
+    # ------------------------------------------------------------------ held-out log-evidence
+    def _check_evidence(self):
+        """log_evidence's scope on the Python side: no observation weights (no kernel applies them to several particles)."""
+        if self._weighted():
+            raise ValueError("log_evidence: this engine is configured with %s, and no kernel applies observation weights to several "
+                             "particles — evaluate on an engine without them"
+                             % ("image_weights" if self.image_weights else "pixel_weights"))
+
+    @_abi.on_device
+    def log_evidence_chunk(self, x, eps, y=None, state: Optional[torch.Tensor] = None, first: bool = True):
+        """Adds one chunk of P particles to the running log-evidence state of the batch x (pv_ivae_evidence_accumulate, beta = 1).
+        eps: (P*B, z_dim) or (P, B, z_dim), rows ordered [p][b]; state: the device (B, 4) float32 tensor a previous chunk returned
+        (None: a new one); first=True initialises it from this chunk.  Returns the state; log_evidence_finish reads it.
+        An engine with fused=1 (fused_channels=True included) evaluates on the layer-by-layer plan, fused=0: both are fp32.
+        The evidence workspace is cached per (batch, P) layout, the largest asked for so far."""
+        self._check_evidence()
+        self.ensure_bound()
+        b = int(x.shape[0])
+        p = self._plan(b, 1.0, what=2)
+        self._check_x(x, p)
+        if eps.numel() % (b * p.z_dim) != 0 or eps.numel() == 0:
+            raise ValueError("log_evidence_chunk: eps must be (P * batch, z_dim) = (P * %d, %d), rows ordered [p][b] (got %s)"
+                             % (b, p.z_dim, tuple(eps.shape)))
+        P = eps.numel() // (b * p.z_dim)
+        x = self._prep(x, "x", (b, p.n_pix))
+        eps = self._prep(eps, "eps", (P * b, p.z_dim))
+        y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
+        if p.c_dim > 0 and y is None:
+            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        if state is None:
+            if not first:
+                raise ValueError("log_evidence_chunk: first=False continues a state, which it needs")
+            state = torch.empty(b, 4, device=self.device, dtype=torch.float32)
+        _abi.require_device(state, "state")
+        if state.dtype != torch.float32 or not state.is_contiguous() or tuple(state.shape) != (b, 4):
+            raise ValueError("log_evidence_chunk: state must be a contiguous float32 tensor of shape (%d, 4)" % b)
+        fused, flags = p.fused, p.flags
+        try:
+            if p.fused == 1:
+                p.fused = 0
+            p.flags = flags & ~_abi.PV_PLAN_FUSED_CHANNELS
+            if self._ev_need is None:
+                self._ev_need = {}
+            key = (b, P, int(p.fused))
+            need = self._ev_need.get(key)
+            if need is None:
+                need = _abi.lib().pv_ivae_evidence_workspace_bytes(C.byref(p), P)
+                if need < 0:
+                    raise _abi.PvError("pyroved_amd: log-evidence unsupported for this plan or particle count %d "
+                                       "(pv_ivae_evidence_workspace_bytes -> %d)" % (P, need))
+                self._ev_need[key] = need
+            if self._ev_ws is None or self._ev_ws.numel() < need:
+                self._ev_ws = torch.empty(int(need), device=self.device, dtype=torch.uint8)
+            p.ws, p.ws_bytes = self._ev_ws.data_ptr(), self._ev_ws.numel()
+            p.x, p.eps = x.data_ptr(), eps.data_ptr()
+            p.y = y.data_ptr() if y is not None else None
+            _abi.check(_abi.lib().pv_ivae_evidence_accumulate(C.byref(p), P, _abi.ptr(state), int(bool(first)), _abi.current_stream()),
+                       "pv_ivae_evidence_accumulate")
+        finally:
+            p.fused, p.flags = fused, flags
+        self._keep = (x, eps, y, state)
+        return state
+
+    @_abi.on_device
+    def log_evidence_finish(self, state, num_samples: int, want_ess: bool = False):
+        """(log p^(x_b), ESS_b or None) on the device from a state that num_samples particles went into (pv_logmeanexp_finish)."""
+        b = int(state.shape[0])
+        out = torch.empty(b, device=self.device, dtype=torch.float32)
+        ess = torch.empty_like(out) if want_ess else None
+        _abi.check(_abi.lib().pv_logmeanexp_finish(_abi.ptr(state), b, int(num_samples), _abi.ptr(out), _abi.ptr(ess),
+                                                   _abi.current_stream()), "pv_logmeanexp_finish")
+        return out, ess
 
     @_abi.on_device
     def decode(self, z, angle: float = 0.0, shift=(0.0, 0.0), scale: float = 1.0):

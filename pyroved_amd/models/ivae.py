@@ -139,6 +139,85 @@ class iVAE(baseVAE):
         s = eng.scalars.cpu().tolist()
         return dict(loss=s[0], ll=s[1], logpz=s[2], logqz=s[3])
 
+    # ---------------------------------------------------------------- held-out log-evidence
+    LOG_EVIDENCE_ROW_CAP = 1 << 19     # decoder rows (P * batch * positions) of one chunk: see log_evidence
+
+    @classmethod
+    def _evidence_chunk(cls, num_samples: int, batch: int, positions: int) -> int:
+        """The default `chunk` of log_evidence: the largest P <= min(num_samples, 1024) with P * batch * positions <=
+        LOG_EVIDENCE_ROW_CAP, at least 1."""
+        return max(1, min(int(num_samples), 1024, cls.LOG_EVIDENCE_ROW_CAP // max(1, int(batch) * int(positions))))
+
+    def _evidence_positions(self) -> int:
+        """Decoder rows per sample: the grid positions of the spatial decoder, 1 for the vanilla decoder (one row per sample)."""
+        import math
+        return math.prod(int(d) for d in self.data_dim) if 0 < self.coord < 5 else 1
+
+    def _evidence_schedule(self, n: int, num_samples: int, chunk: Optional[int], batch_size: int, eps: Optional[torch.Tensor]):
+        """The work list of log_evidence as (lo, hi, first, eps_chunk): image batches [lo, hi) in order (outer), for each the chunks of
+        particles in order (inner), eps_chunk (P, hi - lo, z_dim) on the CPU — the caller's slice, or drawn here in exactly that
+        order with torch.empty(P, hi - lo, z_dim).normal_() on the CPU generator."""
+        for lo in range(0, n, batch_size):
+            hi = min(n, lo + batch_size)
+            P = int(chunk) if chunk is not None else self._evidence_chunk(num_samples, hi - lo, self._evidence_positions())
+            for k0 in range(0, num_samples, P):
+                k1 = min(num_samples, k0 + P)
+                e = eps[k0:k1, lo:hi] if eps is not None else torch.empty(k1 - k0, hi - lo, self.z_dim).normal_()
+                yield lo, hi, k0 == 0, e
+
+    def log_evidence(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, num_samples: int = 64, chunk: Optional[int] = None,
+                     eps: Optional[torch.Tensor] = None, return_ess: bool = False, batch_size: Optional[int] = None):
+        """Held-out log-evidence per image: the K-sample importance-weighted estimate ("IWAE-K", K = num_samples, beta = 1)
+            log p^(x_b) = logsumexp_k [log p(x_b | z_kb [, y_b]) + log N(z_kb; 0, 1) - log N(z_kb; mu_b, sigma_b)] - log K,
+        z_kb = mu_b + sigma_b eps_kb, with every normaliser of the likelihood (the Poisson's -sum lgamma(x + 1) per image included).
+        Returns a CPU float32 tensor (n,); with return_ess=True also the effective sample size (n,), (sum w)^2 / sum w^2 in [1, K].
+        Runs through the HIP library (pv_ivae_evidence_accumulate): the encoder once per image batch, forward-only decoder launches.
+
+        batch_size: images per call, as in encode (default 100).  chunk: particles per call; the estimate streams over
+        ceil(num_samples / chunk) calls against a running (max, sum, sum of squares) per image, the last chunk may be smaller.
+        Default: the largest P <= min(num_samples, 1024) with P * batch * positions <= 2^19 = 524 288 decoder rows (positions: grid
+        points of the spatial decoder, 1 for the vanilla one), which keeps the evidence workspace in the hundreds of MB on every
+        path: about 1.5 kB per row on the layer-by-layer kernels with 128-wide layers (0.8 GB at the cap), about 50 B per row on
+        the fused decoder kernels — there a larger explicit chunk (16 at 28x28, batch 256: 160 MB) is faster, DESIGN.md 4.20.
+        eps: optional (num_samples, n, z_dim) standard-normal draws.  When omitted they are drawn on the CPU generator with
+        torch.empty(P, b, z_dim).normal_() — one draw per call, image batches outer and chunks inner — so a seed fixes the estimate.
+        Precision: the engine's — fused=2 and fused=0 are fp32-class, fused=3 (SVItrainer(precision="bf16")) evaluates with the bf16
+        forward; an engine with fused=1 or fused_channels=True evaluates on the layer-by-layer plan (fused=0): both are fp32.
+        Not for engines configured with pixel_weights / image_weights (no kernel applies observation weights to several particles)."""
+        num_samples = int(num_samples)
+        if num_samples < 1:
+            raise ValueError("log_evidence: num_samples must be >= 1 (got %d)" % num_samples)
+        if chunk is not None and not 1 <= int(chunk) <= 1024:
+            raise ValueError("log_evidence: chunk must be in 1 .. 1024 particles (got %r)" % (chunk,))
+        if self.c_dim > 0 and y is None:
+            raise ValueError("log_evidence: class-conditioned model (c_dim=%d) needs y" % self.c_dim)
+        n = int(x.shape[0])
+        if eps is not None and tuple(eps.shape) != (num_samples, n, self.z_dim):
+            raise ValueError("log_evidence: eps must have shape (num_samples, n, z_dim) = (%d, %d, %d) (got %s)"
+                             % (num_samples, n, self.z_dim, tuple(eps.shape)))
+        eng = self.engine()
+        eng._check_evidence()
+        batch_size = 100 if batch_size is None else int(batch_size)
+        out, ess, state, cur = [], [], None, None
+
+        def flush():
+            lp, es = eng.log_evidence_finish(state, num_samples, return_ess)
+            out.append(lp)
+            if return_ess:
+                ess.append(es)
+
+        for lo, hi, first, e in self._evidence_schedule(n, num_samples, chunk, batch_size, eps):
+            if first:
+                if state is not None:
+                    flush()
+                cur = (x[lo:hi].to(eng.device, torch.float32), None if y is None else y[lo:hi].to(eng.device, torch.float32))
+                state = None
+            state = eng.log_evidence_chunk(cur[0], e.to(eng.device, torch.float32), cur[1], state, first)
+        if state is not None:
+            flush()
+        res = torch.cat(out).cpu() if out else torch.empty(0)
+        return (res, torch.cat(ess).cpu()) if return_ess else res
+
     def model(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, **kwargs: float) -> None:
         """p(x|z)p(z) as a Pyro program (models/ivae.py:165-202) — for users with pyro-ppl (poutine.trace, custom ELBOs,
         pyro.infer.SVI); raises NotImplementedError without it.  SVItrainer evaluates the same objective in HIP kernels

@@ -604,6 +604,20 @@ class SVItrainer:
         """Evaluates the current model state on a single epoch (no gradients)."""
         return self._epoch(test_loader, False, **kwargs)
 
+    def log_evidence(self, loader: Type[torch.utils.data.DataLoader], num_samples: int = 64, **kw) -> float:
+        """Mean over the loader's images of the held-out log-evidence log p^(x_b), in nats: the num_samples-sample importance-weighted
+        estimate at beta = 1 (iVAE.log_evidence, which takes the other keywords: chunk, batch_size).  Unlike the loss it does not
+        depend on the objective, the KL schedule or the particle count the model was trained with.  Batches are (x,) or (x, y)."""
+        if not hasattr(self.model, "log_evidence"):
+            raise ValueError("log_evidence is implemented for models.iVAE (got %s)" % type(self.model).__name__)
+        total, n = 0.0, 0
+        for batch in loader:
+            batch = batch if isinstance(batch, (list, tuple)) else (batch,)
+            lp = self.model.log_evidence(batch[0], batch[1] if len(batch) > 1 else None, num_samples=num_samples, **kw)
+            total += float(lp.double().sum())
+            n += int(lp.numel())
+        return total / max(n, 1)
+
     def step(self,
              train_loader: Type[torch.utils.data.DataLoader],
              test_loader: Optional[Type[torch.utils.data.DataLoader]] = None,
