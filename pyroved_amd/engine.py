@@ -69,29 +69,18 @@ def _linears(seq: nn.Sequential) -> List[nn.Linear]:
     return [m for m in seq if isinstance(m, nn.Linear)]
 
 
+# settings as given -> as the engine keeps them (pixel_weights needs the model: IVAEEngine._pixel_weight_tensor)
+_NORMALISE = dict(fused=int, kl=_kl_name, particles=_particle_count, renyi=_renyi_alpha, fused_channels=bool,
+                  image_weights=_image_weights_flag, fast_weights=bool)
+
+
 class IVAEEngine:
-    """Binds an iVAE-like model (encoder_z: fcEncoderNet, decoder: sDecoderNet | fcDecoderNet)
-    to the HIP library.  A multi-channel model (models.iVAE(..., channels=C), self.C > 1) takes x as (B, *data_dim, C), channel-last,
-    returns loc / decode in that shape, and runs the layer-by-layer kernels whatever `fused` asks for (plan.out.out_dim = C,
-    plan.n_pix = prod(data_dim) * C) — unless fused_channels=True: then fused = 1 or 2 runs the step, evaluate and decode on the
-    fused f32 decoder kernel's multi-channel sibling (plan.fused = 1 + PV_PLAN_FUSED_CHANNELS; fp32-class results) wherever the
-    decoder is the one that kernel is written for (hidden [128, 128], tanh, positions a multiple of 16), and layered elsewhere.
-    pixel_weights=w: one weight >= 0 per observed value (a mask, a gain map), shared by all images, multiplies every log p(x_bi | z_b)
-    of the training step, evaluate and elbo_terms (pv_ivae_weighted_*; encode / decode never see it).  models.iVAE with its own
-    fully connected networks, the one-particle ELBO, fused = 0, 1 or 2.  A one-channel model with fused = 1 or 2 then runs the
-    weighted fused f32 decoder kernel (plan.fused = 1), not the fp16-piece kernel of the unweighted fused = 2 step.
-    image_weights=True: every call of loss_and_grads (and model.elbo_terms) brings one weight >= 0 per observed value of EVERY image
-    of its batch, loss_and_grads(x, eps, ..., image_weights=w) with w of shape (b, *data_dim), (b, *data_dim, C) or (b, n_pix) — masks
-    that differ from image to image: sparse scans, windows cropped at the edge of the field of view, per-frame saturated pixels or
-    exposure maps (pv_ivae_weighted_images_*).  Scope, routing and kernels are those of pixel_weights; the two combine (the
-    library gets their product).  The encoder sees x as given: x must be finite also where w = 0 (utils.weights_from_nan).  Only
-    shape and dtype are checked per call — finite, >= 0 values are the caller's promise (SVItrainer checks them on the host).
-    fast_weights=True (with pixel_weights and / or image_weights, fused = 2 or 3): the weighted step keeps the bf16-class decoder —
-    the weighted instances of the 4-wave fused kernel's bf16 three-product build (fused = 2, fp32-class results) or plain-bf16 build
-    (fused = 3 / precision='bf16', which is refused without the keyword) — instead of the fused f32 kernel (PV_PLAN_FAST_WEIGHTS).
-    For a one-channel spatial decoder of two tanh layers of 128 with positions a multiple of 16; with fused = 2 every other model
-    keeps the routing above, with fused = 3 it is refused."""
-    supports_dp_step = True          # loss_and_grads(step=True, comm=NativeComm): the data-parallel step as one library call
+    """Binds an iVAE-like model (encoder_z: fcEncoderNet, decoder: sDecoderNet | fcDecoderNet) to the HIP library.
+    A multi-channel model (models.iVAE(..., channels=C), self.C > 1) takes x as (B, *data_dim, C), channel-last, and returns loc /
+    decode in that shape.  The settings — fused, kl, particles, renyi, fused_channels, pixel_weights, image_weights, fast_weights,
+    each described at its class default below — are plain attributes read at every call; model.engine(**kw) and configure(**kw)
+    set them.  Which combinations a model takes, and every refusal's text, is `_validate`'s rule list; which kernels a combination
+    runs on is `_plan_fused` / `_plan_flags`.  Per-batch weights come with every call: loss_and_grads(..., image_weights=w)."""
     supports_scalars_out = True      # loss_and_grads can write the 4 loss scalars to a caller-given device slot
     supports_step = True             # loss_and_grads(step=True) = SVI.step in one library call
     # per-plan switches (ABI v14 / v15 plan fields; the library keeps no process-wide switch).  Set on an engine — or, in tests,
@@ -105,32 +94,44 @@ class IVAEEngine:
     conv_x3 = False                  # PV_PLAN_CONV_X3 / conv_bf16 = 0: fp32-class kernel-3 convolutions with both operands as two fp16 pieces
     enc_fold = True                  # PV_PLAN_NO_ENC_FOLD when False (the guide as its own launch even where the decoder launch could host it)
     full_tile_loop = True            # PV_PLAN_GENERIC_TILE_LOOP when False (the image-owning decoder launch keeps its generic tile loop; bit-identical)
-    C = 1                            # channels per grid position (models.iVAE(..., channels=C)); set by _check_model
+    conv_events = None               # (start, stop, ctypes double for the launch's FLOPs) around the convolution launches, or None
+    # the model's facts, established once by _check_model (set_encoder / set_decoder drop the engine):
+    K = 0                            # classes of the discrete latent (jiVAE)
+    C = 1                            # channels per grid position (models.iVAE(..., channels=C))
+    conv_enc = False                 # encoder_z is a convEncoderNet
+    ext_enc = ext_dec = False        # encoder_z / decoder is a user-defined module: it runs in torch
+    ext_y = False                    # ... and so is the label network (SSEngine)
+    own_fc = False                   # models.iVAE itself with its own fully connected encoder and decoder
+    fw_blocker = None                # why the weighted bf16-class decoder kernel does not take this model (None: it does)
+    # the settings (model.engine(**kw) / configure(**kw): normalise -> _validate -> assign):
+    fused = 2                        # 0 layered kernels, 1 fused f32-MFMA decoder, 2 fused bf16x3 decoder, 3 fused plain-bf16 decoder
     fused_channels = False           # PV_PLAN_FUSED_CHANNELS (with C > 1 and fused = 1 or 2): the multi-channel fused f32 decoder kernel
+                                     # (fp32-class; decoder hidden [128, 128], tanh, positions a multiple of 16 — layered elsewhere)
     kl = "sampled"                   # pv_ivae_plan.kl_mode / pv_ved_plan.kl_mode: "sampled" log q(z|x) - log p(z) at the drawn z
                                      # (Trace_ELBO) or "analytic", the closed-form KL(q || N(0, 1)) (TraceMeanField_ELBO)
+    particles = 1                    # particles of the ELBO estimate (num_particles of the Pyro ELBO objects) — pv_ivae_particles_*
     renyi = None                     # None: the ELBO; a float alpha != 1: the importance-weighted bound of that order over the
                                      # `particles` samples (pyro.infer.RenyiELBO(alpha, num_particles); 0 = IWAE) — pv_ivae_renyi_*
-    pixel_weights = None             # None, or the per-observation weights of the likelihood: one contiguous float32 tensor of n_pix
-                                     # values (positions x channels, channel-last), on the device once the engine is bound — pv_ivae_weighted_*
+    pixel_weights = None             # None, or the per-observation weights of the likelihood, shared by all images: one contiguous
+                                     # float32 tensor of n_pix values (positions x channels, channel-last), on the device once the
+                                     # engine is bound — pv_ivae_weighted_* (training step, evaluate, elbo_terms; not encode / decode)
+    image_weights = False            # True: every loss_and_grads call takes image_weights=w, one weight >= 0 per observed value of
+                                     # every image of the batch (x must be finite also where w = 0) — pv_ivae_weighted_images_*;
+                                     # with pixel_weights as well the library gets the product
+    fast_weights = False             # PV_PLAN_FAST_WEIGHTS: weighted steps on the 4-wave bf16-class fused decoder kernel (fused = 2:
+                                     # where the model is one it takes, fp32-class results; fused = 3: refused elsewhere)
     _ev_ws = None                    # log_evidence_chunk: the evidence workspace (grows to the largest layout asked for) and the
     _ev_need = None                  # sizes the library answered, per (batch, P, fused)
-    image_weights = False            # True: every loss_and_grads call takes image_weights=w, one weight per observed value of every
-                                     # image of the batch — pv_ivae_weighted_images_*
-    fast_weights = False             # PV_PLAN_FAST_WEIGHTS: weighted steps on the 4-wave bf16-class fused decoder kernel (fused = 2 or 3)
+    _snap = None                     # _bound's snapshot of the module tree
+    _conv_slices = None              # _check_conv_weight_range's weight slices (None: derive them at the next call)
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
                  particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None,
                  image_weights: bool = False, fast_weights: bool = False):
         self.model = model
-        self.image_weights = _image_weights_flag(image_weights)
-        self.fast_weights = bool(fast_weights)
-        self.fused_channels = bool(fused_channels)
-        self.kl = _kl_name(kl)
-        self.particles = _particle_count(particles)   # particles of the ELBO estimate (num_particles of the Pyro ELBO objects)
-        self.renyi = _renyi_alpha(renyi)
+        new = self._normalise(dict(image_weights=image_weights, fast_weights=fast_weights, fused_channels=fused_channels, kl=kl,
+                                   particles=particles, renyi=renyi, fused=fused))
         self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.fused = int(fused)         # 0 layered kernels, 1 fused f32-MFMA decoder, 2 fused bf16x3 decoder, 3 fused plain-bf16 decoder
         self.adam_t = 0                 # number of optimizer steps taken (incl. evaluate()'s, see SVItrainer)
         self.grads_live = False         # reference: .grad is None until the first backward
         self.device = None
@@ -143,11 +144,11 @@ class IVAEEngine:
         self._layout: Dict[str, int] = {}
         self._views: Dict[str, torch.Tensor] = {}
         self._check_model()
-        self.pixel_weights = self._pixel_weight_tensor(pixel_weights)
-        self._check_particles()
-        self._check_fused_channels()
-        self._check_pixel_weights()
-        self._check_fast_weights()
+        self.own_fc = type(self) is IVAEEngine and not (self.conv_enc or self.ext_enc or self.ext_dec)
+        self.fw_blocker = self._fast_weights_blocker()
+        new.update(self._normalise(dict(pixel_weights=pixel_weights)))      # (needs C)
+        self._validate(dec_kernel=self.dec_kernel, **new)
+        vars(self).update(new)
         self.bind()
 
     # ------------------------------------------------------------------ structure
@@ -162,7 +163,6 @@ class IVAEEngine:
         # a user-defined decoder (models/base.py:179-183) likewise: the library runs the guide half of the step
         # (pv_ivae_guide / pv_ivae_guide_backward), the decoder, the coordinate transform and the likelihood run in PyTorch
         self.ext_dec = not isinstance(dec, (sDecoderNet, fcDecoderNet))
-        self.K = 0
         # channels per grid position (models.iVAE(..., channels=C)): observations are channel-last, n_pix = positions * C
         self.C = int(getattr(m, "channels", 1))
         if self.C != 1:
@@ -194,7 +194,6 @@ class IVAEEngine:
             raise UnsupportedModel("the HIP SVI path needs encoder_z to be pyroved_amd.nets.fcEncoderNet / "
                                    "jfcEncoderNet / convEncoderNet (got %s)" % type(enc).__name__)
         self.K = int(getattr(m, "discrete_dim", 0)) if isinstance(enc, jfcEncoderNet) else 0
-        self._check_kl()
         if self.ext_enc and self.ext_dec:
             return                                   # both user modules: the library keeps the reparameterisation + KL
         if self.ext_enc and isinstance(dec, (sDecoderNet, fcDecoderNet)):
@@ -248,7 +247,7 @@ class IVAEEngine:
                     if not k.startswith("encoder_z.") and not (self.ext_dec and k.startswith("decoder."))]
         if self.ext_dec:                         # only the encoder does
             named = {k: v for k, v in named.items() if not k.startswith("decoder.")}
-        if getattr(self, "ext_y", False):        # a user-defined label network (semi-supervised models) stays in torch
+        if self.ext_y:                           # a user-defined label network (semi-supervised models) stays in torch
             named = {k: v for k, v in named.items() if not k.startswith("encoder_y.")}
         if self.conv_enc:
             return list(named.items())           # features2latent.fc_latent already is the merged [mu | sigma] head
@@ -317,10 +316,10 @@ class IVAEEngine:
         self.device = dev
         self.scalars = self.grad[total:total + N_SCALARS]
         self.grid = self.model.grid.to(dev).contiguous() if self.model.coord > 0 else None
-        if getattr(self, "pixel_weights", None) is not None:
+        if self.pixel_weights is not None:
             self.pixel_weights = self.pixel_weights.to(dev).contiguous()
         self.ws = None
-        if self.ext_enc or self.ext_dec or getattr(self, "ext_y", False):
+        if self._torch_side:
             # the user module's parameters: their own torch Adam (zero_grads semantics)
             owners = ([self.model.encoder_z] if self.ext_enc else []) + ([self.model.decoder] if self.ext_dec else [])
             if not owners:
@@ -329,49 +328,6 @@ class IVAEEngine:
             if self._enc_opt is None or [id(q) for q in self._enc_opt.param_groups[0]["params"]] != [id(q) for q in self._enc_params]:
                 self._enc_opt = torch.optim.Adam(self._enc_params, lr=self.lr, betas=self.betas, eps=self.adam_eps)
         self._static = self._static_plan()
-
-    def _check_kl(self):
-        if self.kl == "analytic" and getattr(self, "K", 0) > 0:
-            raise ValueError("kl='analytic' (TraceMeanField_ELBO) is not defined for models with a discrete latent (jiVAE): "
-                             "their objective enumerates or samples the class (TraceEnum_ELBO / Trace_ELBO)")
-
-    def _check_particles(self):
-        """particles > 1 (pv_ivae_particles_*) and renyi (pv_ivae_renyi_*, at every particle count): the fc-encoder iVAE on the
-        layered or the bf16-class fused decoder path; renyi with the sampled KL form only."""
-        # (the native one-call DP step is the one-particle, single-channel ELBO's)
-        self.supports_dp_step = (type(self).supports_dp_step and self.particles == 1 and self.renyi is None
-                                 and getattr(self, "C", 1) == 1 and not self._weighted())
-        if self.particles == 1 and self.renyi is None:
-            return
-        what = "particles > 1" if self.renyi is None else "renyi"
-        if type(self) is not IVAEEngine:
-            raise ValueError("%s is implemented for models.iVAE only (not for %s)" % (what, type(self.model).__name__))
-        if self.K > 0:
-            raise ValueError("%s is not defined here for models with a discrete latent (jiVAE): their objective "
-                             "enumerates or samples the class" % what)
-        if self.conv_enc or self.ext_enc or self.ext_dec:
-            raise ValueError("%s needs the model's own fully connected encoder and decoder (no convolutional or "
-                             "user-defined networks)" % what)
-        if self.fused == 1:
-            raise ValueError("%s runs on fused = 0, 2 or 3 (not on the f32-MFMA fused kernel, fused = 1)" % what)
-        if self.renyi is not None and self.kl == "analytic":
-            raise ValueError("renyi needs kl='sampled': the closed-form KL has no per-sample term for the bound to weigh")
-
-    def _check_fused_channels(self):
-        """fused_channels=True asks for the multi-channel kernel of the f32 fused decoder: the one-particle ELBO (either KL form) at
-        fp32-class precision, so fused = 1 or 2.  With one channel the keyword changes nothing the library sees."""
-        if not self.fused_channels:
-            return
-        if type(self) is not IVAEEngine:
-            raise ValueError("fused_channels is implemented for models.iVAE only (not for %s)" % type(self.model).__name__)
-        if self.particles > 1 or self.renyi is not None:
-            raise ValueError("fused_channels=True runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound: "
-                             "the f32 fused kernel it selects has no multi-particle form)")
-        if self.fused == 3:
-            raise ValueError("fused_channels=True selects the f32 fused decoder kernel; fused=3 (precision='bf16') asks for the "
-                             "bf16 throughput kernels, which have no multi-channel form")
-        if self.fused == 0:
-            raise ValueError("fused_channels=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2")
 
     def _pixel_weight_tensor(self, w):
         """pixel_weights as the library takes them: None / False -> None; a tensor, ndarray or bool mask of shape data_dim (the same
@@ -384,7 +340,7 @@ class IVAEEngine:
         except Exception as e:
             raise ValueError("pixel_weights must be a tensor, an ndarray or a bool mask (got %s)" % type(w).__name__) from e
         dd = tuple(int(d) for d in self.model.data_dim)
-        Cn = int(getattr(self, "C", 1))
+        Cn = self.C
         if t.dtype == torch.bool:
             t = t.to(torch.float32)
         if not (t.is_floating_point() or t.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
@@ -402,35 +358,98 @@ class IVAEEngine:
             raise ValueError("pixel_weights must be >= 0 (found %g)" % float(t.min()))
         if not bool((t > 0).any()):
             raise ValueError("pixel_weights are all zero: no observation would enter the loss")
-        dev = getattr(self, "device", None)
-        return t.to(dev) if dev is not None else t.clone()
+        return t.to(self.device) if self.device is not None else t.clone()
+
+    def _normalise(self, kw):
+        """Settings as given -> as the engine keeps them; ValueError for a value that has no such form."""
+        return {k: self._pixel_weight_tensor(v) if k == "pixel_weights" else _NORMALISE[k](v) for k, v in kw.items()}
+
+    def _settings(self):
+        return dict(fused=self.fused, kl=self.kl, particles=self.particles, renyi=self.renyi, fused_channels=self.fused_channels,
+                    pixel_weights=self.pixel_weights, image_weights=self.image_weights, fast_weights=self.fast_weights)
+
+    def _validate(self, *, fused, kl, particles, renyi, fused_channels, pixel_weights, image_weights, fast_weights, dec_kernel):
+        """The one rule list: which settings (normalised, _normalise) this model takes.  Raises the first rule the candidate breaks,
+        in the order written; reads the model's facts (K, own_fc, fw_blocker) and no setting off self, and assigns nothing.  The
+        constructor and configure() both validate here before they assign, so a refusal leaves no trace.
+        On fast_weights: fused = 3 promises the bf16 kernel family, so a model the weighted bf16 decoder kernel does not take is
+        refused; fused = 2 promises fp32-class results, which the weighted fused f32 / layer-by-layer kernels deliver as well, so
+        such a model keeps that routing (_fast_weights_on)."""
+        name = type(self.model).__name__
+        multi = particles > 1 or renyi is not None
+        what = "particles > 1" if renyi is None else "renyi"
+        kw = " / ".join(k for k, on in (("pixel_weights", pixel_weights is not None), ("image_weights", image_weights)) if on)
+        weighted = bool(kw)
+        why = self.fw_blocker
+        only_ivae = "%s is implemented for models.iVAE only (not for " + name + ")"
+
+        def scope(on, what, discrete):
+            """The scope rule of `what`: models.iVAE itself, no discrete latent, its own fully connected encoder and decoder."""
+            return ((on and type(self) is not IVAEEngine, only_ivae % what),
+                    (on and self.K > 0, discrete),
+                    (on and not self.own_fc, "%s needs the model's own fully connected encoder and decoder (no convolutional or "
+                                             "user-defined networks)" % what))
+        rules = (
+            (kl == "analytic" and self.K > 0,
+             "kl='analytic' (TraceMeanField_ELBO) is not defined for models with a discrete latent (jiVAE): "
+             "their objective enumerates or samples the class (TraceEnum_ELBO / Trace_ELBO)"),
+            *scope(multi, what, "%s is not defined here for models with a discrete latent (jiVAE): their objective "
+                                "enumerates or samples the class" % what),
+            (multi and fused == 1, "%s runs on fused = 0, 2 or 3 (not on the f32-MFMA fused kernel, fused = 1)" % what),
+            (renyi is not None and kl == "analytic",
+             "renyi needs kl='sampled': the closed-form KL has no per-sample term for the bound to weigh"),
+            (fused_channels and type(self) is not IVAEEngine, only_ivae % "fused_channels"),
+            (fused_channels and multi,
+             "fused_channels=True runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound: "
+             "the f32 fused kernel it selects has no multi-particle form)"),
+            (fused_channels and fused == 3,
+             "fused_channels=True selects the f32 fused decoder kernel; fused=3 (precision='bf16') asks for the "
+             "bf16 throughput kernels, which have no multi-channel form"),
+            (fused_channels and fused == 0,
+             "fused_channels=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2"),
+            *scope(weighted, kw, only_ivae % kw),
+            (weighted and multi, "%s runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)" % kw),
+            (weighted and fused == 3 and not fast_weights,
+             "%s is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
+             "no weighted form, and training at another precision than the one asked for is worse than refusing" % kw),
+            (fast_weights and not weighted,
+             "fast_weights=True selects the kernel of a WEIGHTED step: it needs pixel_weights and / or image_weights"),
+            (fast_weights and fused in (0, 1),
+             "fast_weights=True contradicts fused=%d (%s): it selects the bf16-class fused decoder kernels, use "
+             "fused=2 or fused=3 (precision='bf16')"
+             % (fused, "the layer-by-layer kernels" if fused == 0 else "the f32 fused kernel")),
+            (fast_weights and fused == 3 and why is not None,
+             "fast_weights=True with fused=3 (precision='bf16') needs a model the weighted bf16 decoder kernel "
+             "takes, and %s" % why),
+            (fast_weights and dec_kernel not in (0, 1) and why is None,
+             "fast_weights=True runs the 4-wave bf16 decoder kernel (dec_kernel 0 or 1), not dec_kernel=%d" % dec_kernel),
+        )
+        for broken, message in rules:
+            if broken:
+                raise ValueError(message)
+
+    @property
+    def supports_dp_step(self) -> bool:
+        """loss_and_grads(step=True, comm=NativeComm), the data-parallel step as one library call: the one-particle,
+        single-channel, unweighted ELBO's."""
+        return self.particles == 1 and self.renyi is None and self.C == 1 and not self._weighted()
+
+    @property
+    def _torch_side(self) -> bool:
+        """Some module of this model runs in torch (a user-defined encoder_z, decoder or label network), with its own Adam."""
+        return self.ext_enc or self.ext_dec or self.ext_y
 
     def _weighted(self) -> bool:
         """Whether the step runs the weighted entry points (pixel_weights, image_weights or both)."""
-        return getattr(self, "pixel_weights", None) is not None or bool(getattr(self, "image_weights", False))
-
-    def _check_pixel_weights(self):
-        """pixel_weights (pv_ivae_weighted_*) and image_weights (pv_ivae_weighted_images_*): the one-particle ELBO of models.iVAE
-        with its own fully connected networks, on fused = 0, 1 or 2."""
-        if not self._weighted():
-            return
-        kw = " / ".join(k for k, on in (("pixel_weights", getattr(self, "pixel_weights", None) is not None),
-                                        ("image_weights", getattr(self, "image_weights", False))) if on)
-        if type(self) is not IVAEEngine or getattr(self, "K", 0) > 0:
-            raise ValueError("%s is implemented for models.iVAE only (not for %s)" % (kw, type(self.model).__name__))
-        if self.conv_enc or self.ext_enc or self.ext_dec:
-            raise ValueError("%s needs the model's own fully connected encoder and decoder (no convolutional or "
-                             "user-defined networks)" % kw)
-        if self.particles > 1 or self.renyi is not None:
-            raise ValueError("%s runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)" % kw)
-        if self.fused == 3 and not self.fast_weights:
-            raise ValueError("%s is not implemented for fused=3 (precision='bf16'): the bf16 throughput kernels have "
-                             "no weighted form, and training at another precision than the one asked for is worse than refusing" % kw)
+        return self.pixel_weights is not None or self.image_weights
 
     def _fast_weights_blocker(self) -> Optional[str]:
-        """None where the weighted 4-wave bf16-class decoder kernel takes this model; otherwise the condition that fails."""
+        """None where the weighted 4-wave bf16-class decoder kernel takes this model; otherwise the condition that fails.
+        Asked once, by the constructor (self.fw_blocker): the model's structure is fixed for the engine's life."""
         m, dec = self.model, self.model.decoder
-        if int(getattr(self, "C", 1)) != 1:
+        if not self.own_fc:
+            return "it is not models.iVAE with its own fully connected encoder and decoder"
+        if self.C != 1:
             return "the model has %d channels (the kernel computes one)" % self.C
         if m.coord == 0 or not isinstance(dec, sDecoderNet):
             return "the decoder is the vanilla fully connected one (the kernel is the spatial decoder's)"
@@ -444,30 +463,9 @@ class IVAEEngine:
             return "the grid has %d positions, not a multiple of 16" % n_pos
         return None
 
-    def _check_fast_weights(self):
-        """fast_weights=True asks for the weighted instances of the 4-wave bf16-class decoder kernel: a weighted engine on fused = 2
-        or 3.  fused = 3 promises that kernel family, so a model it does not take is refused; fused = 2 promises fp32-class results,
-        which the weighted fused f32 / layer-by-layer kernels deliver as well, so such a model keeps that routing."""
-        if not self.fast_weights:
-            return
-        if not self._weighted():
-            raise ValueError("fast_weights=True selects the kernel of a WEIGHTED step: it needs pixel_weights and / or image_weights")
-        if self.fused in (0, 1):
-            raise ValueError("fast_weights=True contradicts fused=%d (%s): it selects the bf16-class fused decoder kernels, use "
-                             "fused=2 or fused=3 (precision='bf16')"
-                             % (self.fused, "the layer-by-layer kernels" if self.fused == 0 else "the f32 fused kernel"))
-        why = self._fast_weights_blocker()
-        if self.fused == 3 and why is not None:
-            raise ValueError("fast_weights=True with fused=3 (precision='bf16') needs a model the weighted bf16 decoder kernel "
-                             "takes, and %s" % why)
-        if getattr(self, "dec_kernel", 0) not in (0, 1) and why is None:
-            raise ValueError("fast_weights=True runs the 4-wave bf16 decoder kernel (dec_kernel 0 or 1), not dec_kernel=%d"
-                             % self.dec_kernel)
-
     def _fast_weights_on(self) -> bool:
         """Whether the weighted step runs the weighted bf16-class kernel (the plan then carries PV_PLAN_FAST_WEIGHTS and keeps `fused`)."""
-        return (bool(getattr(self, "fast_weights", False)) and self._weighted() and self.fused in (2, 3)
-                and self._fast_weights_blocker() is None)
+        return self.fast_weights and self._weighted() and self.fused in (2, 3) and self.fw_blocker is None
 
     def _image_weight_tensor(self, w, b: int, n_pix: int):
         """image_weights of one call as the library takes them: a float / bool / integer tensor or ndarray of shape (b, *data_dim)
@@ -514,49 +512,19 @@ class IVAEEngine:
         pixel_weights: weights set them, False removes them, None leaves the setting.
         image_weights: True turns the per-image weighted step on, False off, None leaves the setting.
         fast_weights: True / False switches the weighted step to / from the bf16-class decoder kernels, None leaves the setting."""
-        if lr is not None:
-            self.lr = float(lr)
-        if betas is not None:
-            self.betas = (float(betas[0]), float(betas[1]))
-        if eps is not None:
-            self.adam_eps = float(eps)
-        old = (self.fused, self.particles, self.renyi, self.kl, self.fused_channels)
-        old_pw, old_iw, old_fw = self.pixel_weights, self.image_weights, self.fast_weights
-        if fast_weights is not None and bool(fast_weights) != self.fast_weights:
-            self.fast_weights = bool(fast_weights)
-            self.ws = None
-        if image_weights is not None:
-            new_iw = _image_weights_flag(image_weights)                       # (raises before anything is changed)
-        if pixel_weights is not None:
-            self.pixel_weights = self._pixel_weight_tensor(pixel_weights)     # (raises before anything is changed)
-            if self.pixel_weights is not None or old_pw is not None:          # (False on an unweighted engine: nothing to reset)
-                self.ws = None
-        if image_weights is not None and new_iw != old_iw:
-            self.image_weights = new_iw
-            self.ws = None
-        if fused is not None and int(fused) != self.fused:
-            self.fused = int(fused)
-            self.ws = None
-        if fused_channels is not None and bool(fused_channels) != self.fused_channels:
-            self.fused_channels = bool(fused_channels)
-            self.ws = None
-        if particles is not None:
-            self.particles = _particle_count(particles)
-        if renyi is not None:
-            self.renyi = _renyi_alpha(renyi)
-        if kl is not None:
-            self.kl = _kl_name(kl)
-        try:
-            self._check_particles()
-            self._check_kl()
-            self._check_fused_channels()
-            self._check_pixel_weights()
-            self._check_fast_weights()
-        except ValueError:
-            self.fused, self.particles, self.renyi, self.kl, self.fused_channels = old
-            self.pixel_weights, self.image_weights, self.fast_weights = old_pw, old_iw, old_fw
-            self._check_particles()
-            raise
+        given = dict(image_weights=image_weights, fast_weights=fast_weights, fused_channels=fused_channels, kl=kl,
+                     particles=particles, renyi=renyi, fused=fused, pixel_weights=pixel_weights)
+        new = self._normalise({k: v for k, v in given.items() if v is not None})
+        adam = dict(lr=None if lr is None else float(lr), betas=None if betas is None else (float(betas[0]), float(betas[1])),
+                    adam_eps=None if eps is None else float(eps))
+        old = self._settings()
+        self._validate(dec_kernel=self.dec_kernel, **{**old, **new})
+        # accepted: nothing was assigned before this line.  The workspace's layout depends on the kernels the settings select
+        if (any(k in new and new[k] != old[k] for k in ("fast_weights", "image_weights", "fused", "fused_channels"))
+                or ("pixel_weights" in new and (new["pixel_weights"] is not None or old["pixel_weights"] is not None))):
+            self.ws = None                                  # (pixel_weights=False on an unweighted engine: nothing to reset)
+        vars(self).update(new)
+        vars(self).update({k: v for k, v in adam.items() if v is not None})
         if self.flat is not None:
             self._static = self._static_plan()
         return self
@@ -591,7 +559,7 @@ class IVAEEngine:
         fast path walks the snapshot taken at the last full check (a few microseconds; nn.Module.named_parameters() of a
         small model costs ~40 — a third of a 0.1 ms step's host time); anything that differs from it — a tensor moved,
         replaced, added or removed, a submodule swapped — falls through to the full comparison."""
-        snap = getattr(self, "_snap", None)
+        snap = self._snap
         if snap is not None and snap[2] is self._views:
             ok = True
             for mod, npar, nbuf, kids in snap[0]:
@@ -625,7 +593,7 @@ class IVAEEngine:
             named = {k: v for k, v in named.items() if not k.startswith("encoder_z.")}
         if self.ext_dec:
             named = {k: v for k, v in named.items() if not k.startswith("decoder.")}
-        if getattr(self, "ext_y", False):
+        if self.ext_y:
             named = {k: v for k, v in named.items() if not k.startswith("encoder_y.")}
         named.update(dict(self._stat_buffers()))
         if len(named) != len(self._views):
@@ -654,7 +622,7 @@ class IVAEEngine:
         One scalar read-back per 64 calls; Adam moves a weight by at most lr per step, so the margin to fp16's limit (1023)
         cannot be crossed between two checks.  The read-back synchronises: while the current stream is being captured the
         check is skipped (captured steps are never range-checked — check before capturing)."""
-        if getattr(self, "_conv_slices", None) is None:
+        if self._conv_slices is None:
             self._conv_slices = self._conv3_weight_slices()
             self._conv_tick = 0
         if not self._conv_slices or self.wide_weights:
@@ -675,16 +643,16 @@ class IVAEEngine:
 
     def _plan_flags(self) -> int:
         """pv_ivae_plan.flags / pv_ved_plan.flags from the engine's switches (ABI v14; process-wide setters before)."""
-        return ((_abi.PV_PLAN_ENC_TWO_LAUNCH if getattr(self, "enc_two_launch", False) else 0) |
-                (0 if getattr(self, "side_stream", True) else _abi.PV_PLAN_NO_SIDE_STREAM) |
-                (_abi.PV_PLAN_ENC_NO_WAIT if getattr(self, "enc_no_wait", False) else 0) |
-                (0 if getattr(self, "dec1d", True) else _abi.PV_PLAN_NO_DEC1D) |
-                (0 if getattr(self, "enc_fold", True) else _abi.PV_PLAN_NO_ENC_FOLD) |
-                (0 if getattr(self, "enc_per_image", True) else _abi.PV_PLAN_ENC_TILED) |
-                (0 if getattr(self, "full_tile_loop", True) else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
-                (_abi.PV_PLAN_FUSED_CHANNELS if (getattr(self, "fused_channels", False) and getattr(self, "C", 1) > 1) else 0) |
+        return ((_abi.PV_PLAN_ENC_TWO_LAUNCH if self.enc_two_launch else 0) |
+                (0 if self.side_stream else _abi.PV_PLAN_NO_SIDE_STREAM) |
+                (_abi.PV_PLAN_ENC_NO_WAIT if self.enc_no_wait else 0) |
+                (0 if self.dec1d else _abi.PV_PLAN_NO_DEC1D) |
+                (0 if self.enc_fold else _abi.PV_PLAN_NO_ENC_FOLD) |
+                (0 if self.enc_per_image else _abi.PV_PLAN_ENC_TILED) |
+                (0 if self.full_tile_loop else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
+                (_abi.PV_PLAN_FUSED_CHANNELS if (self.fused_channels and self.C > 1) else 0) |
                 (_abi.PV_PLAN_FAST_WEIGHTS if self._fast_weights_on() else 0) |
-                (_abi.PV_PLAN_CONV_X3 if getattr(self, "conv_x3", False) else 0))
+                (_abi.PV_PLAN_CONV_X3 if self.conv_x3 else 0))
 
     def ensure_bound(self):
         if not self._bound():
@@ -801,14 +769,14 @@ class IVAEEngine:
         p.bn_eval = int(not self.model.training)
         p.conv_wide = int(self.wide_weights)
         p.flags = self._plan_flags()
-        p.dec_kernel = int(getattr(self, "dec_kernel", 0))     # 0: the library picks the decoder-kernel build by size (ABI v15)
+        p.dec_kernel = int(self.dec_kernel)                     # 0: the library picks the decoder-kernel build by size (ABI v15)
         p.kl_mode = _abi.KL[self.kl]                            # (ABI v17)
         p.x = p.y = p.eps = p.z_loc = p.z_scale = p.loc = p.alpha = p.ext_head = p.ext_dhead = None
         p.row_w = p.row_elbo = p.dy = None
         p.ext_z = p.ext_dz = p.ext_ll = None
         p.class_onehot = None
         p.ev_start, p.ev_stop = self.events
-        ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
+        ce = self.conv_events                            # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
         if what == 1:                                    # the training step's layout for this engine's objective
             need = _abi.lib().pv_ivae_objective_workspace_bytes(C.byref(p), C.byref(self._objective))
@@ -842,6 +810,26 @@ class IVAEEngine:
         if shape is not None and tuple(t.shape) != tuple(shape):
             t = t.reshape(shape)
         return t
+
+    def _prep_y(self, y, b: int, p) -> Optional[torch.Tensor]:
+        """The conditioning vectors (b, c_dim) of a class-conditioned model; None for every other model."""
+        if p.c_dim <= 0:
+            return None
+        if y is None:
+            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        return self._prep(y, "y", (b, p.c_dim))
+
+    def _ext_head(self, x, b: int, p, want_grads: bool):
+        """A user-defined encoder in PyTorch on the same stream: its outputs are the step's (z_loc, z_scale).  They enter the
+        library through plan.ext_head, and the gradients come back through plan.ext_dhead.  -> (z_loc, z_scale, head, dhead)"""
+        with torch.set_grad_enabled(want_grads):
+            z_loc, z_scale = self.model.encoder_z(x)
+        head = torch.cat([z_loc, z_scale], -1).detach().to(torch.float32).contiguous()
+        if tuple(head.shape) != (b, 2 * p.z_dim):
+            raise ValueError("encoder_z must return (z_loc, z_scale) of shape (batch, %d) each" % p.z_dim)
+        dhead = torch.empty_like(head)
+        p.ext_head, p.ext_dhead = head.data_ptr(), dhead.data_ptr()
+        return z_loc, z_scale, head, dhead
 
     # ------------------------------------------------------------------ calls
     @_abi.on_device
@@ -899,7 +887,7 @@ class IVAEEngine:
             raise ValueError("weights_out belongs to the importance-weighted bound: model.engine(particles=P, renyi=alpha)")
         if self.conv_enc:
             self._check_conv_weight_range()
-        if step and (self.ext_enc or self.ext_dec or getattr(self, "ext_y", False) or not want_grads):
+        if step and (self._torch_side or not want_grads):
             raise ValueError("step=True needs every parameter in the library (no user-defined modules) and want_grads")
         if comm is not None and (not step or scalars_out is not None):
             raise ValueError("comm= goes with step=True and the engine's own scalars (no scalars_out)")
@@ -910,22 +898,13 @@ class IVAEEngine:
         self._check_x(x, p)
         head = dhead = None
         if self.ext_enc:
-            # the user's encoder in PyTorch on the same stream; its outputs are the step's (z_loc, z_scale)
-            with torch.set_grad_enabled(want_grads):
-                z_loc, z_scale = self.model.encoder_z(x)
-            head = torch.cat([z_loc, z_scale], -1).detach().to(torch.float32).contiguous()
-            if tuple(head.shape) != (b, 2 * p.z_dim):
-                raise ValueError("encoder_z must return (z_loc, z_scale) of shape (batch, %d) each" % p.z_dim)
-            dhead = torch.empty_like(head)
-            p.ext_head, p.ext_dhead = head.data_ptr(), dhead.data_ptr()
+            z_loc, z_scale, head, dhead = self._ext_head(x, b, p, want_grads)
         x = self._prep(x, "x", (b, p.n_pix))
         if P > 1 and eps.numel() != P * b * p.z_dim:
             raise ValueError("particles=%d: eps must be (%d, %d) = (particles * batch, z_dim), rows ordered [p][b] (got %s)"
                              % (P, P * b, p.z_dim, tuple(eps.shape)))
         eps = self._prep(eps, "eps", (P * b, p.z_dim))
-        y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
-        if p.c_dim > 0 and y is None:
-            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        y = self._prep_y(y, b, p)
         if P > 1 and loc_out is not None and loc_out.numel() != P * b * p.n_pix:
             raise ValueError("particles=%d: loc_out must hold (%d, %d) values" % (P, P * b, p.n_pix))
         if weights_out is not None:
@@ -1038,20 +1017,12 @@ class IVAEEngine:
         p = self._plan(b, beta)
         x = self._prep(x, "x", (b, p.n_pix))
         eps = self._prep(eps, "eps", (b, p.z_dim))
-        y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
-        if p.c_dim > 0 and y is None:
-            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        y = self._prep_y(y, b, p)
         z = torch.empty(b, p.z_dim, device=self.device, dtype=torch.float32)
         p.x, p.eps, p.y, p.ext_z = x.data_ptr(), eps.data_ptr(), (y.data_ptr() if y is not None else None), z.data_ptr()
         head = dhead = None
-        if self.ext_enc:                             # a user-defined encoder as well: its outputs enter through ext_head
-            with torch.set_grad_enabled(want_grads):
-                z_loc, z_scale = self.model.encoder_z(x.reshape(b, *self.model.data_dim))
-            head = torch.cat([z_loc, z_scale], -1).detach().to(torch.float32).contiguous()
-            if tuple(head.shape) != (b, 2 * p.z_dim):
-                raise ValueError("encoder_z must return (z_loc, z_scale) of shape (batch, %d) each" % p.z_dim)
-            dhead = torch.empty_like(head)
-            p.ext_head, p.ext_dhead = head.data_ptr(), dhead.data_ptr()
+        if self.ext_enc:                             # a user-defined encoder as well (it sees x in the model's data_dim)
+            z_loc, z_scale, head, dhead = self._ext_head(x.reshape(b, *self.model.data_dim), b, p, want_grads)
         if z_out is not None:
             p.z_loc, p.z_scale = z_out[0].data_ptr(), z_out[1].data_ptr()
         if scalars_out is not None:
@@ -1102,7 +1073,7 @@ class IVAEEngine:
             _abi.ptr(self.flat), _abi.ptr(self.grad), _abi.ptr(self.m), _abi.ptr(self.v), self.n_flat,
             self.lr, self.betas[0], self.betas[1], self.adam_eps, self.adam_t, _abi.current_stream()),
             "pv_adam_step")
-        if (self.ext_enc or self.ext_dec or getattr(self, "ext_y", False)) and any(q.grad is not None for q in self._enc_params):
+        if self._torch_side and any(q.grad is not None for q in self._enc_params):
             for g_ in self._enc_opt.param_groups:
                 g_["lr"], g_["betas"], g_["eps"] = self.lr, self.betas, self.adam_eps
             self._enc_opt.step()
@@ -1114,7 +1085,7 @@ class IVAEEngine:
     def adam_step_hist(self, hist_slot: torch.Tensor):
         """adam_step() plus, in the same launch, the copy of the 4 (all-reduced) loss scalars into `hist_slot` — the
         data-parallel step after its one all-reduce (pv_adam_step_hist)."""
-        if self.ext_enc or self.ext_dec or getattr(self, "ext_y", False):
+        if self._torch_side:
             hist_slot.copy_(self.scalars)
             return self.adam_step()
         self.adam_t += 1
@@ -1126,8 +1097,7 @@ class IVAEEngine:
     def extra_grads(self):
         """Gradient tensors that live outside the flat buffer (a user-defined encoder's): reduced separately in
         data-parallel runs."""
-        ext = self.ext_enc or self.ext_dec or getattr(self, "ext_y", False)
-        return [q.grad for q in self._enc_params if q.grad is not None] if ext else []
+        return [q.grad for q in self._enc_params if q.grad is not None] if self._torch_side else []
 
     @_abi.on_device
     def encode(self, x, y=None):
@@ -1142,9 +1112,7 @@ class IVAEEngine:
         p = self._plan(b, what=2)
         self._check_x(x, p)
         x = self._prep(x, "x", (b, p.n_pix))
-        y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
-        if p.c_dim > 0 and y is None:
-            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        y = self._prep_y(y, b, p)
         p.x = x.data_ptr()
         p.y = y.data_ptr() if y is not None else None
         z_loc = torch.empty(b, p.z_dim, device=self.device, dtype=torch.float32)
@@ -1186,9 +1154,7 @@ class IVAEEngine:
         P = eps.numel() // (b * p.z_dim)
         x = self._prep(x, "x", (b, p.n_pix))
         eps = self._prep(eps, "eps", (P * b, p.z_dim))
-        y = self._prep(y, "y", (b, p.c_dim)) if p.c_dim > 0 else None
-        if p.c_dim > 0 and y is None:
-            raise ValueError("class-conditioned model (c_dim=%d) needs y" % p.c_dim)
+        y = self._prep_y(y, b, p)
         if state is None:
             if not first:
                 raise ValueError("log_evidence_chunk: first=False continues a state, which it needs")

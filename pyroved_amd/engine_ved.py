@@ -28,7 +28,6 @@ class VEDEngine(IVAEEngine):
     def _check_model(self):
         m = self.model
         enc, dec = m.encoder_z, m.decoder
-        self.K, self.ext_enc, self.ext_dec, self.conv_enc = 0, False, False, False
         if not isinstance(enc, convEncoderNet) or not isinstance(dec, convDecoderNet):
             raise UnsupportedModel("the HIP VED path needs convEncoderNet / convDecoderNet (got %s / %s)"
                                    % (type(enc).__name__, type(dec).__name__))
@@ -99,7 +98,7 @@ class VEDEngine(IVAEEngine):
         p.flags = self._plan_flags()
         p.kl_mode = _abi.KL[self.kl]
         p.x = p.y = p.eps = p.z_loc = p.z_scale = p.loc = None
-        ce = getattr(self, "conv_events", None)          # (start, stop, ctypes double for the launch's FLOPs) or None
+        ce = self.conv_events                            # (start, stop, ctypes double for the launch's FLOPs) or None
         p.conv_ev_start, p.conv_ev_stop, p.conv_ev_flops = (ce[0], ce[1], C.addressof(ce[2])) if ce else (None, None, None)
         need = _abi.lib().pv_ved_workspace_bytes(C.byref(p))
         if need < 0:
