@@ -58,6 +58,7 @@ struct Layout {
   int nchunk, rows_per_chunk;
   // fused persistent decoder path
   bool fused; int f_grid, f_kmax;
+  PvDecChoice dec;                                          // the decoder kernel the layout's TRAINING launch runs (layout_choice, below)
   float* f_part; float* f_part_hz; float* f_rowtp; float* f_wimg; float* f_park;
   // multi-particle ELBO (pv_ivae_particles_*): P decoder samples per image ordered [p][b]; z, tp, zy, hz, sw, llkb hold P*B rows.
   // The count travels here, not in the ABI struct; 1 everywhere else
@@ -125,6 +126,13 @@ static inline int64_t plan_lat_in(const pv_ivae_plan* p) {
 // and no fp16 build to avoid, so it keeps the plan's dec_kernel and with it the 8-wave forward-only build at large sizes.
 static inline int plan_sel(const pv_ivae_plan* p) {
   return (p->lik == PV_LIK_POISSON_LOG && p->fused == 2 && p->dec_kernel == 0) ? 1 : p->dec_kernel;
+}
+// ... resolved (pv_sdec_fused.h: PvDecChoice) for the launch of `rows` decoder rows in a layout of the training step: plan_sel, because
+// the fp16 builds must stay away from Poisson plans.  (The other resolution is decode_fused_run's.)
+static inline PvDecChoice layout_choice(const pv_ivae_plan* p, int64_t rows, bool grads) {
+  PvDecChoice c = pv_sdec_fused_choice(p->fused, rows / FD_UNIT, grads, plan_sel(p));
+  if (plan_fused_mc(p)) c.family = PV_DEC_F32_MC;
+  return c;
 }
 
 bool valid_plan(const pv_ivae_plan* p) {
@@ -240,6 +248,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.fused = p->fused && plan_fused_ok(p) && !(K > 0 && !L.enc_compact);   // (jiVAE + generic encoder: layered)
   L.f_grid = L.f_kmax = 0;
   L.f_part = L.f_part_hz = L.f_rowtp = L.f_wimg = L.f_park = nullptr;
+  L.dec = PvDecChoice{};
   for (int i = 0; i < p->n_dec; ++i) {
     L.dact[i] = L.fused ? nullptr : c.take(R * p->dec[i].out_dim);
     L.dpre_[i] = (!L.fused && p->dec[i].act == PV_ACT_GELU) ? c.take(R * p->dec[i].out_dim) : nullptr;
@@ -256,12 +265,13 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
       const int64_t units = R / FD_UNIT;
       L.f_grid = pv_sdec_fused_grid(units);
       L.f_kmax = pv_sdec_fused_kmax((int)N, units, L.f_grid);
-      if (p->fused >= 2) L.f_kmax *= pv_sdec_fused_bf16_waves(p->fused == 2, units, plan_sel(p));   // the bf16 kernels publish dL/d(hz) per wave
+      L.dec = layout_choice(p, R, true);
+      L.f_kmax *= L.dec.waves;                                    // the bf16 kernels publish dL/d(hz) per wave
       L.f_part = c.take((int64_t)L.f_grid * FD_REC);
       L.f_part_hz = c.take(S * L.f_kmax * (H0 + PV_RS_W));        // (+ the row-sum slots behind it: PvFused::part_rs, one zero fill)
       L.f_rowtp = c.take(4 * R);
       L.f_wimg = c.take(FB_WIMG_BYTES / (int64_t)sizeof(float));
-      const int64_t park = (p->fused == 2 && !inference_only) ? pv_sdec_fused_bf16_park_bytes(true, units, L.f_grid, plan_sel(p)) : 0;
+      const int64_t park = inference_only ? 0 : L.dec.park_bytes(L.f_grid);
       L.f_park = park ? c.take(park / (int64_t)sizeof(float)) : nullptr;
       upd(pv_colsum_ws(B, (int)H0));
     }
@@ -807,7 +817,7 @@ static bool particles_supported(const pv_ivae_plan* p) {
 }
 
 // the plan-side conditions of the folded guide (PvEncFold): plain-bf16 fused decoder, the plain two-hidden-layer fc encoder, no
-// conditioning vector / discrete latent / per-sample weights; the launch-side ones are pv_sdec_fused_fold_ok's
+// conditioning vector / discrete latent / per-sample weights; the launch-side ones are PvDecChoice::hosts_guide and pv_sdec_fused_w8_fold_ok's
 // (plan_guide_one_image: the architecture one workgroup can run a whole image's guide for — the fold in the decoder launch and the
 //  per-image guide launch, pv_guide_img.hip)
 static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L);
@@ -835,7 +845,7 @@ static bool plan_guide_one_image(const pv_ivae_plan* p, const Layout& L) {
 struct FusedStep {
   const pv_ivae_plan* p; const Layout& L; const ObjArgs& o; bool grads; hipStream_t s;
   const float* zin; int64_t ldz;                     // the decoder's latent input: z's content columns, or the materialised concatenation
-  int rec_fmt;                                       // the record format the decoder launch writes (pv_sdec_fused.h PV_REC_*)
+  PvDecChoice dec;                                   // the kernel the decoder launch runs: record format, hz scale, weight images, fold
   PvFused f{};                                       // the decoder launch's arguments
   PvEncFold ef{};                                    // one image's guide per workgroup: hosted by the decoder launch (fold), the per-image guide
                                                      // launch, and the latent backward + encoder chain in a decoder launch's epilogue (own chain)
@@ -864,7 +874,7 @@ void fused_decoder_args(FusedStep& st) {
   // over per-slot row sums instead of rows.  NOT the 8-wave throughput kernel: it has no registers for five running sums, and
   // keeping them in LDS cost its in-order waves what the next launch saved (read-modify-write: +-0 on the step; ds_add_f32: +1.4 us
   // on the kernel — profiles/r06h_row_sums_ab.txt)
-  f.part_rs = (st.grads && st.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
+  f.part_rs = (st.grads && st.dec.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
   f.wimg = L.f_wimg; f.park = L.f_park;                // (a weighted launch puts the weights in wimg's slot: fused_decoder_launch)
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
   f.sw = multi ? L.sw : p->row_w; f.x_units = multi ? B * N / FD_UNIT : 0;
@@ -903,7 +913,7 @@ int fused_guide(FusedStep& st) {
     // multi-particle: the guide never rides in the decoder launch; the encoder once, the expansion writes hz for the P*B samples
     if (p->fused < 2) return PV_EINVAL;
     if (L.enc_compact) {
-      const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2);
+      const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, st.dec);
       f.hz_scale = prep.scale;
       fold_args(st.ef, p, L);
       const bool img = plan_guide_one_image(p, L) && pv_guide_img_ok(st.ef, (int)B) &&
@@ -911,7 +921,7 @@ int fused_guide(FusedStep& st) {
       PV_TRY(particle_guide(p, L, s, &prep, f.hz_scale, L.hz, img ? &st.ef : nullptr));
     } else {
       PV_TRY(particle_guide(p, L, s, nullptr, 0.0f, L.hz));
-      PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, p->fused == 2, s));
+      PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, st.dec, s));
     }
     st.kl_n = (int)B;
     st.kl_part = true;
@@ -921,8 +931,8 @@ int fused_guide(FusedStep& st) {
   // whole number of images, the plain fc encoder of two hidden layers — BASELINE's headline config is exactly this.  No encoder
   // launch, no weight-image copy, no hand-off: the step is decoder launch -> latent backward + record sums -> small weight gradients.
   if (plan_guide_may_fold(p, L)) {       // (no cross-workgroup hand-off in it: fine under stream capture too)
-    f.hz_scale = 2.8853900817779268f;
-    st.fold = pv_sdec_fused_fold_ok(f, L.f_grid, p->fused == 2);
+    f.hz_scale = st.dec.img_scale;
+    st.fold = st.dec.hosts_guide && pv_sdec_fused_w8_fold_ok(f, L.f_grid);
     if (!st.fold) f.hz_scale = 0.0f;
   }
   if (st.fold) {
@@ -937,7 +947,7 @@ int fused_guide(FusedStep& st) {
     return 0;
   }
   if (p->fused >= 2 && L.enc_compact) {
-    const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2);
+    const PvFbPrep prep = pv_sdec_fused_bf16_prep_args(f, st.grads, st.dec);
     f.hz_scale = prep.scale;                          // the compact encoder's last launch writes scale * hz directly
     // (round 6) the guide as one workgroup per image (pv_guide_img.hip: no tile hand-offs, 11-13 us where the tiled one-launch
     // encoder takes 18-19) for the minibatch sizes where every image streaming the first-layer matrix from L2 is still cheaper
@@ -953,10 +963,10 @@ int fused_guide(FusedStep& st) {
   // conv encoder: the decoder's weight images ride in its weight-tiling launch; generic encoders: a launch of their own
   PvHzReq hzr{st.zin, st.ldz, (int)lat_in, FD_H, Wz, L.hz, false, false};
   const bool prep_in_enc = p->fused >= 2 && L.enc_conv;
-  const PvFbPrep prep = p->fused >= 2 ? pv_sdec_fused_bf16_prep_args(f, st.grads, p->fused == 2) : PvFbPrep{};
+  const PvFbPrep prep = p->fused >= 2 ? pv_sdec_fused_bf16_prep_args(f, st.grads, st.dec) : PvFbPrep{};
   PV_TRY(guide_fwd(p, L, s, prep_in_enc ? &prep : nullptr, 0.0f, &hzr));
   if (p->fused >= 2 && !prep_in_enc) {
-    PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, p->fused == 2, s));
+    PV_TRY(pv_sdec_fused_bf16_prep(f, st.grads, st.dec, s));
   } else if (p->fused < 2 && st.grads) {
     hipError_t e = hipMemsetAsync(L.f_part_hz, 0, (size_t)(plan_S(p) * L.f_kmax * FD_H) * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
@@ -982,7 +992,7 @@ void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) 
   // (round 6) the 4-wave kernels too hand over dL/d(hz) and dL/dz, wherever every workgroup's units are exactly one sample
   // (batch == grid, e.g. C2's 256 on 256 CUs)
   if (!f.dhz_out && f.part_rs && K == 0 && L.P == 1 && lat_in <= 16 && S == L.f_grid && f.units == S * (N / FD_UNIT) && !p->dy &&
-      st.rec_fmt == PV_REC_LANE_F32) {
+      st.dec.rec_fmt == PV_REC_LANE_F32) {
     f.dhz_out = L.dhz; f.dzc_out = L.dzc; f.Wz = Wz; f.lat_in = (int)lat_in;
   }
   PvLatentBwd& lb = st.lb;
@@ -1054,10 +1064,10 @@ int fused_decoder_launch(FusedStep& st) {
     //  which no 4-wave launch reads; the routed plan's dec_kernel = 1 keeps every launch on the 4-wave kernel)
     PvFused f = st.f;
     if (st.o.pw) f.park = const_cast<float*>(st.o.pw);
-    PV_TRY(pv_sdec_fused_bf16_launch(f, st.L.f_grid, st.grads, p->fused == 2, st.s, st.fold ? &st.ef : nullptr,
+    PV_TRY(pv_sdec_fused_bf16_launch(f, st.L.f_grid, st.grads, st.dec, st.s, st.fold ? &st.ef : nullptr,
                                      (st.own_chain() && !st.fold) ? &st.ef : nullptr, st.o.fdm()));
   }
-  else if (plan_fused_mc(p) || st.o.pw) {
+  else if (st.dec.family == PV_DEC_F32_MC || st.o.pw) {
     // several channels per row: the f32 kernel's sibling, then (training) the sums of channels 1 .. C-1 of d(wo), d(bo) into the
     // flat gradient — in front of every launch that reads it, the one that applies Adam included
     // (weighted steps, st.o.pw: its weighted instances at every channel count — the entry point routed the plan here,
@@ -1109,14 +1119,13 @@ int fused_close_forward(const FusedStep& st) {
 // unscaled one itself).
 int fused_renyi_forward(const FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
-  const bool x3 = p->fused == 2;
   PvFused ff = st.f;
   ff.part_rs = nullptr; ff.dhz_out = ff.dzc_out = nullptr;            // rows of ll, as every forward-only launch writes them
-  const PvFbPrep pf = pv_sdec_fused_bf16_prep_args(ff, false, x3), pg = pv_sdec_fused_bf16_prep_args(st.f, true, x3);
-  const bool same_images = pf.mode == pg.mode && pf.scale == pg.scale && pf.qswap == pg.qswap;
-  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(ff, false, x3, s));
-  PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, x3, s));
-  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, x3, s));
+  const PvDecChoice fwd = layout_choice(p, L.rows, false), &trn = st.dec;
+  const bool same_images = fwd.img_mode == trn.img_mode && fwd.img_scale == trn.img_scale && fwd.img_qswap == trn.img_qswap;
+  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(ff, false, fwd, s));
+  PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, fwd, s));
+  if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, trn, s));
   PV_TRY(pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s));
   return renyi_weights(p, L, st.o, s);
 }
@@ -1133,12 +1142,12 @@ int fused_close(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
   if (head_side) pv_fork_arm();
   PvFinish fin{L.llb, (int)p->batch, p->scalars, st.kl_part ? L.kl_part : nullptr, st.kl_n, 1.0f /* partials come scaled */};
   if (st.own_chain()) {
-    PV_TRY(pv_rec_wgrad(L.f_part, L.f_grid, p->grads, o, p->coord_dim, st.rec_fmt, st.tail, st.tail_np, adam, &fin, s));
+    PV_TRY(pv_rec_wgrad(L.f_part, L.f_grid, p->grads, o, p->coord_dim, st.dec.rec_fmt, st.tail, st.tail_np, adam, &fin, s));
     if (adam) *adam_done = true;
     return extra_outputs(p, L, L.dzc, plan_lat_in(p), s);
   }
-  if (L.P > 1) PV_TRY(pv_particle_bwd_reduce(st.pb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
-  else PV_TRY(pv_latent_bwd_reduce(st.lb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.rec_fmt));
+  if (L.P > 1) PV_TRY(pv_particle_bwd_reduce(st.pb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.dec.rec_fmt));
+  else PV_TRY(pv_latent_bwd_reduce(st.lb, L.f_part, L.f_grid, p->grads, o, p->coord_dim, s, st.dec.rec_fmt));
   // the loss scalars ride in the encoder dgrad launch (compact encoder), in the last weight-gradient launch (conv encoder) or get their own
   const bool fin_rides = L.enc_compact || (ab_fin && L.enc_conv && !L.enc_ext);
   if (!fin_rides) PV_TRY(finish_scalars(fin, s));
@@ -1154,7 +1163,7 @@ int loss_and_grads_fused(const pv_ivae_plan* p, const Layout& L, const ObjArgs& 
   if (K > 0 && !L.enc_compact) return PV_EINVAL;
   const bool cat_in = p->c_dim > 0 || K > 0;         // the decoder's latent input is a materialised concatenation
   FusedStep st{p, L, obj, want_grads != 0, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
-               p->fused >= 2 ? pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, plan_sel(p)) : PV_REC_ROWMAJOR};
+               want_grads ? L.dec : layout_choice(p, L.rows, false)};
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
   if (L.renyi && want_grads) PV_TRY(fused_renyi_forward(st));
@@ -1409,8 +1418,11 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   }
   if (lay->fused == 1) return pv_sdec_fused_launch(f, grid, false, s);
   f.hz_scale = 0.0f;                                   // hz is written unscaled here; the 8-wave kernels scale it themselves
-  PV_TRY(pv_sdec_fused_bf16_prep(f, false, true, s));  // weight images (pre-scaled or not: the launch below makes the same choice)
-  return pv_sdec_fused_bf16_launch(f, grid, false, true, s);
+  // The other resolution: decode promises fp32-class output in every bf16-class mode, so fused == 3 too takes the split-precision
+  // kernels (resolved as fused = 2), and — forward-only, no fp16 build to keep a Poisson plan away from — the plan's own dec_kernel, not plan_sel
+  const PvDecChoice c = pv_sdec_fused_choice(2, f.units, false, lay->dec_kernel);
+  PV_TRY(pv_sdec_fused_bf16_prep(f, false, c, s));     // weight images, pre-scaled or not as the launch below reads them
+  return pv_sdec_fused_bf16_launch(f, grid, false, c, s);
 }
 
 // what: PV_WS_ALL = enough for every entry point at this batch; PV_WS_STEP / _ENCODE / _DECODE = for that call alone
@@ -1463,8 +1475,8 @@ extern "C" int pv_ivae_guide_folds(const pv_ivae_plan* plan) {
   carve(plan, nullptr, L);                             // (offsets only: nothing is dereferenced)
   if (!L.fused || !plan_guide_may_fold(plan, L)) return 0;
   PvFused f{};
-  f.M = L.rows; f.units = L.rows / FD_UNIT; f.N = plan->n_pix; f.B = (int)plan_S(plan); f.sel = plan_sel(plan);
-  return pv_sdec_fused_fold_ok(f, L.f_grid, false) ? 1 : 0;
+  f.M = L.rows; f.units = L.rows / FD_UNIT; f.N = plan->n_pix; f.B = (int)plan_S(plan);
+  return L.dec.hosts_guide && pv_sdec_fused_w8_fold_ok(f, L.f_grid) ? 1 : 0;
 }
 
 // test hook (not in include/; pv_convstack.h: conv_trace): offsets into plan->ws of the conv encoder's stored activations and
@@ -1813,7 +1825,7 @@ static int evidence_ll_fused(const pv_ivae_plan* p, const Layout& L, hipStream_t
   const bool cat_in = p->c_dim > 0;
   const ObjArgs obj{};
   FusedStep st{p, L, obj, false, s, cat_in ? L.zy : L.z + (p->z_dim - p->latent_dim), cat_in ? lat_in : (int64_t)p->z_dim,
-               pv_sdec_fused_bf16_record_fmt(p->fused == 2, L.rows / FD_UNIT, plan_sel(p))};
+               layout_choice(p, L.rows, false)};
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
   PV_TRY(fused_decoder_launch(st));

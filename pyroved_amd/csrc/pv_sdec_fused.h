@@ -130,10 +130,9 @@ struct PvFbPrep;
 bool pv_guide_img_ok(const PvEncFold& e, int B);
 // kl_mode: PV_KL_SAMPLED / PV_KL_ANALYTIC — what kl_part holds (a launch argument: PvEncFold is also the hosting decoder launch's, which runs the sampled form only)
 int pv_guide_img_launch(const PvEncFold& e, const PvFbPrep* prep, float hz_mul, int B, hipStream_t s, int kl_mode = PV_KL_SAMPLED);
-// whether the launch of (f, grads) can host the guide of `p`'s encoder (the caller checks the encoder's architecture)
+// whether the launch of f on `grid` workgroups has the geometry that hosts the guide: one image per workgroup (the caller checks the
+// encoder's architecture, and PvDecChoice::hosts_guide that the launch runs the kernel the guide lives in)
 bool pv_sdec_fused_w8_fold_ok(const PvFused& f, int grid);
-// ... and whether the launcher will pick that kernel for (f, x3) at all
-bool pv_sdec_fused_fold_ok(const PvFused& f, int grid, bool x3);
 
 // true when the plan's architecture is the one the fused kernel is specialised for
 bool pv_sdec_fused_supported(const pv_ivae_plan* p);
@@ -167,38 +166,64 @@ bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p, bool per_image =
 // sums the records' entries of channels 1 .. C-1 — (C - 1) (H + 1) outputs, each over the `grid` records in the shared reduction's
 // fixed order (four slices of ascending workgroups) — into G + wo_off + c H and G + bo_off + c; channel 0 is the shared reduction's
 int pv_sdec_fused_mc_reduce_out(const float* part, int grid, float* G, int64_t wo_off, int64_t bo_off, int C, hipStream_t s);
-// same interface, bf16 split-precision ("bf16x3") matrix math (pv_sdec_fused_bf16.hip); _prep must run first on the
-// same stream, once per parameter state: it writes f.wimg and, with grads, zero-fills f.part_hz
-// x3: split precision (pv_sdec_fused_bf16.hip) or plain bf16 operands (pv_sdec_fused_w8.hip, whose images are
-// pre-scaled by 2 log2(e), once a workgroup has enough units to fill its 8-wave tiles; the 4-wave plain-bf16 kernel
-// for smaller problems; PV_W8=0 / 1 in the environment forces one)
-int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, bool x3, hipStream_t s);
+// ---- which fused decoder kernel a launch runs, and everything that follows from it (pv_sdec_fused_bf16.hip) ----
+// ONE resolved decision per (fused mode, units, launch kind, pv_ivae_plan.dec_kernel): layouts, preparations, launches, reductions and
+// the name hooks read its fields and never its inputs.  pv_sdec_fused_choice is the only reader of the size thresholds, the row cap
+// and the experiments build's environment switches.
+enum PvDecFamily {
+  PV_DEC_F32 = 0,      // pv_sdec_fused.hip: the f32-MFMA kernel (fused == 1) ...
+  PV_DEC_F32_MC,       // ... and its multi-channel sibling, pv_sdec_fused_mc.hip (the plan decides between the two: pv_plan.hip)
+  PV_DEC_W4,           // pv_sdec_fused_bf16.hip: the 4-wave source, in the precision build `prec`
+  PV_DEC_W8,           // pv_sdec_fused_w8.hip: the 8-wave plain-bf16 kernel — the one that can host the guide
+  PV_DEC_W8X3,         // pv_sdec_fused_w8x3.hip: the split-precision source with `x3_waves` waves
+  PV_DEC_W8H           // pv_sdec_fused_w8h.hip: the 8-wave fp16 kernel (experiments build; training launches)
+};
+struct PvDecChoice {
+  // the launch of the (grads) the choice was resolved for
+  int family;          // PvDecFamily
+  int prec;            // PV_DEC_W4: the build (pv_sdec_fused_bf16.hip FB_P_*); -1 otherwise
+  int x3_waves;        // PV_DEC_W8X3: 8 or 4 (0: a selection without an instance — the launcher refuses it); 0 otherwise
+  int ds;              // PV_DEC_W8H: dL/dpre split in both dgrads (H231) or not (H221); 0 otherwise
+  int img_mode;        // its weight images (PvFbPrep::mode) ...
+  float img_scale;     // ... what they are pre-scaled by (0: unscaled) — and what hz must arrive multiplied by ...
+  int img_qswap;       // ... and whether they are in the q-swapped column order (pv_fb_layout.h)
+  // the TRAINING form of the same (fused, units, dec_kernel), whatever the launch kind: a step's layout is sized for it, and a
+  // forward-only launch into a training layout leaves its slots and records alone
+  int waves;           // waves per workgroup that publish a dL/d(hz) slot (sizes part_hz; 1: the f32 kernels, one slot per workgroup)
+  int rec_fmt;         // the record format (PV_REC_*) the training launch writes
+  bool parks;          // the training form needs PvFused::park ...
+  int64_t park_bytes(int grid) const;      // ... that many bytes of it (0: none)
+  // both launch kinds
+  bool weighted;       // a weighted instance exists (PV_DEC_W4 in a bf16 build for training and forward-only launches alike)
+  bool hosts_guide;    // the kernel is the one that can host the guide (pv_sdec_fused_w8_fold_ok: whether this launch's geometry can)
+};
+// fused: pv_ivae_plan.fused (<= 1: PV_DEC_F32); units: rows / FD_UNIT; sel: pv_ivae_plan.dec_kernel (0: by problem size)
+PvDecChoice pv_sdec_fused_choice(int fused, int64_t units, bool grads, int sel);
+// whether `sel` (pv_ivae_plan.dec_kernel) names a decoder-kernel build this library contains for the fused mode (the table the
+// resolver reads)
+bool pv_sdec_fused_sel_valid(int fused, int sel);
+
+// the bf16-class kernels (c.family >= PV_DEC_W4), same interface as pv_sdec_fused_launch; _prep must run first on the same stream,
+// once per parameter state: it writes f.wimg as `c` wants the images and, with grads, zero-fills f.part_hz
+int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, const PvDecChoice& c, hipStream_t s);
 // ... or, as arguments for a kernel that hosts the preparation (pv_fb_layout.h: pv_fb_prep)
 struct PvFbPrep;
-PvFbPrep pv_sdec_fused_bf16_prep_args(const PvFused& f, bool grads, bool x3);
+PvFbPrep pv_sdec_fused_bf16_prep_args(const PvFused& f, bool grads, const PvDecChoice& c);
 bool pv_sdec_fused_w8_qswap();          // the 8-wave plain-bf16 kernel's images are in the q-swapped column order (pv_fb_layout.h)
-// weighted (PV_FDM_W_SHARED / PV_FDM_W_IMAGES; pv_ivae_weighted_* with PV_PLAN_FAST_WEIGHTS): the weighted instances of the 4-wave
-// kernel's bf16 builds; the weights — (N), or (M) in the layout of x — travel in f.park.  PV_EINVAL where
-// pv_sdec_fused_bf16_weighted_ok(x3, f.units, f.sel) is false, or with fold, f.sw or f.x_units set
-int pv_sdec_fused_bf16_launch(const PvFused& f, int grid, bool grads, bool x3, hipStream_t s, const PvEncFold* fold = nullptr,
+// c: the choice resolved for (grads).  weighted (PV_FDM_W_SHARED / PV_FDM_W_IMAGES; pv_ivae_weighted_* with PV_PLAN_FAST_WEIGHTS):
+// the weighted instances of the 4-wave kernel's bf16 builds; the weights — (N), or (M) in the layout of x — travel in f.park.
+// PV_EINVAL where c.weighted is false, or with fold, f.sw or f.x_units set
+int pv_sdec_fused_bf16_launch(const PvFused& f, int grid, bool grads, const PvDecChoice& c, hipStream_t s,
+                              const PvEncFold* fold = nullptr,
                               const PvEncFold* chain = nullptr,      // chain: the 4-wave kernels' own-sample epilogue (PvEncFold::chain)
                               int weighted = 0);
-bool pv_sdec_fused_bf16_weighted_ok(bool x3, int64_t units, int sel);
 const char* pv_sdec_fused_bf16_wt_kernel_name(bool x3, int grads, int lik);      // (as rocprofv3 prints it)
 int pv_sdec_fused_w8_launch(const PvFused& f, int grid, bool grads, hipStream_t s, const PvEncFold* fold = nullptr);
 // the 8-wave split-precision kernel (pv_sdec_fused_w8x3.hip; images pre-scaled by 2 log2(e) like the plain 8-wave kernel's)
-int pv_sdec_fused_w8x3_launch(const PvFused& f, int grid, bool grads, hipStream_t s, int waves);   // waves: 8 or 4
+int pv_sdec_fused_w8x3_launch(const PvFused& f, int grid, bool grads, hipStream_t s, const PvDecChoice& c);   // c.x3_waves: 8 or 4
 int64_t pv_sdec_fused_w8x3_park_bytes(int grid);
-// the 8-wave fp16 kernel of the fp32-class path (pv_sdec_fused_w8h.hip; training launches; prep mode 2); ds: dL/dpre split
-int pv_sdec_fused_w8h_launch(const PvFused& f, int grid, bool ds, hipStream_t s);
-// bytes of PvFused::park the launch of (x3, units) needs (0: the kernel that will run has no parking slots)
-int64_t pv_sdec_fused_bf16_park_bytes(bool x3, int64_t units, int grid, int sel);
-// waves per workgroup that publish a dL/d(hz) slot (sizes part_hz)
-int pv_sdec_fused_bf16_waves(bool x3, int64_t units, int sel);
-// the record format (PV_REC_*) the training launch of (x3, units, sel) writes
-int pv_sdec_fused_bf16_record_fmt(bool x3, int64_t units, int sel);
-// whether `sel` (pv_ivae_plan.dec_kernel) names a decoder-kernel build this library contains for the fused mode
-bool pv_sdec_fused_sel_valid(int fused, int sel);
+// the 8-wave fp16 kernel of the fp32-class path (pv_sdec_fused_w8h.hip; training launches; prep mode 2); c.ds: dL/dpre split
+int pv_sdec_fused_w8h_launch(const PvFused& f, int grid, hipStream_t s, const PvDecChoice& c);
 // sums the per-workgroup records (ascending workgroup order) into the flat gradient buffer
 struct PvFusedOffsets { int64_t W1, b1, W2, b2, Wc, wo, bo; };
 int pv_sdec_fused_reduce(const float* part, int grid, float* G, const PvFusedOffsets& o, int cd, int dwo_slots,

@@ -39,6 +39,7 @@
 #include "pv_kernels.h"        // PvHeadBwd, pv_head_dz / pv_head_bwd_math: the own-sample epilogue's latent backward
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 
 typedef int int4_ __attribute__((ext_vector_type(4)));
 
@@ -830,26 +831,54 @@ static int fb_env_x3() {
 static constexpr int fb_env_plain() { return 2; }
 static constexpr int fb_env_x3() { return 2; }
 #endif
+// The builds `sel` can name, per fused mode; 0 names none (by problem size).  One table for pv_sdec_fused_sel_valid and for the
+// resolver: a selection is valid exactly when it has a row that this build of the library contains.
+// kind: the split-precision selection as fb_x3_kind returns it — sel itself, but sel 1 is kind 0; kind 8 is also what the size rule
+// gives forward-only launches in both builds (exp_only is about naming it for training launches)
+struct FbBuild { int fused, sel, kind, family, prec, x3_waves, ds; bool exp_only; };
+static const FbBuild fb_builds[] = {
+  {3, 1, 0, PV_DEC_W4, FB_P_BF16, 0, 0, false},
+  {3, 2, 0, PV_DEC_W8, -1, 0, 0, false},
+  {2, 1, 0, PV_DEC_W4, FB_P_X3, 0, 0, false},
+  {2, 21, 21, PV_DEC_W4, FB_P_H221, 0, 0, false},
+  {2, 28, 28, PV_DEC_W4, FB_P_H231, 0, 0, false},
+  {2, 4, 4, PV_DEC_W8X3, -1, 4, 0, true},
+  {2, 8, 8, PV_DEC_W8X3, -1, 8, 0, true},
+  {2, 23, 23, PV_DEC_W4, FB_P_H223, 0, 0, true},
+  {2, 31, 31, PV_DEC_W4, FB_P_H321, 0, 0, true},
+  {2, 33, 33, PV_DEC_W4, FB_P_H333, 0, 0, true},
+  {2, 26, 26, PV_DEC_W4, FB_P_H2A1, 0, 0, true},
+  {2, 27, 27, PV_DEC_W4, FB_P_H2B1, 0, 0, true},
+  {2, 29, 29, PV_DEC_W4, FB_P_H131, 0, 0, true},
+  {2, 41, 41, PV_DEC_W8H, -1, 0, 0, true},
+  {2, 48, 48, PV_DEC_W8H, -1, 0, 1, true},
+};
+// the row `sel` names for the fused mode; null: 0 (by size) or a selection without a row
+static const FbBuild* fb_named(int fused, int sel) {
+  for (const FbBuild& b : fb_builds)
+    if (b.fused == fused && b.sel == sel) return &b;
+  return nullptr;
+}
 bool pv_sdec_fused_sel_valid(int fused, int sel) {
   if (sel == 0) return true;
-  if (fused == 3) return sel == 1 || sel == 2;
-  if (fused != 2) return false;
-  if (sel == 1 || sel == 21 || sel == 28) return true;
+  const FbBuild* b = fb_named(fused, sel);
 #ifdef PV_EXPERIMENTS
-  return sel == 4 || sel == 8 || sel == 23 || sel == 31 || sel == 33 || sel == 26 || sel == 27 || sel == 29 || sel == 41 || sel == 48;
+  return b != nullptr;
 #else
-  return false;
+  return b && !b->exp_only;
 #endif
 }
 static bool fb_use_w8(int64_t units, int sel) {
-  const int v = sel == 1 ? 0 : (sel == 2 ? 1 : fb_env_plain());          // 0 / 1 forced, 2 by problem size
+  const FbBuild* b = fb_named(3, sel);
+  const int v = b ? (b->family == PV_DEC_W8 ? 1 : 0) : fb_env_plain();   // 0 / 1 forced by a named row, 2 by problem size
   if (v != 2) return v != 0 && units * FD_UNIT < fb_row_cap;
   return units >= 6 * (int64_t)pv_sdec_fused_grid(units) && units * FD_UNIT < fb_row_cap;
 }
 // split precision: 0 = this file's 4-wave bf16 kernel, 21 (23 / 31 / 33) = its fp16 builds, 4 / 8 = pv_sdec_fused_w8x3.hip with
 // that many waves
 static int fb_x3_kind(int64_t units, bool grads, int sel) {
-  const int v = sel == 0 ? fb_env_x3() : (sel == 1 ? 0 : sel);
+  const FbBuild* named = fb_named(2, sel);
+  const int v = sel == 0 ? fb_env_x3() : (named ? named->kind : sel);     // (a selection without a row: fb_x3_build)
   if (v > 8) return grads ? v : (units * FD_UNIT < fb_row_cap && units >= 6 * (int64_t)pv_sdec_fused_grid(units) ? 8 : 0);
   if (units * FD_UNIT >= fb_row_cap) return 0;
   if (v != 2) return v;
@@ -861,29 +890,68 @@ static int fb_x3_kind(int64_t units, bool grads, int sel) {
   if (grads) return 0;
   return units >= 6 * (int64_t)pv_sdec_fused_grid(units) ? 8 : 0;
 }
-static bool fb_kind_here(int kind) { return kind == 0 || (kind > 8 && kind < 40); }   // kinds this file's 4-wave kernel serves
-static bool fb_kind_w8h(int kind) { return kind == 41 || kind == 48; }   // pv_sdec_fused_w8h.hip: H221 / H231 arithmetic, 8 waves
-static int fb_kind_prec(int kind) {
-  return kind == 21 ? FB_P_H221 : kind == 23 ? FB_P_H223 : kind == 31 ? FB_P_H321 : kind == 33 ? FB_P_H333
-       : kind == 26 ? FB_P_H2A1 : kind == 27 ? FB_P_H2B1 : kind == 28 ? FB_P_H231 : kind == 29 ? FB_P_H131 : FB_P_X3;
+// the table's row of a split-precision kind.  A kind without a row — a dec_kernel that pv_sdec_fused_sel_valid refuses, handed
+// straight to the resolver — resolves to the split-precision source with a wave count that has no instance: its images (pre-scaled;
+// fp16 pieces from kind 9 up), row-major records, four slot waves, and a launch that the launcher refuses.  (Before the table, a
+// kind in 9 .. 39 without a build got the 4-wave three-product kernel on unscaled fp16 images instead: DESIGN 4.22.)
+static FbBuild fb_x3_build(int kind) {
+  for (const FbBuild& b : fb_builds)
+    if (b.fused == 2 && b.kind == kind) return b;
+  return FbBuild{2, kind, kind, PV_DEC_W8X3, -1, 0, 0, true};
 }
-int pv_sdec_fused_bf16_waves(bool x3, int64_t units, int sel) {
-  const int kind = x3 ? fb_x3_kind(units, true, sel) : 0;
-  return (x3 ? (kind == 8 || fb_kind_w8h(kind)) : fb_use_w8(units, sel)) ? 8 : FB_WAVES;
-}
-int pv_sdec_fused_bf16_record_fmt(bool x3, int64_t units, int sel) {
+static int fb_qswap_on();
+
+// The resolver: the kernel the launch of (fused, units, grads, sel) runs — fb_use_w8 / fb_x3_kind, whose only caller this is — and
+// what every consumer reads of it (pv_sdec_fused.h: PvDecChoice)
+PvDecChoice pv_sdec_fused_choice(int fused, int64_t units, bool grads, int sel) {
+  PvDecChoice c{};
+  c.prec = -1; c.waves = 1; c.rec_fmt = PV_REC_ROWMAJOR;
+  if (fused < 2) return c;                                             // PV_DEC_F32: no weight images, one slot per workgroup
+  const bool x3 = fused == 2;
+  int train_kind = 0;                                                  // (split precision: the training launch's kind)
+  if (x3) {
+    train_kind = fb_x3_kind(units, true, sel);
+    const int fwd_kind = fb_x3_kind(units, false, sel);
+    const int kind = grads ? train_kind : fwd_kind;
+    const FbBuild b = fb_x3_build(kind), t = fb_x3_build(train_kind);
+    c.family = b.family; c.prec = b.prec; c.x3_waves = b.x3_waves; c.ds = b.ds;
+    c.img_mode = b.family == PV_DEC_W8H ? 2 : (kind > 8 ? 1 : 0);      // (fp16 pieces: every kind above the split-precision source's two)
+    c.img_scale = b.family == PV_DEC_W4 ? 0.0f : 2.8853900817779268f;  // (the 8-wave sources want 2 log2(e) W and 2 log2(e) hz)
+    c.waves = (train_kind == 8 || t.family == PV_DEC_W8H) ? 8 : FB_WAVES;
+    c.rec_fmt = t.family == PV_DEC_W4 ? PV_REC_LANE_F32 : PV_REC_ROWMAJOR;   // (pv_sdec_fused_w8x3 / w8h.hip: row-major)
+    c.weighted = train_kind == 0 && fwd_kind == 0;                     // (the bf16 three-product build for both launch kinds)
+  } else {
+    const bool w8 = fb_use_w8(units, sel);
+    c.family = w8 ? PV_DEC_W8 : PV_DEC_W4;
+    if (!w8) c.prec = FB_P_BF16;
+    c.img_scale = w8 ? 2.8853900817779268f : 0.0f;
+    c.waves = w8 ? 8 : FB_WAVES;
+    c.rec_fmt = w8 ? PV_REC_LANE_BF16 : PV_REC_LANE_F32;
+    c.weighted = !w8;
+    c.hosts_guide = w8;
+  }
+  c.img_qswap = c.img_scale == 0.0f ? fb_qswap_on() : (!x3 && pv_sdec_fused_w8_qswap());
   static const int ablate = pv_exp_int("PV_FD_ABLATE", 0);          // (experiments build, bit 1024: the row-major fp32 form from both kernels)
-  if (ablate & 1024) return PV_REC_ROWMAJOR;
-  if (!x3) return fb_use_w8(units, sel) ? PV_REC_LANE_BF16 : PV_REC_LANE_F32;
-  return fb_kind_here(fb_x3_kind(units, true, sel)) ? PV_REC_LANE_F32 : PV_REC_ROWMAJOR;   // (pv_sdec_fused_w8x3 / w8h.hip: row-major)
-}
-int64_t pv_sdec_fused_bf16_park_bytes(bool x3, int64_t units, int grid, int sel) {
+  if (ablate & 1024) c.rec_fmt = PV_REC_ROWMAJOR;
 #ifdef PV_EXPERIMENTS
-  return (x3 && fb_x3_kind(units, true, sel) == 8) ? pv_sdec_fused_w8x3_park_bytes(grid) : 0;
-#else
-  (void)x3; (void)units; (void)grid; (void)sel;
-  return 0;                                             // (parking slots: the 8-wave split-precision TRAINING form only)
+  c.parks = x3 && train_kind == 8;                    // (parking slots: the 8-wave split-precision TRAINING form only)
 #endif
+  return c;
+}
+int64_t PvDecChoice::park_bytes(int grid) const { return parks ? pv_sdec_fused_w8x3_park_bytes(grid) : 0; }
+
+// test hook (not in include/): the resolved choice of (fused, units, grads, sel) as integers — out[0] pv_sdec_fused_sel_valid, then
+// family, prec, x3_waves, ds, waves, rec_fmt, parks, park_bytes at pv_sdec_fused_grid(units), img_mode, the bits of img_scale,
+// img_qswap, weighted, hosts_guide (14 values).  tests/test_decoder_choice_cpu.py replays a recorded table through it
+extern "C" int pv_debug_decoder_choice(int fused, int64_t units, int grads, int sel, int64_t* out) {
+  if (!out) return PV_EINVAL;
+  const PvDecChoice c = pv_sdec_fused_choice(fused, units, grads != 0, sel);
+  unsigned scale_bits;
+  memcpy(&scale_bits, &c.img_scale, sizeof scale_bits);
+  const int64_t v[14] = {pv_sdec_fused_sel_valid(fused, sel), c.family, c.prec, c.x3_waves, c.ds, c.waves, c.rec_fmt, c.parks,
+                         c.park_bytes(pv_sdec_fused_grid(units)), c.img_mode, scale_bits, c.img_qswap, c.weighted, c.hosts_guide};
+  for (int i = 0; i < 14; ++i) out[i] = v[i];
+  return 0;
 }
 
 // measurement hook (not in include/): the kernel a decoder launch of (fused mode, units, grads, likelihood) dispatches, spelled
@@ -898,20 +966,23 @@ extern "C" const char* pv_debug_decoder_kernel_name_fold(int grads, int lik) {  
 extern "C" const char* pv_debug_decoder_kernel_name(int fused, int64_t units, int grads, int lik) {
   static thread_local char buf[128];
   const char* g = grads ? "true" : "false";
+  const PvDecChoice c = pv_sdec_fused_choice(fused, units, grads != 0, 0);
   if (fused == 1) snprintf(buf, sizeof buf, "void pv_sdec_fused_kernel<%s>(PvFused)", g);
-  else if (fused == 2 && fb_kind_w8h(fb_x3_kind(units, grads != 0, 0))) snprintf(buf, sizeof buf, "void pv_sdec_w8h_kernel<%d, %s>(PvFused)", lik, fb_x3_kind(units, grads != 0, 0) == 48 ? "true" : "false");
-  else if (fused == 2 && !fb_kind_here(fb_x3_kind(units, grads != 0, 0))) snprintf(buf, sizeof buf, "void pv_sdec_w8x3_kernel<%s, %d, %d>(PvFused)", g, lik, fb_x3_kind(units, grads != 0, 0));
-  else if (fused == 3 && fb_use_w8(units, 0)) snprintf(buf, sizeof buf, "void pv_sdec_w8_kernel<%s, %d, 0>(PvFused, PvEncFold)", g, lik);
-  else if (fused >= 2) snprintf(buf, sizeof buf, "void pv_sdec_fused_bf16_kernel<%s, %d, %d>(PvFused, PvEncFold)", g, lik, fused == 2 ? fb_kind_prec(fb_x3_kind(units, grads != 0, 0)) : FB_P_BF16);
-  else snprintf(buf, sizeof buf, "pv_gemm_kernel (layer-by-layer path)");
+  else if (fused < 2) snprintf(buf, sizeof buf, "pv_gemm_kernel (layer-by-layer path)");
+  else if (c.family == PV_DEC_W8H) snprintf(buf, sizeof buf, "void pv_sdec_w8h_kernel<%d, %s>(PvFused)", lik, c.ds ? "true" : "false");
+  else if (c.family == PV_DEC_W8X3) snprintf(buf, sizeof buf, "void pv_sdec_w8x3_kernel<%s, %d, %d>(PvFused)", g, lik, c.x3_waves);
+  else if (c.family == PV_DEC_W8) snprintf(buf, sizeof buf, "void pv_sdec_w8_kernel<%s, %d, 0>(PvFused, PvEncFold)", g, lik);
+  else snprintf(buf, sizeof buf, "void pv_sdec_fused_bf16_kernel<%s, %d, %d>(PvFused, PvEncFold)", g, lik, c.prec);
   return buf;
 }
 
-// ... and the kernel a WEIGHTED decoder launch of the plan's route dispatches (pv_plan.hip: pv_debug_weighted_decoder_kernel_name)
+// ... and the kernel a WEIGHTED decoder launch of the plan's route dispatches (pv_plan.hip: pv_debug_weighted_decoder_kernel_name):
+// the 4-wave source in the bf16 build of the mode, which the routed plan's dec_kernel = 1 selects at every size
 const char* pv_sdec_fused_bf16_wt_kernel_name(bool x3, int grads, int lik) {
   static thread_local char buf[128];
+  const PvDecChoice c = pv_sdec_fused_choice(x3 ? 2 : 3, 0, grads != 0, 1);
   snprintf(buf, sizeof buf, "void pv_sdec_fused_bf16_wt_kernel<%s, %d, %d>(PvFused, PvEncFold, int)", grads ? "true" : "false", lik,
-           x3 ? FB_P_X3 : FB_P_BF16);
+           c.prec);
   return buf;
 }
 
@@ -923,21 +994,18 @@ static int fb_qswap_on() {
   static const int v = pv_exp_int("PV_QSWAP", 0);
   return v != 0;
 }
-PvFbPrep pv_sdec_fused_bf16_prep_args(const PvFused& f, bool grads, bool x3) {
+PvFbPrep pv_sdec_fused_bf16_prep_args(const PvFused& f, bool grads, const PvDecChoice& c) {
   static_assert(FB_WIMG_BYTES >= FB_SCALE_OFF + 16, "pv_sdec_fused.h and the LDS image layout disagree");
   PvFbPrep p{};
   p.W1 = f.W1; p.W2 = f.W2; p.img = f.wimg; p.zero = f.part_hz; p.wo = f.wo;
   p.nzero4 = grads ? (int64_t)f.B * f.kmax * (FD_H + (f.part_rs ? PV_RS_W : 0)) / 4 : 0;      // (dL/d(hz) slots + the row-sum slots behind them)
-  const int kind = x3 ? fb_x3_kind(f.units, grads, f.sel) : -1;
-  p.mode = fb_kind_w8h(kind) ? 2 : (kind > 8 ? 1 : 0);
-  p.scale = (x3 ? !fb_kind_here(kind) : fb_use_w8(f.units, f.sel)) ? 2.8853900817779268f : 0.0f;     // (also what hz arrives multiplied by)
-  p.qswap = p.scale == 0.0f ? fb_qswap_on() : (!x3 && pv_sdec_fused_w8_qswap());
+  p.mode = c.img_mode; p.scale = c.img_scale; p.qswap = c.img_qswap;
   return p;
 }
 
-int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, bool x3, hipStream_t s) {
+int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, const PvDecChoice& c, hipStream_t s) {
   if (!f.wimg) return PV_EINVAL;
-  const PvFbPrep p = pv_sdec_fused_bf16_prep_args(f, grads, x3);
+  const PvFbPrep p = pv_sdec_fused_bf16_prep_args(f, grads, c);
   const int64_t work = p.nzero4 > FD_H * (FD_H / 4) ? p.nzero4 : FD_H * (FD_H / 4);
   int blocks = (int)((work + 255) / 256);
   if (blocks > 256) blocks = 256;
@@ -946,35 +1014,20 @@ int pv_sdec_fused_bf16_prep(const PvFused& f, bool grads, bool x3, hipStream_t s
   return 0;
 }
 
-bool pv_sdec_fused_fold_ok(const PvFused& f, int grid, bool x3) {
-  return !x3 && fb_use_w8(f.units, f.sel) && pv_sdec_fused_w8_fold_ok(f, grid);
-}
-
-// the weighted instances exist for the builds this file's 4-wave kernel runs with bf16 pieces: kind 0 of the split precision and the
-// 4-wave plain-bf16 build (f.sel = 1 selects both at every size, for training and forward-only launches)
-bool pv_sdec_fused_bf16_weighted_ok(bool x3, int64_t units, int sel) {
-  return x3 ? (fb_x3_kind(units, true, sel) == 0 && fb_x3_kind(units, false, sel) == 0) : !fb_use_w8(units, sel);
-}
-
-int pv_sdec_fused_bf16_launch(const PvFused& f_in, int grid, bool grads, bool x3, hipStream_t s, const PvEncFold* fold,
+int pv_sdec_fused_bf16_launch(const PvFused& f_in, int grid, bool grads, const PvDecChoice& c, hipStream_t s, const PvEncFold* fold,
                               const PvEncFold* chain, int weighted) {
-  if (fold && (x3 || !fb_use_w8(f_in.units, f_in.sel))) return PV_EINVAL;      // (the folded guide lives in the 8-wave plain-bf16 kernel)
+  if (fold && !c.hosts_guide) return PV_EINVAL;       // (the folded guide lives in the 8-wave plain-bf16 kernel)
   // (weighted launches: the weights sit in f.park; no sample weights or repeated observations — pv_ivae_weighted_*'s scope)
-  if (weighted && (fold || !f_in.park || f_in.sw || f_in.x_units != 0 || !pv_sdec_fused_bf16_weighted_ok(x3, f_in.units, f_in.sel)))
-    return PV_EINVAL;
-  int prec = FB_P_BF16;
-  if (x3) {
-    const int kind = fb_x3_kind(f_in.units, grads, f_in.sel);
+  if (weighted && (fold || !f_in.park || f_in.sw || f_in.x_units != 0 || !c.weighted)) return PV_EINVAL;
+  if (c.family == PV_DEC_W8) return pv_sdec_fused_w8_launch(f_in, grid, grads, s, fold);
 #ifdef PV_EXPERIMENTS
-    if (fb_kind_w8h(kind)) return grads ? pv_sdec_fused_w8h_launch(f_in, grid, kind == 48, s) : PV_EINVAL;
+  if (c.family == PV_DEC_W8H) return grads ? pv_sdec_fused_w8h_launch(f_in, grid, s, c) : PV_EINVAL;
 #else
-    if (fb_kind_w8h(kind) || (grads && !fb_kind_here(kind))) return PV_EINVAL;   // (dropped variants: the experiments build)
+  if (c.family == PV_DEC_W8H || (grads && c.family == PV_DEC_W8X3)) return PV_EINVAL;   // (dropped variants: the experiments build)
 #endif
-    if (!fb_kind_here(kind)) return pv_sdec_fused_w8x3_launch(f_in, grid, grads, s, kind);
-    prec = fb_kind_prec(kind);
-  } else if (fb_use_w8(f_in.units, f_in.sel)) {
-    return pv_sdec_fused_w8_launch(f_in, grid, grads, s, fold);
-  }
+  if (c.family == PV_DEC_W8X3) return pv_sdec_fused_w8x3_launch(f_in, grid, grads, s, c);
+  if (c.family != PV_DEC_W4) return PV_EINVAL;
+  const int prec = c.prec;
   PvFused f = f_in;
   static const int ablate = pv_exp_int("PV_FD_ABLATE", 0);
   f.ablate = ablate;

@@ -693,8 +693,9 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
   }
 }
 
-// ds: dL/dpre split in both dgrads (H231) or not (H221); training launches only
-int pv_sdec_fused_w8h_launch(const PvFused& f_in, int grid, bool ds, hipStream_t s) {
+// c.ds: dL/dpre split in both dgrads (H231) or not (H221); training launches only
+int pv_sdec_fused_w8h_launch(const PvFused& f_in, int grid, hipStream_t s, const PvDecChoice& c) {
+  const bool ds = c.ds != 0;
   PvFused f = f_in;
   f.ablate = 0;
   const size_t lds = H8_LDS_BYTES;

@@ -951,8 +951,9 @@ __global__ __launch_bounds__(64 * NW) void pv_sdec_w8x3_kernel(PvFused f) {
 
 int64_t pv_sdec_fused_w8x3_park_bytes(int grid) { return (int64_t)grid * 8 * X3_PARK_BYTES_PER_WAVE; }
 
-// waves: 8 or 4 (the template's NW)
-int pv_sdec_fused_w8x3_launch(const PvFused& f_in, int grid, bool grads, hipStream_t s, int waves) {
+// c.x3_waves: 8 or 4 (the template's NW)
+int pv_sdec_fused_w8x3_launch(const PvFused& f_in, int grid, bool grads, hipStream_t s, const PvDecChoice& c) {
+  const int waves = c.x3_waves;
   PvFused f = f_in;
   f.ablate = 0;
   if (waves != 4 && waves != 8) return PV_EINVAL;

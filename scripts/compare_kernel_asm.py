@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Symbol-by-symbol comparison of a HIP source's gfx950 device assembly at two commits.
 
-    python scripts/compare_kernel_asm.py [--source pv_sdec_fused_bf16.hip] [--base HEAD~1] [--keep DIR]
+    python scripts/compare_kernel_asm.py [--source pv_sdec_fused_bf16.hip] [--base HEAD~1] [--keep DIR] [--define PV_EXPERIMENTS]
     python scripts/compare_kernel_asm.py --asm OLD.s NEW.s
 
 Compiles pyroved_amd/csrc/<source> with `-S --cuda-device-only` under the Makefile's flags for that file — once from a
@@ -35,10 +35,10 @@ def makefile_flags(csrc_dir, stem):
     return flags.split()
 
 
-def compile_asm(csrc_dir, source, out):
+def compile_asm(csrc_dir, source, out, defines=()):
     stem = os.path.splitext(source)[0]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc] + makefile_flags(csrc_dir, stem) + ["-S", "--cuda-device-only", source, "-o", out]
+    cmd = [hipcc] + makefile_flags(csrc_dir, stem) + ["-D" + d for d in defines] + ["-S", "--cuda-device-only", source, "-o", out]
     subprocess.check_call(cmd, cwd=csrc_dir, stderr=subprocess.DEVNULL)
 
 
@@ -91,6 +91,7 @@ def main():
     ap.add_argument("--source", default="pv_sdec_fused_bf16.hip")
     ap.add_argument("--base", default="HEAD~1", help="commit to compare the working tree with")
     ap.add_argument("--keep", default=None, help="directory to leave the two .s files in")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME", help="compile both sides with -DNAME (the experiments build: PV_EXPERIMENTS)")
     ap.add_argument("--asm", nargs=2, metavar=("OLD.s", "NEW.s"), help="compare two assembly files already made")
     a = ap.parse_args()
     if a.asm:
@@ -103,8 +104,8 @@ def main():
                               stderr=subprocess.DEVNULL)
         try:
             old_s, new_s = os.path.join(keep, "base.s"), os.path.join(keep, "new.s")
-            compile_asm(os.path.join(tree, CSRC), a.source, old_s)
-            compile_asm(os.path.join(ROOT, CSRC), a.source, new_s)
+            compile_asm(os.path.join(tree, CSRC), a.source, old_s, a.define)
+            compile_asm(os.path.join(ROOT, CSRC), a.source, new_s, a.define)
             ok = compare(old_s, new_s)
         finally:
             subprocess.call(["git", "-C", ROOT, "worktree", "remove", "--force", tree], stdout=subprocess.DEVNULL,
