@@ -366,6 +366,20 @@ int pv_experiments_build(void);
  *   is PV_EINVAL (the fp16 builds and the 8-wave kernel have no weighted form).  The unweighted entry points ignore the bit: with
  *   it pv_ivae_loss_and_grads / pv_ivae_step run exactly what they run without it.  No reference counterpart. */
 #define PV_PLAN_FAST_WEIGHTS 512
+/* PV_PLAN_FUSED_TAIL (pv_ivae_plan; a new bit of `flags`, no layout change, no version bump): a spatial decoder whose position
+ *   count (n_pix / out.out_dim) is NOT a multiple of 16 runs on the fused f32 decoder kernel's tail form instead of the
+ *   layer-by-layer kernels.  Takes effect only for a plan with ALL of: fused == 1, the architecture the fused kernel is specialised
+ *   for (PV_PLAN_FUSED_CHANNELS, above), positions % 16 != 0, a per-value likelihood (not PV_LIK_CATEGORICAL), discrete_dim == 0,
+ *   the plan's own fully connected encoder and decoder, no row_w / row_elbo / dy, and one channel — or 2 .. 6 or 8 channels
+ *   with PV_PLAN_FUSED_CHANNELS as well (seven channels have no tail instance: they stay on the layer-by-layer kernels).
+ *   pv_ivae_uses_fused and pv_ivae_weighted_uses_fused are then 1, the workspace queries return the fused layout with every
+ *   sample's decoder rows rounded up to a multiple of 16, and pv_ivae_loss_and_grads / pv_ivae_step / pv_ivae_decode /
+ *   pv_ivae_weighted_* / pv_ivae_weighted_images_* run that kernel.  x, loc, grid and the weights
+ *   keep their shapes ((batch, n_pix), (positions, coord_dim), (n_pix)): the padding rows exist in the workspace alone, observe
+ *   nothing and contribute exact zeros to every sum.  fp32 matrix instructions throughout: results of fp32 class.
+ *   Everywhere else — fused 0, 2 or 3, positions a multiple of 16, the categorical likelihood, a discrete latent, other networks —
+ *   the bit does nothing: the plan answers and runs exactly as without it.  No reference counterpart. */
+#define PV_PLAN_FUSED_TAIL 1024
 
 /* Bytes of workspace pv_ivae_* calls need for this plan (depends on batch, n_pix,
  * layer widths).  Returns < 0 on an unsupported plan. */

@@ -21,6 +21,7 @@ PV_PLAN_ENC_TILED = 32
 PV_PLAN_GENERIC_TILE_LOOP = 128
 PV_PLAN_FUSED_CHANNELS = 256         # several channels per position on the fused f32 decoder kernel (with fused == 1)
 PV_PLAN_FAST_WEIGHTS = 512           # weighted steps on the 4-wave bf16-class fused decoder kernel's weighted instances (fused 2 / 3)
+PV_PLAN_FUSED_TAIL = 1024            # positions that are no multiple of 16 on the fused f32 decoder kernel's tail form (with fused == 1)
 PV_MAX_LAYERS = 8
 PV_MAX_CHANNELS = 8         # channels per grid position of a spatial decoder (pv_ivae_plan.out.out_dim)
 

@@ -99,6 +99,11 @@ static inline int plan_conv_mode(const pv_ivae_plan* p) {
 // the grid, the row chunks and the per-sample segment sums run over the positions.  Vanilla decoders: C = 1, positions = n_pix
 static inline int64_t plan_C(const pv_ivae_plan* p) { return p->coord_dim > 0 ? p->out.out_dim : 1; }
 static inline int64_t plan_pos(const pv_ivae_plan* p) { return p->n_pix / plan_C(p); }
+// Rows per sample of the plan's DECODER layout: the positions — rounded up to a multiple of 16 where PV_PLAN_FUSED_TAIL takes effect
+// (pv_sdec_fused.h: pv_sdec_fused_tail; the padding rows observe nothing and contribute exact zeros).  The layout's rows, the fused
+// launch's partition, the latent backward and the per-sample segment sums run over plan_rows; the grid, x / loc, the encoder, the
+// Poisson normaliser and the weights keep plan_pos / n_pix.  Everywhere the flag does not take effect the two are the same number
+static inline int64_t plan_rows(const pv_ivae_plan* p) { return pv_sdec_fused_rows_per_sample(p); }
 // PV_LIK_CATEGORICAL: the classes per position — the spatial decoder's channels, or the group width a vanilla plan names in out._pad
 // (its decoder's n_pix outputs are channel-last, C consecutive logits per position); 1 for every per-value likelihood
 static inline int plan_group(const pv_ivae_plan* p) {
@@ -185,7 +190,7 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
   L.ev = evidence && !inference_only;
   const bool bwd = !L.ev;                            // room for what only a backward pass reads or writes
   // N: the decoder's rows per sample (spatial: grid positions) or its output width (vanilla)
-  const int64_t B = p->batch, N = encode_only ? 0 : plan_pos(p), z = p->z_dim, Cn = plan_C(p);
+  const int64_t B = p->batch, N = encode_only ? 0 : plan_rows(p), z = p->z_dim, Cn = plan_C(p);
   const int64_t lat_in = plan_lat_in(p), K = plan_K(p), S = inference_only ? p->batch : plan_S(p) * L.P, hw = plan_head_w(p);
   const bool multi = K > 0 || L.P > 1 || L.ev;      // several decoder samples per input
   L.rows = p->coord_dim > 0 ? S * N : S;
@@ -864,7 +869,7 @@ struct FusedStep {
 
 void fused_decoder_args(FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
-  const int64_t B = p->batch, N = plan_pos(p), R = L.rows, K = plan_K(p), S = step_S(p, L);   // jiVAE: S = K*B decoder samples, rows R = S*N (N: rows per sample)
+  const int64_t B = p->batch, N = plan_rows(p), R = L.rows, K = plan_K(p), S = step_S(p, L);   // jiVAE: S = K*B decoder samples, rows R = S*N (N: rows per sample)
   const bool multi = K > 0 || L.P > 1;               // (multi-particle: S = P*B, each weighted 1/P against the same B observations)
   PvFused& f = st.f;
   fused_weights(f, p);
@@ -877,6 +882,7 @@ void fused_decoder_args(FusedStep& st) {
   f.part_rs = (st.grads && st.dec.rec_fmt == PV_REC_LANE_F32) ? L.f_part_hz + S * L.f_kmax * FD_H : nullptr;
   f.wimg = L.f_wimg; f.park = L.f_park;                // (a weighted launch puts the weights in wimg's slot: fused_decoder_launch)
   f.M = R; f.units = R / FD_UNIT; f.N = (int)N; f.cd = p->coord_dim; f.B = (int)S; f.lik = p->lik;
+  f.n_obs = pv_sdec_fused_tail(p) ? (int)plan_pos(p) : 0;          // (the tail form: a sample observes fewer rows than it occupies)
   f.sw = multi ? L.sw : p->row_w; f.x_units = multi ? B * N / FD_UNIT : 0;
   f.sigmoid_out = p->sigmoid_out; f.kmax = L.f_kmax; f.sig = p->decoder_sig; f.sel = plan_sel(p);
   // fp16 builds of the fp32-class kernel: where the per-row exponent of dL/dlogit is centred (|dL/dlogit| <= 1 for the Bernoulli
@@ -986,7 +992,7 @@ int fused_guide(FusedStep& st) {
 void fused_closing_form(FusedStep& st, const PvAdamFuse* adam, bool* adam_done) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L;
   PvFused& f = st.f;
-  const int64_t N = plan_pos(p), R = L.rows, z = p->z_dim, K = plan_K(p), S = step_S(p, L), lat_in = plan_lat_in(p);
+  const int64_t N = plan_rows(p), R = L.rows, z = p->z_dim, K = plan_K(p), S = step_S(p, L), lat_in = plan_lat_in(p);
   const int H = FD_H;
   const float* Wz = p->params + p->fc_latent.w_off;
   // (round 6) the 4-wave kernels too hand over dL/d(hz) and dL/dz, wherever every workgroup's units are exactly one sample
@@ -1086,7 +1092,7 @@ int fused_decoder_launch(FusedStep& st) {
 // no gradients: ll_b from the decoder's rows, the loss scalars, the extra outputs
 int fused_close_forward(const FusedStep& st) {
   const pv_ivae_plan* p = st.p; const Layout& L = st.L; hipStream_t s = st.s;
-  const int64_t B = p->batch, N = plan_pos(p), K = plan_K(p);
+  const int64_t B = p->batch, N = plan_rows(p), K = plan_K(p);
   if (K > 0) {                                       // llb[b] = sum_k alpha_bk ll_kb
     PvLatentBwd lf{};
     lf.llrow = L.llrow; lf.llb = L.llb; lf.M = L.rows; lf.N = (int)N; lf.H = 0; lf.K = (int)K; lf.alpha = L.alpha;
@@ -1126,7 +1132,7 @@ int fused_renyi_forward(const FusedStep& st) {
   if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(ff, false, fwd, s));
   PV_TRY(pv_sdec_fused_bf16_launch(ff, L.f_grid, false, fwd, s));
   if (!same_images) PV_TRY(pv_sdec_fused_bf16_prep(st.f, true, trn, s));
-  PV_TRY(pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s));
+  PV_TRY(pv_segsum(L.llrow, step_S(p, L), plan_rows(p), L.llkb, s));
   return renyi_weights(p, L, st.o, s);
 }
 
@@ -1351,6 +1357,7 @@ static pv_ivae_plan decode_plan(const pv_ivae_plan* plan) {
     lay.c_dim += lay.discrete_dim;
     lay.head.out_dim -= lay.discrete_dim;
     lay.discrete_dim = 0;
+    lay.flags &= ~PV_PLAN_FUSED_TAIL;                  // (the bit does nothing for a discrete latent: its decode keeps today's kernels)
   }
   return lay;
 }
@@ -1394,7 +1401,7 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   DecodeLayout D;
   carve_decode(lay, (char*)lay->ws, D);
   if (lay->ws_bytes < D.total) return PV_EWS;
-  const int64_t B = lay->batch, N = plan_pos(lay), lat_in = plan_lat_in(lay);      // N: rows per sample
+  const int64_t B = lay->batch, N = plan_rows(lay), lat_in = plan_lat_in(lay);      // N: rows per sample
   const int H = FD_H;
   if (lay->fc_latent.in_dim != lat_in) return PV_EINVAL;
   PV_TRY(pv_fill_tp(D.tp, (int)B, angle, scale, shift_x, shift_y, s));
@@ -1409,6 +1416,7 @@ static int decode_fused_run(const pv_ivae_plan* lay, const float* z, float angle
   fused_weights(f, lay);
   f.llrow = nullptr; f.loc = loc; f.wimg = D.wimg;
   f.M = B * N; f.units = f.M / FD_UNIT; f.N = (int)N; f.cd = lay->coord_dim; f.B = (int)B;
+  f.n_obs = pv_sdec_fused_tail(lay) ? (int)plan_pos(lay) : 0;      // (loc is (B, positions, C): the padding rows write nothing)
   f.lik = loc_lik(lay); f.sigmoid_out = lay->sigmoid_out; f.sig = 1.0f;         // loc = sigmoid(a) or a (Poisson: exp(a))
   f.sel = lay->dec_kernel;                             // (forward-only: no fp16 build, the parent's selection for every likelihood)
   const int grid = pv_sdec_fused_grid(f.units);
@@ -1573,6 +1581,8 @@ static bool weighted_scope(const pv_ivae_plan* p) {
 // (per_image: pv_ivae_weighted_images_* — the same routing over the per-image instances' list, which today is the same list)
 static pv_ivae_plan weighted_route(const pv_ivae_plan* p, bool per_image = false) {
   pv_ivae_plan q = *p;
+  // (PV_PLAN_FUSED_TAIL is the caller's fused == 1 alone: a fused == 2 plan that routes to the f32 kernel below answers as without the bit)
+  if (p->fused != 1) q.flags &= ~PV_PLAN_FUSED_TAIL;
   if (weighted_fast(p)) {
     q.dec_kernel = 1;
     q.flags |= PV_PLAN_NO_ENC_FOLD;
@@ -1595,8 +1605,8 @@ extern "C" const char* pv_debug_weighted_decoder_kernel_name(const pv_ivae_plan*
   const pv_ivae_plan q = weighted_route(plan, per_image != 0);
   if (q.fused != 1) return "pv_gemm_kernel (layer-by-layer path)";
   static thread_local char buf[96];
-  snprintf(buf, sizeof buf, "void pv_sdec_fused_mc_kernel<%s, %d, %d>(PvFused)", grads ? "true" : "false", (int)plan_C(&q),
-           per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED);
+  snprintf(buf, sizeof buf, "void pv_sdec_fused_mc%s_kernel<%s, %d, %d>(PvFused)", pv_sdec_fused_tail(&q) ? "_tail" : "",
+           grads ? "true" : "false", (int)plan_C(&q), per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED);
   return buf;
 }
 
@@ -1829,7 +1839,7 @@ static int evidence_ll_fused(const pv_ivae_plan* p, const Layout& L, hipStream_t
   fused_decoder_args(st);
   PV_TRY(fused_guide(st));
   PV_TRY(fused_decoder_launch(st));
-  return pv_segsum(L.llrow, step_S(p, L), plan_pos(p), L.llkb, s);
+  return pv_segsum(L.llrow, step_S(p, L), plan_rows(p), L.llkb, s);
 }
 
 extern "C" int64_t pv_ivae_evidence_workspace_bytes(const pv_ivae_plan* plan, int32_t P) {

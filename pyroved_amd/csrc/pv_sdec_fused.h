@@ -64,7 +64,12 @@ struct PvFused {
   int sel;               // pv_ivae_plan.dec_kernel: which build of the decoder kernel runs (0: by problem size; pv_sdec_fused_bf16.hip)
   int dl_exp;            // fp16 modes (pv_sdec_fused_bf16.hip): exponent bias of the per-row dL/dlogit factor folded into the
                          // staged activations: 2^dl_exp * |dL/dlogit| should sit around 1 .. 2^8 (Bernoulli 4; Gaussian: -log2(1 / sig^2))
+  int n_obs;             // tail launches of pv_sdec_fused_mc.hip only (pv_sdec_fused_mc_launch with n_obs > 0; PV_PLAN_FUSED_TAIL):
+                         // the positions a sample observes, n_obs < N = 16 ceil(n_obs / 16) — N stays "rows per sample" of the partition,
+                         // M = B N, and rows n >= n_obs of a sample are padding.  x, loc and the per-image weights are (B, n_obs, C).
+                         // 0 everywhere else.  (It takes the struct's four bytes of tail padding: size and every offset stay)
 };
+static_assert(sizeof(PvFused) == 280, "PvFused is a kernel argument: its size is part of every kernel's argument layout");
 
 // ---- the guide folded into the decoder launch (round 5; pv_sdec_fused_w8.hip) -------------------------------------------------
 // When a workgroup's unit range is a whole number of images (batch a multiple of the grid: BASELINE's batch 256 on 256 CUs is one
@@ -146,7 +151,8 @@ int pv_sdec_fused_launch(const PvFused& f, int grid, bool grads, hipStream_t s);
 // the architecture of pv_sdec_fused_supported without its conditions on the output layer's width and the rows per sample
 bool pv_sdec_fused_trunk_supported(const pv_ivae_plan* p);
 // true when the plan runs the multi-channel kernel: the flag, fused == 1, that architecture, 2 <= out.out_dim <= PV_MAX_CHANNELS
-// with an instance of the kernel, and positions (n_pix / out.out_dim) a multiple of 16
+// with an instance of the kernel, and positions (n_pix / out.out_dim) a multiple of 16 — or pv_sdec_fused_tail(p), below, at
+// every channel count it accepts, one included (the plan then runs the kernel's tail form)
 bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p);
 // f as for pv_sdec_fused_launch with C values per row: x and loc are (M, C) channel-last (x null: zeros — forward-only decode),
 // wo (C, H), bo (C); llrow (M) sums the row's C values, c ascending.  Record (PV_REC_ROWMAJOR): channel 0's d(wo) / d(bo) where
@@ -156,12 +162,24 @@ bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p);
 // ll and dL/da of observation (n, c) of every sample are multiplied by pw[n * C + c]; loc is not.  The record is the unweighted launch's
 // weighted == PV_FDM_W_IMAGES (pv_ivae_weighted_images_*): f.pw is (M * C), one weight per observation of every sample in the
 // layout of x — observation (row, c) is multiplied by pw[row * C + c]; the same instances list, everything else as PV_FDM_W_SHARED
+// f.n_obs > 0: the tail form (PV_PLAN_FUSED_TAIL; per-value likelihoods, C = 1 .. 6 and 8 in all three weight forms): a sample
+// occupies f.N = 16 ceil(n_obs / 16) rows, M = B N, of which it observes the first n_obs; x, loc and per-image weights are
+// (B, n_obs, C), shared weights (n_obs, C), the grid (n_obs, cd); llrow (M) and rowtp (4, M) get zeros in the padding rows
 #define PV_FDM_W_SHARED 1
 #define PV_FDM_W_IMAGES 2
 int pv_sdec_fused_mc_launch(const PvFused& f, int C, int grid, bool grads, hipStream_t s, int weighted = 0);
+// ---- positions that are no multiple of 16 (PV_PLAN_FUSED_TAIL; the tail instances of pv_sdec_fused_mc.hip) ----
+// true when the flag takes effect on the plan: fused == 1, the trunk's architecture, positions % 16 != 0, the fc-encoder iVAE (no
+// discrete latent, no convolutional / external networks, no per-image outputs), a per-value likelihood, and one channel or
+// 2 .. 6 or 8 with PV_PLAN_FUSED_CHANNELS (seven: the unweighted instance spills, so the count stays layered).  The unweighted
+// and both weighted entry points then run the tail instances
+bool pv_sdec_fused_tail(const pv_ivae_plan* p);
+// rows per sample of the plan's DECODER layout: the positions (n_pix / channels), rounded up to a multiple of 16 where
+// pv_sdec_fused_tail(p).  Layout, launch arguments and per-sample reductions take it; x, loc, the encoder, the weights keep n_pix
+int64_t pv_sdec_fused_rows_per_sample(const pv_ivae_plan* p);
 // true when a WEIGHTED step of the plan (pv_ivae_weighted_*) runs that kernel: fused == 1, the trunk's architecture, positions a
 // multiple of 16, a weighted instance for the channel count — one channel, or 2 .. PV_MAX_CHANNELS with PV_PLAN_FUSED_CHANNELS
-// (per_image: the instances of pv_ivae_weighted_images_*)
+// (per_image: the instances of pv_ivae_weighted_images_*); or pv_sdec_fused_tail(p): the tail form's weighted instances
 bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p, bool per_image = false);
 // sums the records' entries of channels 1 .. C-1 — (C - 1) (H + 1) outputs, each over the `grid` records in the shared reduction's
 // fixed order (four slices of ascending workgroups) — into G + wo_off + c H and G + bo_off + c; channel 0 is the shared reduction's

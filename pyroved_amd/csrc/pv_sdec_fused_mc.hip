@@ -23,6 +23,8 @@
 // shared reductions finish W1, W2, b1, b2, Wc, Wo[0], bo[0] untouched; channel c >= 1: d(wo)[c] in spare slot 5 + c, d(bo)[c] at
 // slot 5 [c], summed by pv_sdec_fused_mc_reduce_out.
 // PvFused::ablate (profiling switches of the one-channel kernel) is ignored here.
+// Its TAIL instances (pv_sdec_fused_mc_tail_kernel, C = 1 .. 6 and 8, all three weight forms; PV_PLAN_FUSED_TAIL) run plans whose
+// positions are no multiple of 16: described where they are instantiated, below.
 #include "pv_sdec_fused_f32.h"
 
 #define OFF_WOC OFF_DWO            // Wo[C][FD_H]
@@ -69,17 +71,36 @@ __device__ __forceinline__ void fdm_pixel_lik(const PvFused& f, float a, float x
 // observation) and from them  ll = sum_c xw_c (a_c - lse),  dL/da_c = p_c sum_c xw_c - xw_c,  loc_c = p_c = exp(a_c - max) / sum.
 // log p_c is a_c - lse, never log(p_c).  x and w are read twice (cache hits) instead of held in 2 C registers across the pass.
 // Everything from the d(wo) exchange onward is the same code.
+//
+// TAIL (PV_PLAN_FUSED_TAIL; pv_sdec_fused_mc_tail_kernel, instances of their own from the same text): positions that are no multiple
+// of 16.  A sample occupies f.N = 16 ceil(f.n_obs / 16) rows of the partition — units, workgroup ranges, flush_hz and kmax are the
+// padded layout's, unchanged — and observes the first f.n_obs.  A padding row reads neither the grid nor x nor a weight, runs the
+// layers at the coordinates (0, 0) (finite values), and has ll = 0 and dL/da_c = 0 set where they are formed: from there on it is the
+// weighted instances' zero-weight row — tC = 0 (1 - h2^2) = 0, and every staged product, d(x') and dL/d(hz) term it contributes is
+// an exact zero.  It writes no loc and DOES write llrow = 0 and rowtp = 0: the per-sample sums read all f.N rows of a workspace
+// that arrives with any content.  x, loc and per-image weights are indexed by observation, (b n_obs + n) C + c.  C = 1 .. 6 and 8
+// in all three weight forms (not 7: fdm_has_tail_instance), the unweighted C = 1 included (its record is the one-channel
+// kernel's: nothing for the second launch to sum).
 #define FDM_KERNEL pv_sdec_fused_mc_kernel
 #define FDM_CAT 0
+#define FDM_TAIL 0
+#include "pv_sdec_fused_mc_body.inc"
+#undef FDM_KERNEL
+#undef FDM_TAIL
+#define FDM_KERNEL pv_sdec_fused_mc_tail_kernel
+#define FDM_TAIL 1
 #include "pv_sdec_fused_mc_body.inc"
 #undef FDM_KERNEL
 #undef FDM_CAT
+#undef FDM_TAIL
 // the categorical instances: C = 2 .. 8 (one class is no distribution), unweighted and both weighted forms
 #define FDM_KERNEL pv_sdec_fused_mc_cat_kernel
 #define FDM_CAT 1
+#define FDM_TAIL 0
 #include "pv_sdec_fused_mc_body.inc"
 #undef FDM_KERNEL
 #undef FDM_CAT
+#undef FDM_TAIL
 
 // ---- channels 1 .. C-1 of d(wo), d(bo): per-workgroup records -> flat gradient buffer -----------------------
 // 64 outputs x 4 slices of the workgroup range per 256-thread block, slices combined in fixed order: the shared reduction's order
@@ -132,8 +153,31 @@ static bool fdm_has_cat_instance(int C, int weighted = 0) { return weighted >= 0
 static bool fdm_lik_instance(int lik, int C, int weighted) {
   return lik == PV_LIK_CATEGORICAL ? fdm_has_cat_instance(C, weighted) : fdm_has_instance(C, weighted);
 }
+// the tail form (pv_sdec_fused_mc_tail_kernel): per-value likelihoods, C = 1 .. 6 and 8 in all three weight forms.  C = 7 is taken
+// out: its unweighted training instance spills (3 VGPRs, 16 bytes of scratch per lane; profiles/any_size_resource_usage.txt), and
+// one list serves the three forms because a plan's unweighted and weighted calls share the layout — seven channels whose
+// positions are no multiple of 16 stay on the layer-by-layer kernels, and no C = 7 tail instance is compiled
+static bool fdm_has_tail_instance(int lik, int C, int weighted = 0) {
+  return lik != PV_LIK_CATEGORICAL && weighted >= 0 && weighted <= 2 && C >= 1 && C <= 8 && C != 7;
+}
+
+bool pv_sdec_fused_tail(const pv_ivae_plan* p) {
+  if (!p || !(p->flags & PV_PLAN_FUSED_TAIL) || p->fused != 1 || !pv_sdec_fused_trunk_supported(p)) return false;
+  if (p->discrete_dim > 0 || p->n_enc_ops > 0 || p->ext_encoder || p->ext_decoder || p->row_w || p->row_elbo || p->dy) return false;
+  const int C = p->out.out_dim;
+  if (C < 1 || C > PV_MAX_CHANNELS || p->n_pix % C != 0 || (C > 1 && !(p->flags & PV_PLAN_FUSED_CHANNELS))) return false;
+  // (one list for the three weight forms: a plan's unweighted and weighted calls share the decision, and with it the layout)
+  for (int w = 0; w <= 2; ++w)
+    if (!fdm_has_tail_instance(p->lik, C, w)) return false;
+  return (p->n_pix / C) % FD_UNIT != 0;
+}
+int64_t pv_sdec_fused_rows_per_sample(const pv_ivae_plan* p) {
+  const int64_t pos = p->n_pix / (p->coord_dim > 0 ? p->out.out_dim : 1);
+  return pv_sdec_fused_tail(p) ? (pos + FD_UNIT - 1) / FD_UNIT * FD_UNIT : pos;
+}
 
 bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p) {
+  if (pv_sdec_fused_tail(p)) return true;              // (one channel too: the unweighted tail form exists at C = 1)
   if (!p || !(p->flags & PV_PLAN_FUSED_CHANNELS) || p->fused != 1) return false;
   if (!pv_sdec_fused_trunk_supported(p)) return false;
   const int C = p->out.out_dim;
@@ -142,6 +186,7 @@ bool pv_sdec_fused_mc_supported(const pv_ivae_plan* p) {
 }
 
 bool pv_sdec_fused_mc_weighted_supported(const pv_ivae_plan* p, bool per_image) {
+  if (pv_sdec_fused_tail(p)) return true;
   if (!p || p->fused != 1 || !pv_sdec_fused_trunk_supported(p)) return false;
   const int C = p->out.out_dim;
   if (C < 1 || C > PV_MAX_CHANNELS || !fdm_lik_instance(p->lik, C, per_image ? PV_FDM_W_IMAGES : PV_FDM_W_SHARED) || p->n_pix % C != 0) return false;
@@ -191,6 +236,34 @@ static int fdm_launch(const PvFused& f, int grid, bool grads, hipStream_t s) {
   return 0;
 }
 
+template <int C, int W>
+static int fdm_tail_launch(const PvFused& f, int grid, bool grads, hipStream_t s) {
+  const size_t lds = FD_LDS_FLOATS * sizeof(float);
+  if (grads) {
+    PV_TRY(pv_set_dynamic_lds(reinterpret_cast<const void*>(&pv_sdec_fused_mc_tail_kernel<true, C, W>), (int)lds));
+    hipLaunchKernelGGL((pv_sdec_fused_mc_tail_kernel<true, C, W>), dim3(grid), dim3(FD_THREADS), lds, s, f);
+  } else {
+    PV_TRY(pv_set_dynamic_lds(reinterpret_cast<const void*>(&pv_sdec_fused_mc_tail_kernel<false, C, W>), (int)lds));
+    hipLaunchKernelGGL((pv_sdec_fused_mc_tail_kernel<false, C, W>), dim3(grid), dim3(FD_THREADS), lds, s, f);
+  }
+  PV_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int W>
+static int fdm_tail_launch_any(const PvFused& f, int C, int grid, bool grads, hipStream_t s) {
+  switch (C) {
+    case 1: return fdm_tail_launch<1, W>(f, grid, grads, s);
+    case 2: return fdm_tail_launch<2, W>(f, grid, grads, s);
+    case 3: return fdm_tail_launch<3, W>(f, grid, grads, s);
+    case 4: return fdm_tail_launch<4, W>(f, grid, grads, s);
+    case 5: return fdm_tail_launch<5, W>(f, grid, grads, s);
+    case 6: return fdm_tail_launch<6, W>(f, grid, grads, s);
+    case 8: return fdm_tail_launch<8, W>(f, grid, grads, s);
+  }
+  return PV_EINVAL;
+}
+
 template <int W>
 static int fdm_launch_weighted(const PvFused& f, int C, int grid, bool grads, hipStream_t s) {
   switch (C) {
@@ -209,9 +282,17 @@ static int fdm_launch_weighted(const PvFused& f, int C, int grid, bool grads, hi
 int pv_sdec_fused_mc_launch(const PvFused& f_in, int C, int grid, bool grads, hipStream_t s, int w) {
   if (f_in.sw || f_in.x_units != 0 || f_in.part_rs || f_in.dhz_out || f_in.dzc_out) return PV_EINVAL;
   if (w ? !f_in.pw : f_in.wimg != nullptr) return PV_EINVAL;         // (one slot: the weights of a weighted launch, else nothing)
-  if (!fdm_lik_instance(f_in.lik, C, w) || grid < 1 || f_in.N % FD_UNIT != 0 || f_in.units * FD_UNIT != f_in.M) return PV_EINVAL;
+  if (grid < 1 || f_in.N % FD_UNIT != 0 || f_in.units * FD_UNIT != f_in.M || f_in.n_obs < 0) return PV_EINVAL;
+  const bool tail = f_in.n_obs > 0;                                  // the rows a sample observes are fewer than the rows it occupies
+  if (tail ? !fdm_has_tail_instance(f_in.lik, C, w) : !fdm_lik_instance(f_in.lik, C, w)) return PV_EINVAL;
+  if (tail && (f_in.n_obs >= f_in.N || f_in.N - f_in.n_obs >= FD_UNIT || (int64_t)f_in.B * f_in.N != f_in.M)) return PV_EINVAL;
   PvFused f = f_in;
   f.ablate = 0;
+  if (tail) {
+    if (w == PV_FDM_W_IMAGES) return fdm_tail_launch_any<PV_FDM_W_IMAGES>(f, C, grid, grads, s);
+    if (w == PV_FDM_W_SHARED) return fdm_tail_launch_any<PV_FDM_W_SHARED>(f, C, grid, grads, s);
+    return fdm_tail_launch_any<0>(f, C, grid, grads, s);
+  }
   if (f.lik == PV_LIK_CATEGORICAL) {                                 // the likelihood kind is a compile-time property of its instances
     if (w == PV_FDM_W_IMAGES) return fdm_cat_launch_any<PV_FDM_W_IMAGES>(f, C, grid, grads, s);
     if (w == PV_FDM_W_SHARED) return fdm_cat_launch_any<PV_FDM_W_SHARED>(f, C, grid, grads, s);

@@ -1,13 +1,18 @@
 // pv_sdec_fused_mc_body.inc — the kernel of pv_sdec_fused_mc.hip, included once per likelihood family with
 //   FDM_KERNEL  the __global__'s name        FDM_CAT  0: the per-value likelihoods (fdm_pixel_lik), 1: PV_LIK_CATEGORICAL
+//   FDM_TAIL    0: every sample's positions fill its units (f.N % 16 == 0); 1: the tail form (PV_PLAN_FUSED_TAIL) — a sample
+//               occupies f.N = 16 ceil(f.n_obs / 16) rows of the partition and observes the first f.n_obs of them
 // so that each family is a kernel template of its own, written once: the per-value instances compile from this text with the
 // categorical pass a constant-false block (their registers and code are what they were before the categorical family existed:
 // profiles/categorical_resource_usage.txt), and the categorical instances carry no run-time likelihood switch.
 template <bool GRADS, int C, int WEIGHTED>
 __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
   constexpr bool CAT = FDM_CAT != 0;
+  constexpr bool TAIL = FDM_TAIL != 0;
   static_assert(!CAT || C >= 2, "classes per row");
-  static_assert(WEIGHTED >= 0 && WEIGHTED <= 2 && C >= (WEIGHTED ? 1 : 2) && C <= 8 && C * FD_H <= FD_WAVES * FD_H && FD_UNIT * C <= FD_H && 40 + C <= 64, "LDS regions");
+  static_assert(!CAT || !TAIL, "the tail form exists for the per-value likelihoods");
+  static_assert(WEIGHTED >= 0 && WEIGHTED <= 2 && C >= ((WEIGHTED || TAIL) ? 1 : 2) && C <= 8, "instances");
+  static_assert(C * FD_H <= FD_WAVES * FD_H && FD_UNIT * C <= FD_H && 40 + C <= 64, "LDS regions");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // uniform: unit, sample and every 16 * wave offset stay scalar
@@ -44,7 +49,7 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
 #pragma unroll
   for (int c = 0; c < C; ++c) adwo[c] = 0.0f;
   int cur_b = -1;
-  const int upb = f.N / FD_UNIT;                       // units per sample (N = positions, N % 16 == 0)
+  const int upb = f.N / FD_UNIT;                       // units per sample (N = rows per sample, N % 16 == 0)
 
   auto flush_hz = [&](int b) {
     // sample b's rows end (or the workgroup's do): publish this workgroup's partial dL/d(hz[b])
@@ -67,6 +72,11 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
     const int unit = (int)u0 + (active ? wave : 0);          // 32-bit index math: units < 2^31 / 16
     const int b = unit / upb, n = (unit - b * upb) * FD_UNIT + r;
     const int64_t row = (int64_t)unit * FD_UNIT + r;
+    // TAIL: rows n >= f.n_obs of a sample are padding — no grid position, no observation, no weight: they read none of the three,
+    // take the coordinates (0, 0) and dL/da = 0, and write zeros where the per-sample sums read all f.N rows (llrow, rowtp).
+    // x, loc and the per-image weights keep the caller's layout: observation (b, n, c) at (b * n_obs + n) * C + c
+    const bool valid = !TAIL || n < f.n_obs;
+    const int64_t orow = TAIL ? (int64_t)b * f.n_obs + n : row;
     // three register tiles (16 rows x 128 cols each, 32 VGPRs) are rotated through the roles
     // h0 -> h1 -> h2/dpre2 -> dpre1 -> h0 (recomputed) -> dpre0 so that at most three are live
     f32x4 tA[8], tB[8], tC[8];
@@ -90,7 +100,9 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
     if (active) {
       // ---- x' = rotate/scale/translate(grid[n])   (coord.py:47-88) ----
       const float* t = f.tp + (int64_t)b * 8;
-      if (f.cd == 2) {
+      if (!valid) {
+        // (x0 = x1 = 0)
+      } else if (f.cd == 2) {
         const float gx = f.grid[2 * n], gy = f.grid[2 * n + 1];
         const float u0c = gx * t[0] - gy * t[1];
         const float u1c = gx * t[1] + gy * t[0];
@@ -128,13 +140,14 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
           FD_SCHED_FENCE();
           continue;
         }
-        const float xv = f.x ? f.x[row * C + c] : 0.0f;
-        const float pwv = WEIGHTED == 2 ? f.pw[row * C + c] : WEIGHTED == 1 ? f.pw[n * C + c] : 1.0f;
+        const float xv = (f.x && valid) ? f.x[orow * C + c] : 0.0f;
+        const float pwv = !valid ? 0.0f : WEIGHTED == 2 ? f.pw[orow * C + c] : WEIGHTED == 1 ? f.pw[n * C + c] : 1.0f;
         float ll, locv;
         fdm_pixel_lik(f, a, xv, ll, dlda[c], locv);
         if (WEIGHTED) { ll *= pwv; dlda[c] *= pwv; }
+        if (TAIL && !valid) { ll = 0.0f; dlda[c] = 0.0f; }
         llsum += ll;
-        if (q == 0 && f.loc) f.loc[row * C + c] = locv;
+        if (q == 0 && valid && f.loc) f.loc[orow * C + c] = locv;
         FD_SCHED_FENCE();        // one channel at a time: hoisted, the C channels' Wo reads alone would take 32 C VGPRs
       }
       if (CAT) {
@@ -250,7 +263,9 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
         //  through the tile's dgrad streams, where the registers run out)
         float u0c, u1c = 0.0f, sc = 1.0f;
         const float* t = f.tp + (int64_t)b * 8;
-        if (f.cd == 2) {
+        if (!valid) {
+          u0c = 0.0f;                                  // (d0 = d1 = 0 exactly: the row's four entries are zeros)
+        } else if (f.cd == 2) {
           const float gx = f.grid[2 * n], gy = f.grid[2 * n + 1];
           u0c = gx * t[0] - gy * t[1];
           u1c = gx * t[1] + gy * t[0];

@@ -71,13 +71,14 @@ def _linears(seq: nn.Sequential) -> List[nn.Linear]:
 
 # settings as given -> as the engine keeps them (pixel_weights needs the model: IVAEEngine._pixel_weight_tensor)
 _NORMALISE = dict(fused=int, kl=_kl_name, particles=_particle_count, renyi=_renyi_alpha, fused_channels=bool,
-                  image_weights=_image_weights_flag, fast_weights=bool)
+                  image_weights=_image_weights_flag, fast_weights=bool, fused_any_size=bool)
 
 
 class IVAEEngine:
     """Binds an iVAE-like model (encoder_z: fcEncoderNet, decoder: sDecoderNet | fcDecoderNet) to the HIP library.
     A multi-channel model (models.iVAE(..., channels=C), self.C > 1) takes x as (B, *data_dim, C), channel-last, and returns loc /
     decode in that shape.  The settings — fused, kl, particles, renyi, fused_channels, pixel_weights, image_weights, fast_weights,
+    fused_any_size,
     each described at its class default below — are plain attributes read at every call; model.engine(**kw) and configure(**kw)
     set them.  Which combinations a model takes, and every refusal's text, is `_validate`'s rule list; which kernels a combination
     runs on is `_plan_fused` / `_plan_flags`.  Per-batch weights come with every call: loss_and_grads(..., image_weights=w)."""
@@ -120,6 +121,10 @@ class IVAEEngine:
                                      # with pixel_weights as well the library gets the product
     fast_weights = False             # PV_PLAN_FAST_WEIGHTS: weighted steps on the 4-wave bf16-class fused decoder kernel (fused = 2:
                                      # where the model is one it takes, fp32-class results; fused = 3: refused elsewhere)
+    fused_any_size = False           # PV_PLAN_FUSED_TAIL (with fused = 1 or 2): a spatial model whose grid positions are no multiple
+                                     # of 16 runs on the fused f32 decoder kernel's tail form instead of the layer-by-layer kernels
+                                     # (fp32-class; models.iVAE, decoder hidden [128, 128], tanh, per-value likelihoods, one channel —
+                                     # or several with fused_channels; everything else keeps today's routing: _any_size_on)
     _ev_ws = None                    # log_evidence_chunk: the evidence workspace (grows to the largest layout asked for) and the
     _ev_need = None                  # sizes the library answered, per (batch, P, fused)
     _snap = None                     # _bound's snapshot of the module tree
@@ -127,10 +132,10 @@ class IVAEEngine:
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, fused: int = 2, kl: str = "sampled",
                  particles: int = 1, renyi=None, fused_channels: bool = False, pixel_weights=None,
-                 image_weights: bool = False, fast_weights: bool = False):
+                 image_weights: bool = False, fast_weights: bool = False, fused_any_size: bool = False):
         self.model = model
         new = self._normalise(dict(image_weights=image_weights, fast_weights=fast_weights, fused_channels=fused_channels, kl=kl,
-                                   particles=particles, renyi=renyi, fused=fused))
+                                   particles=particles, renyi=renyi, fused=fused, fused_any_size=fused_any_size))
         self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.adam_t = 0                 # number of optimizer steps taken (incl. evaluate()'s, see SVItrainer)
         self.grads_live = False         # reference: .grad is None until the first backward
@@ -366,9 +371,11 @@ class IVAEEngine:
 
     def _settings(self):
         return dict(fused=self.fused, kl=self.kl, particles=self.particles, renyi=self.renyi, fused_channels=self.fused_channels,
-                    pixel_weights=self.pixel_weights, image_weights=self.image_weights, fast_weights=self.fast_weights)
+                    pixel_weights=self.pixel_weights, image_weights=self.image_weights, fast_weights=self.fast_weights,
+                    fused_any_size=self.fused_any_size)
 
-    def _validate(self, *, fused, kl, particles, renyi, fused_channels, pixel_weights, image_weights, fast_weights, dec_kernel):
+    def _validate(self, *, fused, kl, particles, renyi, fused_channels, pixel_weights, image_weights, fast_weights, dec_kernel,
+                  fused_any_size=False):
         """The one rule list: which settings (normalised, _normalise) this model takes.  Raises the first rule the candidate breaks,
         in the order written; reads the model's facts (K, own_fc, fw_blocker) and no setting off self, and assigns nothing.  The
         constructor and configure() both validate here before they assign, so a refusal leaves no trace.
@@ -407,6 +414,15 @@ class IVAEEngine:
              "bf16 throughput kernels, which have no multi-channel form"),
             (fused_channels and fused == 0,
              "fused_channels=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2"),
+            (fused_any_size and type(self) is not IVAEEngine, only_ivae % "fused_any_size"),
+            (fused_any_size and multi,
+             "fused_any_size=True runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound: "
+             "the f32 fused kernel it selects has no multi-particle form)"),
+            (fused_any_size and fused == 3,
+             "fused_any_size=True selects the f32 fused decoder kernel; fused=3 (precision='bf16') asks for the "
+             "bf16 throughput kernels, which have no form for positions that are no multiple of 16"),
+            (fused_any_size and fused == 0,
+             "fused_any_size=True contradicts fused=0 (the layer-by-layer kernels): use fused=1 or 2"),
             *scope(weighted, kw, only_ivae % kw),
             (weighted and multi, "%s runs the one-particle ELBO only (not num_particles > 1 or the Renyi bound)" % kw),
             (weighted and fused == 3 and not fast_weights,
@@ -432,7 +448,7 @@ class IVAEEngine:
     def supports_dp_step(self) -> bool:
         """loss_and_grads(step=True, comm=NativeComm), the data-parallel step as one library call: the one-particle,
         single-channel, unweighted ELBO's."""
-        return self.particles == 1 and self.renyi is None and self.C == 1 and not self._weighted()
+        return self.particles == 1 and self.renyi is None and self.C == 1 and not self._weighted() and not self._any_size_on()
 
     @property
     def _torch_side(self) -> bool:
@@ -462,6 +478,24 @@ class IVAEEngine:
         if n_pos % 16 != 0:
             return "the grid has %d positions, not a multiple of 16" % n_pos
         return None
+
+    def _any_size_on(self) -> bool:
+        """Whether fused_any_size takes effect (the plan then carries PV_PLAN_FUSED_TAIL and fused = 1): models.iVAE with its own
+        fully connected networks and no discrete latent, the spatial decoder of two tanh layers of 128, a per-value likelihood, one
+        channel or fused_channels, fused 1 or 2, and a number of grid positions that is NO multiple of 16.  Elsewhere the setting
+        is a no-op: the model keeps the routing it has without it."""
+        if not (self.fused_any_size and self.own_fc and self.K == 0 and self.fused in (1, 2)):
+            return False
+        m, dec = self.model, self.model.decoder
+        if m.coord == 0 or not isinstance(dec, sDecoderNet) or m.sampler_d.name in _abi.LIK_JOINT:
+            return False
+        if (self.C > 1 and not self.fused_channels) or self.C == 7:      # (seven channels: the tail instance spills, none is built)
+            return False
+        lins = _linears(dec.fc_layers)
+        if (len(lins) != 2 or any(l.in_features != 128 or l.out_features != 128 or l.bias is None for l in lins)
+                or dec.activation != "tanh" or dec.coord_latent.fc_coord.out_features != 128):
+            return False
+        return math.prod(int(d) for d in m.data_dim) % 16 != 0
 
     def _fast_weights_on(self) -> bool:
         """Whether the weighted step runs the weighted bf16-class kernel (the plan then carries PV_PLAN_FAST_WEIGHTS and keeps `fused`)."""
@@ -498,6 +532,8 @@ class IVAEEngine:
         fast_weights keeps it on the bf16-class kernels."""
         if self.fused_channels and self.C > 1 and self.fused in (1, 2):
             return 1
+        if self._any_size_on():
+            return 1
         if self._fast_weights_on():
             return int(self.fused)
         if self._weighted() and self.C == 1 and self.fused in (1, 2):
@@ -505,22 +541,23 @@ class IVAEEngine:
         return int(self.fused)
 
     def configure(self, lr=None, betas=None, eps=None, fused=None, kl=None, particles=None, renyi=None, fused_channels=None,
-                  pixel_weights=None, image_weights=None, fast_weights=None):
+                  pixel_weights=None, image_weights=None, fast_weights=None, fused_any_size=None):
         """Applies trainer-level settings to an engine that already exists (model.engine(**kw) on a model whose engine
         was created earlier — by encode(), manifold2d(), a previous trainer — must not silently drop them).
         renyi: a float alpha selects the importance-weighted bound, False returns to the ELBO, None leaves the setting.
         pixel_weights: weights set them, False removes them, None leaves the setting.
         image_weights: True turns the per-image weighted step on, False off, None leaves the setting.
-        fast_weights: True / False switches the weighted step to / from the bf16-class decoder kernels, None leaves the setting."""
+        fast_weights: True / False switches the weighted step to / from the bf16-class decoder kernels, None leaves the setting.
+        fused_any_size: True / False switches a model whose positions are no multiple of 16 to / from the fused f32 kernel's tail form."""
         given = dict(image_weights=image_weights, fast_weights=fast_weights, fused_channels=fused_channels, kl=kl,
-                     particles=particles, renyi=renyi, fused=fused, pixel_weights=pixel_weights)
+                     particles=particles, renyi=renyi, fused=fused, pixel_weights=pixel_weights, fused_any_size=fused_any_size)
         new = self._normalise({k: v for k, v in given.items() if v is not None})
         adam = dict(lr=None if lr is None else float(lr), betas=None if betas is None else (float(betas[0]), float(betas[1])),
                     adam_eps=None if eps is None else float(eps))
         old = self._settings()
         self._validate(dec_kernel=self.dec_kernel, **{**old, **new})
         # accepted: nothing was assigned before this line.  The workspace's layout depends on the kernels the settings select
-        if (any(k in new and new[k] != old[k] for k in ("fast_weights", "image_weights", "fused", "fused_channels"))
+        if (any(k in new and new[k] != old[k] for k in ("fast_weights", "image_weights", "fused", "fused_channels", "fused_any_size"))
                 or ("pixel_weights" in new and (new["pixel_weights"] is not None or old["pixel_weights"] is not None))):
             self.ws = None                                  # (pixel_weights=False on an unweighted engine: nothing to reset)
         vars(self).update(new)
@@ -652,6 +689,7 @@ class IVAEEngine:
                 (0 if self.full_tile_loop else _abi.PV_PLAN_GENERIC_TILE_LOOP) |
                 (_abi.PV_PLAN_FUSED_CHANNELS if (self.fused_channels and self.C > 1) else 0) |
                 (_abi.PV_PLAN_FAST_WEIGHTS if self._fast_weights_on() else 0) |
+                (_abi.PV_PLAN_FUSED_TAIL if self._any_size_on() else 0) |
                 (_abi.PV_PLAN_CONV_X3 if self.conv_x3 else 0))
 
     def ensure_bound(self):

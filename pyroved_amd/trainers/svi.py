@@ -74,6 +74,15 @@ class SVItrainer:
             sampler_d="categorical" (label maps: the C channels of a position are one categorical observation) trains wherever a
             multi-channel Bernoulli model does — every loss and num_particles on the layer-by-layer kernels, and with this keyword
             on the kernel's categorical instances
+        fused_any_size: True — a spatial model whose number of grid positions is NO multiple of 16 (27 x 27, 50 x 50, a spectrum of
+            100 points: three of every four square windows) trains, evaluates and decodes on the fused f32 decoder kernel's tail
+            form instead of the layer-by-layer kernels such a model otherwise takes whatever `fused` says (default False;
+            fp32-class results).  models.iVAE with its own fully connected networks, decoder hidden [128, 128] with tanh, the
+            per-value likelihoods, the one-particle ELBO, with or without pixel_weights / image_weights; 2 ... 6 or 8 channels with
+            fused_channels=True as well (seven channels stay on the layer-by-layer kernels: that instance of the kernel spills
+            registers and is not built).  A ValueError with num_particles > 1, loss="RenyiELBO", fused=0, fused=3 or
+            precision="bf16"; changes nothing where the positions are a multiple of 16, for other decoders, models.jiVAE or
+            sampler_d="categorical" (DESIGN.md 4.23 has the measured cost)
         pixel_weights: per-observation weights of the likelihood, shared by all images: a tensor, ndarray or bool mask of shape
             data_dim (the same weight in every channel of a multi-channel model) or (*data_dim, C); entries >= 0, not all zero.
             Every log p(x_bi | z_b) of train / evaluate is multiplied by w_i (its normaliser included) — a circular aperture for
@@ -183,7 +192,7 @@ class SVItrainer:
             if pvdist.world(self.group)[1] > 1:
                 raise ValueError("Pyro optimizer / loss objects cannot be combined with data-parallel training: replicas "
                                  "would train unsynchronised (pass optimizer=None or a dict of Adam arguments)")
-            bad = [k for k in ("precision", "fused", "fused_channels", "pixel_weights", "image_weights", "fast_weights", "rng", "device_feed",
+            bad = [k for k in ("precision", "fused", "fused_channels", "fused_any_size", "pixel_weights", "image_weights", "fast_weights", "rng", "device_feed",
                                "mirror_evaluate_update") if k in kwargs]
             if bad:
                 raise ValueError("%s only apply to the HIP training path, not to Pyro optimizer / loss objects" % bad)
@@ -226,6 +235,14 @@ class SVItrainer:
             if fused_channels and precision == "bf16":
                 raise ValueError("fused_channels=True selects the f32 fused decoder kernel (fp32-class results); it cannot be "
                                  "combined with precision='bf16'")
+            fas = kwargs.get("fused_any_size", False)
+            if fas is None:
+                fas = False
+            if not isinstance(fas, bool):
+                raise ValueError("fused_any_size must be True or False (got %s)" % type(fas).__name__)
+            if fas and precision == "bf16":
+                raise ValueError("fused_any_size=True selects the f32 fused decoder kernel (fp32-class results); it cannot be "
+                                 "combined with precision='bf16'")
             if precision == "bf16" and getattr(model, "channels", 1) != 1:
                 raise ValueError("precision='bf16' is not implemented for channels=%d: no bf16 multi-channel decoder kernel "
                                  "exists, and training at another precision than the one asked for is worse than refusing"
@@ -246,7 +263,7 @@ class SVItrainer:
                                        fused=int(kwargs.get("fused", 3 if precision == "bf16" else 2)), kl=kl, particles=P,
                                        renyi=False if self.alpha is None else self.alpha, fused_channels=fused_channels,
                                        pixel_weights=False if pw is None else pw,      # (no keyword: a later trainer is unweighted)
-                                       image_weights=iw, fast_weights=fw)
+                                       image_weights=iw, fast_weights=fw, fused_any_size=fas)
             self.image_weights = iw
         self.engine.lr, self.engine.betas, self.engine.adam_eps = float(adam["lr"]), tuple(adam["betas"]), float(adam["eps"])
         if hasattr(self.engine, "reset_optimizer"):
