@@ -79,7 +79,8 @@ def tanh_c(cx: torch.Tensor) -> torch.Tensor:
 
 
 def partition(units: int, grid: int) -> List[Tuple[int, int, bool]]:
-    """The 8-wave kernel's work split: (u_lo, u_hi, has_tail) per workgroup (`u_lo`, `u_hi`, `has_tail` in pv_sdec_w8_kernel, pv_sdec_fused_w8.hip)."""
+    """The 8-wave kernel's work split: (u_lo, u_hi, has_tail) per workgroup (`u_lo`, `u_hi`, `has_tail` in pv_sdec_w8_kernel:
+    sd_unit_bound and sd_ends_in_tail at 8-unit tiles, pv_sdec_partition.h — held against them by tests/test_partition_cases_cpu.py)."""
     out = []
     for g in range(grid):
         lo, hi = g * units // grid, (g + 1) * units // grid
@@ -88,7 +89,7 @@ def partition(units: int, grid: int) -> List[Tuple[int, int, bool]]:
 
 
 def grid_of(units: int, cus: int) -> int:
-    """pv_sdec_fused_grid (pv_sdec_fused.hip)."""
+    """pv_sdec_fused_grid (pv_sdec_fused.hip): sd_grid of pv_sdec_partition.h."""
     return max(1, min(units, cus))
 
 

@@ -285,6 +285,36 @@ def categorical_decoder_kernel_name(plan, weighted, grads):
     return fn(C.byref(plan), int(weighted), int(bool(grads))).decode()
 
 
+def partition_table(upb, samples, cus, waves):
+    """The fused decoder kernels' row partition as pyroved_amd/csrc/pv_sdec_partition.h computes it on the host
+    (pv_debug_partition_table, a test hook outside include/pyroved_amd.h; no device needed): for `samples` samples of `upb` units on
+    `cus` compute units — (bounds (G + 1) int64, gfirst (samples) int32, tail (G, 2) int32: the range ends in a column-parallel tail
+    at 4- / 8-unit tiles, grid, kmax for `waves` publishing waves)."""
+    import numpy as np
+    fn = lib().pv_debug_partition_table
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5
+    bounds, gfirst = np.zeros(cus + 1, np.int64), np.zeros(samples, np.int32)
+    tail, out = np.zeros((cus, 2), np.int32), np.zeros(2, np.int32)
+    check(fn(upb, samples, cus, waves, bounds.ctypes.data, gfirst.ctypes.data, tail.ctypes.data, out.ctypes.data,
+             out.ctypes.data + 4), "pv_debug_partition_table")
+    grid = int(out[0])
+    return bounds[:grid + 1], gfirst, tail[:grid], grid, int(out[1])
+
+
+def partition_walk(upb, samples, grid, waves, x_units):
+    """(b, loc, xu) of every unit as the kernels' division-free walk reaches it (pv_debug_partition_walk, likewise a test hook): wave w
+    of each of `grid` workgroups starts at its range's unit w and advances by `waves`; x_units 0, or the observations' period."""
+    import numpy as np
+    fn = lib().pv_debug_partition_walk
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 4 + [C.c_int64] + [C.c_void_p] * 3
+    n = upb * samples
+    b, loc, xu = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.full(n, -1, np.int64)
+    check(fn(upb, samples, grid, waves, x_units, b.ctypes.data, loc.ctypes.data, xu.ctypes.data), "pv_debug_partition_walk")
+    return b, loc, xu
+
+
 def check(code, what):
     if code != 0:
         kind = "hipError_t" if code > 0 else {-1: "PV_EINVAL", -2: "PV_EWS", -3: "PV_ECOLL"}.get(code, "PV error")

@@ -269,9 +269,8 @@ void carve(const pv_ivae_plan* p, char* base, Layout& L, bool inference_only = f
     if (L.fused) {
       const int64_t units = R / FD_UNIT;
       L.f_grid = pv_sdec_fused_grid(units);
-      L.f_kmax = pv_sdec_fused_kmax((int)N, units, L.f_grid);
       L.dec = layout_choice(p, R, true);
-      L.f_kmax *= L.dec.waves;                                    // the bf16 kernels publish dL/d(hz) per wave
+      L.f_kmax = pv_sdec_fused_kmax((int)N, units, L.f_grid, L.dec.waves);   // (the bf16 kernels publish dL/d(hz) per wave)
       L.f_part = c.take((int64_t)L.f_grid * FD_REC);
       L.f_part_hz = c.take(S * L.f_kmax * (H0 + PV_RS_W));        // (+ the row-sum slots behind it: PvFused::part_rs, one zero fill)
       L.f_rowtp = c.take(4 * R);

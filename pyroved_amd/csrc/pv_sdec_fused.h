@@ -1,9 +1,9 @@
 // pv_sdec_fused.h — the fused persistent spatial-decoder forward+backward kernel (pv_sdec_fused.hip).
 #pragma once
 #include "pv_common.h"
+#include "pv_sdec_partition.h"  // FD_UNIT (rows per wave tile) and the row partition's arithmetic
 
 #define FD_H 128               // hidden width the kernel is specialised for (hidden_dim_d = [128, 128])
-#define FD_UNIT 16             // rows per wave tile (one 16x16x4 MFMA column block)
 #define FD_WAVES 8             // waves per workgroup (2 per SIMD)
 #define FD_REC (2 * FD_H * FD_H + 14 * FD_H)  // floats of one per-workgroup partial-gradient record:
 // [dW1 HxH | dW2 HxH | db1 H | db2 H | dWc0 H | dWc1 H | dwo H | dbo (1, padded to H) | 8 spare slots x H]
@@ -141,10 +141,10 @@ bool pv_sdec_fused_w8_fold_ok(const PvFused& f, int grid);
 
 // true when the plan's architecture is the one the fused kernel is specialised for
 bool pv_sdec_fused_supported(const pv_ivae_plan* p);
-// workgroups the kernel runs with (<= number of CUs, <= units)
+// workgroups the kernel runs with: sd_grid (pv_sdec_partition.h) at the device's number of CUs
 int pv_sdec_fused_grid(int64_t units);
-// max workgroups that can touch one sample's rows
-int pv_sdec_fused_kmax(int n_pix, int64_t units, int grid);
+// dL/d(hz) slots per sample of `rows` rows (sd_kmax: the workgroups that can touch one sample's rows, times the waves that publish)
+int pv_sdec_fused_kmax(int rows, int64_t units, int grid, int waves);
 // launches the kernel (grads = false: forward + likelihood only)
 int pv_sdec_fused_launch(const PvFused& f, int grid, bool grads, hipStream_t s);
 // ---- several output channels per row (pv_sdec_fused_mc.hip; the plan asks with PV_PLAN_FUSED_CHANNELS, fused == 1) ----

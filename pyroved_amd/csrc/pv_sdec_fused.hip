@@ -61,17 +61,15 @@ __global__ __launch_bounds__(FD_THREADS, 2) void pv_sdec_fused_kernel(PvFused f)
   for (int kb = 0; kb < 8; ++kb) { accW1[kb] = f32x4{0, 0, 0, 0}; accW2[kb] = f32x4{0, 0, 0, 0}; }
   float db1 = 0.0f, db2 = 0.0f, aWc0 = 0.0f, aWc1 = 0.0f, ahz = 0.0f, dbo = 0.0f;
   int cur_b = -1;
-  const int upb = f.N / FD_UNIT;                       // units per sample (N % 16 == 0)
+  const int upb = sd_units_per_sample(f.N);            // (the partition, its slots: pv_sdec_partition.h)
 
   auto flush_hz = [&](int b) {
     // sample b's rows end (or the workgroup's do): publish this workgroup's partial dL/d(hz[b])
     const float t = fd_sum_q(ahz);
-    const int64_t ub = (int64_t)b * upb;
-    const int gfirst = (int)(((ub + 1) * G + f.units - 1) / f.units) - 1;   // first workgroup touching sample b
-    if (q == 0) f.part_hz[((int64_t)b * f.kmax + (g - gfirst)) * FD_H + 16 * wave + r] = t;
+    if (q == 0) f.part_hz[sd_slot<1>(b, g, 0, f.kmax, upb, G, f.units) * FD_H + 16 * wave + r] = t;
   };
 
-  const int64_t u_lo = (int64_t)g * f.units / G, u_hi = (int64_t)(g + 1) * f.units / G;
+  const int64_t u_lo = sd_unit_bound(g, f.units, G), u_hi = sd_unit_bound(g + 1, f.units, G);
   for (int64_t u0 = u_lo; u0 < u_hi; u0 += FD_WAVES) {
     const int nact = (int)((u_hi - u0) < FD_WAVES ? (u_hi - u0) : FD_WAVES);
     const bool active = wave < nact;
@@ -339,14 +337,59 @@ static int fd_num_cus() {
   return cus;
 }
 
-int pv_sdec_fused_grid(int64_t units) {
-  const int cus = fd_num_cus();
-  return (int)(units < cus ? (units < 1 ? 1 : units) : cus);
+int pv_sdec_fused_grid(int64_t units) { return sd_grid(units, fd_num_cus()); }
+
+int pv_sdec_fused_kmax(int rows, int64_t units, int grid, int waves) { return sd_kmax(rows, units, grid, waves); }
+
+// ---- test hooks (outside include/pyroved_amd.h): pv_sdec_partition.h evaluated on the host, in bulk.  Nothing touches the GPU ----
+// bounds (G + 1): the workgroups' ranges; gfirst (samples); tail (2 G): [2 g] whether range g ends in a tail at 4-unit tiles, [2 g + 1] at
+// 8-unit tiles; *grid = G for `cus` compute units (the caller sizes bounds and tail for G <= cus); *kmax for `waves` publishing waves
+extern "C" int pv_debug_partition_table(int upb, int samples, int cus, int waves, int64_t* bounds, int32_t* gfirst, int32_t* tail,
+                                        int32_t* grid, int32_t* kmax) {
+  if (upb < 1 || samples < 1 || cus < 1 || waves < 1 || upb > INT32_MAX / FD_UNIT) return PV_EINVAL;
+  const int rows = upb * FD_UNIT;
+  const int64_t units = (int64_t)samples * sd_units_per_sample(rows);
+  const int G = sd_grid(units, cus);
+  for (int g = 0; g <= G; ++g) bounds[g] = sd_unit_bound(g, units, G);
+  for (int g = 0; g < G; ++g) {
+    tail[2 * g] = sd_ends_in_tail(bounds[g], bounds[g + 1], 4);
+    tail[2 * g + 1] = sd_ends_in_tail(bounds[g], bounds[g + 1], 8);
+  }
+  for (int b = 0; b < samples; ++b) gfirst[b] = sd_gfirst(b, upb, G, units);
+  *grid = G;
+  *kmax = sd_kmax(rows, units, G, waves);
+  return 0;
 }
 
-int pv_sdec_fused_kmax(int n_pix, int64_t units, int grid) {
-  const int64_t upb = n_pix / FD_UNIT;
-  return (int)((upb * grid) / (units > 0 ? units : 1)) + 2;
+// the kernels' walk over every unit with U as the unit type: wave w of a workgroup starts at sd_pos_of(u_lo + w) and reaches its later
+// units by sd_pos_advance(..., waves).  check: compare with the arrays instead of filling them.  Returns the units that differ
+template <class U>
+static int64_t fd_partition_walk(int upb, int64_t units, int G, int waves, int64_t x_units, int32_t* b, int32_t* loc, int64_t* xu,
+                                 bool check) {
+  int64_t bad = 0;
+  for (int g = 0; g < G; ++g) {
+    const U lo = (U)sd_unit_bound(g, units, G), hi = (U)sd_unit_bound(g + 1, units, G);
+    for (int w = 0; w < waves && lo + w < hi; ++w) {
+      SdPos<U> p = sd_pos_of<U>(lo + w, upb, (U)x_units);
+      for (;; sd_pos_advance(p, waves, upb, (U)x_units)) {
+        if (p.unit < lo || p.unit >= hi) return -1;
+        if (check) bad += b[p.unit] != p.b || loc[p.unit] != p.loc || xu[p.unit] != (int64_t)p.xu;
+        else { b[p.unit] = p.b; loc[p.unit] = p.loc; xu[p.unit] = (int64_t)p.xu; }
+        if (p.unit + waves >= hi) break;
+      }
+    }
+  }
+  return bad;
+}
+
+// b, loc, xu (samples upb each): every unit's walked position on `grid` workgroups of `waves` waves; the 64-bit walk fills them and
+// the 32-bit walk must agree.  x_units: 0, or the period of the observations in units
+extern "C" int pv_debug_partition_walk(int upb, int samples, int grid, int waves, int64_t x_units, int32_t* b, int32_t* loc,
+                                       int64_t* xu) {
+  const int64_t units = (int64_t)samples * upb;
+  if (upb < 1 || samples < 1 || waves < 1 || x_units < 0 || units > INT32_MAX / FD_UNIT || grid < 1 || grid > units) return PV_EINVAL;
+  if (fd_partition_walk<int64_t>(upb, units, grid, waves, x_units, b, loc, xu, false) != 0) return PV_EINVAL;
+  return fd_partition_walk<int>(upb, units, grid, waves, x_units, b, loc, xu, true) == 0 ? 0 : PV_EINVAL;
 }
 
 int pv_sdec_fused_launch(const PvFused& f_in, int grid, bool grads, hipStream_t s) {

@@ -80,7 +80,7 @@
 #pragma unroll
   for (int jb = 0; jb < (PP::KEEP_WO ? 8 : 1); ++jb) accWo[jb] = f32x4{0, 0, 0, 0};
   int cur_b = -1;                                    // the sample whose dL/d(hz) this WAVE is accumulating
-  const int upb = f.N / FD_UNIT;
+  const int upb = sd_units_per_sample(f.N);          // (the partition, its slots and the walk: pv_sdec_partition.h)
   float* rec = f.part + (int64_t)g * FD_REC;
   // this wave's column-sum accumulators (lane l owns columns 2l, 2l+1 of each): d(wo), dL/d(hz[cur_b]) (flushed when the wave's
   // sample changes), dWc0, dWc1
@@ -93,9 +93,8 @@
   auto flush_hz = [&](int b) {
     // the wave's rows of sample b end (or the workgroup's do): publish its partial dL/d(hz[b]) in its own slot
     // (kmax counts FB_WAVES slots per workgroup that can touch a sample; unused slots stay zero)
-    const int64_t ub = (int64_t)b * upb;
-    const int gfirst = (int)(((ub + 1) * G + f.units - 1) / f.units) - 1;
-    const int64_t slot = (int64_t)b * f.kmax + (g - gfirst) * FB_WAVES + wave;
+    const int gfirst = sd_gfirst(b, upb, G, f.units);
+    const int64_t slot = (int64_t)b * f.kmax + (g - gfirst) * FB_WAVES + wave;       // (sd_slot<FB_WAVES>, written out)
     *reinterpret_cast<float2*>(f.part_hz + slot * FD_H + 2 * lane) = cs_hz;
     cs_hz = float2{0.0f, 0.0f};
     if (GRADS && f.part_rs) {
@@ -109,22 +108,11 @@
     }
   };
 
-  // A unit's sample b / offset inside the sample / observation unit are carried incrementally from tile to tile (round 2):
-  // the int64 divisions this replaced expanded to ~900 scalar instructions per tile.  Units stay 64-bit here (this kernel
-  // also serves problems beyond 2^31 rows).
-  const int64_t u_lo = (int64_t)g * f.units / G, u_hi = (int64_t)(g + 1) * f.units / G;
-  struct Pos { int64_t unit; int b, loc; int64_t xu; };   // unit = b * upb + loc ; xu = unit mod x_units (x_units > 0)
-  auto pos_of = [&](int64_t unit_) {
-    Pos p_;
-    p_.unit = unit_; p_.b = (int)(unit_ / upb); p_.loc = (int)(unit_ - (int64_t)p_.b * upb);
-    p_.xu = f.x_units > 0 ? unit_ % f.x_units : unit_;
-    return p_;
-  };
-  auto advance = [&](Pos& p_, int by) {
-    p_.unit += by; p_.loc += by; p_.xu += by;
-    while (p_.loc >= upb) { p_.loc -= upb; ++p_.b; }
-    if (f.x_units > 0) { while (p_.xu >= f.x_units) p_.xu -= f.x_units; }
-  };
+  // A unit's position is carried from tile to tile (round 2).  Units stay 64-bit here (this kernel also serves problems beyond 2^31 rows).
+  const int64_t u_lo = sd_unit_bound(g, f.units, G), u_hi = sd_unit_bound(g + 1, f.units, G);
+  using Pos = SdPos<int64_t>;
+  auto pos_of = [&](int64_t unit_) { return sd_pos_of<int64_t>(unit_, upb, f.x_units); };
+  auto advance = [&](Pos& p_, int by) { sd_pos_advance<int64_t>(p_, by, upb, f.x_units); };
   // (H231 build) a range of 4 n + 1 units ends with a column-parallel tail (below): the row-parallel tiles cover [u_lo, u_end), and
   // what a wave without a further unit prefetches is the TAIL unit's inputs (every wave takes part in the tail)
   constexpr bool TAIL = FB_TAIL && GRADS && PREC == FB_P_H231;
@@ -133,7 +121,7 @@
 #else
   constexpr int qsw = 0;
 #endif
-  const bool has_tail = TAIL && ((u_hi - u_lo) & (TILE_UNITS - 1)) == 1 && !(f.ablate & 512);   // (ablate: experiments build only)
+  const bool has_tail = TAIL && sd_ends_in_tail(u_lo, u_hi, TILE_UNITS) && !(f.ablate & 512);   // (ablate: experiments build only)
   const int64_t u_end = has_tail ? u_hi - 1 : u_hi;
   const Pos pos_lo = pos_of(has_tail ? u_end : u_lo);   // what an out-of-range wave fetches instead (valid; unused without a tail)
   Pos pos_cur = pos_of(u_lo + wave < u_end ? u_lo + wave : (has_tail ? u_end : u_lo));

@@ -49,17 +49,15 @@ __global__ __launch_bounds__(FD_THREADS, 2) void FDM_KERNEL(PvFused f) {
 #pragma unroll
   for (int c = 0; c < C; ++c) adwo[c] = 0.0f;
   int cur_b = -1;
-  const int upb = f.N / FD_UNIT;                       // units per sample (N = rows per sample, N % 16 == 0)
+  const int upb = sd_units_per_sample(f.N);            // (N = rows per sample; the partition, its slots: pv_sdec_partition.h)
 
   auto flush_hz = [&](int b) {
     // sample b's rows end (or the workgroup's do): publish this workgroup's partial dL/d(hz[b])
     const float t = fd_sum_q(ahz);
-    const int64_t ub = (int64_t)b * upb;
-    const int gfirst = (int)(((ub + 1) * G + f.units - 1) / f.units) - 1;   // first workgroup touching sample b
-    if (q == 0) f.part_hz[((int64_t)b * f.kmax + (g - gfirst)) * FD_H + 16 * wave + r] = t;
+    if (q == 0) f.part_hz[sd_slot<1>(b, g, 0, f.kmax, upb, G, f.units) * FD_H + 16 * wave + r] = t;
   };
 
-  const int64_t u_lo = (int64_t)g * f.units / G, u_hi = (int64_t)(g + 1) * f.units / G;
+  const int64_t u_lo = sd_unit_bound(g, f.units, G), u_hi = sd_unit_bound(g + 1, f.units, G);
   for (int64_t u0 = u_lo; u0 < u_hi; u0 += FD_WAVES) {
     const int nact = (int)((u_hi - u0) < FD_WAVES ? (u_hi - u0) : FD_WAVES);
     const bool active = wave < nact;

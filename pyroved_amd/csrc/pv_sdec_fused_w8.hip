@@ -898,14 +898,13 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
   float dbo = 0.0f;
   float llacc = 0.0f;                                // OWN: the log-likelihood of this lane's rows so far (lanes q == 0)
   int cur_b = -1;                                    // the sample whose dL/d(hz) this WAVE is accumulating
-  const int upb = f.N / FD_UNIT;
+  const int upb = sd_units_per_sample(f.N);          // (the partition, its slots and the walk: pv_sdec_partition.h)
   float* rec = f.part + (int64_t)g * FD_REC;
 
   auto flush_hz = [&](int b) {
     // the wave's rows of sample b end: publish its partial dL/d(hz[b]) (column 0 of accS: lanes r == 0) in its own slot
-    const int64_t ub = (int64_t)b * upb;
-    const int gfirst = (int)(((ub + 1) * G + f.units - 1) / f.units) - 1;
-    gfloat* dst = a_part_hz + ((int64_t)b * f.kmax + (g - gfirst) * W8_WAVES + wave) * FD_H + 4 * q;
+    const int gfirst = sd_gfirst(b, upb, G, f.units);
+    gfloat* dst = a_part_hz + ((int64_t)b * f.kmax + (g - gfirst) * W8_WAVES + wave) * FD_H + 4 * q;   // (sd_slot<W8_WAVES>, written out)
     if (r == 0) {
 #pragma unroll
       for (int jb = 0; jb < 8; ++jb) *(__attribute__((address_space(1))) f32x4*)(dst + 16 * jb) = accS[jb] * SD_RC2;
@@ -916,25 +915,16 @@ __global__ __launch_bounds__(W8_THREADS) void pv_sdec_w8_kernel(PvFused f, PvEnc
       for (int i = 0; i < 4; ++i) accS[jb][i] = r == 0 ? 0.0f : accS[jb][i];
   };
 
-  // units are 32-bit here (the launcher falls back to the 4-wave kernel beyond 2^31 rows), and a unit's sample b / offset
-  // inside the sample / observation unit are carried incrementally from tile to tile: no integer division in the loop
-  // (FULL: one image per workgroup, its units counted from 0 — u_x / u_loc point at the image's rows)
-  const int u_lo = FULL ? 0 : (int)((int64_t)g * f.units / G), u_hi = FULL ? upb : (int)((int64_t)(g + 1) * f.units / G);
+  // units are 32-bit here (the launcher falls back to the 4-wave kernel beyond 2^31 rows), and a unit's position is carried from
+  // tile to tile  (FULL: one image per workgroup, its units counted from 0 — u_x / u_loc point at the image's rows)
+  const int u_lo = FULL ? 0 : sd_unit_bound32(g, f.units, G), u_hi = FULL ? upb : sd_unit_bound32(g + 1, f.units, G);
   const int xun = (int)f.x_units;
-  struct Pos { int unit, b, loc, xu; };                 // unit = b * upb + loc ; xu = unit mod x_units (x_units > 0)
-  auto pos_of = [&](int unit_) {
-    Pos p_;
-    p_.unit = unit_; p_.b = unit_ / upb; p_.loc = unit_ - p_.b * upb; p_.xu = xun > 0 ? unit_ % xun : unit_;
-    return p_;
-  };
-  auto advance = [&](Pos& p_, int by) {
-    p_.unit += by; p_.loc += by; p_.xu += by;
-    while (p_.loc >= upb) { p_.loc -= upb; ++p_.b; }
-    if (xun > 0) { while (p_.xu >= xun) p_.xu -= xun; }
-  };
+  using Pos = SdPos<int>;
+  auto pos_of = [&](int unit_) { return sd_pos_of<int>(unit_, upb, xun); };
+  auto advance = [&](Pos& p_, int by) { sd_pos_advance<int>(p_, by, upb, xun); };
   // a range of 8 n + 1 units ends with a column-parallel tail (below): the row-parallel tiles cover [u_lo, u_end), and what a
   // wave without a further unit prefetches is the tail unit's inputs (every wave takes part in the tail)
-  const bool has_tail = W8_TAIL && ((u_hi - u_lo) & (W8_WAVES - 1)) == 1;
+  const bool has_tail = W8_TAIL && sd_ends_in_tail(u_lo, u_hi, W8_WAVES);
   const int u_end = has_tail ? u_hi - 1 : u_hi;
   const Pos pos_lo = pos_of(has_tail ? u_end : u_lo);   // what an out-of-range wave fetches instead (valid; unused without a tail)
   // (FULL: at least one full tile — wave w starts on unit u_lo + w of image g; nothing below carries a position from tile to tile)

@@ -363,14 +363,13 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
   }
   float dbo = 0.0f;
   int cur_b = -1;                                    // the sample whose dL/d(hz) this WAVE is accumulating
-  const int upb = f.N / FD_UNIT;
+  const int upb = sd_units_per_sample(f.N);          // (the partition, its slots and the walk: pv_sdec_partition.h)
   float* rec = f.part + (int64_t)g * FD_REC;
 
   auto flush_hz = [&](int b, int r_, int q_) {
     // the wave's rows of sample b end: publish its partial dL/d(hz[b]) (column 0 of accS: lanes r == 0) in its own slot
-    const int64_t ub = (int64_t)b * upb;
-    const int gfirst = (int)(((ub + 1) * G + f.units - 1) / f.units) - 1;
-    gfloat* dst = a_part_hz + ((int64_t)b * f.kmax + (g - gfirst) * H8_WAVES + wave) * FD_H + 4 * q_;
+    const int gfirst = sd_gfirst(b, upb, G, f.units);
+    gfloat* dst = a_part_hz + ((int64_t)b * f.kmax + (g - gfirst) * H8_WAVES + wave) * FD_H + 4 * q_;   // (sd_slot<H8_WAVES>, written out)
     if (r_ == 0) {
 #pragma unroll
       for (int jb = 0; jb < 8; ++jb) *(__attribute__((address_space(1))) f32x4*)(dst + 16 * jb) = accS[jb] * u0p;
@@ -381,19 +380,11 @@ __global__ __launch_bounds__(H8_THREADS) void pv_sdec_w8h_kernel(PvFused f) {
       for (int i = 0; i < 4; ++i) accS[jb][i] = r_ == 0 ? 0.0f : accS[jb][i];
   };
 
-  const int u_lo = (int)((int64_t)g * f.units / G), u_hi = (int)((int64_t)(g + 1) * f.units / G);
+  const int u_lo = sd_unit_bound32(g, f.units, G), u_hi = sd_unit_bound32(g + 1, f.units, G);
   const int xun = (int)f.x_units;
-  struct Pos { int unit, b, loc, xu; };                 // unit = b * upb + loc ; xu = unit mod x_units (x_units > 0)
-  auto pos_of = [&](int unit_) {
-    Pos p_;
-    p_.unit = unit_; p_.b = unit_ / upb; p_.loc = unit_ - p_.b * upb; p_.xu = xun > 0 ? unit_ % xun : unit_;
-    return p_;
-  };
-  auto advance = [&](Pos& p_, int by) {
-    p_.unit += by; p_.loc += by; p_.xu += by;
-    while (p_.loc >= upb) { p_.loc -= upb; ++p_.b; }
-    if (xun > 0) { while (p_.xu >= xun) p_.xu -= xun; }
-  };
+  using Pos = SdPos<int>;
+  auto pos_of = [&](int unit_) { return sd_pos_of<int>(unit_, upb, xun); };
+  auto advance = [&](Pos& p_, int by) { sd_pos_advance<int>(p_, by, upb, xun); };
   const Pos pos_lo = pos_of(u_lo);                      // what an out-of-range wave fetches instead (valid, unused)
   Pos pos_cur = pos_of(u_lo + wave < u_hi ? u_lo + wave : u_lo);
   Pos pos_nx = pos_cur;

@@ -2,7 +2,8 @@
 _partition_cases.py — the row partition every fused decoder kernel shares, restated in Python, and the case table the tests of
 its edges run on (tests/test_partition_cases_cpu.py, tests/test_gpu_partition_edges.py).
 
-The partition (pv_sdec_fused.hip: pv_sdec_fused_grid / pv_sdec_fused_kmax; `u_lo`, `u_hi`, `gfirst` in every kernel):
+The partition (pyroved_amd/csrc/pv_sdec_partition.h: sd_grid, sd_unit_bound, sd_gfirst, sd_slot, sd_kmax — the one text the kernels
+and the host compile; tests/test_partition_cases_cpu.py holds this restatement against it through pv_debug_partition_table):
   * a unit is 16 rows of one decoder sample; a sample of N positions has upb = N / 16 units; S samples make units = S upb;
   * G = min(units, CUs) workgroups; workgroup g owns units [g units / G, (g + 1) units / G);
   * it publishes its partial dL/d(hz[b]) (in some builds the sample's row sums too) into slot g - gfirst(b) of sample b's
@@ -52,7 +53,7 @@ def partition(N, S, cus=CUS):
     last = np.searchsorted(bounds, (b + 1) * upb - 1, side="right") - 1         # ... its last unit
     gfirst = ((b * upb + 1) * G + units - 1) // units - 1                       # the kernels' formula
     kmax = kmax_of(upb, units, G)
-    return dict(N=N, S=S, upb=upb, units=units, grid=G, kmax=kmax,
+    return dict(N=N, S=S, upb=upb, units=units, grid=G, kmax=kmax, bounds=bounds, first=first,
                 units_per_wg=sorted(set(per_wg.tolist())), units_per_wg_counts={int(v): int((per_wg == v).sum()) for v in set(per_wg.tolist())},
                 samples_per_wg=sorted(set(spw.tolist())), samples_per_wg_counts={int(v): int((spw == v).sum()) for v in set(spw.tolist())},
                 wgs_per_sample=(int((last - first + 1).min()), int((last - first + 1).max())),

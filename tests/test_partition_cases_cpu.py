@@ -1,6 +1,8 @@
 """
 CPU tests of tests/_partition_cases.py: the case table of tests/test_gpu_partition_edges.py says what it claims, the slot bound of
-the fused decoder kernels' row partition holds and is tight, and no cell of that GPU test is blind.
+the fused decoder kernels' row partition holds and is tight, the text the kernels compile (pyroved_amd/csrc/pv_sdec_partition.h,
+through the library's host-side hooks) agrees with both Python restatements and with the divisions its walk replaces, and no cell
+of that GPU test is blind.
 
 Blindness.  The slot arithmetic (`gfirst`, `kmax`) decides where a workgroup's partial of ONE sample lands; an off-by-one there
 puts one workgroup's share of one sample — one or a few 16-row units — into another sample's slots or drops it.  So a cell can
@@ -11,6 +13,8 @@ decoder sample, and the first and the last unit of that sample, at least one che
 the cell carries them) — moves by at least 5x its own bar in that family.  (The loss scalars, z and loc_out are left out of the
 condition on purpose: they would meet it everywhere, and none of them depends on the slots.)
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -92,9 +96,12 @@ def test_slot_bound_holds_and_is_tight():
     assert tight > 0
 
 
+SMALL_SHAPES = ((16, 257, 256), (48, 171, 256), (784, 6, 256), (64, 600, 256), (16, 7, 4), (32, 5, 3))       # (N, S, CUs)
+
+
 def test_restatement_against_a_walk_over_the_units():
     """partition() against the kernels' loop written out: every workgroup walks its units and flushes at a sample's end."""
-    for N, S, cus in ((16, 257, 256), (48, 171, 256), (784, 6, 256), (64, 600, 256), (16, 7, 4), (32, 5, 3)):
+    for N, S, cus in SMALL_SHAPES:
         p = pc.partition(N, S, cus)
         upb, units, G = p["upb"], p["units"], p["grid"]
         slots = {}
@@ -107,6 +114,81 @@ def test_restatement_against_a_walk_over_the_units():
         assert all(min(v) == 0 and sorted(v) == list(range(len(v))) for v in slots.values())
         assert max(max(v) for v in slots.values()) == p["max_slot"] <= p["kmax"] - 1
         assert (min(len(v) for v in slots.values()), max(len(v) for v in slots.values())) == p["wgs_per_sample"]
+
+
+# ------------------------------------------------------------------------------- 2b. the text the kernels compile
+# pyroved_amd/csrc/pv_sdec_partition.h, evaluated on the host by the library's hooks (pv_debug_partition_table / _walk: no device)
+def _hooks():
+    from pyroved_amd import _abi
+    if not os.path.exists(_abi.LIB_PATH):
+        pytest.skip("the shipped library (make -C pyroved_amd/csrc) is not built: the header's arithmetic cannot be evaluated")
+    return _abi
+
+
+def _brute_force_shapes():
+    """(N, S, CUs) of test_slot_bound_holds_and_is_tight, then SMALL_SHAPES (grids of 4 and 3 among them)"""
+    for upb in list(range(1, 20)) + [49, 64, 100, 256]:
+        for B in list(range(1, 700)) + [1024, 2048, 4096]:
+            yield upb * pc.UNIT, B, 256
+    yield from SMALL_SHAPES
+
+
+def test_header_against_the_restatement():
+    """bounds, gfirst, grid and kmax (1, 4 and 8 publishing waves) of the header equal partition()'s: gfirst is held against `first`,
+    the owner of a sample's first unit found by a search over the bounds — the library's and the restatement's alike."""
+    abi = _hooks()
+    n = 0
+    for N, S, cus in _brute_force_shapes():
+        p = pc.partition(N, S, cus)
+        upb = p["upb"]
+        for waves in (1, 4, 8):
+            bounds, gfirst, _, grid, kmax = abi.partition_table(upb, S, cus, waves)
+            assert grid == p["grid"] and kmax == pc.kmax_of(upb, p["units"], p["grid"]) * waves, (N, S, cus, waves, grid, kmax)
+        assert np.array_equal(bounds, p["bounds"]), (N, S, cus)
+        assert np.array_equal(gfirst, p["first"]), (N, S, cus)
+        assert np.array_equal(gfirst, np.searchsorted(bounds, np.arange(S, dtype=np.int64) * upb, side="right") - 1), (N, S, cus)
+        n += 1
+    print("shapes: %d" % n)
+    assert n == 23 * 702 + len(SMALL_SHAPES)
+
+
+def test_header_against_the_oracles_partition():
+    """oracle/bf16_plan.partition (the 8-wave kernel's ranges and its 1-mod-8 tail, restated for the record rounding) against the
+    header: the case table's shapes, and every unit count up to 4096 on 256 compute units."""
+    from oracle import bf16_plan
+    abi = _hooks()
+    shapes = [(pc.n_pos(c) // pc.UNIT, pc.n_samples(c)) for c in pc.CASES.values()] + [(1, units) for units in range(1, 4097)]
+    for upb, S in shapes:
+        units = upb * S
+        bounds, _, tail, grid, _ = abi.partition_table(upb, S, 256, 8)
+        assert grid == bf16_plan.grid_of(units, 256), (upb, S)
+        want = bf16_plan.partition(units, grid)
+        assert [(int(lo), int(hi), bool(t)) for lo, hi, t in zip(bounds[:-1], bounds[1:], tail[:, 1])] == want, (upb, S)
+
+
+def _walk_shapes():
+    """(upb, S, CUs, observation periods in units): 0 and B upb — the jiVAE / particle form, S = K B samples observing B images"""
+    for N, S, cus in SMALL_SHAPES:
+        upb = N // pc.UNIT
+        yield upb, S, cus, sorted({0, S * upb, max(1, S // 3) * upb})          # (no B of their own: every sample, and a third of them)
+    for c in pc.CASES.values():
+        upb = pc.n_pos(c) // pc.UNIT
+        yield upb, pc.n_samples(c), 256, (0, c["B"] * upb)
+
+
+def test_walk_reaches_every_unit_where_the_divisions_put_it():
+    """sd_pos_of at a wave's first unit and sd_pos_advance from there on (4 and 8 waves, 32- and 64-bit units: the hook runs both)
+    give every unit u the (sample, offset, observation unit) = (u // upb, u % upb, u % x_units or u) of the divisions they replace."""
+    abi = _hooks()
+    for upb, S, cus, periods in _walk_shapes():
+        u = np.arange(S * upb, dtype=np.int64)
+        grid = pc.grid_of(S * upb, cus)
+        for waves in (4, 8):
+            for x_units in periods:
+                b, loc, xu = abi.partition_walk(upb, S, grid, waves, x_units)
+                key = (upb, S, cus, waves, x_units)
+                assert np.array_equal(b, u // upb) and np.array_equal(loc, u % upb), key
+                assert np.array_equal(xu, u % x_units if x_units else u), key
 
 
 # ------------------------------------------------------------------------------- 3. no cell is blind
